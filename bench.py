@@ -6,13 +6,19 @@ ref:multigrid_throughput.cc:1132-1133) on the finest level of the workload, with
 already resident in HBM.  Workloads (config.workload):
 
   octant_p4 (default)  BASELINE.json configs[2]: 3D octant (GeometryType "quadrant"), global coarsening, p = 4, FP64,
-                       SmootherDegree 3 -- the configuration the metric is quoted on.  At N = 1 the line also carries, under
-                       "also", the octant p = 1 number north_star asks for and p = 1 on a uniform mesh that fills the GPU
-                       (BASELINE.json configs[1]).
+                       SmootherDegree 3 -- the configuration the metric is quoted on.  With --full at N = 1 the line also
+                       carries, under "also", the octant p = 1 number north_star asks for and p = 1 on a uniform mesh that
+                       fills the GPU (BASELINE.json configs[1]).
   pmg_annulus          BASELINE.json configs[4]: polynomial global coarsening p = 4 -> 2 -> 1 on the annulus; the p = 1
                        coarse level is solved by CG preconditioned with its Chebyshev smoother (ref:multigrid_throughput.cc:922-944).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets the workload up, warms up, times the K steps and prints the headline line, nothing else.  --full adds
+  what takes runs or checks of its own: the dominant kernel's roofline (HIP events inside the timed steps), stage times,
+  the cycle without the tabulated coarse levels, the CG solve, the secondary workloads (also, also_uniform_p1, also_float,
+  also_sharded_size), the CPU baseline and, for N > 1, the RCCL diagnostics.  --dump-outputs DIR writes, after the timed
+  steps, the vector z = P^-1 b of the last step as DIR/z.npy (float64; above 2^22 DoFs the entries at a fixed seeded set
+  of indices) and DIR/z_summary.npy ([n_dofs, |z|_2, |z|_inf, sum z] of the whole vector); rank 0's local part for N > 1.
   (N > 1: launched by torch.distributed.run, one rank per GPU.  The SAME global problem is sharded by spatial domain
    decomposition: every rank owns a Morton chunk of the octree, shared DoFs are exchanged with grouped RCCL
    send/recv over xGMI, the replicated coarse levels take one RCCL all-reduce -> "scaling": "strong",
@@ -51,8 +57,30 @@ def algorithmic_bytes_per_vcycle(n_dofs_per_level, k=3, word=8):
     return word * ((10 * k + 3) * sum(N[1:]) + 2 * sum(N[:-1]))
 
 
+DUMP_SAMPLE = 1 << 22  # entries of z that --dump-outputs keeps (32 MiB of float64)
+
+
+def output_arrays(z_host):
+    """--dump-outputs: z = P^-1 b, whole up to DUMP_SAMPLE entries, else at DUMP_SAMPLE draws of numpy's default_rng(0) over
+    [0, n) (sorted, duplicates dropped: the same indices for the same n), and [n, |z|_2, |z|_inf, sum z] of the whole vector."""
+    import numpy as np
+
+    n = z_host.size
+    z = z_host if n <= DUMP_SAMPLE else z_host[np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))]
+    summary = np.array([n, np.linalg.norm(z_host), np.abs(z_host).max() if n else 0.0, z_host.sum()], dtype=np.float64)
+    return {"z": np.ascontiguousarray(z, dtype=np.float64), "z_summary": summary}
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_workload(m, ctx, geometry, n_ref, degree, mg_type, coarse, steps, warmup, barrier, sync, profile, comm=None, details=False,
-                 number_type=None, diagnostics=False, coarse_cycles=1, subset_group=None):
+                 number_type=None, diagnostics=False, coarse_cycles=1, subset_group=None, cg=True, dump=False):
     t0 = time.time()
     number_type = m.F64 if number_type is None else number_type
     word = 8 if number_type == m.F64 else 4
@@ -90,6 +118,8 @@ def run_workload(m, ctx, geometry, n_ref, degree, mg_type, coarse, steps, warmup
     sync()
     barrier()
     elapsed = time.perf_counter() - t0
+    # the output of the last timed step, read before anything else writes z
+    outputs = output_arrays(z.to_host()) if dump else None
     prof = None
     if profile:
         prof = ctx.kernel_profile_read() + (ctx.kernel_profile_bytes_moved(),)
@@ -100,7 +130,7 @@ def run_workload(m, ctx, geometry, n_ref, degree, mg_type, coarse, steps, warmup
         N = h.global_level_dofs(ctx)
     res = dict(n_dofs=h.n_dofs, n_cells=h.trias[-1].n_cells, n_levels=len(N), level_dofs=N, elapsed=elapsed, setup_s=setup_s,
                bytes_per_vcycle=algorithmic_bytes_per_vcycle(N, word=word), groups=h.dofs[-1].groups(), prof=prof,
-               coarse_solver=h.mg.coarse_solver_used(),
+               coarse_solver=h.mg.coarse_solver_used(), outputs=outputs,
                fused_transfer_bricks=sum(t.n_fused_bricks() for t in h.transfers[1:] if t is not None))
     if comm is not None:
         # pieces every level is cut into: n_ranks, n_ranks / group on the subset tier (each part held by a group of ranks), 1 = replicated
@@ -137,7 +167,7 @@ def run_workload(m, ctx, geometry, n_ref, degree, mg_type, coarse, steps, warmup
                                  achieved_GBps=8.0 * words * N[L] / (ms[6, L] * 1e-3) / 1e9)
     # reference protocol for context: CG solve to reltol 1e-4 (ref:multigrid_throughput.cc:1238-1254); the reference's
     # own headline column throughput = n_dofs * n_iterations / time (ref:multigrid_throughput.cc:1282)
-    if number_type != m.F64 and comm is not None:
+    if not cg or (number_type != m.F64 and comm is not None):
         return res
     x = h.fine_operator.initialize_dof_vector() if number_type == m.F64 else m.Vector(ctx, h.dofs[-1].n_dofs)
     m.solve_cg(h.fine_operator, h.mg, x, b, 1e-4)  # warm-up
@@ -299,6 +329,10 @@ def main():
                     "DoFs are cut into N / group parts; default 4 from 8 ranks on, 2 from 4 on; 1 = replicate those levels)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline figure: roofline, stage times, CG solve, "
+                    "secondary workloads, float levels, CPU baseline, RCCL diagnostics (--nref-p1, --nref-uniform-p1, --cpu-nref and "
+                    "the --no-* switches act on these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write z of the last timed step to DIR/*.npy (see the module docstring)")
     args = ap.parse_args()
     geometry, nref_default, degree, mg_type, coarse, cfg_name = WORKLOADS[args.workload]
     coarse = args.coarse or coarse
@@ -347,8 +381,9 @@ def main():
                 uid.copy_(torch.frombuffer(bytearray(m.Communicator.rccl_unique_id()), dtype=torch.uint8))
             dist.broadcast(uid, 0)
             comm = m.Communicator.rccl(ctx, world, rank, bytes(uid.cpu().numpy().tobytes()))
-        prim = run_workload(m, ctx, geometry, nref, degree, mg_type, coarse, args.steps, args.warmup, barrier, sync, profile=True, comm=comm,
-                            details=world == 1, diagnostics=True, coarse_cycles=args.coarse_cycles, subset_group=args.subset_group)
+        prim = run_workload(m, ctx, geometry, nref, degree, mg_type, coarse, args.steps, args.warmup, barrier, sync, profile=args.full,
+                            comm=comm, details=args.full and world == 1, diagnostics=args.full, coarse_cycles=args.coarse_cycles,
+                            subset_group=args.subset_group, cg=args.full, dump=args.dump_outputs is not None and rank == 0)
     except Exception as e:  # noqa: BLE001
         # no fallback, no relabelled metric: the other ranks may be blocked inside a collective, so leave hard with a
         # non-zero status and let the launcher tear the job down
@@ -390,8 +425,8 @@ def main():
                 f"domain decomposition over {world} GPUs: RCCL send/recv halo exchange, rank-group tier for the mid-size levels (level_layout), "
                 f"all-reduce onto the replicated coarse levels"
                 if mode == "sharded" else f"replicas x{world} (no data-path collective)"),
-            "cg_iterations_reltol_1e-4": prim["cg_iterations"],
-            "cg_throughput_dofs_x_iterations_per_s": prim["cg_throughput"],
+            **({"cg_iterations_reltol_1e-4": prim["cg_iterations"], "cg_throughput_dofs_x_iterations_per_s": prim["cg_throughput"]}
+               if "cg_iterations" in prim else {}),
             "chebyshev_start_vector": "deal.II's (i mod 11) - mean on the local numbering" if world == 1 or mode == "replicas" else
                                       "sharded run: numbering-independent hash of the geometric DoF key (mod 11) - mean; a 1-GPU run uses "
                                       "the index-based vector, so eigenvalue estimates (and borderline CG counts) can differ slightly",
@@ -441,7 +476,7 @@ def main():
     for k in ("stage_ms_finest", "stage_ms_total", "stage_ms_per_level"):
         if k in prim:
             out[k] = prim[k]
-    if not args.no_secondary and args.workload == "octant_p4" and (rank == 0 or mode == "sharded"):
+    if args.full and not args.no_secondary and args.workload == "octant_p4" and (rank == 0 or mode == "sharded"):
         # octant p=1: on one GPU (rank 0), or sharded like the primary workload when that ran sharded
         sharded2 = mode == "sharded"
         try:
@@ -473,7 +508,7 @@ def main():
                                       "unit": "DoF/s", "n_gpus": 1, "ms_per_step": tu * 1e3, "n_dofs": uni["n_dofs"],
                                       "NRefGlobal": args.nref_uniform_p1, "vcycle_frac_of_hbm_peak": uni["bytes_per_vcycle"] / tu / 1e9 / HBM_PEAK_GBS,
                                       "cg_iterations_reltol_1e-4": uni["cg_iterations"]}
-    if world == 1 and args.workload == "octant_p4" and not args.no_float:
+    if args.full and world == 1 and args.workload == "octant_p4" and not args.no_float:
         # MGNumberType "float" is the reference's default (ref:scripts/default.json:16, ref:multigrid_throughput.cc:2430-2433): the
         # same hierarchy with FP32 level vectors under the FP64 outer vectors (copy_to_mg / copy_from_mg cast); 4-byte words in
         # the byte model.  Its own line: a different dtype, never mixed into `value`.
@@ -486,7 +521,7 @@ def main():
                              "vcycle_frac_of_hbm_peak": flt["bytes_per_vcycle"] / tf / 1e9 / HBM_PEAK_GBS,
                              "fused_transfer_bricks": flt["fused_transfer_bricks"], "cg_iterations_reltol_1e-4": flt.get("cg_iterations"),
                              "note": "same kernels as FP64 (persistent 17^3 bricks, fused transfers) on float level vectors with float constants"}
-    if world == 1 and args.workload == "pmg_annulus" and nref != 8 and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "pmg_annulus" and nref != 8 and not args.no_secondary:
         # the size BASELINE.json configs[4] shards over 8 GPUs, on one GPU for reference
         sm = run_workload(m, ctx, geometry, 8, degree, mg_type, coarse, args.steps, args.warmup, lambda: None, sync, profile=False,
                           coarse_cycles=args.coarse_cycles)
@@ -494,8 +529,10 @@ def main():
         out["also_sharded_size"] = {"metric": out["metric"], "value": sm["n_dofs"] / ts, "unit": "DoF/s", "n_gpus": 1, "ms_per_step": ts * 1e3,
                                     "n_dofs": sm["n_dofs"], "NRefGlobal": 8, "coarse_solver": sm["coarse_solver"],
                                     "cg_iterations_reltol_1e-4": sm["cg_iterations"]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(m, "quadrant", args.cpu_nref, 4, nref if args.workload == "octant_p4" else -1)
+    if prim["outputs"] is not None:
+        write_outputs(args.dump_outputs, prim["outputs"])
     barrier()
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -4,9 +4,9 @@
 #   tools/profile_pmg.sh <tag>   -> gpurun_out/<tag>_bench_pmg_annulus*.json
 set -o pipefail
 tag=${1:-rXX}; O=$PWD/gpurun_out
-timeout -k 10 500 python3 bench.py --workload pmg_annulus --no-cpu-baseline > $O/${tag}_bench_pmg_annulus9_p4_amg.json 2> $O/${tag}_pmg9.err || exit 1
+timeout -k 10 500 python3 bench.py --full --workload pmg_annulus --no-cpu-baseline > $O/${tag}_bench_pmg_annulus9_p4_amg.json 2> $O/${tag}_pmg9.err || exit 1
 for c in amg gmg_vcycle cg_with_chebyshev cg_with_amg; do
-  timeout -k 10 200 python3 bench.py --workload pmg_annulus --nref 8 --coarse $c --no-cpu-baseline --no-secondary > $O/${tag}_bench_pmg_annulus8_p4_$c.json 2> $O/${tag}_pmg8_$c.err || exit 1
+  timeout -k 10 200 python3 bench.py --full --workload pmg_annulus --nref 8 --coarse $c --no-cpu-baseline --no-secondary > $O/${tag}_bench_pmg_annulus8_p4_$c.json 2> $O/${tag}_pmg8_$c.err || exit 1
 done
 python3 - <<PY
 import json, glob
