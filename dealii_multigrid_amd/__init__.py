@@ -246,6 +246,10 @@ class DoFs:
         _chk(_lib.mgamd_dofs_amg_setup_info(self._h, C.byref(n), rows, nnz, 32))
         return [(rows[l], nnz[l]) for l in range(n.value)]
 
+    def amg_hierarchy(self) -> "AmgHostHierarchy":
+        """the host setup of the AMG coarse solver on this level, level by level (development entry, mgamd_dev.h)"""
+        return AmgHostHierarchy(self)
+
     def cell_slots(self):
         grp, slot = np.zeros(self.info.n_cells, np.uint8), np.zeros(self.info.n_cells, np.uint32)
         _chk(_lib.mgamd_dofs_get_cell_slots(self._h, _ptr(grp), _ptr(slot)))
@@ -624,6 +628,57 @@ def solve_cg(A: Operator, preconditioner, x: Vector, b: Vector, reltol=1e-4, abs
     ph = preconditioner._h if preconditioner is not None else None
     _chk(_lib.mgamd_solve_cg(A._h, ph, x._h, b._h, C.c_double(reltol), C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
     return it.value, res.value
+
+
+class AmgHostHierarchy:
+    """Smoothed-aggregation hierarchy of the "amg" coarse solvers as the host setup builds it (amg.hpp; mgamd_dev.h), finest level
+    first: level(l) returns dict(A, P, agg, n_aggregates, lambda_max) with A, P as (row_ptr, col, val) CSR triples (P None on
+    the coarsest level) and agg the aggregate of each row (-1: decoupled; None on the coarsest level)."""
+
+    def __init__(self, dofs: DoFs):
+        self._h = C.c_void_p()
+        _chk(_lib.mgamd_debug_amg_host_create(dofs._h, C.byref(self._h)))
+        n = C.c_uint32()
+        _chk(_lib.mgamd_debug_amg_host_n_levels(self._h, C.byref(n)))
+        self.n_levels = n.value
+
+    def level(self, l: int):
+        rows, nnz_a, cols_p, nnz_p, na, lam = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_double()
+        _chk(_lib.mgamd_debug_amg_host_level_info(self._h, C.c_uint32(l), C.byref(rows), C.byref(nnz_a), C.byref(cols_p), C.byref(nnz_p),
+                                                 C.byref(na), C.byref(lam)))
+        n, coarsest = rows.value, l + 1 == self.n_levels
+        A = (np.zeros(n + 1, np.uint32), np.zeros(nnz_a.value, np.uint32), np.zeros(nnz_a.value))
+        P = (np.zeros(n + 1, np.uint32), np.zeros(nnz_p.value, np.uint32), np.zeros(nnz_p.value))
+        agg = np.zeros(n, np.int32)
+        _chk(_lib.mgamd_debug_amg_host_level_get(self._h, C.c_uint32(l), *[_ptr(a) for a in A], *([None] * 3 if coarsest else [_ptr(a) for a in P]),
+                                                None if coarsest else _ptr(agg)))
+        return dict(A=A, P=None if coarsest else P, n_cols_P=cols_p.value, agg=None if coarsest else agg, n_aggregates=na.value,
+                    lambda_max=lam.value)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mgamd_debug_amg_host_destroy(self._h)
+            self._h = None
+
+
+SPMV_PLAIN, SPMV_ADD, SPMV_RESID, SPMV_CHEB = 0, 1, 2, 3
+
+
+def debug_csr_spmv(ctx: "Context", number_type, mode, lanes, ptr, col, val, x, y, b=None, xold=None, xold_is_y=False, dinv=None, f1=0.0,
+                   f2=0.0):
+    """one launch of the AMG cycle's CSR kernel (K7) through the production launcher (mgamd_debug_csr_spmv): returns (y, lanes used);
+    y is the output's initial content (read by SPMV_ADD, and as xold when xold_is_y)"""
+    ptr, col = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(col, np.uint32)
+    val, x, y = (np.ascontiguousarray(a, np.float64) for a in (val, x, y))
+    y = y.copy()
+    opt = [None if a is None else np.ascontiguousarray(a, np.float64) for a in (b, xold, dinv)]
+    n_rows = len(ptr) - 1
+    assert len(y) == n_rows and len(col) == len(val) == ptr[-1]
+    used = C.c_int()
+    _chk(_lib.mgamd_debug_csr_spmv(ctx._h, number_type, mode, lanes, C.c_uint32(n_rows), C.c_uint32(len(x)), _ptr(ptr), _ptr(col), _ptr(val),
+                                   _ptr(x), _ptr(y), *[None if a is None else _ptr(a) for a in opt[:2]], 1 if xold_is_y else 0,
+                                   None if opt[2] is None else _ptr(opt[2]), C.c_double(f1), C.c_double(f2), C.byref(used)))
+    return y, used.value
 
 
 AMG_COARSE_SOLVERS = ("amg", "cg_with_amg", "amg_petsc")

@@ -236,10 +236,11 @@ namespace mgamd
   // ---------------------------------------------------------------- smoothed aggregation
   struct AmgLevelHost
   {
-    CSR                 A, P, R; // P: this level <- next coarser, R = P^T (empty on the coarsest level)
-    std::vector<double> dinv;    // 1 / a_ii
-    double              lambda_max = 1.0; // of D^-1 A (power iteration x 1.1)
-    uint32_t            n_aggregates = 0;
+    CSR                  A, P, R; // P: this level <- next coarser, R = P^T (empty on the coarsest level)
+    std::vector<double>  dinv;    // 1 / a_ii
+    double               lambda_max = 1.0; // of D^-1 A (power iteration x 1.1)
+    uint32_t             n_aggregates = 0;
+    std::vector<int32_t> agg; // aggregate of each row, -1: decoupled row (empty on the coarsest level)
   };
   struct AmgHierarchyHost
   {
@@ -418,6 +419,7 @@ namespace mgamd
         if (na == 0 || na >= n)
           break; // no coarsening possible
         lv.n_aggregates = na;
+        lv.agg          = agg;
         // tentative prolongator: piecewise constant, columns of unit length
         std::vector<uint32_t> size(na, 0);
         for (uint32_t i = 0; i < n; ++i)

@@ -793,3 +793,72 @@ mgamd_ctx_kernel_profile_bytes_moved(mgamd_ctx *ctx, double *bytes_moved)
 }
 
 } // extern "C"
+
+namespace
+{
+  template <typename T>
+  void
+  debug_csr_spmv(Ctx &c, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr, const uint32_t *col, const double *val,
+                 const double *x, double *y, const double *b, const double *xold, bool xold_is_y, const double *dinv, double f1, double f2)
+  {
+    const size_t nnz = ptr[n_rows];
+    auto         dev = [&](DBuf<T> &buf, const double *h, size_t n) -> T * {
+      if (!h)
+        return nullptr;
+      std::vector<T> v(std::max<size_t>(n, 1), T(0));
+      std::copy(h, h + n, v.begin());
+      buf.upload(v);
+      return buf.p;
+    };
+    DBuf<uint32_t> dptr, dcol;
+    dptr.upload(std::vector<uint32_t>(ptr, ptr + n_rows + 1));
+    dcol.upload(std::vector<uint32_t>(std::max<size_t>(nnz, 1), 0));
+    if (nnz)
+      HIP_CHECK(hipMemcpy(dcol.p, col, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    DBuf<T> dval, dx, dy, db, dxold, ddinv;
+    dev(dval, val, nnz);
+    dev(dx, x, n_cols);
+    T *yp = dev(dy, y, n_rows);
+    launch_csr_spmv<T>(c.stream, mode, lanes, n_rows, dptr.p, dcol.p, dval.p, dx.p, yp, dev(db, b, n_rows),
+                       xold_is_y ? yp : dev(dxold, xold, n_rows), dev(ddinv, dinv, n_rows), f1, f2);
+    std::vector<T> out(std::max<size_t>(n_rows, 1));
+    HIP_CHECK(hipMemcpyAsync(out.data(), yp, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, c.stream));
+    HIP_CHECK(hipStreamSynchronize(c.stream));
+    std::copy(out.begin(), out.begin() + n_rows, y);
+  }
+} // namespace
+
+extern "C" {
+
+int
+mgamd_debug_csr_spmv(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr,
+                     const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold, int xold_is_y,
+                     const double *dinv, double f1, double f2, int *lanes_used)
+{
+  MGAMD_TRY
+  REQUIRE(ctx && ptr && x && y);
+  REQUIRE(number_type == MGAMD_F64 || number_type == MGAMD_F32);
+  REQUIRE(mode >= 0 && mode <= 3);
+  REQUIRE(lanes == 0 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32);
+  // every index the kernel follows is checked here, on the host
+  REQUIRE(ptr[0] == 0);
+  for (uint32_t i = 0; i < n_rows; ++i)
+    REQUIRE(ptr[i + 1] >= ptr[i]);
+  REQUIRE(ptr[n_rows] == 0 || (col && val));
+  for (uint32_t k = 0; k < ptr[n_rows]; ++k)
+    REQUIRE(col[k] < n_cols);
+  REQUIRE(mode != 2 || b);
+  REQUIRE(mode != 3 || (b && dinv && n_cols == n_rows));
+  REQUIRE(!(xold_is_y && xold));
+  if (!lanes)
+    lanes = csr_spmv_lanes(n_rows, ptr[n_rows]);
+  if (lanes_used)
+    *lanes_used = lanes;
+  if (number_type == MGAMD_F64)
+    debug_csr_spmv<double>(*ctx->ctx, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y != 0, dinv, f1, f2);
+  else
+    debug_csr_spmv<float>(*ctx->ctx, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y != 0, dinv, f1, f2);
+  MGAMD_CATCH
+}
+
+} // extern "C"

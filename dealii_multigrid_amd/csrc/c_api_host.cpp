@@ -8,6 +8,11 @@ namespace mgamd
   thread_local std::string g_last_error;
 }
 
+struct mgamd_amg_host
+{
+  AmgHierarchyHost H;
+};
+
 extern "C" {
 
 const char *
@@ -91,6 +96,87 @@ mgamd_dofs_amg_setup_info(const mgamd_dofs *d, uint32_t *n_levels, uint32_t *row
       if (nnz)
         nnz[l] = H.levels[l].A.nnz();
     }
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_host_create(const mgamd_dofs *d, mgamd_amg_host **out)
+{
+  MGAMD_TRY
+  if (!d || !out)
+    throw std::invalid_argument("null argument");
+  if (d->halo)
+    throw std::invalid_argument("mgamd_debug_amg_host_create: the level is distributed");
+  *out = new mgamd_amg_host{build_smoothed_aggregation(assemble_level_matrix(*d->tables))};
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_host_destroy(mgamd_amg_host *h)
+{
+  delete h;
+  return MGAMD_OK;
+}
+
+int
+mgamd_debug_amg_host_n_levels(const mgamd_amg_host *h, uint32_t *n_levels)
+{
+  MGAMD_TRY
+  if (!h || !n_levels)
+    throw std::invalid_argument("null argument");
+  *n_levels = (uint32_t)h->H.levels.size();
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_host_level_info(const mgamd_amg_host *h, uint32_t level, uint32_t *n_rows, uint64_t *nnz_A, uint32_t *n_cols_P,
+                                uint64_t *nnz_P, uint32_t *n_aggregates, double *lambda_max)
+{
+  MGAMD_TRY
+  if (!h)
+    throw std::invalid_argument("null argument");
+  if (level >= h->H.levels.size())
+    throw std::invalid_argument("mgamd_debug_amg_host_level_info: level out of range");
+  const AmgLevelHost &L = h->H.levels[level];
+  if (n_rows)
+    *n_rows = L.A.n_rows;
+  if (nnz_A)
+    *nnz_A = L.A.nnz();
+  if (n_cols_P)
+    *n_cols_P = L.P.n_cols;
+  if (nnz_P)
+    *nnz_P = L.P.nnz();
+  if (n_aggregates)
+    *n_aggregates = L.n_aggregates;
+  if (lambda_max)
+    *lambda_max = L.lambda_max;
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_host_level_get(const mgamd_amg_host *h, uint32_t level, uint32_t *A_ptr, uint32_t *A_col, double *A_val, uint32_t *P_ptr,
+                               uint32_t *P_col, double *P_val, int32_t *agg)
+{
+  MGAMD_TRY
+  if (!h)
+    throw std::invalid_argument("null argument");
+  if (level >= h->H.levels.size())
+    throw std::invalid_argument("mgamd_debug_amg_host_level_get: level out of range");
+  const AmgLevelHost &L = h->H.levels[level];
+  if (A_ptr)
+    std::copy(L.A.ptr.begin(), L.A.ptr.end(), A_ptr);
+  if (A_col)
+    std::copy(L.A.col.begin(), L.A.col.end(), A_col);
+  if (A_val)
+    std::copy(L.A.val.begin(), L.A.val.end(), A_val);
+  if (P_ptr)
+    std::copy(L.P.ptr.begin(), L.P.ptr.end(), P_ptr);
+  if (P_col)
+    std::copy(L.P.col.begin(), L.P.col.end(), P_col);
+  if (P_val)
+    std::copy(L.P.val.begin(), L.P.val.end(), P_val);
+  if (agg)
+    std::copy(L.agg.begin(), L.agg.end(), agg);
   MGAMD_CATCH
 }
 

@@ -1058,6 +1058,74 @@ namespace mgamd
   }
 
   // ------------------------------------------------------------------------------------------
+  // K7 launcher (kernels_amg.hpp): the one path of the AMG cycle and of mgamd_debug_csr_spmv
+  // ------------------------------------------------------------------------------------------
+  int
+  csr_spmv_lanes(uint32_t n_rows, size_t nnz)
+  {
+    const double avg = n_rows ? (double)nnz / n_rows : 0.0;
+    return avg <= 6 ? 4 : (avg <= 24 ? 8 : (avg <= 64 ? 16 : 32));
+  }
+
+  template <typename T>
+  void
+  launch_csr_spmv(hipStream_t stream, int mode, int lanes, uint32_t n_rows, const uint32_t *ptr, const uint32_t *col, const T *val, const T *x,
+                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
+  {
+    if (!n_rows)
+      return;
+    auto launch = [&](auto mode_tag, auto lanes_tag) {
+      constexpr int MODE  = decltype(mode_tag)::value;
+      constexpr int LANES = decltype(lanes_tag)::value;
+      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
+      hipLaunchKernelGGL((csr_spmv_kernel<T, MODE, LANES>), grid, 256, 0, stream, n_rows, ptr, col, val, x, y, b, xold, dinv, T(f1), T(f2));
+    };
+    auto with_lanes = [&](auto mode_tag) {
+      switch (lanes)
+        {
+          case 4:
+            launch(mode_tag, std::integral_constant<int, 4>());
+            break;
+          case 8:
+            launch(mode_tag, std::integral_constant<int, 8>());
+            break;
+          case 16:
+            launch(mode_tag, std::integral_constant<int, 16>());
+            break;
+          case 32:
+            launch(mode_tag, std::integral_constant<int, 32>());
+            break;
+          default:
+            throw std::invalid_argument("csr_spmv: lanes must be 4, 8, 16 or 32");
+        }
+    };
+    switch (mode)
+      {
+        case SPMV_PLAIN:
+          with_lanes(std::integral_constant<int, SPMV_PLAIN>());
+          break;
+        case SPMV_ADD:
+          with_lanes(std::integral_constant<int, SPMV_ADD>());
+          break;
+        case SPMV_RESID:
+          with_lanes(std::integral_constant<int, SPMV_RESID>());
+          break;
+        case SPMV_CHEB:
+          with_lanes(std::integral_constant<int, SPMV_CHEB>());
+          break;
+        default:
+          throw std::invalid_argument("csr_spmv: unknown mode");
+      }
+    HIP_CHECK(hipGetLastError());
+  }
+  template void
+  launch_csr_spmv<double>(hipStream_t, int, int, uint32_t, const uint32_t *, const uint32_t *, const double *, const double *, double *,
+                          const double *, const double *, const double *, double, double);
+  template void
+  launch_csr_spmv<float>(hipStream_t, int, int, uint32_t, const uint32_t *, const uint32_t *, const float *, const float *, float *,
+                         const float *, const float *, const float *, double, double);
+
+  // ------------------------------------------------------------------------------------------
   // Algebraic multigrid coarse solver on the device (host setup: amg.hpp).  The reference's "amg" / "cg_with_amg" coarse solvers
   // (ref:multigrid_throughput.cc:945-1016) apply Trilinos ML to Operator::get_trilinos_system_matrix; this is an own
   // smoothed-aggregation V-cycle on the same matrix: CSR products fused with the Chebyshev update (kernels.hpp K7).
@@ -1081,8 +1149,7 @@ namespace mgamd
         std::vector<T> v(std::max<size_t>(A.val.size(), 1), T(0));
         std::copy(A.val.begin(), A.val.end(), v.begin());
         val.upload(v);
-        const double avg = A.n_rows ? (double)A.nnz() / A.n_rows : 0.0;
-        lanes            = avg <= 6 ? 4 : (avg <= 24 ? 8 : (avg <= 64 ? 16 : 32));
+        lanes = csr_spmv_lanes(A.n_rows, A.nnz());
       }
     };
     struct Lvl
@@ -1139,29 +1206,7 @@ namespace mgamd
     void
     spmv(const Mat &A, const T *x, T *y, const T *b = nullptr, const T *xold = nullptr, const T *dinv = nullptr, double f1 = 0, double f2 = 0)
     {
-      if (!A.n_rows)
-        return;
-      auto launch = [&](auto lanes_tag) {
-        constexpr int LANES = decltype(lanes_tag)::value;
-        const int     grid  = (int)std::min<size_t>(((size_t)A.n_rows * LANES + 255) / 256, 4096);
-        hipLaunchKernelGGL((csr_spmv_kernel<T, MODE, LANES>), grid, 256, 0, ctx->stream, A.n_rows, A.ptr.p, A.col.p, A.val.p, x, y, b, xold, dinv,
-                           T(f1), T(f2));
-      };
-      switch (A.lanes)
-        {
-          case 4:
-            launch(std::integral_constant<int, 4>());
-            break;
-          case 8:
-            launch(std::integral_constant<int, 8>());
-            break;
-          case 16:
-            launch(std::integral_constant<int, 16>());
-            break;
-          default:
-            launch(std::integral_constant<int, 32>());
-        }
-      HIP_CHECK(hipGetLastError());
+      launch_csr_spmv<T>(ctx->stream, MODE, A.lanes, A.n_rows, A.ptr.p, A.col.p, A.val.p, x, y, b, xold, dinv, f1, f2);
     }
     // Chebyshev of degree `degree` in D^-1 A, zero start (deal.II / ML recurrences): result in x (t: scratch)
     void
@@ -1432,6 +1477,14 @@ namespace mgamd
               coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
               amg         = std::make_unique<AmgDevice<T>>(ctx, *ops[0]->tables);
             }
+        }
+      else if (coarse == "gmg_vcycle")
+        {
+          // no nested multigrid to hand the coarse problem to: a small level is solved exactly, a large one is an error
+          if (ops[0]->n_dofs() > 4096)
+            throw std::invalid_argument("multigrid: CoarseGridSolverType 'gmg_vcycle' on a level of more than 4096 DoFs needs a nested "
+                                        "multigrid");
+          coarse_type = "direct";
         }
       coarse_used = coarse_type;
       if (coarse_type == "gmg_vcycle" || coarse_type == "amg")

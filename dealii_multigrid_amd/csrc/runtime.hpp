@@ -321,6 +321,14 @@ namespace mgamd
   void
   solve_cg(LevelOperatorBase &A, MultigridBase *M, mgamd_vec &x, const mgamd_vec &b, double reltol, double abstol, unsigned maxiter,
            unsigned &n_iterations, double &residual);
+  // K7 (kernels_amg.hpp) as the AMG cycle launches it: lanes per row from the average row length, a grid of at most 4096 blocks
+  // (grid-stride above); mode: SpmvMode; lanes 0 = csr_spmv_lanes
+  int
+  csr_spmv_lanes(uint32_t n_rows, size_t nnz);
+  template <typename T>
+  void
+  launch_csr_spmv(hipStream_t stream, int mode, int lanes, uint32_t n_rows, const uint32_t *ptr, const uint32_t *col, const T *val, const T *x,
+                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2);
 } // namespace mgamd
 
 struct mgamd_level_op

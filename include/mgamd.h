@@ -287,7 +287,8 @@ int mgamd_transfer2_n_fused_bricks(const mgamd_transfer2 *t, uint64_t *n);
  *                        counts cannot be parity-checked against ML.
  * mgamd_mg_create_nested additionally takes n_cycles (CoarseSolverNCycles) and, optionally, `coarse_mg`: a geometric multigrid
  * whose finest level IS levels[0]; if given, it takes the AMG's place ("gmg_vcycle": x = V(b), x += V(b - A x) ...; the only choice
- * on a sharded coarse level).  mgamd_mg_coarse_solver_used returns what runs: "direct" | "cg" | "cg_with_chebyshev" | "amg" |
+ * on a sharded coarse level); "gmg_vcycle" without `coarse_mg` is "direct" on a level of <= 4096 DoFs and MGAMD_ERR_INVALID on a
+ * larger one.  mgamd_mg_coarse_solver_used returns what runs: "direct" | "cg" | "cg_with_chebyshev" | "amg" |
  * "cg_with_amg" | "gmg_vcycle". */
 int mgamd_mg_create(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
                     mgamd_cheb *const *smoothers, const char *coarse_solver, mgamd_mg **out);

@@ -25,6 +25,30 @@ int mgamd_ctx_kernel_profile_read(mgamd_ctx *ctx, double *total_ms, uint64_t *n_
  * p = 1 and the persistent 17-point lattice kernels, one word less than SURVEY 8(d)'s figure in `algorithmic_bytes`) */
 int mgamd_ctx_kernel_profile_bytes_moved(mgamd_ctx *ctx, double *bytes_moved);
 
+/* ---- the algebraic multigrid of the "amg" coarse solvers, for tests against an independent restatement ----
+ * host hierarchy (amg.hpp) of the smoothed aggregation built on the level's assembled matrix (mgamd_dofs_matrix); level 0 finest */
+typedef struct mgamd_amg_host mgamd_amg_host;
+int mgamd_debug_amg_host_create(const mgamd_dofs *d, mgamd_amg_host **out);
+int mgamd_debug_amg_host_destroy(mgamd_amg_host *h);
+int mgamd_debug_amg_host_n_levels(const mgamd_amg_host *h, uint32_t *n_levels);
+/* sizes of level l: rows of A, non-zeros of A, columns and non-zeros of P (0 on the coarsest level), aggregates, lambda_max (the
+ * upper end of the Chebyshev interval of that level's smoother) */
+int mgamd_debug_amg_host_level_info(const mgamd_amg_host *h, uint32_t level, uint32_t *n_rows, uint64_t *nnz_A, uint32_t *n_cols_P,
+                                    uint64_t *nnz_P, uint32_t *n_aggregates, double *lambda_max);
+/* the arrays of level l (any pointer may be null): A and P as CSR with sorted columns, the aggregate of each row (-1: decoupled row;
+ * n_rows entries, none on the coarsest level) */
+int mgamd_debug_amg_host_level_get(const mgamd_amg_host *h, uint32_t level, uint32_t *A_ptr, uint32_t *A_col, double *A_val,
+                                   uint32_t *P_ptr, uint32_t *P_col, double *P_val, int32_t *agg);
+
+/* one launch of the AMG cycle's CSR kernel (K7, kernels_amg.hpp) through the production launcher on host data converted to
+ * number_type: mode 0 y = A x, 1 y += A x, 2 y = b - A x, 3 y = x + f1 (x - xold) + f2 dinv (b - A x) (n_cols == n_rows).
+ * lanes 4/8/16/32, or 0 for the production choice from the average row length (returned in *lanes_used).  y (n_rows) is uploaded
+ * before and downloaded after the launch; b, xold, dinv may be null where the mode does not read them; xold_is_y: xold is the
+ * device buffer of y itself (how the Chebyshev recurrence calls the kernel) */
+int mgamd_debug_csr_spmv(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr,
+                         const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold,
+                         int xold_is_y, const double *dinv, double f1, double f2, int *lanes_used);
+
 #ifdef __cplusplus
 }
 #endif
