@@ -39,6 +39,7 @@ namespace mgamd
     static_assert(!WAVE || (B == 1 && !CONSTR), "wave-scoped slots: single cells");
     using G  = Geo<P, B, WAVE ? 64 : 256>;
     using IM = InteriorMap<P, B, WAVE ? 64 : 256>;
+    static_assert(G::ROUNDS == 1, "one line per thread: the 17^3 lattices take the persistent kernel");
     T *bufA = reinterpret_cast<T *>(smem_raw);
     T *bufB = bufA + G::SPW * G::N3;
 
@@ -62,9 +63,9 @@ namespace mgamd
     if constexpr (brick_may_be_constrained(B, CONSTR))
       if (args.g.fmask != nullptr && tid < nslots)
         fm_early = args.g.fmask[slot0 + tid];
-    const double h_mine = G::ROUNDS == 1 ? args.g.h[slot0 + (act ? sl : 0)] : 0.0;
-    uint32_t     fm_line = 0; // constraint mask of this thread's line (one line per thread when ROUNDS == 1)
-    if constexpr (brick_may_be_constrained(B, CONSTR) && G::ROUNDS == 1)
+    const double h_mine  = args.g.h[slot0 + (act ? sl : 0)];
+    uint32_t     fm_line = 0; // constraint mask of this thread's line
+    if constexpr (brick_may_be_constrained(B, CONSTR))
       if (args.g.fmask != nullptr && act)
         fm_line = args.g.fmask[slot0 + sl];
 
@@ -265,24 +266,19 @@ namespace mgamd
         // constrained bricks: whole-face / whole-edge hanging nodes (uniform branch: one mask per slot)
         any_hanging = __syncthreads_or((int)(fm_early != 0)) != 0;
         if (any_hanging)
-          brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, false, G::ROUNDS == 1 ? &fm_line : nullptr);
+          brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, false, &fm_line);
       }
     MGAMD_STAMP(5)
 
     if (!MGAMD_ABLATED(1))
-      {
-        if constexpr (G::ROUNDS == 1)
-          lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true);
-        else
-          lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0);
-      }
+      lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true);
     MGAMD_STAMP(6)
 
     if (B == 1 && any_hanging)
       hanging_passes<T, P, WAVE>(bufA, args.m, sl, u, v, act, mask, true);
     if constexpr (brick_may_be_constrained(B, CONSTR))
       if (any_hanging)
-        brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, true, G::ROUNDS == 1 ? &fm_line : nullptr);
+        brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, true, &fm_line);
     MGAMD_STAMP(2)
 
     // ---- interior DoFs are complete: fused epilogue, contiguous stores -----------------------------------
@@ -364,14 +360,11 @@ namespace mgamd
     constexpr int  MODE   = base_mode(MODE_);
     constexpr bool FUSE_R = MODE_ == MODE_RESIDUAL_RESTRICT, FUSE_P = MODE_ == MODE_CHEB_PROLONGATE, FUSE = FUSE_R || FUSE_P;
     static_assert(!FUSE || (!CONSTR && B >= 2 && G::ABLOCK == 256), "fused transfers: plain bricks, 256 threads");
+    static_assert(!CONSTR || P == 1, "constrained bricks larger than a family: p = 1 only (LevelTables::build)");
     constexpr int BC = B >= 2 ? B / 2 : 1, NC = P * BC + 1, NC3 = NC * NC * NC; // coarse lattice under the brick
     T *bufA = reinterpret_cast<T *>(smem_raw);
     T *bufB = bufA + G::N3;
     T *dtab = bufB + G::N3; // [P^3] s = d/h, [P^3] 1/s
-    T *Etab = dtab + 2 * P * P * P + 1; // constrained bricks: the embedding E = [I0; I1] for brick_face_passes
-    // hanging-node passes node by node over the hanging faces (brick_face_passes) instead of line by line
-    // (P >= 2: at p = 1 the line form is cheap -- 3 x 2 weights -- and faster: octant p = 1 L = 9 1.37 ms against 1.58 ms with the node form)
-    constexpr bool FACE_PASSES = CONSTR && P >= 2 && B > 2 && face_table_words<P, B>() > 0 && G::N * (G::N - 2) <= G::ABLOCK;
 
     constexpr int BLOCK = G::ABLOCK;
     constexpr int ITER  = (G::N_INT + BLOCK - 1) / BLOCK;
@@ -385,12 +378,6 @@ namespace mgamd
     if (w >= n)
       return;
 
-    if constexpr (FACE_PASSES)
-      for (int t = tid; t < (2 * P + 1) * (P + 1); t += BLOCK)
-        {
-          const int a = t / (P + 1), b = t % (P + 1);
-          Etab[t]     = a <= P ? args.m.I0[a * (P + 1) + b] : args.m.I1[(a - P) * (P + 1) + b];
-        }
     if (is_cheb(MODE))
       {
         for (int t = tid; t < P3; t += BLOCK)
@@ -671,23 +658,13 @@ namespace mgamd
             // constrained bricks: whole-face / whole-edge hanging nodes (uniform branch: one mask per slot)
             any_hanging = fmcur != 0;
             if (any_hanging)
-              {
-                if constexpr (FACE_PASSES)
-                  brick_face_passes<T, P, B, BLOCK>(bufA, Etab, (uint32_t)__builtin_amdgcn_readfirstlane((int)fmcur), tid, false);
-                else
-                  brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, false, &fmcur);
-              }
+              brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, false, &fmcur);
           }
         // cell prefetch in the streamed sweeps (-4 % on the 2-4-word passes); the 5-word mode has no registers left for it
         lattice_sweeps<T, P, B, BLOCK, NoHook, true, (MODE != MODE_CHEB || sizeof(T) == 4)>(bufA, bufB, args.m, tid, 1, &hcur);
         if constexpr (brick_may_be_constrained(B, CONSTR))
           if (any_hanging)
-            {
-              if constexpr (FACE_PASSES)
-                brick_face_passes<T, P, B, BLOCK>(bufA, Etab, (uint32_t)__builtin_amdgcn_readfirstlane((int)fmcur), tid, true);
-              else
-                brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, true, &fmcur);
-            }
+            brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, true, &fmcur);
         MGAMD_STAMP(2)
 
         // ---- values of the next slot: requested now, consumed at the top of the next iteration ------------------
@@ -825,7 +802,7 @@ namespace mgamd
 
   template <typename T, int P, int B, int MODE, bool CONSTR = false>
   __global__ void
-  __launch_bounds__((Geo<P, B>::ABLOCK), (Geo<P, B>::ROUNDS > 1 ? 2 : (B == 1 ? 6 : (B == 2 ? 4 : 1)))) lattice_apply_kernel(const ApplyArgs<T, P> args)
+  __launch_bounds__((Geo<P, B>::ABLOCK), (B == 1 ? 6 : (B == 2 ? 4 : 1))) lattice_apply_kernel(const ApplyArgs<T, P> args)
   {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     lattice_apply_body<T, P, B, MODE, CONSTR>(args, blockIdx.x, gridDim.x, smem_raw);
@@ -889,7 +866,7 @@ namespace mgamd
   };
   template <typename T, int P, int B, int MODE>
   __global__ void
-  __launch_bounds__((Geo<P, B>::ABLOCK), (Geo<P, B>::ROUNDS > 1 ? 2 : 1)) lattice_apply_pair_kernel(const BrickPairArgs<T, P> args)
+  __launch_bounds__((Geo<P, B>::ABLOCK), 1) lattice_apply_pair_kernel(const BrickPairArgs<T, P> args)
   {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     if (blockIdx.x < args.n_wg_plain)

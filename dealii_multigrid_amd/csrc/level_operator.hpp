@@ -60,21 +60,6 @@ namespace mgamd
     done[{ctx->device, kern}] = lds;
   }
 
-  // persistent workgroups for the one-slot-per-workgroup lattices (kernels.hpp, lattice_apply_persistent_body); (until the
-  // constants of the float kernels became floats, Mats<P, T>, float at p = 4 spilled and was excluded)
-  template <typename T, int P>
-  inline bool
-  use_persistent()
-  {
-    static const bool on = getenv("MGAMD_NO_PERSISTENT") == nullptr;
-    return on;
-  }
-  inline bool
-  use_cell_waves()
-  {
-    static const bool on = getenv("MGAMD_NO_CELL_WAVES") == nullptr;
-    return on;
-  }
   // two 4-wave workgroups with a 17^3 lattice pair each fit one CU; a multiple of 8 keeps a workgroup in its XCD's range
   inline int
   resident_workgroups(const Ctx *ctx, int per_cu = 2)
@@ -82,6 +67,7 @@ namespace mgamd
     return std::max(8, per_cu * ctx->n_cu / 8 * 8);
   }
 
+  // one slot group: its diagonal, or one operator application with the kernel of its lattice
   template <typename T, int P, int B, int MODE, bool CONSTR = false>
   inline void
   launch_lattice(Ctx *ctx, hipStream_t st, const ApplyArgs<T, P> &a, bool diag)
@@ -97,27 +83,33 @@ namespace mgamd
         ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
         hipLaunchKernelGGL(kern, grid, G::BLOCK, lds, st, a);
       }
+    else if constexpr (B == 1 && P >= 2)
+      { // single cells wave-scoped (kernels.hpp cell_waves_kernel)
+        using GW = Geo<P, 1, 64>;
+        const uint32_t n_w    = (uint32_t)((a.g.n_slots + GW::SPW - 1) / GW::SPW);
+        const uint32_t grid_w = (n_w + CELL_WAVES - 1) / CELL_WAVES;
+        const size_t   lds    = CELL_WAVES * cell_wave_lds<T, P>();
+        hipLaunchKernelGGL((cell_waves_kernel<T, P, MODE>), grid_w, 64 * CELL_WAVES, lds, st, a);
+      }
     else
       {
-        const size_t lds  = (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW + face_table_words<P, B>()) * sizeof(T);
+        const size_t lds  = (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T);
         if constexpr (G::SPW == 1 && G::N_INT > 0 && G::ROUNDS > 1)
           {
             // one-slot-per-workgroup lattices (17^3): persistent workgroups with a software pipeline over their slots
             // (kernels.hpp, lattice_apply_persistent_body).  Two workgroups fit a CU (LDS); the grid is a multiple of 8 so
-            // that a workgroup stays inside the Morton range of its XCD.  MGAMD_NO_PERSISTENT=1: one workgroup per slot.
-            if (use_persistent<T, P>())
-              {
-                const int resident = resident_workgroups(ctx, persistent_wgs_per_cu<T, P>());
-                auto      kern     = lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR>;
-                ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-                hipLaunchKernelGGL(kern, std::min(grid, resident), G::ABLOCK, lds, st, a);
-                HIP_CHECK(hipGetLastError());
-                return;
-              }
+            // that a workgroup stays inside the Morton range of its XCD.
+            const int resident = resident_workgroups(ctx, persistent_wgs_per_cu<T, P>());
+            auto      kern     = lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR>;
+            ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
+            hipLaunchKernelGGL(kern, std::min(grid, resident), G::ABLOCK, lds, st, a);
           }
-        auto         kern = lattice_apply_kernel<T, P, B, MODE, CONSTR>;
-        ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-        hipLaunchKernelGGL(kern, grid, G::ABLOCK, lds, st, a);
+        else
+          {
+            auto kern = lattice_apply_kernel<T, P, B, MODE, CONSTR>;
+            ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
+            hipLaunchKernelGGL(kern, grid, G::ABLOCK, lds, st, a);
+          }
       }
     HIP_CHECK(hipGetLastError());
   }
@@ -129,33 +121,20 @@ namespace mgamd
   {
     if (constrained)
       {
-        if constexpr (P * 4 + 1 <= 17)
-          if (B == 4)
-            return launch_lattice<T, P, 4, MODE, true>(ctx, st, a, diag);
-        if constexpr (P * 8 + 1 <= 17)
-          if (B == 8)
-            return launch_lattice<T, P, 8, MODE, true>(ctx, st, a, diag);
-        if constexpr (P * 16 + 1 <= 17)
-          if (B == 16)
-            return launch_lattice<T, P, 16, MODE, true>(ctx, st, a, diag);
+        if constexpr (P == 1)
+          {
+            if (B == 4)
+              return launch_lattice<T, P, 4, MODE, true>(ctx, st, a, diag);
+            if (B == 8)
+              return launch_lattice<T, P, 8, MODE, true>(ctx, st, a, diag);
+            if (B == 16)
+              return launch_lattice<T, P, 16, MODE, true>(ctx, st, a, diag);
+          }
         throw std::runtime_error("constrained bricks of this size/degree are not instantiated");
       }
     switch (B)
       {
         case 1:
-          if constexpr (P >= 2)
-            if (!diag && use_cell_waves())
-              { // single cells wave-scoped (kernels.hpp cell_waves_kernel); MGAMD_NO_CELL_WAVES=1: the workgroup-scoped kernel
-                using GW = Geo<P, 1, 64>;
-                if (a.g.n_slots == 0)
-                  return;
-                const uint32_t n_w  = (uint32_t)((a.g.n_slots + GW::SPW - 1) / GW::SPW);
-                const uint32_t grid = (n_w + CELL_WAVES - 1) / CELL_WAVES;
-                const size_t   lds  = CELL_WAVES * cell_wave_lds<T, P>();
-                hipLaunchKernelGGL((cell_waves_kernel<T, P, MODE>), grid, 64 * CELL_WAVES, lds, st, a);
-                HIP_CHECK(hipGetLastError());
-                return;
-              }
           launch_lattice<T, P, 1, MODE>(ctx, st, a, diag);
           return;
         case 2:
@@ -279,11 +258,10 @@ namespace mgamd
     T *coarse = nullptr, *scratch = nullptr, *x_inout = nullptr;
   };
   // degrees whose 17-point lattice kernel carries the fused modes (p = 3 has 13-point lattices, one workgroup per brick)
-  template <typename T>
   inline bool
   fused_transfer_supported(int p)
   {
-    return (p == 1 && use_persistent<T, 1>()) || (p == 2 && use_persistent<T, 2>()) || (p == 4 && use_persistent<T, 4>());
+    return p == 1 || p == 2 || p == 4;
   }
 
   template <typename T>
@@ -300,7 +278,6 @@ namespace mgamd
     uint32_t                                  ablate = 0; // debug: MGAMD_ABLATE
     DBuf<unsigned long long>                  stamps;     // debug: MGAMD_STAMPS=<mode>, 8 stamps per workgroup of the largest group
     int                                       stamp_mode = -1;
-    bool                                      merge_small = true; // MGAMD_NO_MERGE_SMALL=1: separate launches (development A/B)
     bool                                      halo_overlap = true; // MGAMD_NO_HALO_OVERLAP=1: exchange after all slots, on the main queue
 
     // sharded runs: device image of the halo plan
@@ -352,7 +329,7 @@ namespace mgamd
               d->shell_pos.upload(g.shell_pos);
               if (std::any_of(g.fmask.begin(), g.fmask.end(), [](uint32_t m) { return m != 0; }))
                 d->fmask.upload(g.fmask);
-              if (p == 1 && g.B == 1 && !getenv("MGAMD_NO_CELL_CLUSTERS") && !tables->ls_level)
+              if (p == 1 && g.B == 1 && !tables->ls_level)
                 d->build_clusters(g); // (the cluster tables bake in which nodes are constrained: not on local-smoothing levels)
             }
           const size_t work = d->n_slots * (size_t)g.N * g.N * g.N;
@@ -367,7 +344,6 @@ namespace mgamd
         ablate = (uint32_t)atoi(e);
       if (const char *e = getenv("MGAMD_STAMP_B")) // debug: stamp the group of this brick size instead of the largest one
         prof_B = atoi(e);
-      merge_small = getenv("MGAMD_NO_MERGE_SMALL") == nullptr;
       halo_overlap = getenv("MGAMD_NO_HALO_OVERLAP") == nullptr;
       if (const char *e = getenv("MGAMD_STAMPS"))
         {
@@ -523,33 +499,30 @@ namespace mgamd
       pa.g_constrained = g_constrained->view();
       pa.n_wg_plain    = (uint32_t)((a.g.n_slots + G::SPW - 1) / G::SPW);
       const uint32_t n_wg_c = (uint32_t)((g_constrained->n_slots + G::SPW - 1) / G::SPW);
-      const size_t   lds    = (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW + face_table_words<P, B>()) * sizeof(T);
+      const size_t   lds    = (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T);
       if constexpr (G::SPW == 1 && G::N_INT > 0 && G::ROUNDS > 1)
-        if (use_persistent<T, P>())
-          {
-            const int resident = resident_workgroups(ctx);
-            uint32_t  np = pa.n_wg_plain, nc = n_wg_c;
-            if ((int)(np + nc) > resident)
-              { // every workgroup walks both kinds (kernels.hpp)
-                np = 0;
-                nc = (uint32_t)resident;
-              }
-            pa.n_wg_plain = np;
-            auto kern     = lattice_apply_persistent_pair_kernel<T, P, B, MODE>;
-            ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-            hipLaunchKernelGGL(kern, np + nc, G::ABLOCK, lds, st, pa);
-            HIP_CHECK(hipGetLastError());
-            return;
-          }
-      if constexpr (MODE != base_mode(MODE))
+        {
+          const int resident = resident_workgroups(ctx);
+          uint32_t  np = pa.n_wg_plain, nc = n_wg_c;
+          if ((int)(np + nc) > resident)
+            { // every workgroup walks both kinds (kernels.hpp)
+              np = 0;
+              nc = (uint32_t)resident;
+            }
+          pa.n_wg_plain = np;
+          auto kern     = lattice_apply_persistent_pair_kernel<T, P, B, MODE>;
+          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
+          hipLaunchKernelGGL(kern, np + nc, G::ABLOCK, lds, st, pa);
+        }
+      else if constexpr (MODE != base_mode(MODE))
         throw std::runtime_error("fused transfers need the persistent brick kernel");
       else
         {
           auto kern = lattice_apply_pair_kernel<T, P, B, MODE>;
           ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
           hipLaunchKernelGGL(kern, pa.n_wg_plain + n_wg_c, G::ABLOCK, lds, st, pa);
-          HIP_CHECK(hipGetLastError());
         }
+      HIP_CHECK(hipGetLastError());
     }
 
     // the 17-point lattice group that carries fused transfers (slots [begin, begin + a.g.n_slots) of it)
@@ -562,7 +535,7 @@ namespace mgamd
           constexpr int B = 16 / P;
           using G         = Geo<P, B>;
           constexpr int NC = P * B / 2 + 1, NC3 = NC * NC * NC;
-          if (f.nc3 != (uint32_t)NC3 || f.E.size() != (size_t)(2 * P + 1) * (P + 1) || !use_persistent<T, P>())
+          if (f.nc3 != (uint32_t)NC3 || f.E.size() != (size_t)(2 * P + 1) * (P + 1))
             throw std::runtime_error("fused transfer: tables do not match the brick kernel");
           a.fused.flags      = f.flags + begin * G::ABLOCK;
           a.fused.coarse_idx = f.coarse_idx + begin * NC3;
@@ -581,7 +554,7 @@ namespace mgamd
                 return launch_pair<P, B, MODE>(st, a, partner_constrained);
               throw std::runtime_error("brick pair launch: size not instantiated");
             }
-          const size_t lds      = (2 * (size_t)G::N3 + 2 * P * P * P + 1 + face_table_words<P, B>()) * sizeof(T);
+          const size_t lds      = (2 * (size_t)G::N3 + 2 * P * P * P + 1) * sizeof(T);
           const int    resident = resident_workgroups(ctx, persistent_wgs_per_cu<T, P>());
           auto         kern     = lattice_apply_persistent_kernel<T, P, B, MODE>;
           ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
@@ -704,7 +677,7 @@ namespace mgamd
           const FusedTransferHost<T> *fused = nullptr)
     {
       constexpr bool FUSED_MODE = MODE != base_mode(MODE);
-      if (FUSED_MODE && (!fused || fused->group < 0 || !fused_transfer_supported<T>(p)))
+      if (FUSED_MODE && (!fused || fused->group < 0 || !fused_transfer_supported(p)))
         throw std::runtime_error("fused transfer pass without fused tables");
       switch (p)
         {

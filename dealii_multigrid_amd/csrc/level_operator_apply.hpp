@@ -25,7 +25,7 @@ namespace mgamd
     a.epi        = epi;
     // 2^3 bricks and single cells in one launch (lattice_apply_small_kernel) when both exist
     GroupDev<T> *g2 = nullptr, *g1 = nullptr;
-    if (P >= 2 && !diag && merge_small)
+    if (P >= 2 && !diag)
       for (auto &g : groups)
         {
           if (g->n_slots && g->B == 2)
@@ -36,7 +36,7 @@ namespace mgamd
     const bool merged = g2 && g1;
     // p = 1: the 8^3 bricks together with the cell clusters (lattice_cluster_kernel)
     GroupDev<T> *g8 = nullptr, *gc = nullptr;
-    if (P == 1 && !diag && merge_small)
+    if (P == 1 && !diag)
       for (auto &g : groups)
         {
           if (g->n_slots && g->B == 8 && g->B != prof_B && !g->constrained)
@@ -119,7 +119,7 @@ namespace mgamd
       // (D^-1 of slot-interior DoFs is evaluated in closed form, not read, by the p = 1 kernels and by the persistent
       // 17-point lattice kernels: one word less per interior DoF)
       // prof_bytes keeps SURVEY 8(d)'s per-unit figure (the algorithm's words); prof_bytes_moved is the kernel's own count
-      const bool   closed_dinv = P == 1 || (g.N * g.N > 256 && use_persistent<T, P>());
+      const bool   closed_dinv = P == 1 || g.N * g.N > 256;
       const double w_interior  = words - (closed_dinv ? 1.0 : 0.0);
       const double n1 = (double)(g.N - 1), n2 = (double)(g.N - 2);
       ctx->prof_bytes += sizeof(T) * (double)n_slots * (words * n2 * n2 * n2 + 2.0 * (n1 * n1 * n1 - n2 * n2 * n2));
@@ -127,7 +127,7 @@ namespace mgamd
     };
     // plain + constrained bricks of one size share a launch (p = 1: the only degree with constrained bricks above B = 2)
     auto constrained_partner = [&](GroupDev<T> *g) -> GroupDev<T> * {
-      if (P != 1 || diag || !merge_small || g->constrained || g->B <= 2 || (merged_p1 && g == g8))
+      if (P != 1 || diag || g->constrained || g->B <= 2 || (merged_p1 && g == g8))
         return nullptr;
       for (auto &q : groups)
         if (q->constrained && q->B == g->B && q->n_slots)
@@ -141,7 +141,7 @@ namespace mgamd
           continue;
         if ((merged && g == g1) || (merged_p1 && g == gc))
           continue; // done together with the 2^3 (8^3) bricks
-        if (g->constrained && !diag && merge_small && P == 1)
+        if (g->constrained && !diag && P == 1)
           {
             bool has_plain = false;
             for (auto &q : groups)

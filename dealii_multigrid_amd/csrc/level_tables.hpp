@@ -809,13 +809,10 @@ namespace mgamd
       // lattice kernel on small lattices and saves a launch per size and application (octant, 17 M DoFs, measured:
       // sizes {16,8,4,2,1} 2.93 ms per V-cycle, {16,8,4,1} 2.66, later {16,8,4,1} 2.31, {16,8,1} 2.23, {16,1} 2.29)
       const bool hanging_bricks = getenv("MGAMD_NO_HANGING_BRICKS") == nullptr;
-      // MGAMD_MAX_CONSTRAINED_BRICK=2: only families (the 8 children of one cell) may be constrained bricks (development A/B)
+      // p >= 2: only families (the 8 children of one cell) may be constrained bricks
       // (larger constrained bricks only at p = 1: kernels.hpp brick_may_be_constrained, with the measurements)
-      const int  max_constrained_brick =
-        getenv("MGAMD_MAX_CONSTRAINED_BRICK") ? std::max(2, atoi(getenv("MGAMD_MAX_CONSTRAINED_BRICK"))) : (p != 1 ? 2 : 1 << 30);
-      int        skip           = p == 1 ? 6 : 0;
-      if (const char *e = getenv("MGAMD_SKIP_BRICKS")) // development: bit mask of brick sizes to leave out
-        skip = atoi(e);
+      const int  max_constrained_brick = p != 1 ? 2 : 1 << 30;
+      const int  skip                  = p == 1 ? 6 : 0; // bit mask of the brick sizes left out
       std::vector<bool> constrained_only;
       for (int B = Bmax; B >= 1; B /= 2)
         if (B == 1 || B == Bmax || !(skip & B))

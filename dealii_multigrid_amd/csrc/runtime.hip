@@ -351,12 +351,10 @@ namespace mgamd
   {
     LevelOperator<T> *lop;
     DBuf<T>           dinv, tmp;
-    bool              fuse_first = true; // MGAMD_NO_FUSED_START=1: materialise x_1 (development A/B)
 
     Chebyshev(LevelOperator<T> *o, unsigned deg, double smoothing_range, unsigned eig_cg_n_iterations)
       : lop(o)
     {
-      fuse_first = getenv("MGAMD_NO_FUSED_START") == nullptr;
       op     = o;
       degree = deg;
       Ctx         *ctx = o->ctx;
@@ -483,7 +481,7 @@ namespace mgamd
       // x_1 = D^-1 b / theta is only materialised when it is the result; the first operator pass computes it on the
       // fly from b and D^-1 (which it reads anyway) and the second one uses it as x_old the same way
       const bool passes = degree >= 2 && std::fabs(delta) >= 1e-40;
-      if (!passes || !fuse_first)
+      if (!passes)
         hipLaunchKernelGGL(vec_scaled_product_kernel<T>, grid_for(n), 256, 0, ctx->stream, cur, T(1.0 / theta), dinv.p, b, n);
       if (passes)
         {
@@ -493,10 +491,10 @@ namespace mgamd
               const double rhokp = 1.0 / (2.0 * sigma - rhok);
               const double f1 = rhokp * rhok, f2 = 2.0 * rhokp / delta;
               rhok = rhokp;
-              if (fuse_first && j < 2)
+              if (j < 2)
                 lop->cheb_raw(oth, j == 0 ? nullptr : cur, nullptr, b, dinv.p, f1, f2, (int)j + 1, 1.0 / theta);
               else
-                lop->cheb_raw(oth, cur, j == 0 ? nullptr : oth, b, dinv.p, f1, f2);
+                lop->cheb_raw(oth, cur, oth, b, dinv.p, f1, f2);
               std::swap(cur, oth);
             }
         }
@@ -660,20 +658,18 @@ namespace mgamd
       fop    = f;
       cop    = c;
       ctx    = f->ctx;
-      const char *nb         = getenv("MGAMD_NO_BRICK_TRANSFER");
-      const bool  use_bricks = !(nb && atoi(nb));
-      // the fine group whose bricks carry the fused transfers: the plain 17-point lattices of an h-transfer, if the level's
-      // operator runs them with persistent workgroups; not on local-smoothing levels (edge rows, partial coverage)
+      // the fine group whose bricks carry the fused transfers: the plain 17-point lattices of an h-transfer (persistent
+      // workgroups); not on local-smoothing levels (edge rows, partial coverage)
       int fuse_group = -1;
-      if (use_bricks && !getenv("MGAMD_NO_FUSED_TRANSFER") && f->tables->tria != c->tables->tria && f->tables->p == c->tables->p &&
-          !f->tables->ls_level && !c->tables->ls_level && fused_transfer_supported<T>(f->tables->p))
+      if (!getenv("MGAMD_NO_FUSED_TRANSFER") && f->tables->tria != c->tables->tria && f->tables->p == c->tables->p &&
+          !f->tables->ls_level && !c->tables->ls_level && fused_transfer_supported(f->tables->p))
         for (size_t gi = 0; gi < f->tables->groups.size(); ++gi)
           {
             const SlotGroup &g = f->tables->groups[gi];
             if (g.N == 17 && !g.constrained_group && g.n_slots() > 0)
               fuse_group = (int)gi;
           }
-      TransferTables tt(*f->tables, *c->tables, use_bricks, fuse_group);
+      TransferTables tt(*f->tables, *c->tables, true, fuse_group);
       // sharded fine level: a residual entry that is a copy of another rank's DoF is restricted by its owner only
       const uint32_t copy_lo = f->tables->n_interior + f->tables->n_tail_owned, copy_hi = f->tables->n_interior + f->tables->n_tail;
       auto           owned_only = [&](std::vector<uint32_t> v) {
@@ -742,7 +738,7 @@ namespace mgamd
               grp[k].fine_idx.upload(tt.groups[k].fine_idx);
               if (copy_hi > copy_lo)
                 grp[k].fine_idx_restrict.upload(owned_only(tt.groups[k].fine_idx));
-              if (k == 1 && tt.pc == 1 && grp[k].nf == 3 && !getenv("MGAMD_NO_P1_PATCH_KERNELS"))
+              if (k == 1 && tt.pc == 1 && grp[k].nf == 3)
                 {
                   if (copy_hi > copy_lo)
                     {
@@ -845,16 +841,13 @@ namespace mgamd
           ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
           hipLaunchKernelGGL(kern, (int)n_launch, G::BLOCK, lds, ctx->stream, a);
         }
-      else if (G::NF == 17 && getenv("MGAMD_NO_PERSISTENT") == nullptr)
+      else if constexpr (G::NF == 17)
         {
           // persistent workgroups, three per CU (<= 168 VGPRs), a multiple of 8 (kernels.hpp)
-          if constexpr (G::NF == 17)
-            {
-              auto kern = brick_restrict_persistent_kernel<T, P, B>;
-              ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-              const int resident = std::max(8, 3 * ctx->n_cu / 8 * 8);
-              hipLaunchKernelGGL(kern, std::min((int)n_launch, resident), G::BLOCK, lds, ctx->stream, a);
-            }
+          auto kern = brick_restrict_persistent_kernel<T, P, B>;
+          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
+          const int resident = std::max(8, 3 * ctx->n_cu / 8 * 8);
+          hipLaunchKernelGGL(kern, std::min((int)n_launch, resident), G::BLOCK, lds, ctx->stream, a);
         }
       else
         {
@@ -1280,8 +1273,6 @@ namespace mgamd
     std::vector<LevelOperator<T> *>  ops;
     std::vector<Transfer2<T> *>      tr;
     std::vector<Chebyshev<T> *>      sm;
-    double *wide_out          = nullptr;                                  // see vcycle_raw: the outer result vector while a cycle runs
-    bool    wide_copy_from_mg = getenv("MGAMD_NO_WIDE_COPY_FROM_MG") == nullptr; // development switch
     std::vector<std::unique_ptr<DBuf<T>>> defect, S, Tb, res; // defect: only the finest level owns memory,
     DBuf<T>                               defect_slab;        // the coarser defects share one slab (ONE memset per cycle)
     std::vector<T *>                      dptr;               // defect vector of every level
@@ -1703,9 +1694,10 @@ namespace mgamd
       coarse_iterations += its;
     }
 
-    // the cycle on level vectors; defect[nl-1] must be set, coarser defects zero
+    // the cycle on level vectors; defect[nl-1] must be set, coarser defects zero.  wide_out (float levels under double outer
+    // vectors, finest level only): the last post-smoothing pass stores the level solution there as doubles, see vcycle_raw
     void
-    level_v_step(unsigned l)
+    level_v_step(unsigned l, double *wide_out = nullptr)
     {
       if (l == 0)
         {
@@ -1783,17 +1775,15 @@ namespace mgamd
         }
       stage(5, false, l);
       stage(6, true, l);
-      // (finest level of float levels under double outer vectors: the last pass writes the doubles of copy_from_mg itself)
-      double *wide = (l == nl - 1) ? wide_out : nullptr;
       if (fuse)
         {
           FusedTransferHost<T> f = tr[l]->fused;
           f.coarse               = sol[l - 1];
           f.scratch              = res[l]->p; // the residual vector is free again
-          sol[l]                 = sm[l]->step_raw(sview[l], tview[l], dview[l], &f, wide);
+          sol[l]                 = sm[l]->step_raw(sview[l], tview[l], dview[l], &f, wide_out);
         }
       else
-        sol[l] = sm[l]->step_raw(sview[l], tview[l], dview[l], nullptr, wide); // post-smoothing
+        sol[l] = sm[l]->step_raw(sview[l], tview[l], dview[l], nullptr, wide_out); // post-smoothing
       stage(6, false, l);
     }
 
@@ -1870,16 +1860,15 @@ namespace mgamd
       stage(7, false, L);
       // copy_from_mg inside the last post-smoothing pass (Epilogue::out_wide): float levels, double outer vectors, a smoother of
       // degree >= 2 (its last pass is a plain Chebyshev pass), no stage callbacks (they want the reference's separate stages)
-      wide_out = nullptr;
+      double *wide_out = nullptr;
       if constexpr (sizeof(T) == 4 && sizeof(TO) == 8)
-        if (nl > 1 && !cb && wide_copy_from_mg)
+        if (nl > 1 && !cb)
           wide_out = reinterpret_cast<double *>(z);
-      level_v_step(L);
+      level_v_step(L, wide_out);
       stage(8, true, L);
       // (sol[L] == nullptr: the last smoothing pass has written z; a collapsed finest level leaves its result in a level vector)
       if (sol[L] != nullptr && (const void *)sol[L] != (const void *)z)
         hipLaunchKernelGGL((vec_copy_kernel<TO, T>), grid_for(n), 256, 0, ctx->stream, z, sol[L], n);
-      wide_out = nullptr;
       stage(8, false, L);
     }
 

@@ -20,7 +20,7 @@ fused = [t.n_fused_bricks() for t in h.transfers if t is not None]
 print(f"  iterations {it:3d} residual {res:.3e} n_dofs {h.n_dofs} fused bricks per transfer {fused}", flush=True)
 """ % ROOT
 
-SWITCHES = [{}, {"MGAMD_NO_FUSED_TRANSFER": "1"}, {"MGAMD_NO_CELL_WAVES": "1"}, {"MGAMD_NO_PERSISTENT": "1"}]
+SWITCHES = [{}, {"MGAMD_NO_FUSED_TRANSFER": "1"}]
 for case in sys.argv[1:]:
     parts = case.split(":")
     geo, L, p = parts[0], parts[1], parts[2]
