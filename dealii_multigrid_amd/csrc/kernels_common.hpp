@@ -76,6 +76,30 @@ namespace mgamd
     static constexpr int ROUNDS  = (SPW * LINES + ABLOCK - 1) / ABLOCK;
   };
 
+  // Host side: the lattices whose kernels run with PERSISTENT workgroups (a resident grid that walks the slots) are the
+  // 17-point ones: one slot per workgroup and more lines than threads (Geo: SPW == 1, N_INT > 0, ROUNDS > 1).
+  constexpr bool
+  persistent_lattice(int n)
+  {
+    return n == 17;
+  }
+  // the brick size of degree p with that lattice (p = 1: 16, p = 2: 8, p = 4: 4); 0: the degree has none (p = 3: 13 points)
+  constexpr int
+  persistent_brick(int p)
+  {
+    return 16 % p == 0 ? 16 / p : 0;
+  }
+  // dynamic LDS of the operator kernels of Geo<P, B> (lattice_apply_body, lattice_apply_persistent_body): two lattices per
+  // slot, the closed-form D^-1 tables [P^3] s and [P^3] 1/s, and 1/h per slot
+  template <typename T, int P, int B>
+  constexpr size_t
+  apply_lds_bytes()
+  {
+    using G = Geo<P, B>;
+    static_assert(persistent_lattice(G::N) == (G::SPW == 1 && G::N_INT > 0 && G::ROUNDS > 1), "persistent_lattice() and Geo disagree");
+    return (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T);
+  }
+
   struct SlotGroupDev
   {
     const uint32_t *interior_base;

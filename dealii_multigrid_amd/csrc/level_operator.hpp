@@ -60,11 +60,53 @@ namespace mgamd
     done[{ctx->device, kern}] = lds;
   }
 
+  // a launch with dynamic LDS above the default limit
+  template <typename A>
+  inline void
+  launch_lds(Ctx *ctx, hipStream_t st, void (*kern)(A), int grid, int block, size_t lds, const A &args)
+  {
+    ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args);
+  }
+
   // two 4-wave workgroups with a 17^3 lattice pair each fit one CU; a multiple of 8 keeps a workgroup in its XCD's range
   inline int
   resident_workgroups(const Ctx *ctx, int per_cu = 2)
   {
     return std::max(8, per_cu * ctx->n_cu / 8 * 8);
+  }
+
+  // a launch of PERSISTENT workgroups: at most the resident ones (per_cu on every CU), which walk the n_work items
+  template <typename A>
+  inline void
+  launch_persistent(Ctx *ctx, hipStream_t st, void (*kern)(A), int n_work, int per_cu, int block, size_t lds, const A &args)
+  {
+    launch_lds(ctx, st, kern, std::min(n_work, resident_workgroups(ctx, per_cu)), block, lds, args);
+  }
+
+  // f(std::integral_constant<int, V>) for the V among Vs... that equals v; false if there is none
+  template <int... Vs, typename F>
+  inline bool
+  dispatch_value(int v, F &&f)
+  {
+    return ((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+  }
+  // the instantiated degrees
+  template <typename F>
+  inline bool
+  dispatch_degree(int p, F &&f)
+  {
+    return dispatch_value<1, 2, 3, 4>(p, f);
+  }
+  // the brick sizes among Bs... whose lattice of degree P has at most 17 points
+  template <int P, int... Bs, typename F>
+  inline bool
+  dispatch_brick_size(int B, F &&f)
+  {
+    return P * B + 1 <= 17 && dispatch_value<Bs...>(B, [&](auto b) {
+             if constexpr (P * b() + 1 <= 17)
+               f(b);
+           });
   }
 
   // one slot group: its diagonal, or one operator application with the kernel of its lattice
@@ -77,12 +119,7 @@ namespace mgamd
       return;
     const int grid = (int)((a.g.n_slots + G::SPW - 1) / G::SPW);
     if (diag)
-      {
-        const size_t lds  = 3 * (size_t)G::SPW * G::N3 * sizeof(T);
-        auto         kern = lattice_diag_kernel<T, P, B, CONSTR>;
-        ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-        hipLaunchKernelGGL(kern, grid, G::BLOCK, lds, st, a);
-      }
+      launch_lds(ctx, st, lattice_diag_kernel<T, P, B, CONSTR>, grid, G::BLOCK, 3 * (size_t)G::SPW * G::N3 * sizeof(T), a);
     else if constexpr (B == 1 && P >= 2)
       { // single cells wave-scoped (kernels.hpp cell_waves_kernel)
         using GW = Geo<P, 1, 64>;
@@ -91,82 +128,15 @@ namespace mgamd
         const size_t   lds    = CELL_WAVES * cell_wave_lds<T, P>();
         hipLaunchKernelGGL((cell_waves_kernel<T, P, MODE>), grid_w, 64 * CELL_WAVES, lds, st, a);
       }
+    else if constexpr (persistent_lattice(G::N))
+      // one-slot-per-workgroup lattices (17^3): persistent workgroups with a software pipeline over their slots
+      // (kernels.hpp, lattice_apply_persistent_body).  Two workgroups fit a CU (LDS); the grid is a multiple of 8 so
+      // that a workgroup stays inside the Morton range of its XCD.
+      launch_persistent(ctx, st, lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR>, grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK,
+                        apply_lds_bytes<T, P, B>(), a);
     else
-      {
-        const size_t lds  = (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T);
-        if constexpr (G::SPW == 1 && G::N_INT > 0 && G::ROUNDS > 1)
-          {
-            // one-slot-per-workgroup lattices (17^3): persistent workgroups with a software pipeline over their slots
-            // (kernels.hpp, lattice_apply_persistent_body).  Two workgroups fit a CU (LDS); the grid is a multiple of 8 so
-            // that a workgroup stays inside the Morton range of its XCD.
-            const int resident = resident_workgroups(ctx, persistent_wgs_per_cu<T, P>());
-            auto      kern     = lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR>;
-            ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-            hipLaunchKernelGGL(kern, std::min(grid, resident), G::ABLOCK, lds, st, a);
-          }
-        else
-          {
-            auto kern = lattice_apply_kernel<T, P, B, MODE, CONSTR>;
-            ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-            hipLaunchKernelGGL(kern, grid, G::ABLOCK, lds, st, a);
-          }
-      }
+      launch_lds(ctx, st, lattice_apply_kernel<T, P, B, MODE, CONSTR>, grid, G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
     HIP_CHECK(hipGetLastError());
-  }
-
-  // constrained = the group of constrained bricks larger than a family (p = 1 only, LevelTables::build)
-  template <typename T, int P, int MODE>
-  inline void
-  dispatch_B(Ctx *ctx, hipStream_t st, int B, bool constrained, const ApplyArgs<T, P> &a, bool diag)
-  {
-    if (constrained)
-      {
-        if constexpr (P == 1)
-          {
-            if (B == 4)
-              return launch_lattice<T, P, 4, MODE, true>(ctx, st, a, diag);
-            if (B == 8)
-              return launch_lattice<T, P, 8, MODE, true>(ctx, st, a, diag);
-            if (B == 16)
-              return launch_lattice<T, P, 16, MODE, true>(ctx, st, a, diag);
-          }
-        throw std::runtime_error("constrained bricks of this size/degree are not instantiated");
-      }
-    switch (B)
-      {
-        case 1:
-          launch_lattice<T, P, 1, MODE>(ctx, st, a, diag);
-          return;
-        case 2:
-          if constexpr (P * 2 + 1 <= 17)
-            {
-              launch_lattice<T, P, 2, MODE>(ctx, st, a, diag);
-              return;
-            }
-          break;
-        case 4:
-          if constexpr (P * 4 + 1 <= 17)
-            {
-              launch_lattice<T, P, 4, MODE>(ctx, st, a, diag);
-              return;
-            }
-          break;
-        case 8:
-          if constexpr (P * 8 + 1 <= 17)
-            {
-              launch_lattice<T, P, 8, MODE>(ctx, st, a, diag);
-              return;
-            }
-          break;
-        case 16:
-          if constexpr (P * 16 + 1 <= 17)
-            {
-              launch_lattice<T, P, 16, MODE>(ctx, st, a, diag);
-              return;
-            }
-          break;
-      }
-    throw std::runtime_error("unsupported brick size");
   }
 
   template <typename T>
@@ -206,6 +176,12 @@ namespace mgamd
     cluster_view() const
     {
       return CellClusterDev{uniq_ptr.p, uniq_idx.p, loc.p, mask.p, h.p, (uint32_t)n_slots, max_uniq};
+    }
+    // dynamic LDS of the cluster kernel (cell_cluster_body): the values and the sums of a cluster's distinct nodes
+    size_t
+    cluster_lds_bytes() const
+    {
+      return 2 * (size_t)std::max<uint32_t>(max_uniq, 1) * sizeof(T);
     }
     void
     build_clusters(const SlotGroup &g)
@@ -258,10 +234,10 @@ namespace mgamd
     T *coarse = nullptr, *scratch = nullptr, *x_inout = nullptr;
   };
   // degrees whose 17-point lattice kernel carries the fused modes (p = 3 has 13-point lattices, one workgroup per brick)
-  inline bool
+  constexpr bool
   fused_transfer_supported(int p)
   {
-    return p == 1 || p == 2 || p == 4;
+    return persistent_brick(p) != 0;
   }
 
   template <typename T>
@@ -274,7 +250,9 @@ namespace mgamd
     DBuf<uint8_t>                             dinv_code;
     DBuf<T>                                   dinv_table;
     const T                                  *dinv_coded = nullptr;
-    int                                       prof_B = 0; // brick size whose CHEB launches are profiled
+    // brick size of the DOMINANT slot group, the one with the most lattice points: the group the launch plan keeps in a
+    // launch of its own at p = 1, the one whose workgroups are stamped, and the default of the profiled brick size
+    int                                       dominant_B = 0;
     uint32_t                                  ablate = 0; // debug: MGAMD_ABLATE
     DBuf<unsigned long long>                  stamps;     // debug: MGAMD_STAMPS=<mode>, 8 stamps per workgroup of the largest group
     int                                       stamp_mode = -1;
@@ -288,6 +266,30 @@ namespace mgamd
       DBuf<T>        send, recv;
     };
     std::unique_ptr<HaloDev> halo;
+
+    // The kernel launches of one operator application, planned once (build_launch_plan): one step per launch, in launch order.
+    enum class LaunchKind
+    {
+      LATTICE,             // the plain bricks / cells of g with the kernel of their lattice (launch_lattice)
+      LATTICE_CONSTRAINED, // the same for a group of constrained bricks (p = 1)
+      BRICK_PAIR,          // the plain bricks g + the constrained bricks `partner` of the same size (p = 1, launch_pair)
+      BRICKS_AND_CELLS,    // the 2^3 bricks g + the single cells `partner` (p >= 2, lattice_apply_small_kernel)
+      BRICKS_AND_CLUSTERS, // the 8^3 bricks g + the cell clusters `partner` (p = 1, lattice_cluster_kernel)
+      CLUSTERS             // the cell clusters of g (p = 1, cell_cluster_apply_kernel)
+    };
+    struct LaunchStep
+    {
+      LaunchKind   kind;
+      GroupDev<T> *g, *partner;
+      size_t       begin, end; // slots of g (the whole group except in the halo-overlap pass)
+    };
+    struct LaunchPlan
+    {
+      std::vector<LaunchStep> ordinary, diagonal;
+      // halo-overlap pass of a sharded level: the slots that touch shared DoFs, then (under the exchange) the others; both
+      // empty where the pass does not apply (the ordinary steps are launched instead)
+      std::vector<LaunchStep> halo_slots, interior_slots;
+    } plan;
 
     LevelOperator(Ctx *c, const mgamd_dofs *dofs, std::shared_ptr<Comm> cm)
     {
@@ -335,28 +337,102 @@ namespace mgamd
           const size_t work = d->n_slots * (size_t)g.N * g.N * g.N;
           if (work > best)
             {
-              best   = work;
-              prof_B = g.B;
+              best       = work;
+              dominant_B = g.B;
             }
           groups.push_back(std::move(d));
         }
       if (const char *e = getenv("MGAMD_ABLATE"))
         ablate = (uint32_t)atoi(e);
-      if (const char *e = getenv("MGAMD_STAMP_B")) // debug: stamp the group of this brick size instead of the largest one
-        prof_B = atoi(e);
+      // debug: stamp the group of this brick size instead of the dominant one.  It REPLACES dominant_B, so it also decides
+      // whether the p = 1 launch plan merges the 8^3 bricks with the cell clusters (build_launch_plan).
+      if (const char *e = getenv("MGAMD_STAMP_B"))
+        dominant_B = atoi(e);
       halo_overlap = getenv("MGAMD_NO_HALO_OVERLAP") == nullptr;
       if (const char *e = getenv("MGAMD_STAMPS"))
         {
           stamp_mode = atoi(e);
           size_t nwg = 0;
           for (auto &g : groups)
-            if (g->B == prof_B)
+            if (g->B == dominant_B)
               nwg = g->n_slots; // >= number of workgroups
           stamps.alloc(nwg * 8 + 8);
           stamps.zero(ctx->stream);
         }
       tail_acc.alloc(std::max<uint32_t>(tables->n_tail + tables->n_edge, 1));
       tail_acc.zero(ctx->stream);
+      build_launch_plan();
+    }
+
+    // Which kernel runs which slot group, and with whom: every merging rule of the operator's launches is here.
+    void
+    build_launch_plan()
+    {
+      using K        = LaunchKind;
+      auto non_empty = [&](int B, bool constrained) -> GroupDev<T> * {
+        for (auto &g : groups)
+          if (g->n_slots && g->B == B && g->constrained == constrained)
+            return g.get();
+        return nullptr;
+      };
+      auto on_its_own = [&](GroupDev<T> *g, size_t begin, size_t end) {
+        // single cells at p = 1 go through their cluster tables wherever the level has them (GroupDev::build_clusters)
+        const K kind = g->has_clusters() ? K::CLUSTERS : (g->constrained ? K::LATTICE_CONSTRAINED : K::LATTICE);
+        return LaunchStep{kind, g, nullptr, begin, end};
+      };
+      // The diagonal pass: no merges, lattice_diag_kernel on every group (the clusters have no diagonal kernel).
+      for (auto &g : groups)
+        if (g->n_slots)
+          plan.diagonal.push_back({g->constrained ? K::LATTICE_CONSTRAINED : K::LATTICE, g.get(), nullptr, 0, g->n_slots});
+
+      // An ordinary pass.  Two small groups that are a fraction of one round of workgroups each share a launch (a launch
+      // costs a workgroup lifetime whatever it does):
+      GroupDev<T> *cells = non_empty(1, false);
+      // p >= 2: the 2^3 bricks and the single cells
+      GroupDev<T> *bricks2 = (p >= 2 && cells) ? non_empty(2, false) : nullptr;
+      // p = 1: the plain 8^3 bricks and the cell clusters, unless the 8^3 bricks are the dominant group of the level
+      GroupDev<T> *bricks8 = (p == 1 && cells && cells->has_clusters() && dominant_B != 8) ? non_empty(8, false) : nullptr;
+      for (auto &gp : groups)
+        {
+          GroupDev<T> *g = gp.get();
+          if (!g->n_slots || (g == cells && (bricks2 || bricks8)))
+            continue; // (the cells: launched with the bricks)
+          if (g == bricks2)
+            plan.ordinary.push_back({K::BRICKS_AND_CELLS, g, cells, 0, g->n_slots});
+          else if (g == bricks8)
+            plan.ordinary.push_back({K::BRICKS_AND_CLUSTERS, g, cells, 0, g->n_slots});
+          else
+            {
+              // p = 1 (the only degree with constrained bricks above B = 2): the constrained bricks of one size ride with
+              // the plain ones of that size, unless those ride with the cell clusters
+              GroupDev<T> *other = (p == 1 && g->B > 2) ? non_empty(g->B, !g->constrained) : nullptr;
+              if (other && other != bricks8)
+                {
+                  if (!g->constrained)
+                    plan.ordinary.push_back({K::BRICK_PAIR, g, other, 0, g->n_slots});
+                }
+              else
+                plan.ordinary.push_back(on_its_own(g, 0, g->n_slots));
+            }
+        }
+
+      // The halo-overlap pass of a sharded level: no merges, every group split at the end of its halo slots (LevelTables
+      // puts them at the front of every group).  Only where some slots are left to run under the exchange.
+      if (!halo || !halo_overlap)
+        return;
+      auto halo_end = [&](const GroupDev<T> &g) {
+        size_t nh = g.n_halo;
+        if (g.has_clusters()) // the cluster kernel works on whole 256-cell clusters
+          nh = std::min(g.n_slots, (nh + CLUSTER_CELLS - 1) / CLUSTER_CELLS * CLUSTER_CELLS);
+        return nh;
+      };
+      for (auto &g : groups)
+        if (halo_end(*g) < g->n_slots)
+          plan.interior_slots.push_back(on_its_own(g.get(), halo_end(*g), g->n_slots));
+      if (!plan.interior_slots.empty())
+        for (auto &g : groups)
+          if (halo_end(*g) > 0)
+            plan.halo_slots.push_back(on_its_own(g.get(), 0, halo_end(*g)));
     }
 
     // tail[t] <- sum over the sharing ranks (ascending rank order) of their partial tail[t]
@@ -445,50 +521,38 @@ namespace mgamd
       return m;
     }
 
+    // the cluster kernel's arguments for the single cells g in the pass described by a (clusters exist at p = 1 only)
+    template <int P>
     ClusterArgs<T>
-    cluster_args(const GroupDev<T> &g, const T *src, const Epilogue<T> &epi, bool first)
+    cluster_args(const GroupDev<T> &g, const ApplyArgs<T, P> &a, bool first)
     {
-      ClusterArgs<T> a;
-      a.c          = g.cluster_view();
-      a.m          = mats<1>();
-      a.src        = src;
-      a.tail_acc   = tail_acc.p;
-      a.n_interior = tables->n_interior;
-      a.b          = epi.b;
-      a.dinv       = epi.dinv;
-      a.c0         = epi.c0;
-      a.from_b     = first ? 1 : 0;
-      a.cluster_offset = 0;
-      return a;
+      ClusterArgs<T> c;
+      c.c          = g.cluster_view();
+      c.m          = mats<1>();
+      c.src        = a.src;
+      c.tail_acc   = a.tail_acc;
+      c.n_interior = a.n_interior;
+      c.b          = a.epi.b;
+      c.dinv       = a.epi.dinv;
+      c.c0         = a.epi.c0;
+      c.from_b     = first ? 1 : 0;
+      c.cluster_offset = 0;
+      return c;
     }
 
+    // the clusters that hold the cells [begin, end) of g
+    template <int P>
     void
-    launch_clusters(hipStream_t st, const GroupDev<T> &g, const T *src, const Epilogue<T> &epi, bool first, uint32_t cluster_begin = 0,
-                    uint32_t cluster_end = 0xFFFFFFFFu)
+    launch_clusters(hipStream_t st, const GroupDev<T> &g, const ApplyArgs<T, P> &a, bool first, size_t begin, size_t end)
     {
-      ClusterArgs<T> a;
-      a.c          = g.cluster_view();
-      a.m          = mats<1>();
-      a.src        = src;
-      a.tail_acc   = tail_acc.p;
-      a.n_interior = tables->n_interior;
-      a.b          = epi.b;
-      a.dinv       = epi.dinv;
-      a.c0         = epi.c0;
-      a.from_b     = first ? 1 : 0;
-      a.cluster_offset = 0;
-      const uint32_t n_cl = (uint32_t)((g.n_slots + CLUSTER_CELLS - 1) / CLUSTER_CELLS);
-      cluster_end         = std::min(cluster_end, n_cl);
-      if (cluster_begin >= cluster_end)
-        return;
-      a.cluster_offset    = cluster_begin;
-      const uint32_t grid = cluster_end - cluster_begin;
-      hipLaunchKernelGGL(cell_cluster_apply_kernel<T>, grid, CLUSTER_CELLS, 2 * (size_t)std::max<uint32_t>(g.max_uniq, 1) * sizeof(T), st, a);
+      ClusterArgs<T> c    = cluster_args(g, a, first);
+      c.cluster_offset    = (uint32_t)(begin / CLUSTER_CELLS);
+      const uint32_t grid = (uint32_t)((end + CLUSTER_CELLS - 1) / CLUSTER_CELLS) - c.cluster_offset;
+      hipLaunchKernelGGL(cell_cluster_apply_kernel<T>, grid, CLUSTER_CELLS, g.cluster_lds_bytes(), st, c);
       HIP_CHECK(hipGetLastError());
     }
 
-    // launches of one slot group (with its merge partner, if any) on stream st; [begin, end) restricts an unmerged group
-    // to a slot range
+    // the plain bricks a.g and the constrained bricks of the same size in one launch
     template <int P, int B, int MODE>
     void
     launch_pair(hipStream_t st, const ApplyArgs<T, P> &a, GroupDev<T> *g_constrained)
@@ -498,30 +562,17 @@ namespace mgamd
       pa.a             = a;
       pa.g_constrained = g_constrained->view();
       pa.n_wg_plain    = (uint32_t)((a.g.n_slots + G::SPW - 1) / G::SPW);
-      const uint32_t n_wg_c = (uint32_t)((g_constrained->n_slots + G::SPW - 1) / G::SPW);
-      const size_t   lds    = (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T);
-      if constexpr (G::SPW == 1 && G::N_INT > 0 && G::ROUNDS > 1)
+      const int n_wg   = (int)(pa.n_wg_plain + (uint32_t)((g_constrained->n_slots + G::SPW - 1) / G::SPW));
+      if constexpr (persistent_lattice(G::N))
         {
-          const int resident = resident_workgroups(ctx);
-          uint32_t  np = pa.n_wg_plain, nc = n_wg_c;
-          if ((int)(np + nc) > resident)
-            { // every workgroup walks both kinds (kernels.hpp)
-              np = 0;
-              nc = (uint32_t)resident;
-            }
-          pa.n_wg_plain = np;
-          auto kern     = lattice_apply_persistent_pair_kernel<T, P, B, MODE>;
-          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-          hipLaunchKernelGGL(kern, np + nc, G::ABLOCK, lds, st, pa);
+          if (n_wg > resident_workgroups(ctx))
+            pa.n_wg_plain = 0; // every workgroup walks both kinds (kernels.hpp)
+          launch_persistent(ctx, st, lattice_apply_persistent_pair_kernel<T, P, B, MODE>, n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
         }
       else if constexpr (MODE != base_mode(MODE))
         throw std::runtime_error("fused transfers need the persistent brick kernel");
       else
-        {
-          auto kern = lattice_apply_pair_kernel<T, P, B, MODE>;
-          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-          hipLaunchKernelGGL(kern, pa.n_wg_plain + n_wg_c, G::ABLOCK, lds, st, pa);
-        }
+        launch_lds(ctx, st, lattice_apply_pair_kernel<T, P, B, MODE>, n_wg, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
       HIP_CHECK(hipGetLastError());
     }
 
@@ -530,9 +581,9 @@ namespace mgamd
     void
     launch_fused(hipStream_t st, ApplyArgs<T, P> &a, size_t begin, GroupDev<T> *partner_constrained, const FusedTransferHost<T> &f)
     {
-      if constexpr (P == 1 || P == 2 || P == 4)
+      if constexpr (fused_transfer_supported(P))
         {
-          constexpr int B = 16 / P;
+          constexpr int B = persistent_brick(P);
           using G         = Geo<P, B>;
           constexpr int NC = P * B / 2 + 1, NC3 = NC * NC * NC;
           if (f.nc3 != (uint32_t)NC3 || f.E.size() != (size_t)(2 * P + 1) * (P + 1))
@@ -554,82 +605,96 @@ namespace mgamd
                 return launch_pair<P, B, MODE>(st, a, partner_constrained);
               throw std::runtime_error("brick pair launch: size not instantiated");
             }
-          const size_t lds      = (2 * (size_t)G::N3 + 2 * P * P * P + 1) * sizeof(T);
-          const int    resident = resident_workgroups(ctx, persistent_wgs_per_cu<T, P>());
-          auto         kern     = lattice_apply_persistent_kernel<T, P, B, MODE>;
-          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-          hipLaunchKernelGGL(kern, std::min((int)a.g.n_slots, resident), G::ABLOCK, lds, st, a);
+          launch_persistent(ctx, st, lattice_apply_persistent_kernel<T, P, B, MODE>, (int)a.g.n_slots, persistent_wgs_per_cu<T, P>(),
+                            G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
           HIP_CHECK(hipGetLastError());
         }
       else
         throw std::runtime_error("fused transfers: degree without 17-point lattice kernel");
     }
 
+    // the 8^3 bricks a.g and the cell clusters of gc in one launch (p = 1)
+    template <int MODE>
+    void
+    launch_bricks_and_clusters(hipStream_t st, const ApplyArgs<T, 1> &a, const GroupDev<T> &gc)
+    {
+      using G8 = Geo<1, 8>;
+      P1SmallArgs<T> sa;
+      sa.a           = a;
+      sa.c           = cluster_args(gc, a, MODE == MODE_CHEB_FIRST);
+      sa.n_wg_bricks = (uint32_t)((a.g.n_slots + G8::SPW - 1) / G8::SPW);
+      const uint32_t n_wg_cl = (uint32_t)((gc.n_slots + CLUSTER_CELLS - 1) / CLUSTER_CELLS);
+      const size_t   lds     = std::max(apply_lds_bytes<T, 1, 8>(), gc.cluster_lds_bytes());
+      hipLaunchKernelGGL((lattice_cluster_kernel<T, MODE>), sa.n_wg_bricks + n_wg_cl, 256, lds, st, sa);
+      HIP_CHECK(hipGetLastError());
+    }
+
+    // the 2^3 bricks a.g and the single cells of g1 in one launch (p >= 2)
+    template <int P, int MODE>
+    void
+    launch_bricks_and_cells(hipStream_t st, const ApplyArgs<T, P> &a, const GroupDev<T> &g1)
+    {
+      using G2 = Geo<P, 2>;
+      SmallSlotsArgs<T, P> sa;
+      sa.a           = a;
+      sa.g_cells     = g1.view();
+      sa.n_wg_bricks = (uint32_t)((a.g.n_slots + G2::SPW - 1) / G2::SPW);
+      // the cells wave-scoped: four wavefronts per workgroup with their own cells (kernels.hpp cell_waves_body)
+      using GW = Geo<P, 1, 64>;
+      const uint32_t n_w        = (uint32_t)((g1.n_slots + GW::SPW - 1) / GW::SPW);
+      const uint32_t n_wg_cells = (n_w + CELL_WAVES - 1) / CELL_WAVES;
+      const size_t   lds        = std::max(apply_lds_bytes<T, P, 2>(), CELL_WAVES * cell_wave_lds<T, P>());
+      hipLaunchKernelGGL((lattice_apply_small_kernel<T, P, MODE>), sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
+      HIP_CHECK(hipGetLastError());
+    }
+
+    // One step of the launch plan on stream st.  MODE_ a fused mode: the step of the group that carries the fused transfers
+    // runs it (with the partner the plan gives it), every other step the base mode.  stamp: an ordinary pass (debug stamps).
     template <int P, int MODE_>
     void
-    launch_group(hipStream_t st, ApplyArgs<T, P> &a, GroupDev<T> *g, GroupDev<T> *partner_cells, GroupDev<T> *partner_clusters,
-                 const T *src, const Epilogue<T> &epi, bool diag, size_t begin, size_t end, GroupDev<T> *partner_constrained = nullptr,
-                 const FusedTransferHost<T> *fused = nullptr)
+    launch_step(hipStream_t st, ApplyArgs<T, P> &a, const LaunchStep &s, bool diag, const FusedTransferHost<T> *fused, bool stamp = false)
     {
-      constexpr int MODE = base_mode(MODE_); // every group but the fused one runs the base mode of a fused pass
-      a.g      = (begin == 0 && end == g->n_slots) ? g->view() : g->view(begin, end);
+      constexpr int MODE = base_mode(MODE_);
+      using K            = LaunchKind;
+      GroupDev<T> *g     = s.g;
+      a.g                = g->view(s.begin, s.end);
+      a.stamps           = nullptr;
       if constexpr (MODE_ != MODE)
         if (fused && fused->group >= 0 && g == groups[fused->group].get())
-          return launch_fused<P, MODE_>(st, a, begin, partner_constrained, *fused);
-      if (partner_constrained)
+          return launch_fused<P, MODE_>(st, a, s.begin, s.partner, *fused);
+      if (stamp && stamps.p && s.kind != K::BRICK_PAIR && g->B == dominant_B && !g->constrained && MODE == stamp_mode)
+        a.stamps = stamps.p;
+      bool done = false;
+      switch (s.kind)
         {
-          if constexpr (P == 1)
-            {
-              if (g->B == 16)
-                return launch_pair<P, 16, MODE>(st, a, partner_constrained);
-              if (g->B == 8)
-                return launch_pair<P, 8, MODE>(st, a, partner_constrained);
-            }
-          throw std::runtime_error("brick pair launch: size not instantiated");
+          case K::LATTICE:
+            if (!dispatch_brick_size<P, 1, 2, 4, 8, 16>(g->B, [&](auto B) { launch_lattice<T, P, B(), MODE>(ctx, st, a, diag); }))
+              throw std::runtime_error("unsupported brick size");
+            break;
+          case K::LATTICE_CONSTRAINED:
+            if constexpr (P == 1)
+              done = dispatch_brick_size<P, 4, 8, 16>(g->B, [&](auto B) { launch_lattice<T, P, B(), MODE, true>(ctx, st, a, diag); });
+            if (!done)
+              throw std::runtime_error("constrained bricks of this size/degree are not instantiated");
+            break;
+          case K::BRICK_PAIR:
+            if constexpr (P == 1)
+              done = dispatch_brick_size<P, 8, 16>(g->B, [&](auto B) { launch_pair<P, B(), MODE>(st, a, s.partner); });
+            if (!done)
+              throw std::runtime_error("brick pair launch: size not instantiated");
+            break;
+          case K::BRICKS_AND_CELLS:
+            if constexpr (P >= 2)
+              launch_bricks_and_cells<P, MODE>(st, a, *s.partner);
+            break;
+          case K::BRICKS_AND_CLUSTERS:
+            if constexpr (P == 1)
+              launch_bricks_and_clusters<MODE>(st, a, *s.partner);
+            break;
+          case K::CLUSTERS:
+            launch_clusters(st, *g, a, MODE == MODE_CHEB_FIRST, s.begin, s.end);
+            break;
         }
-      a.stamps = (stamps.p && g->B == prof_B && !g->constrained && MODE == stamp_mode && !diag && begin == 0) ? stamps.p : nullptr;
-      if (partner_clusters)
-        {
-          if constexpr (P == 1)
-            {
-              using G8 = Geo<1, 8>;
-              GroupDev<T>   *gc = partner_clusters;
-              P1SmallArgs<T> sa;
-              sa.a           = a;
-              sa.c           = cluster_args(*gc, src, epi, MODE == MODE_CHEB_FIRST);
-              sa.n_wg_bricks = (uint32_t)((g->n_slots + G8::SPW - 1) / G8::SPW);
-              const uint32_t n_wg_cl = (uint32_t)((gc->n_slots + CLUSTER_CELLS - 1) / CLUSTER_CELLS);
-              const size_t   lds     = std::max((2 * (size_t)G8::SPW * G8::N3 + 2 + G8::SPW) * sizeof(T),
-                                          2 * (size_t)std::max<uint32_t>(gc->max_uniq, 1) * sizeof(T));
-              hipLaunchKernelGGL((lattice_cluster_kernel<T, MODE>), sa.n_wg_bricks + n_wg_cl, 256, lds, st, sa);
-              HIP_CHECK(hipGetLastError());
-            }
-        }
-      else if (P == 1 && !diag && g->has_clusters())
-        launch_clusters(st, *g, src, epi, MODE == MODE_CHEB_FIRST);
-      else if (partner_cells)
-        {
-          if constexpr (P >= 2)
-            {
-              using G2 = Geo<P, 2>;
-              using G1 = Geo<P, 1>;
-              GroupDev<T>         *g1 = partner_cells;
-              SmallSlotsArgs<T, P> sa;
-              sa.a           = a;
-              sa.g_cells     = g1->view();
-              sa.n_wg_bricks = (uint32_t)((g->n_slots + G2::SPW - 1) / G2::SPW);
-              // the cells wave-scoped: four wavefronts per workgroup with their own cells (kernels.hpp cell_waves_body)
-              using GW = Geo<P, 1, 64>;
-              const uint32_t n_w        = (uint32_t)((g1->n_slots + GW::SPW - 1) / GW::SPW);
-              const uint32_t n_wg_cells = (n_w + CELL_WAVES - 1) / CELL_WAVES;
-              const size_t   lds        = std::max((2 * (size_t)G2::SPW * G2::N3 + 2 * P * P * P + G2::SPW) * sizeof(T), CELL_WAVES * cell_wave_lds<T, P>());
-              (void)sizeof(G1);
-              hipLaunchKernelGGL((lattice_apply_small_kernel<T, P, MODE>), sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
-              HIP_CHECK(hipGetLastError());
-            }
-        }
-      else
-        dispatch_B<T, P, MODE>(ctx, st, g->B, g->constrained, a, diag);
     }
 
     template <int MODE>
@@ -652,8 +717,8 @@ namespace mgamd
       HIP_CHECK(hipGetLastError());
     }
 
-    // One operator application: the slot groups of the level (merged launches where two groups are a fraction of one round of
-    // workgroups each), then the epilogue of the tail and the constrained DoFs.
+    // One operator application: the steps of the launch plan (build_launch_plan), then the epilogue of the tail and the
+    // constrained DoFs.
     // Refinement-edge DoFs of a local-smoothing level (LevelTables::n_edge, numbered right after the tail):
     //   EDGE_OUT   the level operator (Operator::vmult, ref:include/operator.h:152-183): zero input, identity rows
     //   EDGE_ROWS  zero input, but their ROWS are computed: the residual that is restricted (deal.II edge_out /
@@ -679,24 +744,12 @@ namespace mgamd
       constexpr bool FUSED_MODE = MODE != base_mode(MODE);
       if (FUSED_MODE && (!fused || fused->group < 0 || !fused_transfer_supported(p)))
         throw std::runtime_error("fused transfer pass without fused tables");
-      switch (p)
-        {
-          case 1:
-            apply_P<1, MODE>(src, epi, diag, words, edge_mode, fused);
-            break;
-          case 2:
-            apply_P<2, MODE>(src, epi, diag, words, edge_mode, fused);
-            break;
-          case 3:
-            if constexpr (!FUSED_MODE)
-              apply_P<3, MODE>(src, epi, diag, words, edge_mode, fused);
-            break;
-          case 4:
-            apply_P<4, MODE>(src, epi, diag, words, edge_mode, fused);
-            break;
-          default:
-            throw std::runtime_error("degree not instantiated");
-        }
+      auto run = [&](auto P) {
+        if constexpr (!FUSED_MODE || fused_transfer_supported(P())) // (apply_inst.hip instantiates no others)
+          apply_P<P(), MODE>(src, epi, diag, words, edge_mode, fused);
+      };
+      if (!dispatch_degree(p, run))
+        throw std::runtime_error("degree not instantiated");
     }
 
     // raw-pointer entry points used by smoother / multigrid

@@ -666,7 +666,7 @@ namespace mgamd
         for (size_t gi = 0; gi < f->tables->groups.size(); ++gi)
           {
             const SlotGroup &g = f->tables->groups[gi];
-            if (g.N == 17 && !g.constrained_group && g.n_slots() > 0)
+            if (persistent_lattice(g.N) && !g.constrained_group && g.n_slots() > 0)
               fuse_group = (int)gi;
           }
       TransferTables tt(*f->tables, *c->tables, true, fuse_group);
@@ -836,52 +836,13 @@ namespace mgamd
       a.dst            = dst;
       const size_t lds = (size_t)G::LDS * sizeof(T);
       if (prolongate)
-        {
-          auto kern = brick_prolongate_kernel<T, P, B>;
-          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-          hipLaunchKernelGGL(kern, (int)n_launch, G::BLOCK, lds, ctx->stream, a);
-        }
-      else if constexpr (G::NF == 17)
-        {
-          // persistent workgroups, three per CU (<= 168 VGPRs), a multiple of 8 (kernels.hpp)
-          auto kern = brick_restrict_persistent_kernel<T, P, B>;
-          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-          const int resident = std::max(8, 3 * ctx->n_cu / 8 * 8);
-          hipLaunchKernelGGL(kern, std::min((int)n_launch, resident), G::BLOCK, lds, ctx->stream, a);
-        }
+        launch_lds(ctx, ctx->stream, brick_prolongate_kernel<T, P, B>, (int)n_launch, G::BLOCK, lds, a);
+      else if constexpr (persistent_lattice(G::NF))
+        // persistent workgroups, three per CU (<= 168 VGPRs) (kernels.hpp)
+        launch_persistent(ctx, ctx->stream, brick_restrict_persistent_kernel<T, P, B>, (int)n_launch, 3, G::BLOCK, lds, a);
       else
-        {
-          auto kern = brick_restrict_kernel<T, P, B>;
-          ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), lds);
-          hipLaunchKernelGGL(kern, (int)n_launch, G::BLOCK, lds, ctx->stream, a);
-        }
+        launch_lds(ctx, ctx->stream, brick_restrict_kernel<T, P, B>, (int)n_launch, G::BLOCK, lds, a);
       HIP_CHECK(hipGetLastError());
-    }
-
-    template <int P>
-    void
-    dispatch_brick(const BrickD &b, const T *src, T *dst, bool prolongate, size_t n_launch)
-    {
-      switch (b.B)
-        {
-          case 2:
-            if constexpr (P * 2 + 1 <= 17)
-              return launch_brick<P, 2>(b, src, dst, prolongate, n_launch);
-            break;
-          case 4:
-            if constexpr (P * 4 + 1 <= 17)
-              return launch_brick<P, 4>(b, src, dst, prolongate, n_launch);
-            break;
-          case 8:
-            if constexpr (P * 8 + 1 <= 17)
-              return launch_brick<P, 8>(b, src, dst, prolongate, n_launch);
-            break;
-          case 16:
-            if constexpr (P * 16 + 1 <= 17)
-              return launch_brick<P, 16>(b, src, dst, prolongate, n_launch);
-            break;
-        }
-      throw std::runtime_error("brick transfer: unsupported brick size");
     }
 
     // skip_fused: leave out the bricks whose transfer happens inside the operator passes
@@ -891,23 +852,11 @@ namespace mgamd
       for (auto &b : bricks)
         {
           const size_t nb = skip_fused ? b->n_unfused : b->n_bricks;
-          switch (pc)
-          {
-            case 1:
-              dispatch_brick<1>(*b, src, dst, prolongate, nb);
-              break;
-            case 2:
-              dispatch_brick<2>(*b, src, dst, prolongate, nb);
-              break;
-            case 3:
-              dispatch_brick<3>(*b, src, dst, prolongate, nb);
-              break;
-            case 4:
-              dispatch_brick<4>(*b, src, dst, prolongate, nb);
-              break;
-            default:
-              throw std::runtime_error("brick transfer: degree not instantiated");
-          }
+          if (!dispatch_degree(pc, [&](auto P) {
+                if (!dispatch_brick_size<P(), 2, 4, 8, 16>(b->B, [&](auto B) { launch_brick<P(), B()>(*b, src, dst, prolongate, nb); }))
+                  throw std::runtime_error("brick transfer: unsupported brick size");
+              }))
+            throw std::runtime_error("brick transfer: degree not instantiated");
         }
       for (int k = 0; k < 3; ++k)
         {
@@ -916,23 +865,10 @@ namespace mgamd
             continue;
           const int key = pc * 100 + g.nf;
           if (k == 0)
-            switch (pc)
-              {
-                case 1:
-                  launch<1, 2, true>(g, src, dst, prolongate);
-                  break;
-                case 2:
-                  launch<2, 3, true>(g, src, dst, prolongate);
-                  break;
-                case 3:
-                  launch<3, 4, true>(g, src, dst, prolongate);
-                  break;
-                case 4:
-                  launch<4, 5, true>(g, src, dst, prolongate);
-                  break;
-                default:
-                  throw std::runtime_error("transfer: degree not instantiated");
-              }
+            {
+              if (!dispatch_degree(pc, [&](auto P) { launch<P(), P() + 1, true>(g, src, dst, prolongate); }))
+                throw std::runtime_error("transfer: degree not instantiated");
+            }
           else
             switch (key)
               {
