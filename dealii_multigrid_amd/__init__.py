@@ -24,6 +24,8 @@ import numpy as np
 # MGAMD_LIBRARY: another build of the same library (development: the -DMGAMD_KERNEL_DEBUG build of `make debug`)
 _LIB_PATH = os.environ.get("MGAMD_LIBRARY") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libmgamd.so")
 F64, F32 = 8, 4
+# levels of the sharded AMG with at most this many global rows are replicated (mgamd.h: a guess, unmeasured on multi-GPU hardware)
+AMG_MIN_SHARDED_ROWS_DEFAULT = 20000
 INVALID_DOF = 0xFFFFFFFF
 
 
@@ -559,17 +561,26 @@ class PreconditionMG:
     """Multigrid<Vector> + PreconditionMG over MGTransferGlobalCoarsening."""
 
     def __init__(self, ctx: Context, levels, transfers, smoothers, coarse_solver="direct", nested: "PreconditionMG" = None,
-                 n_cycles: int = 1, local_smoothing: "DoFs" = None):
+                 n_cycles: int = 1, local_smoothing: "DoFs" = None, sharded_amg: "DoFs" = None,
+                 amg_min_sharded_rows: int = AMG_MIN_SHARDED_ROWS_DEFAULT):
         """nested: geometric stand-in for the AMG coarse solvers on a large coarse level (an h-multigrid whose finest level
         is levels[0]), applied n_cycles times per coarse solve; see mgamd.h.
-        local_smoothing: the DoFs of the ACTIVE mesh; `levels` are then operators on the refinement levels (HMG-local)"""
+        local_smoothing: the DoFs of the ACTIVE mesh; `levels` are then operators on the refinement levels (HMG-local)
+        sharded_amg: the GLOBAL DoFs of level 0's space; the AMG coarse solvers then run on the sharded level 0 (replicated setup,
+        sharded cycle: mgamd_mg_create_sharded_amg), levels of at most amg_min_sharded_rows rows replicated"""
         self.ctx, self.levels, self.transfers, self.smoothers, self.nested = ctx, levels, transfers, smoothers, nested
+        self.sharded_amg = sharded_amg
         n = len(levels)
         L = (C.c_void_p * n)(*[l._h for l in levels])
         T = (C.c_void_p * n)(*[(t._h if t is not None else None) for t in transfers])
         S = (C.c_void_p * n)(*[(s._h if s is not None else None) for s in smoothers])
         self._h = C.c_void_p()
-        if local_smoothing is not None:
+        if sharded_amg is not None:
+            if local_smoothing is not None or nested is not None:
+                raise MgamdError("sharded_amg excludes local smoothing and a nested multigrid")
+            _chk(_lib.mgamd_mg_create_sharded_amg(ctx._h, n, L, T, S, coarse_solver.encode(), sharded_amg._h, n_cycles,
+                                                  C.c_uint32(amg_min_sharded_rows), C.byref(self._h)))
+        elif local_smoothing is not None:
             _chk(_lib.mgamd_mg_create_local_smoothing(ctx._h, n, L, T, S, local_smoothing._h, coarse_solver.encode(), C.byref(self._h)))
         else:
             _chk(_lib.mgamd_mg_create_nested(ctx._h, n, L, T, S, coarse_solver.encode(), nested._h if nested is not None else None, n_cycles,
@@ -586,6 +597,20 @@ class PreconditionMG:
         buf = C.create_string_buffer(32)
         _chk(_lib.mgamd_mg_coarse_solver_used(self._h, buf))
         return buf.value.decode()
+
+    def coarse_iterations(self) -> int:
+        """inner CG iterations of the coarse solver (cg, cg_with_chebyshev, cg_with_amg) since construction"""
+        n = C.c_uint64()
+        _chk(_lib.mgamd_mg_coarse_iterations(self._h, C.byref(n)))
+        return n.value
+
+    def amg_layout(self):
+        """the levels of the algebraic coarse solver that runs, finest first: dicts of global_rows, owned_rows, ghosts, peers,
+        replicated (mgamd_mg_amg_layout); empty if no AMG runs"""
+        n, info = C.c_uint32(), (C.c_uint32 * (5 * 32))()
+        _chk(_lib.mgamd_mg_amg_layout(self._h, C.byref(n), info, 32))
+        return [dict(global_rows=info[5 * l], owned_rows=info[5 * l + 1], ghosts=info[5 * l + 2], peers=info[5 * l + 3],
+                     replicated=bool(info[5 * l + 4])) for l in range(min(n.value, 32))]
 
     def vmult(self, z: Vector, r: Vector):
         _chk(_lib.mgamd_mg_vcycle(self._h, z._h, r._h))
@@ -658,6 +683,42 @@ class AmgHostHierarchy:
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mgamd_debug_amg_host_destroy(self._h)
+            self._h = None
+
+
+class AmgShardPlans:
+    """Host-only shard plans of the sharded AMG for every rank of a partition (amg_shard.hpp; mgamd_dev.h, no GPU needed): the AMG
+    of multigrid level `level` (mesh index of the partition) at `degree`.  level(rank, l) returns a dict: replicated, n_global,
+    n_rows, n_mirror, n_interior, n_ghost, n_recv, rows, ghost, peers, peer_offset, send_count, recv_count, send_idx and the local
+    CSR triples A, P, R (None on replicated levels, which hold the global matrices of AmgHostHierarchy)."""
+
+    def __init__(self, partition: "Partition", level: int, degree: int, max_brick: int = -1,
+                 min_sharded_rows: int = AMG_MIN_SHARDED_ROWS_DEFAULT):
+        self._h = C.c_void_p()
+        _chk(_lib.mgamd_debug_amg_shard_create(partition._h, level, degree, max_brick, C.c_uint32(min_sharded_rows), C.byref(self._h)))
+        n, ns = C.c_uint32(), C.c_uint32()
+        _chk(_lib.mgamd_debug_amg_shard_n_levels(self._h, C.byref(n), C.byref(ns)))
+        self.n_levels, self.n_sharded_levels, self.n_ranks = n.value, ns.value, partition.n_ranks
+
+    def level(self, rank: int, l: int):
+        info = (C.c_uint32 * 12)()
+        _chk(_lib.mgamd_debug_amg_shard_level_info(self._h, rank, C.c_uint32(l), info))
+        rep, ng, nr, nm, ni, ngh, nrecv, npeer, nza, nzp, nzr, rrows = (int(v) for v in info)
+        out = dict(replicated=bool(rep), n_global=ng, n_rows=nr, n_mirror=nm, n_interior=ni, n_ghost=ngh, n_recv=nrecv, A=None, P=None, R=None)
+        if rep:
+            return out
+        u32 = lambda n: np.zeros(n, np.uint32)  # noqa: E731
+        out.update(rows=u32(nr), ghost=u32(nrecv), peers=np.zeros(npeer, np.int32), peer_offset=u32(npeer + 1), send_count=u32(npeer),
+                   recv_count=u32(npeer), send_idx=u32(nrecv), A=(u32(nr + 1), u32(nza), np.zeros(nza)), P=(u32(nr + 1), u32(nzp), np.zeros(nzp)),
+                   R=(u32(rrows + 1), u32(nzr), np.zeros(nzr)))
+        _chk(_lib.mgamd_debug_amg_shard_level_get(self._h, rank, C.c_uint32(l), *[_ptr(out[k]) for k in ("rows", "ghost", "peers", "peer_offset",
+                                                                                                      "send_count", "recv_count", "send_idx")],
+                                                 *[_ptr(a) for a in out["A"]], *[_ptr(a) for a in out["P"]], *[_ptr(a) for a in out["R"]]))
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mgamd_debug_amg_shard_destroy(self._h)
             self._h = None
 
 
@@ -793,7 +854,11 @@ class DistributedHierarchy:
 
     def __init__(self, ctx: Context, comm: Communicator, geometry="quadrant", n_ref_global=3, degree=1, smoother_degree=3,
                  smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64, hanging_weight=2.0, max_brick=-1,
-                 min_root_dofs=4_000_000, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None, min_subset_dofs=1_000_000):
+                 min_root_dofs=4_000_000, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None, min_subset_dofs=1_000_000,
+                 sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT):
+        """sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
+        smoothed-aggregation AMG cut into rows over the ranks (replicated setup, sharded cycle; levels of at most
+        amg_min_sharded_rows rows replicated) instead of the geometric stand-in "gmg_vcycle".  Off by default."""
         self.ctx, self.comm = ctx, comm
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global)
         self.mesh_sequence = create_geometric_coarsening_sequence(fine)
@@ -843,14 +908,22 @@ class DistributedHierarchy:
         self.coarse = None
         self.plan = plan
         n0 = self.global_level_dofs(ctx)[0]
-        if (coarse_solver == "gmg_vcycle" or (coarse_solver in AMG_COARSE_SOLVERS and self.distributed[0])) and n0 > 4096:
+        self.amg_global_dofs = None
+        if sharded_amg and coarse_solver in AMG_COARSE_SOLVERS and n0 > 4096:
+            # every rank builds the one-rank AMG from the global tables of level 0's space and keeps its rows (amg_shard.hpp)
+            mi0, p0 = plan[0]
+            self.amg_global_dofs = DoFs(self.mesh_sequence[mi0], p0, max_brick)
+            self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, None, coarse_n_cycles,
+                                     sharded_amg=self.amg_global_dofs, amg_min_sharded_rows=amg_min_sharded_rows)
+        elif (coarse_solver == "gmg_vcycle" or (coarse_solver in AMG_COARSE_SOLVERS and self.distributed[0])) and n0 > 4096:
             # geometric stand-in for the AMG coarse solvers: the h-multigrid on level 0's space (mgamd.h, "gmg_vcycle"); the
             # algebraic multigrid is built from ONE rank's assembled matrix, so a sharded coarse level takes the stand-in
             mi0, p0 = plan[0]
             cd, cdist, cops, ctr, csm = build([(l, p0) for l in range(mi0 + 1)], (self.dofs[0], self.operators[0], self.smoothers[0]))
             self.coarse = PreconditionMG(ctx, cops, ctr, csm, "amg")
             self.coarse.parts = (cd, cdist)
-        self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, self.coarse, coarse_n_cycles)
+        if self.amg_global_dofs is None:
+            self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, self.coarse, coarse_n_cycles)
         self.fine_operator = self.operators[-1]
         self.n_local = self.dofs[-1].n_dofs
         self.n_dofs = self.global_level_dofs(ctx)[-1]

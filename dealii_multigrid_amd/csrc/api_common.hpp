@@ -6,6 +6,7 @@
 #include "transfer_tables.hpp"
 #include "partition.hpp"
 #include "amg.hpp"
+#include "amg_shard.hpp"
 
 #include <memory>
 #include <string>

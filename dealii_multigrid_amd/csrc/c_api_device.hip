@@ -588,6 +588,64 @@ mgamd_mg_create_nested(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const 
 }
 
 int
+mgamd_mg_create_sharded_amg(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
+                            mgamd_cheb *const *smoothers, const char *coarse_solver, const mgamd_dofs *global_coarse_dofs, unsigned n_cycles,
+                            uint32_t min_sharded_rows, mgamd_mg **out)
+{
+  MGAMD_TRY
+  REQUIRE(ctx && levels && out && global_coarse_dofs && n_levels > 0 && (n_levels == 1 || (transfers && smoothers)));
+  if (global_coarse_dofs->halo)
+    throw std::invalid_argument("mgamd_mg_create_sharded_amg: global_coarse_dofs must be the GLOBAL level (mgamd_dofs_create)");
+  std::vector<LevelOperatorBase *> L(n_levels, nullptr);
+  std::vector<Transfer2Base *>     Tr(n_levels, nullptr);
+  std::vector<ChebyshevBase *>     Sm(n_levels, nullptr);
+  for (unsigned l = 0; l < n_levels; ++l)
+    {
+      REQUIRE(levels[l]);
+      L[l] = levels[l]->op.get();
+      if (transfers && transfers[l])
+        Tr[l] = transfers[l]->t.get();
+      if (smoothers && smoothers[l])
+        Sm[l] = smoothers[l]->c.get();
+    }
+  auto *h = new mgamd_mg;
+  try
+    {
+      h->mg.reset(make_multigrid(ctx->ctx.get(), n_levels, L.data(), Tr.data(), Sm.data(), coarse_solver ? coarse_solver : "amg", nullptr,
+                                 n_cycles, global_coarse_dofs->tables.get(), min_sharded_rows));
+    }
+  catch (...)
+    {
+      delete h;
+      throw;
+    }
+  *out = h;
+  MGAMD_CATCH
+}
+
+int
+mgamd_mg_coarse_iterations(const mgamd_mg *mg, uint64_t *n_iterations)
+{
+  MGAMD_TRY
+  REQUIRE(mg && n_iterations);
+  *n_iterations = mg->mg->coarse_cg_iterations();
+  MGAMD_CATCH
+}
+
+int
+mgamd_mg_amg_layout(const mgamd_mg *mg, uint32_t *n_levels, uint32_t *info, uint32_t max_levels)
+{
+  MGAMD_TRY
+  REQUIRE(mg && n_levels);
+  std::vector<uint32_t> v;
+  mg->mg->amg_layout(v);
+  *n_levels = (uint32_t)(v.size() / 5);
+  if (info)
+    std::copy(v.begin(), v.begin() + 5 * std::min<size_t>(v.size() / 5, max_levels), info);
+  MGAMD_CATCH
+}
+
+int
 mgamd_mg_create_local_smoothing(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
                                 mgamd_cheb *const *smoothers, const mgamd_dofs *active_mesh_dofs, const char *coarse_solver, mgamd_mg **out)
 {

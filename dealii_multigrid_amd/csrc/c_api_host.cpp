@@ -13,6 +13,13 @@ struct mgamd_amg_host
   AmgHierarchyHost H;
 };
 
+struct mgamd_amg_shard
+{
+  AmgHierarchyHost          H;
+  unsigned                  n_sharded = 0;
+  std::vector<AmgShardPlan> plans; // one per rank
+};
+
 extern "C" {
 
 const char *
@@ -177,6 +184,123 @@ mgamd_debug_amg_host_level_get(const mgamd_amg_host *h, uint32_t level, uint32_t
     std::copy(L.P.val.begin(), L.P.val.end(), P_val);
   if (agg)
     std::copy(L.agg.begin(), L.agg.end(), agg);
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_shard_create(const mgamd_partition *p, unsigned level, int degree, int max_brick, uint32_t min_sharded_rows,
+                             mgamd_amg_shard **out)
+{
+  MGAMD_TRY
+  if (!p || !out || level >= p->trias.size())
+    throw std::invalid_argument("bad argument");
+  if (p->part.subset((int)level) && p->part.group > 1)
+    throw std::invalid_argument("sharded AMG: the level is held by groups of ranks (a subset tier of the partition)");
+  const int  n_ranks = p->part.n_ranks;
+  const bool cut     = n_ranks > 1 && !p->part.replicated((int)level);
+  mgamd_tria t{p->trias[level]};
+  mgamd_dofs *gd = nullptr;
+  if (mgamd_dofs_create(&t, degree, max_brick, &gd) != MGAMD_OK)
+    throw std::invalid_argument(g_last_error);
+  std::unique_ptr<mgamd_dofs> global(gd);
+  auto                        h = std::make_unique<mgamd_amg_shard>();
+  h->H                          = build_smoothed_aggregation(assemble_level_matrix(*global->tables));
+  const uint32_t n0             = h->H.levels[0].A.n_rows;
+  h->n_sharded                  = cut ? amg_n_sharded_levels(h->H, n_ranks, min_sharded_rows) : 0;
+  std::vector<uint32_t>              count(n0, cut ? 0 : 1);
+  std::vector<int32_t>               owner0(n0, 0);
+  std::vector<std::vector<uint32_t>> mirror(n_ranks);
+  if (cut)
+    for (int r = 0; r < n_ranks; ++r)
+      {
+        mgamd_dofs *ld = nullptr;
+        if (mgamd_dofs_create_local(p, level, (unsigned)r, degree, max_brick, &ld) != MGAMD_OK)
+          throw std::runtime_error(g_last_error);
+        std::unique_ptr<mgamd_dofs> local(ld);
+        const auto                  grow = match_rows_by_key(*global->tables, *local->tables);
+        const auto                  own  = local_dof_owned(*local->tables);
+        for (uint32_t d = 0; d < local->tables->n_dofs; ++d)
+          if (own[d])
+            {
+              ++count[grow[d]];
+              owner0[grow[d]] = r;
+            }
+          else if (d >= local->tables->first_constrained())
+            mirror[r].push_back(grow[d]);
+        std::sort(mirror[r].begin(), mirror[r].end());
+      }
+  check_owned_once(count, "level 0");
+  const auto owners = amg_level_owners(h->H, owner0, n_ranks, h->n_sharded);
+  for (int r = 0; r < n_ranks; ++r)
+    h->plans.push_back(build_amg_shard_plan(h->H, owners, mirror[r], n_ranks, r));
+  *out = h.release();
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_shard_destroy(mgamd_amg_shard *h)
+{
+  delete h;
+  return MGAMD_OK;
+}
+
+int
+mgamd_debug_amg_shard_n_levels(const mgamd_amg_shard *h, uint32_t *n_levels, uint32_t *n_sharded_levels)
+{
+  MGAMD_TRY
+  if (!h)
+    throw std::invalid_argument("null argument");
+  if (n_levels)
+    *n_levels = (uint32_t)h->H.levels.size();
+  if (n_sharded_levels)
+    *n_sharded_levels = h->n_sharded;
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_shard_level_info(const mgamd_amg_shard *h, unsigned rank, uint32_t level, uint32_t info[12])
+{
+  MGAMD_TRY
+  if (!h || !info || rank >= h->plans.size() || level >= h->H.levels.size())
+    throw std::invalid_argument("bad argument");
+  const AmgShardLevel &L = h->plans[rank].levels[level];
+  const uint32_t       v[12] = {L.replicated ? 1u : 0u, L.n_global,          L.n_rows,           L.n_mirror,
+                                L.n_interior,           L.n_ghost,           L.n_recv,           (uint32_t)L.peers.size(),
+                                (uint32_t)L.A.nnz(),    (uint32_t)L.P.nnz(), (uint32_t)L.R.nnz(), L.R.n_rows};
+  std::copy(v, v + 12, info);
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_shard_level_get(const mgamd_amg_shard *h, unsigned rank, uint32_t level, uint32_t *rows, uint32_t *ghost, int32_t *peers,
+                                uint32_t *peer_offset, uint32_t *send_count, uint32_t *recv_count, uint32_t *send_idx, uint32_t *A_ptr,
+                                uint32_t *A_col, double *A_val, uint32_t *P_ptr, uint32_t *P_col, double *P_val, uint32_t *R_ptr,
+                                uint32_t *R_col, double *R_val)
+{
+  MGAMD_TRY
+  if (!h || rank >= h->plans.size() || level >= h->H.levels.size())
+    throw std::invalid_argument("bad argument");
+  const AmgShardLevel &L   = h->plans[rank].levels[level];
+  auto                 cpy = [](auto *dst, const auto &v) {
+    if (dst && !v.empty())
+      std::copy(v.begin(), v.end(), dst);
+  };
+  cpy(rows, L.rows);
+  cpy(ghost, L.ghost);
+  cpy(peers, L.peers);
+  cpy(peer_offset, L.peer_offset);
+  cpy(send_count, L.send_count);
+  cpy(recv_count, L.recv_count);
+  cpy(send_idx, L.send_idx);
+  cpy(A_ptr, L.A.ptr);
+  cpy(A_col, L.A.col);
+  cpy(A_val, L.A.val);
+  cpy(P_ptr, L.P.ptr);
+  cpy(P_col, L.P.col);
+  cpy(P_val, L.P.val);
+  cpy(R_ptr, L.R.ptr);
+  cpy(R_col, L.R.col);
+  cpy(R_val, L.R.val);
   MGAMD_CATCH
 }
 

@@ -789,6 +789,15 @@ namespace mgamd
       for (size_t t = 0; t < key_list.size(); ++t)
         f(key_list[t], key_index[t]);
     }
+    // sharded runs: does this rank own the T/D/H DoF behind `key` (it is not shared, or this rank is its shared_owner)?
+    bool
+    key_owned(uint64_t key) const
+    {
+      if (!shared)
+        return true;
+      const auto it = shared->find(key);
+      return it == shared->end() || shared_owner(it->second) == my_rank;
+    }
 
   private:
     std::vector<uint64_t>               key_list;  // keys of T/D/H DoFs in creation order

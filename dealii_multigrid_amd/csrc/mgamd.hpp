@@ -648,6 +648,55 @@ namespace mgamd
       slots.resize(9);
       n_levels = n;
     }
+    // The AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a SHARDED mg_matrices[0] (mgamd_mg_create_sharded_amg): replicated
+    // setup from `global_coarse_dofs` (the DoFHandler of level 0's space on the whole mesh, built as a one-rank hierarchy builds
+    // it), sharded cycle; levels of at most min_sharded_rows rows replicated.  Not the default: without it a sharded coarse level
+    // takes the geometric stand-in (coarse_mg above).
+    struct ShardedAMG
+    {
+      const DoFHandler *global_coarse_dofs;
+      uint32_t          min_sharded_rows = MGAMD_AMG_MIN_SHARDED_ROWS_DEFAULT;
+    };
+    PreconditionMG(const Context &ctx, const std::vector<Operator> &mg_matrices, const std::vector<MGTwoLevelTransfer> &transfers,
+                   const std::vector<PreconditionChebyshev> &smoothers, const std::string &coarse_grid_solver_type, const ShardedAMG &amg,
+                   unsigned n_cycles = 1)
+    {
+      const unsigned                 n = mg_matrices.size();
+      std::vector<mgamd_level_op *>  L(n);
+      std::vector<mgamd_transfer2 *> T(n, nullptr);
+      std::vector<mgamd_cheb *>      S(n);
+      for (unsigned l = 0; l < n; ++l)
+        {
+          L[l] = mg_matrices[l].get();
+          S[l] = smoothers[l].get();
+          if (l > 0)
+            T[l] = transfers[l].get();
+        }
+      if (!amg.global_coarse_dofs)
+        throw std::invalid_argument("PreconditionMG: ShardedAMG needs the global DoFs of level 0's space");
+      mgamd_mg *m = nullptr;
+      check(mgamd_mg_create_sharded_amg(ctx.get(), n, L.data(), T.data(), S.data(), coarse_grid_solver_type.c_str(),
+                                        amg.global_coarse_dofs->get(), n_cycles, amg.min_sharded_rows, &m));
+      h.reset(m, mgamd_mg_destroy);
+      slots.resize(9);
+      n_levels = n;
+    }
+    // the levels of the algebraic coarse solver that runs, finest first (mgamd_mg_amg_layout); empty: no AMG runs
+    struct AmgLevelLayout
+    {
+      uint32_t global_rows, owned_rows, ghosts, peers;
+      bool     replicated;
+    };
+    std::vector<AmgLevelLayout>
+    amg_layout() const
+    {
+      uint32_t n = 0, info[5 * 32];
+      check(mgamd_mg_amg_layout(h.get(), &n, info, 32));
+      std::vector<AmgLevelLayout> out;
+      for (uint32_t l = 0; l < n && l < 32; ++l)
+        out.push_back({info[5 * l], info[5 * l + 1], info[5 * l + 2], info[5 * l + 3], info[5 * l + 4] != 0});
+      return out;
+    }
     // the coarse solver that actually runs: "direct" | "cg" | "cg_with_chebyshev" | "amg" | "cg_with_amg" | "gmg_vcycle" (mgamd.h)
     std::string
     coarse_solver_used() const

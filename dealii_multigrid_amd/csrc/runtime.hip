@@ -2,6 +2,7 @@
 #include "runtime.hpp"
 #include "level_operator.hpp"
 #include "amg.hpp"
+#include "amg_shard.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -1199,6 +1200,371 @@ namespace mgamd
     }
   };
 
+  // K7 on the rows [row_begin, row_end) (csr_spmv_range_kernel): the launcher of the sharded AMG cycle
+  template <typename T>
+  void
+  launch_csr_spmv_range(hipStream_t stream, int mode, int lanes, uint32_t row_begin, uint32_t row_end, const uint32_t *ptr, const uint32_t *col,
+                        const T *val, const T *x, T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
+  {
+    if (row_end <= row_begin)
+      return;
+    const uint32_t n_rows = row_end - row_begin;
+    auto           launch = [&](auto mode_tag, auto lanes_tag) {
+      constexpr int MODE  = decltype(mode_tag)::value;
+      constexpr int LANES = decltype(lanes_tag)::value;
+      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
+      hipLaunchKernelGGL((csr_spmv_range_kernel<T, MODE, LANES>), grid, 256, 0, stream, row_begin, row_end, ptr, col, val, x, y, b, xold,
+                         dinv, T(f1), T(f2));
+    };
+    auto with_lanes = [&](auto mode_tag) {
+      switch (lanes)
+        {
+          case 4:
+            launch(mode_tag, std::integral_constant<int, 4>());
+            break;
+          case 8:
+            launch(mode_tag, std::integral_constant<int, 8>());
+            break;
+          case 16:
+            launch(mode_tag, std::integral_constant<int, 16>());
+            break;
+          case 32:
+            launch(mode_tag, std::integral_constant<int, 32>());
+            break;
+          default:
+            throw std::invalid_argument("csr_spmv: lanes must be 4, 8, 16 or 32");
+        }
+    };
+    switch (mode)
+      {
+        case SPMV_PLAIN:
+          with_lanes(std::integral_constant<int, SPMV_PLAIN>());
+          break;
+        case SPMV_ADD:
+          with_lanes(std::integral_constant<int, SPMV_ADD>());
+          break;
+        case SPMV_RESID:
+          with_lanes(std::integral_constant<int, SPMV_RESID>());
+          break;
+        case SPMV_CHEB:
+          with_lanes(std::integral_constant<int, SPMV_CHEB>());
+          break;
+        default:
+          throw std::invalid_argument("csr_spmv: unknown mode");
+      }
+    HIP_CHECK(hipGetLastError());
+  }
+
+  // ------------------------------------------------------------------------------------------
+  // The same V-cycle on a SHARDED coarse level (amg_shard.hpp: replicated setup, sharded cycle).  Every rank builds the one-rank
+  // hierarchy from the global tables of the coarse space and keeps its rows of A, P and R; a product is: interior rows, ghost
+  // import on ctx->side underneath them, boundary rows (the level operator's scheme, MGAMD_NO_HALO_OVERLAP=1: one launch after the
+  // import).  The level-0 vectors of the multigrid are consistent copies in the local [I|T|D|H] numbering: the owned rows are
+  // gathered on entry; on exit the owned results are scattered, the copies of other ranks' DoFs are zero and the level
+  // operator's exchange_add completes them (exact: it adds zeros).
+  // ------------------------------------------------------------------------------------------
+  template <typename T>
+  struct AmgSharded
+  {
+    using Mat = typename AmgDevice<T>::Mat;
+    struct Lvl
+    {
+      Mat                   A, P, R;
+      DBuf<T>               dinv, x, b, r, t, send;
+      DBuf<uint32_t>        send_idx;
+      double                theta = 1, delta = 0;
+      uint32_t              n = 0, n_int = 0, n_recv = 0, n_global = 0, n_owned = 0, n_ghost = 0;
+      bool                  replicated = true;
+      std::vector<int>      peers;
+      std::vector<uint32_t> peer_offset;
+    };
+    Ctx                              *ctx = nullptr;
+    LevelOperator<T>                 *op0 = nullptr;
+    std::shared_ptr<Comm>             comm;
+    std::vector<std::unique_ptr<Lvl>> lv;
+    DBuf<double>                      coarse_inv;
+    unsigned                          degree  = 2;
+    bool                              overlap = true;
+    // level 0 <-> geometric vector
+    DBuf<uint32_t> in_amg, in_geo, out_amg, out_geo;
+    uint32_t       n_in = 0, n_out = 0;
+
+    AmgSharded(Ctx *c, LevelOperator<T> *op, const LevelTables &global, uint32_t min_sharded_rows)
+      : ctx(c)
+      , op0(op)
+      , comm(op->comm)
+    {
+      if (const char *e = getenv("MGAMD_AMG_SMOOTHER_DEGREE"))
+        degree = std::max(1, atoi(e));
+      overlap = getenv("MGAMD_NO_HALO_OVERLAP") == nullptr;
+      if (auto *sub = dynamic_cast<SubsetComm *>(comm.get()))
+        if (sub->group > 1)
+          throw std::invalid_argument("sharded AMG: level 0 is held by groups of ranks (a subset tier of the partition); the sharded "
+                                      "algebraic multigrid needs a level 0 that is cut over all ranks");
+      const int          n_ranks = comm ? comm->n_ranks : 1, rank = comm ? comm->rank : 0;
+      const LevelTables &local   = *op->tables;
+      const std::vector<uint32_t> grow = match_rows_by_key(global, local); // (refuses another space)
+      const std::vector<uint8_t>  own  = local_dof_owned(local);
+      AmgHierarchyHost            H    = build_smoothed_aggregation(assemble_level_matrix(global)); // (refuses local-smoothing levels)
+      if (H.levels.back().A.n_rows > 4096)
+        throw std::runtime_error("AMG: coarsening stalled at " + std::to_string(H.levels.back().A.n_rows) + " rows");
+      const uint32_t n0 = H.levels[0].A.n_rows;
+      // owner stamps: one all-reduce builds the owner map of level 0 and checks that every row is owned exactly once
+      std::vector<double> stamp(2 * (size_t)n0, 0.0);
+      for (uint32_t d = 0; d < local.n_dofs; ++d)
+        if (own[d])
+          {
+            stamp[grow[d]] += 1.0;
+            stamp[n0 + grow[d]] += (double)(rank + 1);
+          }
+      if (comm)
+        {
+          DBuf<double> ds;
+          ds.upload(stamp);
+          comm->allreduce_sum(ds.p, stamp.size(), 8, ctx->stream);
+          HIP_CHECK(hipMemcpyAsync(stamp.data(), ds.p, stamp.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+          ctx->sync();
+        }
+      std::vector<uint32_t> count(n0);
+      std::vector<int32_t>  owner0(n0);
+      for (uint32_t i = 0; i < n0; ++i)
+        {
+          count[i]  = (uint32_t)std::lround(stamp[i]);
+          owner0[i] = (int32_t)std::lround(stamp[n0 + i]) - 1;
+        }
+      check_owned_once(count, "level 0");
+      std::vector<uint32_t> mirror0;
+      for (uint32_t d = local.first_constrained(); d < local.n_dofs; ++d)
+        if (!own[d])
+          mirror0.push_back(grow[d]);
+      std::sort(mirror0.begin(), mirror0.end());
+      const unsigned     n_sharded = amg_n_sharded_levels(H, n_ranks, min_sharded_rows);
+      const AmgShardPlan S = build_amg_shard_plan(H, amg_level_owners(H, owner0, n_ranks, n_sharded), mirror0, n_ranks, rank);
+
+      for (size_t l = 0; l < H.levels.size(); ++l)
+        {
+          const AmgLevelHost  &G = H.levels[l];
+          const AmgShardLevel &P = S.levels[l];
+          auto                 L = std::make_unique<Lvl>();
+          L->replicated          = P.replicated;
+          L->n_global            = P.n_global;
+          L->n                   = P.n_rows;
+          L->n_int               = P.replicated ? P.n_rows : P.launch_interior();
+          L->n_recv              = P.n_recv;
+          L->n_owned             = P.n_owned();
+          L->n_ghost             = P.n_ghost;
+          L->peers               = P.peers;
+          L->peer_offset         = P.peer_offset;
+          const bool last        = l + 1 == H.levels.size();
+          L->A.upload(P.replicated ? G.A : P.A);
+          L->A.lanes = csr_spmv_lanes(G.A.n_rows, G.A.nnz()); // the one-rank launch's lanes: the same additions per row
+          if (!last)
+            {
+              L->P.upload(P.replicated ? G.P : P.P);
+              L->R.upload(P.replicated ? G.R : P.R);
+              L->P.lanes = csr_spmv_lanes(G.P.n_rows, G.P.nnz());
+              L->R.lanes = csr_spmv_lanes(G.R.n_rows, G.R.nnz());
+            }
+          std::vector<T> d(std::max<uint32_t>(L->n, 1), T(1));
+          for (uint32_t i = 0; i < L->n; ++i)
+            d[i] = (T)G.dinv[P.replicated ? i : P.rows[i]];
+          L->dinv.upload(d);
+          // x, r, t are read through the columns of a product: room for the ghosts behind the local rows
+          const size_t nv = std::max<size_t>((size_t)L->n + L->n_recv, 1);
+          for (DBuf<T> *v : {&L->x, &L->r, &L->t})
+            {
+              v->alloc(nv);
+              v->zero(ctx->stream);
+            }
+          L->b.alloc(std::max<uint32_t>(L->n, 1));
+          L->b.zero(ctx->stream);
+          if (L->n_recv)
+            {
+              L->send.alloc(L->n_recv);
+              L->send_idx.upload(P.send_idx);
+            }
+          const double mx = G.lambda_max, mn = mx / 20.0;
+          L->theta = 0.5 * (mx + mn);
+          L->delta = 0.5 * (mx - mn);
+          lv.push_back(std::move(L));
+        }
+      coarse_inv.upload(H.coarse_inv);
+
+      std::vector<uint32_t> ia, ig, oa, og;
+      if (S.levels[0].replicated)
+        {
+          // the whole vector on every rank: owned entries in, all-reduce; every local entry (copies included) out
+          for (uint32_t d = 0; d < local.n_dofs; ++d)
+            {
+              if (own[d])
+                {
+                  ia.push_back(grow[d]);
+                  ig.push_back(d);
+                }
+              oa.push_back(grow[d]);
+              og.push_back(d);
+            }
+          in_amg.upload(ia);
+          out_amg.upload(oa);
+        }
+      else
+        {
+          std::vector<uint32_t> local_of(n0, INVALID_DOF);
+          for (uint32_t d = 0; d < local.n_dofs; ++d)
+            local_of[grow[d]] = d;
+          for (uint32_t g : S.levels[0].rows)
+            {
+              if (local_of[g] == INVALID_DOF)
+                throw std::runtime_error("sharded AMG: a local row of level 0 is not a DoF of this rank");
+              ig.push_back(local_of[g]);
+            }
+          og = ig;
+        }
+      n_in  = (uint32_t)ig.size();
+      n_out = (uint32_t)og.size();
+      in_geo.upload(ig);
+      out_geo.upload(og);
+      ctx->sync();
+    }
+
+    // refresh the ghost entries of v (a vector of level L): pack on the main queue, import on `st`
+    void
+    import_ghosts(Lvl &L, T *v, hipStream_t st)
+    {
+      if (!L.peers.empty())
+        hipLaunchKernelGGL(amg_pack_ghosts_kernel<T>, grid_for(L.n_recv), 256, 0, ctx->stream, L.send.p, v, L.send_idx.p, L.n_recv);
+      if (st != ctx->stream)
+        ctx->order_after(st, ctx->stream);
+      // (a rank without peers on this level still takes part: the simulator's exchange is a barrier of all ranks)
+      comm->exchange(L.send.p, v + L.n, L.peers, L.peer_offset, sizeof(T), st);
+    }
+    // y (rows of M) <- product with x, a vector of level `in` (null: no ghosts to import); n_int: rows that read no ghost
+    template <int MODE>
+    void
+    spmv(const Mat &M, Lvl *in, uint32_t n_int, T *x, T *y, const T *b = nullptr, const T *xold = nullptr, const T *dinv = nullptr,
+         double f1 = 0, double f2 = 0)
+    {
+      auto rows = [&](uint32_t r0, uint32_t r1) {
+        launch_csr_spmv_range<T>(ctx->stream, MODE, M.lanes, r0, r1, M.ptr.p, M.col.p, M.val.p, x, y, b, xold, dinv, f1, f2);
+      };
+      if (!in || in->replicated || !comm)
+        {
+          rows(0, M.n_rows);
+          return;
+        }
+      if (overlap && !in->peers.empty() && n_int > 0 && n_int < M.n_rows)
+        {
+          import_ghosts(*in, x, ctx->side);
+          rows(0, n_int);
+          ctx->order_after(ctx->stream, ctx->side);
+          rows(n_int, M.n_rows);
+        }
+      else
+        {
+          import_ghosts(*in, x, ctx->stream);
+          rows(0, M.n_rows);
+        }
+    }
+    void
+    smooth_zero(Lvl &L, T *x, T *t, const T *b)
+    {
+      T *cur = (degree % 2 == 1) ? x : t, *oth = (cur == x) ? t : x;
+      hipLaunchKernelGGL(vec_scaled_product_kernel<T>, grid_for(std::max<uint32_t>(L.n, 1)), 256, 0, ctx->stream, cur, T(1.0 / L.theta),
+                         L.dinv.p, b, (size_t)L.n);
+      double       rhok  = L.delta / L.theta;
+      const double sigma = L.theta / L.delta;
+      for (unsigned j = 0; j + 1 < degree; ++j)
+        {
+          const double rhokp = 1.0 / (2.0 * sigma - rhok);
+          spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, j == 0 ? nullptr : oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
+          rhok = rhokp;
+          std::swap(cur, oth);
+        }
+    }
+    void
+    smooth_step(Lvl &L, T *x, T *t, const T *b)
+    {
+      T *cur = x, *oth = t;
+      spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, nullptr, L.dinv.p, 0.0, 1.0 / L.theta);
+      std::swap(cur, oth);
+      double       rhok  = L.delta / L.theta;
+      const double sigma = L.theta / L.delta;
+      for (unsigned j = 0; j + 1 < degree; ++j)
+        {
+          const double rhokp = 1.0 / (2.0 * sigma - rhok);
+          spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
+          rhok = rhokp;
+          std::swap(cur, oth);
+        }
+      if (cur != x && L.n)
+        HIP_CHECK(hipMemcpyAsync(x, cur, (size_t)L.n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    void
+    cycle(size_t l, T *x, const T *b)
+    {
+      Lvl &L = *lv[l];
+      if (l + 1 == lv.size())
+        {
+          hipLaunchKernelGGL(dense_matvec_kernel<T>, (int)std::min<uint32_t>(L.n, 1024), 256, 0, ctx->stream, coarse_inv.p, b, x, (int)L.n);
+          return;
+        }
+      Lvl &C = *lv[l + 1];
+      smooth_zero(L, x, L.t.p, b);
+      spmv<SPMV_RESID>(L.A, &L, L.n_int, x, L.r.p, b);
+      if (!L.replicated && C.replicated)
+        {
+          // partial sums over my owned columns, completed over the ranks
+          spmv<SPMV_PLAIN>(L.R, nullptr, 0, L.r.p, C.b.p);
+          if (comm)
+            comm->allreduce_sum(C.b.p, C.n, (int)sizeof(T), ctx->stream);
+        }
+      else
+        spmv<SPMV_PLAIN>(L.R, &L, C.n_int, L.r.p, C.b.p);
+      cycle(l + 1, C.x.p, C.b.p);
+      spmv<SPMV_ADD>(L.P, &C, L.n_int, C.x.p, x);
+      smooth_step(L, x, L.t.p, b);
+    }
+    // z = V(r) on the level-0 vectors of the multigrid (local numbering, consistent copies)
+    void
+    vcycle(T *z, const T *r)
+    {
+      Lvl &L = *lv[0];
+      if (L.replicated)
+        {
+          if (comm)
+            L.b.zero(ctx->stream);
+          if (n_in)
+            hipLaunchKernelGGL(amg_level0_gather_kernel<T>, grid_for(n_in), 256, 0, ctx->stream, L.b.p, in_amg.p, r, in_geo.p, n_in);
+          if (comm)
+            comm->allreduce_sum(L.b.p, L.n, (int)sizeof(T), ctx->stream);
+        }
+      else if (n_in)
+        hipLaunchKernelGGL(amg_level0_gather_kernel<T>, grid_for(n_in), 256, 0, ctx->stream, L.b.p, (const uint32_t *)nullptr, r, in_geo.p,
+                           n_in);
+      cycle(0, L.x.p, L.b.p);
+      if (L.replicated)
+        hipLaunchKernelGGL(amg_level0_scatter_kernel<T>, grid_for(n_out), 256, 0, ctx->stream, z, out_geo.p, L.x.p, out_amg.p, n_out);
+      else
+        {
+          HIP_CHECK(hipMemsetAsync(z, 0, (size_t)op0->n_dofs() * sizeof(T), ctx->stream));
+          if (n_out)
+            hipLaunchKernelGGL(amg_level0_scatter_kernel<T>, grid_for(n_out), 256, 0, ctx->stream, z, out_geo.p, L.x.p,
+                               (const uint32_t *)nullptr, n_out);
+          op0->exchange_add_raw(z + op0->tables->n_interior);
+        }
+      HIP_CHECK(hipGetLastError());
+    }
+    // per level: global rows, owned rows, ghosts, peers, replicated
+    void
+    layout(std::vector<uint32_t> &out) const
+    {
+      out.clear();
+      for (const auto &L : lv)
+        for (uint32_t v : {L->n_global, L->n_owned, L->n_ghost, (uint32_t)L->peers.size(), (uint32_t)(L->replicated ? 1 : 0)})
+          out.push_back(v);
+    }
+  };
+
   // ------------------------------------------------------------------------------------------
   // Multigrid V-cycle  (deal.II Multigrid::level_v_step + PreconditionMG::vmult)
   // ------------------------------------------------------------------------------------------
@@ -1302,6 +1668,7 @@ namespace mgamd
 
     uint64_t       coarse_iterations = 0; // inner CG iterations of the coarse solver, accumulated
     std::unique_ptr<AmgDevice<T>> amg;  // coarse solvers "amg", "cg_with_amg"
+    std::unique_ptr<AmgSharded<T>> amg_sharded; // the same on a sharded level 0 (by request: amg_global)
     DBuf<T>                       amg_r, amg_z;
     MultigridBase *nested   = nullptr; // coarse solver "gmg_vcycle"
     unsigned       n_cycles = 1;
@@ -1311,6 +1678,22 @@ namespace mgamd
     {
       return ops[nl - 1];
     }
+    uint64_t
+    coarse_cg_iterations() const override
+    {
+      return coarse_iterations;
+    }
+    void
+    amg_layout(std::vector<uint32_t> &out) const override
+    {
+      out.clear();
+      if (amg_sharded)
+        amg_sharded->layout(out);
+      else if (amg)
+        for (const auto &sz : amg->sizes) // one rank: every level whole, no ghosts, no peers
+          for (uint32_t v : {sz.first, sz.first, 0u, 0u, 1u})
+            out.push_back(v);
+    }
     void
     vcycle_level_raw(void *z, const void *r) override
     {
@@ -1318,7 +1701,8 @@ namespace mgamd
     }
 
     MultigridT(Ctx *c, unsigned n_levels, LevelOperatorBase *const *levels, Transfer2Base *const *transfers,
-               ChebyshevBase *const *smoothers, const std::string &coarse, MultigridBase *nested_mg, unsigned nested_cycles)
+               ChebyshevBase *const *smoothers, const std::string &coarse, MultigridBase *nested_mg, unsigned nested_cycles,
+               const LevelTables *amg_global = nullptr, uint32_t amg_min_sharded_rows = AMG_MIN_SHARDED_ROWS_DEFAULT)
     {
       ctx         = c;
       nl          = n_levels;
@@ -1379,11 +1763,21 @@ namespace mgamd
       //   larger coarse level (PMG, HPMG with MinLevel): the library's own smoothed-aggregation AMG on the assembled level matrix
       //     (amg.hpp, AmgDevice) -> "amg" / "cg_with_amg" (amg_petsc: BoomerAMG's role, the same SA hierarchy -> "amg");
       //   a `nested` geometric multigrid on level 0's space, if the caller supplies one, takes the coarse solver's place as
-      //     "gmg_vcycle" (the round-1/2 stand-in, still the only choice on a SHARDED coarse level).
+      //     "gmg_vcycle" (the round-1/2 stand-in, still the DEFAULT on a SHARDED coarse level);
+      //   `amg_global` (the global tables of level 0's space), if the caller supplies them, asks for the algebraic multigrid on a
+      //     sharded level 0: replicated setup, sharded cycle (AmgSharded) -> "amg" / "cg_with_amg".
       // Never a silent substitution: coarse_used names what runs (harness table column / bench JSON).
       coarse_type = coarse;
       const bool amg_like = coarse == "amg" || coarse == "cg_with_amg" || coarse == "amg_petsc";
-      if (nested)
+      if (amg_global)
+        {
+          if (nested || !amg_like)
+            throw std::invalid_argument("multigrid: the sharded algebraic multigrid takes the place of the AMG coarse solvers (amg, "
+                                        "cg_with_amg, amg_petsc) and excludes a nested multigrid");
+          coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
+          amg_sharded = std::make_unique<AmgSharded<T>>(ctx, ops[0], *amg_global, amg_min_sharded_rows);
+        }
+      else if (nested)
         {
           if (!amg_like && coarse != "gmg_vcycle")
             throw std::invalid_argument("multigrid: a nested multigrid is the stand-in for the AMG coarse solvers only");
@@ -1595,11 +1989,17 @@ namespace mgamd
     amg_apply(T *z, const T *r, T *rr, T *zz)
     {
       const size_t n = ops[0]->n_dofs();
-      amg->vcycle(z, r);
+      auto         V = [&](T *out, const T *in) {
+        if (amg_sharded)
+          amg_sharded->vcycle(out, in);
+        else
+          amg->vcycle(out, in);
+      };
+      V(z, r);
       for (unsigned c = 1; c < n_cycles; ++c)
         {
           ops[0]->residual_raw(rr, r, z);
-          amg->vcycle(zz, rr);
+          V(zz, rr);
           hipLaunchKernelGGL(vec_sadd_kernel<T>, grid_for(n), 256, 0, ctx->stream, z, T(1), T(1), zz, n);
         }
     }
@@ -1883,13 +2283,16 @@ namespace mgamd
 
   MultigridBase *
   make_multigrid(Ctx *ctx, unsigned n_levels, LevelOperatorBase *const *levels, Transfer2Base *const *transfers,
-                 ChebyshevBase *const *smoothers, const std::string &coarse_solver, MultigridBase *nested, unsigned n_cycles)
+                 ChebyshevBase *const *smoothers, const std::string &coarse_solver, MultigridBase *nested, unsigned n_cycles,
+                 const LevelTables *amg_global, uint32_t amg_min_sharded_rows)
   {
     if (!n_levels || !levels || !levels[0])
       throw std::invalid_argument("multigrid: no levels");
     if (levels[0]->type == MGAMD_F64)
-      return new MultigridT<double>(ctx, n_levels, levels, transfers, smoothers, coarse_solver, nested, n_cycles);
-    return new MultigridT<float>(ctx, n_levels, levels, transfers, smoothers, coarse_solver, nested, n_cycles);
+      return new MultigridT<double>(ctx, n_levels, levels, transfers, smoothers, coarse_solver, nested, n_cycles, amg_global,
+                                    amg_min_sharded_rows);
+    return new MultigridT<float>(ctx, n_levels, levels, transfers, smoothers, coarse_solver, nested, n_cycles, amg_global,
+                                 amg_min_sharded_rows);
   }
 
   // ------------------------------------------------------------------------------------------

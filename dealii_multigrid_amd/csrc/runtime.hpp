@@ -260,6 +260,12 @@ namespace mgamd
     // z = V-cycle(r) on raw device pointers of the LEVEL number type (nested use)
     virtual void
     vcycle_level_raw(void *z, const void *r) = 0;
+    // the algebraic coarse solver's levels, 5 numbers each: global rows, owned rows, ghosts, peers, replicated (empty: no AMG)
+    virtual void
+    amg_layout(std::vector<uint32_t> &out) const = 0;
+    // inner CG iterations of the coarse solvers cg, cg_with_chebyshev, cg_with_amg, accumulated since construction
+    virtual uint64_t
+    coarse_cg_iterations() const = 0;
 
     // Stage times without host synchronisation: a HIP event pair is recorded on the stream around every stage of the
     // UNCHANGED cycle (same code path as an un-instrumented cycle, collapsed coarse levels included) and resolved when read.
@@ -312,12 +318,14 @@ namespace mgamd
   make_chebyshev(LevelOperatorBase *op, unsigned degree, double smoothing_range, unsigned eig_cg_n_iterations);
   Transfer2Base *
   make_transfer2(LevelOperatorBase *fine, LevelOperatorBase *coarse);
+  // amg_global != nullptr (the global tables of level 0's space): the AMG coarse solvers run on a sharded level 0 (amg_shard.hpp),
+  // levels of at most amg_min_sharded_rows rows replicated
   // nested != nullptr: the coarse problem is handed to `n_cycles` V-cycles of another multigrid whose finest level is
   // levels[0] (the geometric stand-in for the reference's Trilinos/PETSc AMG coarse solvers on large coarse levels)
   MultigridBase *
   make_multigrid(Ctx *ctx, unsigned n_levels, LevelOperatorBase *const *levels, Transfer2Base *const *transfers,
                  ChebyshevBase *const *smoothers, const std::string &coarse_solver, MultigridBase *nested = nullptr,
-                 unsigned n_cycles = 1);
+                 unsigned n_cycles = 1, const LevelTables *amg_global = nullptr, uint32_t amg_min_sharded_rows = 0);
   void
   solve_cg(LevelOperatorBase &A, MultigridBase *M, mgamd_vec &x, const mgamd_vec &b, double reltol, double abstol, unsigned maxiter,
            unsigned &n_iterations, double &residual);

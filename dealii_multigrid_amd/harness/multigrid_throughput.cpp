@@ -133,6 +133,10 @@ struct RunParameters
   std::string  simulation_type = "Constant";
   int          min_level       = -1;
   int          min_n_cells     = -1;
+  // this project's extensions (sharded runs): "ShardedAMG": true runs the AMG coarse solvers on a sharded coarse level as the
+  // library's smoothed-aggregation AMG cut into rows over the ranks instead of the geometric stand-in; default false
+  bool         sharded_amg          = false;
+  unsigned     amg_min_sharded_rows = MGAMD_AMG_MIN_SHARDED_ROWS_DEFAULT;
   MultigridParameters mg_data;
 
   void
@@ -169,6 +173,8 @@ struct RunParameters
     get("CoarseSolverNCycles", mg_data.coarse_solver.n_cycles);
     get("RelativeTolerance", mg_data.cg_normal.reltol);
     get("MGNumberType", mg_number_type);
+    get("ShardedAMG", sharded_amg);
+    get("AMGMinShardedRows", amg_min_sharded_rows);
     get("SimulationType", simulation_type); // unknown keys are ignored (skip_undefined = true)
   }
 };
@@ -423,7 +429,10 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
   const std::string coarse = hp_local ? std::string("gmg_vcycle") : params.mg_data.coarse_solver.type;
   // (a SHARDED coarse level takes the geometric stand-in for the AMG choices too: the AMG is built from one rank's matrix)
   const bool amg_name = coarse == "amg" || coarse == "cg_with_amg" || coarse == "amg_petsc";
-  const bool amg_like = !hp_local && (coarse == "gmg_vcycle" || (comm && distributed(0) && amg_name));
+  // "ShardedAMG": true (sharded runs): the AMG itself, set up from the global tables of the coarse space on every rank, its
+  // cycle cut into rows over the ranks
+  const bool sharded_amg = comm && !hp_local && amg_name && params.sharded_amg && dof_handlers[0].n_dofs() > 4096;
+  const bool amg_like    = !hp_local && !sharded_amg && (coarse == "gmg_vcycle" || (comm && distributed(0) && amg_name));
   std::vector<DoFHandler>            c_dof_handlers;
   std::vector<Operator>              c_operators;
   std::vector<MGTwoLevelTransfer>    c_transfers;
@@ -458,8 +467,19 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
       std::cout << "note: CoarseGridSolverType '" << coarse << "' on the " << dof_handlers[0].n_dofs() << "-DoF coarse level: "
                 << params.mg_data.coarse_solver.n_cycles << " V-cycle(s) of the geometric multigrid on that level" << std::endl;
     }
-  PreconditionMG preconditioner(ctx, operators, transfers, smoothers, coarse, hp_local ? ls_mg.get() : coarse_mg.get(),
-                                hp_local ? 1u : params.mg_data.coarse_solver.n_cycles, active_dof_handler.get());
+  std::unique_ptr<DoFHandler> amg_global_dofs;
+  if (sharded_amg)
+    {
+      amg_global_dofs = std::make_unique<DoFHandler>(mesh_sequence[mesh_index[0]], degrees[0]);
+      std::cout << "note: CoarseGridSolverType '" << coarse << "' on the sharded " << amg_global_dofs->n_dofs() << "-DoF coarse level: "
+                << params.mg_data.coarse_solver.n_cycles << " cycle(s) of the smoothed-aggregation AMG, rows cut over the ranks (levels of <= "
+                << params.amg_min_sharded_rows << " rows replicated)" << std::endl;
+    }
+  PreconditionMG preconditioner =
+    sharded_amg ? PreconditionMG(ctx, operators, transfers, smoothers, coarse, PreconditionMG::ShardedAMG{amg_global_dofs.get(), params.amg_min_sharded_rows},
+                                 params.mg_data.coarse_solver.n_cycles) :
+                  PreconditionMG(ctx, operators, transfers, smoothers, coarse, hp_local ? ls_mg.get() : coarse_mg.get(),
+                                 hp_local ? 1u : params.mg_data.coarse_solver.n_cycles, active_dof_handler.get());
 
   // fine (outer, double) operator, right-hand side (ref:multigrid_throughput.cc:2262-2324)
   Operator op;

@@ -286,8 +286,8 @@ int mgamd_transfer2_n_fused_bricks(const mgamd_transfer2 *t, uint64_t *n);
  *                        of the coarse CG ("cg_with_amg").  Same role and inputs as ML, not the same aggregates: its iteration
  *                        counts cannot be parity-checked against ML.
  * mgamd_mg_create_nested additionally takes n_cycles (CoarseSolverNCycles) and, optionally, `coarse_mg`: a geometric multigrid
- * whose finest level IS levels[0]; if given, it takes the AMG's place ("gmg_vcycle": x = V(b), x += V(b - A x) ...; the only choice
- * on a sharded coarse level); "gmg_vcycle" without `coarse_mg` is "direct" on a level of <= 4096 DoFs and MGAMD_ERR_INVALID on a
+ * whose finest level IS levels[0]; if given, it takes the AMG's place ("gmg_vcycle": x = V(b), x += V(b - A x) ...; the default
+ * on a sharded coarse level, where mgamd_mg_create_sharded_amg is the alternative); "gmg_vcycle" without `coarse_mg` is "direct" on a level of <= 4096 DoFs and MGAMD_ERR_INVALID on a
  * larger one.  mgamd_mg_coarse_solver_used returns what runs: "direct" | "cg" | "cg_with_chebyshev" | "amg" |
  * "cg_with_amg" | "gmg_vcycle". */
 int mgamd_mg_create(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
@@ -296,6 +296,25 @@ int mgamd_mg_create_nested(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *co
                            mgamd_cheb *const *smoothers, const char *coarse_solver, mgamd_mg *coarse_mg, unsigned n_cycles,
                            mgamd_mg **out);
 int mgamd_mg_coarse_solver_used(const mgamd_mg *mg, char name[32]);
+/* The AMG coarse solvers on a SHARDED level 0 ("replicated setup, sharded cycle"; not the default: without this entry a sharded
+ * coarse level keeps the geometric stand-in "gmg_vcycle" or refuses).  `global_coarse_dofs` = mgamd_dofs_create on the mesh and
+ * degree of levels[0] with the max_brick a one-rank hierarchy would pass: every rank builds the one-rank smoothed-aggregation
+ * hierarchy from it (identical aggregates, P, R A P, lambda_max, coarsest inverse) and keeps its rows of A, P and R.  Level 0: the
+ * owner of the DoF in the partition owns the row; an aggregate belongs to the rank that owns most of its members.  Levels of at most
+ * `min_sharded_rows` global rows (and always the dense coarsest one) are replicated; MGAMD_AMG_MIN_SHARDED_ROWS_DEFAULT is a guess,
+ * the cost of the ghost imports has not been measured on multi-GPU hardware.  coarse_solver: "amg" | "cg_with_amg" | "amg_petsc";
+ * mgamd_mg_coarse_solver_used then reports "amg" or "cg_with_amg" (the distributed coarse CG preconditioned by the sharded cycle).
+ * MGAMD_ERR_INVALID for local-smoothing levels and for a level 0 held by groups of ranks (mgamd_comm_subset with group > 1). */
+#define MGAMD_AMG_MIN_SHARDED_ROWS_DEFAULT 20000u
+int mgamd_mg_create_sharded_amg(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
+                                mgamd_cheb *const *smoothers, const char *coarse_solver, const mgamd_dofs *global_coarse_dofs,
+                                unsigned n_cycles, uint32_t min_sharded_rows, mgamd_mg **out);
+/* read-only: the levels of the algebraic coarse solver that runs (finest first), 5 numbers each: global rows, rows this rank owns,
+ * ghost columns it imports, peers it exchanges with, 1 if the level is replicated.  *n_levels = 0: no AMG runs.  `info` may be
+ * null; at most max_levels levels are written. */
+/* inner CG iterations of the coarse solvers "cg", "cg_with_chebyshev", "cg_with_amg", accumulated since the multigrid was built */
+int mgamd_mg_coarse_iterations(const mgamd_mg *mg, uint64_t *n_iterations);
+int mgamd_mg_amg_layout(const mgamd_mg *mg, uint32_t *n_levels, uint32_t *info, uint32_t max_levels);
 /* Local smoothing (`HMG-local`: solve_with_local_smoothing, ref:multigrid_throughput.cc:1670-1873).  levels[l] = Operator on
  * refinement level l (mgamd_dofs_create_level: edge-constrained level operator, ref:include/operator.h:49-120,152-183),
  * transfers = MGTransferMatrixFree between the refinement levels, Multigrid with the interface (edge) matrices

@@ -40,6 +40,29 @@ int mgamd_debug_amg_host_level_info(const mgamd_amg_host *h, uint32_t level, uin
 int mgamd_debug_amg_host_level_get(const mgamd_amg_host *h, uint32_t level, uint32_t *A_ptr, uint32_t *A_col, double *A_val,
                                    uint32_t *P_ptr, uint32_t *P_col, double *P_val, int32_t *agg);
 
+/* ---- the shard plans of the sharded AMG (amg_shard.hpp), host only, no GPU: what every rank of `partition` would hold for the AMG
+ * on multigrid level `level` (a mesh index of the partition) at `degree`.  Built as on the device path: global tables
+ * (mgamd_dofs_create), the one-rank hierarchy, owners of level 0 from every rank's local tables (checked: every row exactly once),
+ * aggregates to the rank owning most members. */
+typedef struct mgamd_amg_shard mgamd_amg_shard;
+int mgamd_debug_amg_shard_create(const mgamd_partition *partition, unsigned level, int degree, int max_brick, uint32_t min_sharded_rows,
+                                 mgamd_amg_shard **out);
+int mgamd_debug_amg_shard_destroy(mgamd_amg_shard *h);
+int mgamd_debug_amg_shard_n_levels(const mgamd_amg_shard *h, uint32_t *n_levels, uint32_t *n_sharded_levels);
+/* info[12] of one rank's level: replicated, global rows, local rows, mirror rows (identity rows of constrained DoFs computed here
+ * but owned elsewhere; local rows are [mirror | owned interior | owned boundary]), owned interior rows, ghosts, length of the padded
+ * send / receive buffers, peers, non-zeros of the local A, P, R, rows of the local R.  Replicated levels hold the global matrices
+ * (mgamd_debug_amg_host_level_get) and report zero sizes for the local ones. */
+int mgamd_debug_amg_shard_level_info(const mgamd_amg_shard *h, unsigned rank, uint32_t level, uint32_t info[12]);
+/* the arrays (any pointer may be null): rows = global row of every local row; ghost = global row behind every receive slot
+ * (0xFFFFFFFF: padding); peers, peer_offset (peers + 1, padded), send_count / recv_count (true counts per peer); send_idx = local row
+ * packed into every send slot (0xFFFFFFFF: padding); A, P, R = local CSR, columns numbered [local rows | receive slots] of the
+ * level they read (P: of the next level, or global if that one is replicated) */
+int mgamd_debug_amg_shard_level_get(const mgamd_amg_shard *h, unsigned rank, uint32_t level, uint32_t *rows, uint32_t *ghost, int32_t *peers,
+                                    uint32_t *peer_offset, uint32_t *send_count, uint32_t *recv_count, uint32_t *send_idx, uint32_t *A_ptr,
+                                    uint32_t *A_col, double *A_val, uint32_t *P_ptr, uint32_t *P_col, double *P_val, uint32_t *R_ptr,
+                                    uint32_t *R_col, double *R_val);
+
 /* one launch of the AMG cycle's CSR kernel (K7, kernels_amg.hpp) through the production launcher on host data converted to
  * number_type: mode 0 y = A x, 1 y += A x, 2 y = b - A x, 3 y = x + f1 (x - xold) + f2 dinv (b - A x) (n_cols == n_rows).
  * lanes 4/8/16/32, or 0 for the production choice from the average row length (returned in *lanes_used).  y (n_rows) is uploaded
