@@ -17,7 +17,7 @@ $(LIBDIR)/runtime.o: $(CSRC)/runtime.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the operator kernels: one translation unit per (number type, degree), see csrc/apply_inst.hip
-APPLY_OBJS := $(foreach t,f64 f32,$(foreach p,1 2 3 4,$(LIBDIR)/apply_$(t)_p$(p).o))
+APPLY_OBJS := $(foreach t,f64 f32,$(foreach p,1 2 3 4 5 6 7,$(LIBDIR)/apply_$(t)_p$(p).o))
 $(LIBDIR)/apply_f64_p%.o: $(CSRC)/apply_inst.hip $(HDRS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -DMGAMD_INST_T=double -DMGAMD_INST_P=$* -c $< -o $@

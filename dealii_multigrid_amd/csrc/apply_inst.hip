@@ -1,5 +1,5 @@
 // Explicit instantiations of LevelOperator<T>::apply_P<P, MODE> for ONE number type and ONE degree
-// (-DMGAMD_INST_T=double|float -DMGAMD_INST_P=1..4): the kernels of kernels.hpp are compiled here, in eight translation units
+// (-DMGAMD_INST_T=double|float -DMGAMD_INST_P=1..7): the kernels of kernels.hpp are compiled here, in fourteen translation units
 // built in parallel (Makefile), instead of in one.
 #include "level_operator_apply.hpp"
 

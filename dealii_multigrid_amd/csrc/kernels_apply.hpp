@@ -32,7 +32,9 @@ namespace mgamd
   // dependent phases of a hanging cell (three interpolation passes, three sweeps, three transposed passes) cost an LDS round
   // trip each instead of a workgroup barrier with the slowest of four waves (measured with tools/stamps.py on the
   // workgroup-scoped kernel: 5-7 of the 9 us a workgroup lives are spent between those barriers).
-  template <typename T, int P, int B, int MODE, bool CONSTR = false, bool WAVE = false>
+  // NTHREADS: the threads of the workgroup if they are more than the lattice's own block (lattice_apply_small_kernel runs the
+  // 13-point bricks of p = 6, whose 169 lines make a 192-thread block, in its 256-thread workgroups); 0: Geo's ABLOCK
+  template <typename T, int P, int B, int MODE, bool CONSTR = false, bool WAVE = false, int NTHREADS = 0>
   __device__ __forceinline__ void
   lattice_apply_body(const ApplyArgs<T, P> &args, const uint32_t block, const uint32_t nblocks, unsigned char *smem_raw)
   {
@@ -43,8 +45,10 @@ namespace mgamd
     T *bufA = reinterpret_cast<T *>(smem_raw);
     T *bufB = bufA + G::SPW * G::N3;
 
-    constexpr int BLOCK = G::ABLOCK;
-    constexpr int ITER  = IM::ITER;
+    // every entry loop below strides by BLOCK = the number of threads that run this body
+    constexpr int BLOCK = NTHREADS > 0 ? NTHREADS : G::ABLOCK;
+    static_assert(BLOCK >= G::ABLOCK && (!WAVE || NTHREADS == 0), "the workgroup holds the lattice's lines");
+    constexpr int ITER  = (G::SPW * IM::NIN_ + BLOCK - 1) / BLOCK;
     constexpr int ITERS = (G::SPW * G::N_SHELL + BLOCK - 1) / BLOCK;
 
     const int tid    = WAVE ? (int)(threadIdx.x & 63u) : (int)threadIdx.x;
@@ -800,14 +804,6 @@ namespace mgamd
 #undef MGAMD_STAMP
 #undef MGAMD_ABLATED
 
-  template <typename T, int P, int B, int MODE, bool CONSTR = false>
-  __global__ void
-  __launch_bounds__((Geo<P, B>::ABLOCK), (B == 1 ? 6 : (B == 2 ? 4 : 1))) lattice_apply_kernel(const ApplyArgs<T, P> args)
-  {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    lattice_apply_body<T, P, B, MODE, CONSTR>(args, blockIdx.x, gridDim.x, smem_raw);
-  }
-
   // single cells, WAVE-SCOPED: a 256-thread workgroup = four wavefronts with their own cells (64 / (p+1)^2 cells each) and their
   // own LDS regions; no workgroup barrier anywhere (lattice_apply_body, WAVE)
   constexpr int CELL_WAVES = 4;
@@ -817,6 +813,81 @@ namespace mgamd
   {
     using G = Geo<P, 1, 64>;
     return (((2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T) + 15) / 16) * 16;
+  }
+
+  // ---- Workgroups per CU that the one-slot-group-per-workgroup kernels are compiled for (the second __launch_bounds__
+  // argument).  A CU has 160 KiB of LDS and four SIMDs with 512 VGPRs each; n 4-wave workgroups per CU are n waves per SIMD,
+  // that is 512 / n VGPRs per thread (n = 6: 80, 4: 128, 3: 168, 2: 256).  The value is
+  //     min(what the kernel was tuned for at the small lattices,  what the LDS of this lattice admits,  VGPR cap)
+  // where the VGPR cap is the largest n whose budget holds the kernel's whole-line sweeps (three lines of P B + 1 values, the
+  // gathered values and the epilogue operands) without scratch.  For p <= 4 this gives today's 4 / 6 on every lattice; the 11-,
+  // 13- and 15-point lattices of p = 5, 6, 7 come out at what their LDS admits or below (DESIGN.md section 4 has the table).
+  constexpr size_t CU_LDS_BYTES = 160 * 1024;
+  constexpr int
+  wgs_lds_admits(size_t lds_bytes)
+  {
+    return (int)(CU_LDS_BYTES / lds_bytes);
+  }
+  constexpr int
+  min_of(int a, int b, int c)
+  {
+    return a < b ? (a < c ? a : c) : (b < c ? b : c);
+  }
+  // dynamic LDS of lattice_apply_small_kernel: the larger of the 2^3-brick lattices and the four wave regions of the cells
+  template <typename T, int P>
+  constexpr size_t
+  small_slots_lds_bytes()
+  {
+    return apply_lds_bytes<T, P, 2>() > CELL_WAVES * cell_wave_lds<T, P>() ? apply_lds_bytes<T, P, 2>() : CELL_WAVES * cell_wave_lds<T, P>();
+  }
+  // VGPR caps (double: measured with -Rpass-analysis=kernel-resource-usage, tools/kernel_resources.sh; a float value is half
+  // the registers and stays inside the budget of the small lattices)
+  template <typename T, int P>
+  constexpr int
+  brick2_vgpr_cap() // 2^3 bricks: lattice_apply_kernel<P, 2> and lattice_apply_small_kernel
+  {
+    return (sizeof(T) == 8 && P >= 7) ? 2 : (sizeof(T) == 8 && P >= 5 ? 3 : 4); // 193 VGPRs at p = 7, 152 / 166 at p = 5 / 6
+  }
+  template <typename T, int P>
+  constexpr int
+  cell_waves_vgpr_cap() // wave-scoped single cells
+  {
+    return (sizeof(T) == 8 && P >= 7) ? 4 : ((sizeof(T) == 8 && P == 6) || (sizeof(T) == 4 && P >= 7) ? 5 : 6); // 122; 95, 89 VGPRs
+  }
+  template <typename T, int P>
+  constexpr int
+  small_slots_wgs_per_cu()
+  {
+    return min_of(4, wgs_lds_admits(small_slots_lds_bytes<T, P>()), brick2_vgpr_cap<T, P>());
+  }
+  template <typename T, int P, int B>
+  constexpr int
+  lattice_wgs_per_cu()
+  {
+    if constexpr (B == 2)
+      return min_of(4, wgs_lds_admits(apply_lds_bytes<T, P, 2>()), brick2_vgpr_cap<T, P>());
+    else
+      return B == 1 ? 6 : 1;
+  }
+  template <typename T, int P>
+  constexpr int
+  cell_waves_wgs_per_cu()
+  {
+    return min_of(6, wgs_lds_admits(CELL_WAVES * cell_wave_lds<T, P>()), cell_waves_vgpr_cap<T, P>());
+  }
+  static_assert(small_slots_wgs_per_cu<double, 2>() == 4 && small_slots_wgs_per_cu<double, 3>() == 4 && small_slots_wgs_per_cu<double, 4>() == 4 &&
+                  small_slots_wgs_per_cu<float, 4>() == 4 && lattice_wgs_per_cu<double, 1, 2>() == 4 && lattice_wgs_per_cu<double, 4, 2>() == 4 &&
+                  lattice_wgs_per_cu<float, 3, 2>() == 4 && lattice_wgs_per_cu<double, 1, 1>() == 6 && lattice_wgs_per_cu<double, 3, 4>() == 1 &&
+                  cell_waves_wgs_per_cu<double, 2>() == 6 && cell_waves_wgs_per_cu<double, 3>() == 6 && cell_waves_wgs_per_cu<double, 4>() == 6 &&
+                  cell_waves_wgs_per_cu<float, 4>() == 6,
+                "the kernels of p <= 4 keep the occupancy bounds they were measured with");
+
+  template <typename T, int P, int B, int MODE, bool CONSTR = false>
+  __global__ void
+  __launch_bounds__((Geo<P, B>::ABLOCK), (lattice_wgs_per_cu<T, P, B>())) lattice_apply_kernel(const ApplyArgs<T, P> args)
+  {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    lattice_apply_body<T, P, B, MODE, CONSTR>(args, blockIdx.x, gridDim.x, smem_raw);
   }
   template <typename T, int P, int MODE>
   __device__ __forceinline__ void
@@ -831,7 +902,7 @@ namespace mgamd
   }
   template <typename T, int P, int MODE>
   __global__ void
-  __launch_bounds__(64 * CELL_WAVES, 6) cell_waves_kernel(const ApplyArgs<T, P> args)
+  __launch_bounds__(64 * CELL_WAVES, (cell_waves_wgs_per_cu<T, P>())) cell_waves_kernel(const ApplyArgs<T, P> args)
   {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     cell_waves_body<T, P, MODE>(args, blockIdx.x, gridDim.x, smem_raw);
@@ -864,6 +935,7 @@ namespace mgamd
     SlotGroupDev    g_constrained; // the constrained bricks of the same size
     uint32_t        n_wg_plain;
   };
+  static_assert(sizeof(BrickPairArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "BrickPairArgs exceeds the kernel-argument segment");
   template <typename T, int P, int B, int MODE>
   __global__ void
   __launch_bounds__((Geo<P, B>::ABLOCK), 1) lattice_apply_pair_kernel(const BrickPairArgs<T, P> args)
@@ -922,13 +994,14 @@ namespace mgamd
     SlotGroupDev    g_cells; // the single-cell group
     uint32_t        n_wg_bricks;
   };
+  static_assert(sizeof(SmallSlotsArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "SmallSlotsArgs exceeds the kernel-argument segment");
   template <typename T, int P, int MODE>
   __global__ void
-  __launch_bounds__(256, 4) lattice_apply_small_kernel(const SmallSlotsArgs<T, P> args)
+  __launch_bounds__(256, (small_slots_wgs_per_cu<T, P>())) lattice_apply_small_kernel(const SmallSlotsArgs<T, P> args)
   {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     if (blockIdx.x < args.n_wg_bricks)
-      lattice_apply_body<T, P, 2, MODE>(args.a, blockIdx.x, args.n_wg_bricks, smem_raw);
+      lattice_apply_body<T, P, 2, MODE, false, false, 256>(args.a, blockIdx.x, args.n_wg_bricks, smem_raw);
     else
       {
         ApplyArgs<T, P> a = args.a;
@@ -971,6 +1044,7 @@ namespace mgamd
     int      from_b;
     uint32_t cluster_offset; // first cluster of this launch (the halo / interior split of sharded levels)
   };
+  static_assert(sizeof(ClusterArgs<double>) <= KERNARG_LIMIT, "ClusterArgs exceeds the kernel-argument segment");
 
   template <typename T, bool TRANSPOSE>
   __device__ __forceinline__ void
@@ -1165,6 +1239,7 @@ namespace mgamd
     ClusterArgs<T>  c;
     uint32_t        n_wg_bricks;
   };
+  static_assert(sizeof(P1SmallArgs<double>) <= KERNARG_LIMIT, "P1SmallArgs exceeds the kernel-argument segment");
   template <typename T, int MODE>
   __global__ void
   __launch_bounds__(256) lattice_cluster_kernel(const P1SmallArgs<T> args)

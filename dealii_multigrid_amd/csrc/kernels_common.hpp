@@ -9,6 +9,11 @@ namespace mgamd
 {
   constexpr uint32_t DEV_INVALID = 0xFFFFFFFFu;
 
+  // Kernel arguments are passed by value and carry the 1D matrices (Mats<7, double> alone is 2560 bytes): every argument struct
+  // is checked against the 4 KiB kernel-argument segment at the largest degree (fe1d.hpp MAX_DEGREE) in double.
+  constexpr size_t KERNARG_LIMIT     = 4096;
+  constexpr int    MAX_KERNEL_DEGREE = 7;
+
   // Once-touched streams (slot-interior x / x_old / b / out, the tail epilogue's vectors, the fine vectors of the brick
   // transfers) are loaded and stored NON-TEMPORALLY, so that L2 and the Infinity Cache keep what IS touched again within a
   // pass: the shell values several bricks gather and the tail accumulator lines that take several atomic adds and are then
@@ -1037,6 +1042,7 @@ namespace mgamd
     uint32_t gather_limit, scatter_limit;
     FusedTransferDev<T, P> fused; // MODE_RESIDUAL_RESTRICT / MODE_CHEB_PROLONGATE only
   };
+  static_assert(sizeof(ApplyArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "ApplyArgs exceeds the kernel-argument segment");
 
   // Interior-slot bookkeeping shared by the gather and the epilogue of lattice_apply_kernel: thread `tid`
   // handles interior entries idx = tid + it*BLOCK, it < ITER, of the workgroup's slots.

@@ -31,6 +31,9 @@ namespace mgamd
     const T        *src;
     T              *dst;
   };
+  // (the largest patch: the h-transfer of the largest degree)
+  static_assert(sizeof(TransferArgs<double, MAX_KERNEL_DEGREE, 2 * MAX_KERNEL_DEGREE + 1>) <= KERNARG_LIMIT,
+                "TransferArgs exceeds the kernel-argument segment");
 
   // dst[owned fine DoFs] += buf  (every fine DoF has exactly one owning patch: plain read-modify-write);
   // all index loads, then all value loads, then the stores
@@ -318,6 +321,7 @@ namespace mgamd
     const T        *src;
     T              *dst;
   };
+  static_assert(sizeof(PatchP1Args<double>) <= KERNARG_LIMIT, "PatchP1Args exceeds the kernel-argument segment");
   constexpr int PATCH_P1_BLOCK = 256;
   constexpr int PATCH_P1_ITERS = 8;
 
@@ -504,6 +508,7 @@ namespace mgamd
     const T        *src;
     T              *dst;
   };
+  static_assert(sizeof(BrickTransferArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "BrickTransferArgs exceeds the kernel-argument segment");
 
   template <typename T, int P, int B>
   __global__ void

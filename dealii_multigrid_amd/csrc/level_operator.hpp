@@ -96,7 +96,7 @@ namespace mgamd
   inline bool
   dispatch_degree(int p, F &&f)
   {
-    return dispatch_value<1, 2, 3, 4>(p, f);
+    return dispatch_value<1, 2, 3, 4, 5, 6, 7>(p, f);
   }
   // the brick sizes among Bs... whose lattice of degree P has at most 17 points
   template <int P, int... Bs, typename F>
@@ -125,7 +125,8 @@ namespace mgamd
         using GW = Geo<P, 1, 64>;
         const uint32_t n_w    = (uint32_t)((a.g.n_slots + GW::SPW - 1) / GW::SPW);
         const uint32_t grid_w = (n_w + CELL_WAVES - 1) / CELL_WAVES;
-        const size_t   lds    = CELL_WAVES * cell_wave_lds<T, P>();
+        constexpr size_t lds  = CELL_WAVES * cell_wave_lds<T, P>();
+        static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit the launch has to go through launch_lds");
         hipLaunchKernelGGL((cell_waves_kernel<T, P, MODE>), grid_w, 64 * CELL_WAVES, lds, st, a);
       }
     else if constexpr (persistent_lattice(G::N))
@@ -311,8 +312,6 @@ namespace mgamd
           halo->send.alloc(std::max<size_t>(halo_plan->pack_idx.size(), 1));
           halo->recv.alloc(std::max<size_t>(halo_plan->pack_idx.size(), 1));
         }
-      if (p > 4)
-        throw std::runtime_error("degrees above 4 are not instantiated in this build");
       size_t best = 0;
       for (const SlotGroup &g : tables->groups)
         {
@@ -643,7 +642,8 @@ namespace mgamd
       using GW = Geo<P, 1, 64>;
       const uint32_t n_w        = (uint32_t)((g1.n_slots + GW::SPW - 1) / GW::SPW);
       const uint32_t n_wg_cells = (n_w + CELL_WAVES - 1) / CELL_WAVES;
-      const size_t   lds        = std::max(apply_lds_bytes<T, P, 2>(), CELL_WAVES * cell_wave_lds<T, P>());
+      constexpr size_t lds      = small_slots_lds_bytes<T, P>();
+      static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit the launch has to go through launch_lds");
       hipLaunchKernelGGL((lattice_apply_small_kernel<T, P, MODE>), sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
       HIP_CHECK(hipGetLastError());
     }

@@ -779,10 +779,11 @@ namespace mgamd
       a.dst            = dst;
       const size_t lds = 2 * (size_t)G::SPW * G::NF3 * sizeof(T);
       const int    grid = (int)((g.n_patches + G::SPW - 1) / G::SPW);
+      // (two 15-point patch lattices of p = 7 are 54 KB in double: through launch_lds like every launch with large dynamic LDS)
       if (prolongate)
-        hipLaunchKernelGGL((prolongate_kernel<T, PC, NF, IDENTITY>), grid, G::BLOCK, lds, ctx->stream, a);
+        launch_lds(ctx, ctx->stream, prolongate_kernel<T, PC, NF, IDENTITY>, grid, G::BLOCK, lds, a);
       else
-        hipLaunchKernelGGL((restrict_kernel<T, PC, NF, IDENTITY>), grid, G::BLOCK, lds, ctx->stream, a);
+        launch_lds(ctx, ctx->stream, restrict_kernel<T, PC, NF, IDENTITY>, grid, G::BLOCK, lds, a);
       HIP_CHECK(hipGetLastError());
     }
 
@@ -885,11 +886,26 @@ namespace mgamd
                 case 205:
                   launch<2, 5, false>(g, src, dst, prolongate);
                   break;
+                case 206: // p-transfer 5 -> 2
+                  launch<2, 6, false>(g, src, dst, prolongate);
+                  break;
                 case 307:
                   launch<3, 7, false>(g, src, dst, prolongate);
                   break;
+                case 308: // p-transfer 7 -> 3
+                  launch<3, 8, false>(g, src, dst, prolongate);
+                  break;
                 case 409:
                   launch<4, 9, false>(g, src, dst, prolongate);
+                  break;
+                case 511:
+                  launch<5, 11, false>(g, src, dst, prolongate);
+                  break;
+                case 613:
+                  launch<6, 13, false>(g, src, dst, prolongate);
+                  break;
+                case 715:
+                  launch<7, 15, false>(g, src, dst, prolongate);
                   break;
                 default:
                   throw std::runtime_error("transfer: (coarse degree, fine patch) combination not instantiated");

@@ -223,7 +223,8 @@ int mgamd_vec_sadd(mgamd_vec *y, double s, double a, const mgamd_vec *x); /* y =
 int mgamd_vec_dot(const mgamd_vec *x, const mgamd_vec *y, double *result);
 int mgamd_vec_norm2(const mgamd_vec *x, double *result);
 
-/* Operator::reinit (ref:include/operator.h:24-47) */
+/* Operator::reinit (ref:include/operator.h:24-47).  Every degree mgamd_dofs_create accepts (1 ... 7) has device kernels in both
+ * number types; degrees above 7 are refused by mgamd_dofs_create with MGAMD_ERR_INVALID. */
 int mgamd_level_op_create(mgamd_ctx *ctx, const mgamd_dofs *dofs, int number_type, mgamd_level_op **out);
 /* same, for a level built with mgamd_dofs_create_local: vmult / inverse diagonal / rhs / smoother / transfers complete
  * the sums of shared DoFs across ranks through `comm` (may be NULL for replicated levels) */
