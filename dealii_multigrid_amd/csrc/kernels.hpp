@@ -19,7 +19,8 @@
 // with 1D matrices assembled over the B cells of a lattice line; each 1D product is evaluated
 // cell by cell with the dense (p+1)^2 reference matrices held in SGPRs (kernel arguments).
 //
-// K7  csr_spmv_kernel        CSR products of the algebraic coarse solver, fused with the Chebyshev update.
+// K7  csr_spmv_kernel        CSR products of the algebraic coarse solver, fused with the Chebyshev update; one body
+//                            (csr_spmv_rows), two entry points: all rows, and csr_spmv_range_kernel for a sharded level's rows.
 //
 // The kernels live in kernels_common.hpp (1D products, sweeps, constraint passes, argument structs), kernels_apply.hpp (K1-K3),
 // kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header includes them all.

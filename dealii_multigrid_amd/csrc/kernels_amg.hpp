@@ -2,8 +2,9 @@
 #include "kernels_common.hpp"
 
 // ------------------------------------------------------------------------------------------------
-// K7  CSR kernels of the algebraic coarse solver (amg.hpp; runtime.hip AmgDevice): one row per group of LANES adjacent lanes
-// (the level matrices have 27-70 entries per row), fused with the vector update they feed:
+// K7  CSR kernels of the algebraic coarse solver (amg.hpp; runtime.hip AmgCycle): one row per group of LANES adjacent lanes
+// (the level matrices have 27-70 entries per row), fused with the vector update they feed; one body, two entry points
+// (all rows / a range of rows):
 //   SPMV_PLAIN   y = A x                      SPMV_ADD      y += A x  (prolongation)
 //   SPMV_RESID   y = b - A x                  SPMV_CHEB     y = x + f1 (x - xold) + f2 dinv (b - A x)   (xold may be null)
 // ------------------------------------------------------------------------------------------------
@@ -16,53 +17,12 @@ namespace mgamd
     SPMV_RESID = 2,
     SPMV_CHEB  = 3
   };
+  // the rows [row_begin, row_end) of the product: the one body of both entry points below
   template <typename T, int MODE, int LANES>
-  __global__ void
-  __launch_bounds__(256) csr_spmv_kernel(uint32_t n_rows, const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ col,
-                                         const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, const T *__restrict__ b,
-                                         const T *__restrict__ xold, const T *__restrict__ dinv, T f1, T f2)
-  {
-    const uint32_t rows_per_block = 256 / LANES;
-    const uint32_t sub = threadIdx.x % LANES, lrow = threadIdx.x / LANES;
-    for (uint32_t row0 = blockIdx.x * rows_per_block; row0 < n_rows; row0 += gridDim.x * rows_per_block)
-      {
-        const uint32_t row = row0 + lrow;
-        T              s   = T(0);
-        if (row < n_rows)
-          {
-            const uint32_t e = ptr[row + 1];
-            for (uint32_t k = ptr[row] + sub; k < e; k += LANES)
-              s += val[k] * x[col[k]];
-          }
-#pragma unroll
-        for (int off = LANES / 2; off > 0; off >>= 1)
-          s += __shfl_down(s, off, LANES);
-        if (row < n_rows && sub == 0)
-          {
-            if (MODE == SPMV_PLAIN)
-              y[row] = s;
-            else if (MODE == SPMV_ADD)
-              y[row] += s;
-            else if (MODE == SPMV_RESID)
-              y[row] = b[row] - s;
-            else
-              {
-                const T xv = x[row], xo = xold ? xold[row] : T(0);
-                y[row]     = xv + f1 * (xv - xo) + f2 * dinv[row] * (b[row] - s);
-              }
-          }
-      }
-  }
-
-  // The same product on the rows [row_begin, row_end) only: the sharded cycle (runtime.hip AmgSharded) launches the interior rows
-  // of a level, imports the ghost columns underneath them, then launches the boundary rows.  Same four modes, same lanes per row
-  // and the same order of additions within a row as csr_spmv_kernel, so a row's result does not depend on how the rows are cut.
-  template <typename T, int MODE, int LANES>
-  __global__ void
-  __launch_bounds__(256) csr_spmv_range_kernel(uint32_t row_begin, uint32_t row_end, const uint32_t *__restrict__ ptr,
-                                               const uint32_t *__restrict__ col, const T *__restrict__ val, const T *__restrict__ x,
-                                               T *__restrict__ y, const T *__restrict__ b, const T *__restrict__ xold,
-                                               const T *__restrict__ dinv, T f1, T f2)
+  __device__ __forceinline__ void
+  csr_spmv_rows(uint32_t row_begin, uint32_t row_end, const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ col,
+                const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, const T *__restrict__ b,
+                const T *__restrict__ xold, const T *__restrict__ dinv, T f1, T f2)
   {
     const uint32_t rows_per_block = 256 / LANES;
     const uint32_t sub = threadIdx.x % LANES, lrow = threadIdx.x / LANES;
@@ -94,6 +54,29 @@ namespace mgamd
               }
           }
       }
+  }
+
+  // all rows: the products of a whole level (one rank; the replicated levels of a sharded cycle) and mgamd_debug_csr_spmv
+  template <typename T, int MODE, int LANES>
+  __global__ void
+  __launch_bounds__(256) csr_spmv_kernel(uint32_t n_rows, const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ col,
+                                         const T *__restrict__ val, const T *__restrict__ x, T *__restrict__ y, const T *__restrict__ b,
+                                         const T *__restrict__ xold, const T *__restrict__ dinv, T f1, T f2)
+  {
+    csr_spmv_rows<T, MODE, LANES>(0, n_rows, ptr, col, val, x, y, b, xold, dinv, f1, f2);
+  }
+
+  // The rows [row_begin, row_end) only: a sharded level of the cycle (runtime.hip AmgCycle) launches its interior rows, imports the
+  // ghost columns underneath them, then launches the boundary rows.  The same lanes per row and the same order of additions within
+  // a row as csr_spmv_kernel, so a row's result does not depend on how the rows are cut.
+  template <typename T, int MODE, int LANES>
+  __global__ void
+  __launch_bounds__(256) csr_spmv_range_kernel(uint32_t row_begin, uint32_t row_end, const uint32_t *__restrict__ ptr,
+                                               const uint32_t *__restrict__ col, const T *__restrict__ val, const T *__restrict__ x,
+                                               T *__restrict__ y, const T *__restrict__ b, const T *__restrict__ xold,
+                                               const T *__restrict__ dinv, T f1, T f2)
+  {
+    csr_spmv_rows<T, MODE, LANES>(row_begin, row_end, ptr, col, val, x, y, b, xold, dinv, f1, f2);
   }
 
   // owned entries -> send buffer of the ghost import (idx: local row per send slot; 0xFFFFFFFF: padding of the pair's segment)

@@ -1004,7 +1004,7 @@ namespace mgamd
   }
 
   // ------------------------------------------------------------------------------------------
-  // K7 launcher (kernels_amg.hpp): the one path of the AMG cycle and of mgamd_debug_csr_spmv
+  // K7 launchers (kernels_amg.hpp): the one path of the AMG cycle and of mgamd_debug_csr_spmv
   // ------------------------------------------------------------------------------------------
   int
   csr_spmv_lanes(uint32_t n_rows, size_t nnz)
@@ -1013,33 +1013,25 @@ namespace mgamd
     return avg <= 6 ? 4 : (avg <= 24 ? 8 : (avg <= 64 ? 16 : 32));
   }
 
-  template <typename T>
+  // f(mode tag, lanes tag) with the run-time mode and lane count as compile-time constants
+  template <typename F>
   void
-  launch_csr_spmv(hipStream_t stream, int mode, int lanes, uint32_t n_rows, const uint32_t *ptr, const uint32_t *col, const T *val, const T *x,
-                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
+  dispatch_spmv(int mode, int lanes, F &&f)
   {
-    if (!n_rows)
-      return;
-    auto launch = [&](auto mode_tag, auto lanes_tag) {
-      constexpr int MODE  = decltype(mode_tag)::value;
-      constexpr int LANES = decltype(lanes_tag)::value;
-      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
-      hipLaunchKernelGGL((csr_spmv_kernel<T, MODE, LANES>), grid, 256, 0, stream, n_rows, ptr, col, val, x, y, b, xold, dinv, T(f1), T(f2));
-    };
     auto with_lanes = [&](auto mode_tag) {
       switch (lanes)
         {
           case 4:
-            launch(mode_tag, std::integral_constant<int, 4>());
+            f(mode_tag, std::integral_constant<int, 4>());
             break;
           case 8:
-            launch(mode_tag, std::integral_constant<int, 8>());
+            f(mode_tag, std::integral_constant<int, 8>());
             break;
           case 16:
-            launch(mode_tag, std::integral_constant<int, 16>());
+            f(mode_tag, std::integral_constant<int, 16>());
             break;
           case 32:
-            launch(mode_tag, std::integral_constant<int, 32>());
+            f(mode_tag, std::integral_constant<int, 32>());
             break;
           default:
             throw std::invalid_argument("csr_spmv: lanes must be 4, 8, 16 or 32");
@@ -1062,6 +1054,22 @@ namespace mgamd
         default:
           throw std::invalid_argument("csr_spmv: unknown mode");
       }
+  }
+
+  // all rows of the matrix (csr_spmv_kernel)
+  template <typename T>
+  void
+  launch_csr_spmv(hipStream_t stream, int mode, int lanes, uint32_t n_rows, const uint32_t *ptr, const uint32_t *col, const T *val, const T *x,
+                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
+  {
+    if (!n_rows)
+      return;
+    dispatch_spmv(mode, lanes, [&](auto mode_tag, auto lanes_tag) {
+      constexpr int MODE  = decltype(mode_tag)::value;
+      constexpr int LANES = decltype(lanes_tag)::value;
+      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
+      hipLaunchKernelGGL((csr_spmv_kernel<T, MODE, LANES>), grid, 256, 0, stream, n_rows, ptr, col, val, x, y, b, xold, dinv, T(f1), T(f2));
+    });
     HIP_CHECK(hipGetLastError());
   }
   template void
@@ -1071,13 +1079,40 @@ namespace mgamd
   launch_csr_spmv<float>(hipStream_t, int, int, uint32_t, const uint32_t *, const uint32_t *, const float *, const float *, float *,
                          const float *, const float *, const float *, double, double);
 
+  // the rows [row_begin, row_end) only (csr_spmv_range_kernel): the interior and boundary launches of a sharded level
+  template <typename T>
+  void
+  launch_csr_spmv_range(hipStream_t stream, int mode, int lanes, uint32_t row_begin, uint32_t row_end, const uint32_t *ptr, const uint32_t *col,
+                        const T *val, const T *x, T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
+  {
+    if (row_end <= row_begin)
+      return;
+    const uint32_t n_rows = row_end - row_begin;
+    dispatch_spmv(mode, lanes, [&](auto mode_tag, auto lanes_tag) {
+      constexpr int MODE  = decltype(mode_tag)::value;
+      constexpr int LANES = decltype(lanes_tag)::value;
+      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
+      hipLaunchKernelGGL((csr_spmv_range_kernel<T, MODE, LANES>), grid, 256, 0, stream, row_begin, row_end, ptr, col, val, x, y, b, xold,
+                         dinv, T(f1), T(f2));
+    });
+    HIP_CHECK(hipGetLastError());
+  }
+
   // ------------------------------------------------------------------------------------------
   // Algebraic multigrid coarse solver on the device (host setup: amg.hpp).  The reference's "amg" / "cg_with_amg" coarse solvers
   // (ref:multigrid_throughput.cc:945-1016) apply Trilinos ML to Operator::get_trilinos_system_matrix; this is an own
   // smoothed-aggregation V-cycle on the same matrix: CSR products fused with the Chebyshev update (kernels.hpp K7).
+  //
+  // ONE cycle, two set-ups.  On one rank every level is whole and the cycle runs on the caller's vectors.  On a SHARDED coarse level
+  // (amg_shard.hpp: replicated setup, sharded cycle) every rank builds the one-rank hierarchy from the global tables of the coarse
+  // space and keeps its rows of A, P and R; a product is: interior rows, ghost import on ctx->side underneath them, boundary rows
+  // (the level operator's scheme, MGAMD_NO_HALO_OVERLAP=1: one launch after the import).  A whole level is a cut without a cut:
+  // its products are one launch over all rows.  The level-0 vectors of a sharded multigrid are consistent copies in the local
+  // [I|T|D|H] numbering: the owned rows are gathered on entry; on exit the owned results are scattered, the copies of other ranks'
+  // DoFs are zero and the level operator's exchange_add completes them (exact: it adds zeros).
   // ------------------------------------------------------------------------------------------
   template <typename T>
-  struct AmgDevice
+  struct AmgCycle
   {
     struct Mat
     {
@@ -1095,194 +1130,8 @@ namespace mgamd
         std::vector<T> v(std::max<size_t>(A.val.size(), 1), T(0));
         std::copy(A.val.begin(), A.val.end(), v.begin());
         val.upload(v);
-        lanes = csr_spmv_lanes(A.n_rows, A.nnz());
       }
     };
-    struct Lvl
-    {
-      Mat      A, P, R;
-      DBuf<T>  dinv, x, b, r, t;
-      double   theta = 1, delta = 0;
-      uint32_t n = 0;
-    };
-    Ctx                                        *ctx = nullptr;
-    std::vector<std::unique_ptr<Lvl>>           lv;
-    DBuf<double>                                coarse_inv;
-    std::vector<std::pair<uint32_t, uint64_t>>  sizes; // rows, non-zeros per level
-    unsigned                                    degree = 2; // Chebyshev smoother degree (MGAMD_AMG_SMOOTHER_DEGREE: development)
-
-    AmgDevice(Ctx *c, const LevelTables &tables)
-      : ctx(c)
-    {
-      if (const char *e = getenv("MGAMD_AMG_SMOOTHER_DEGREE"))
-        degree = std::max(1, atoi(e));
-      AmgHierarchyHost H = build_smoothed_aggregation(assemble_level_matrix(tables));
-      if (H.levels.back().A.n_rows > 4096)
-        throw std::runtime_error("AMG: coarsening stalled at " + std::to_string(H.levels.back().A.n_rows) + " rows");
-      for (size_t l = 0; l < H.levels.size(); ++l)
-        {
-          auto L = std::make_unique<Lvl>();
-          L->n   = H.levels[l].A.n_rows;
-          L->A.upload(H.levels[l].A);
-          if (l + 1 < H.levels.size())
-            {
-              L->P.upload(H.levels[l].P);
-              L->R.upload(H.levels[l].R);
-            }
-          std::vector<T> d(H.levels[l].dinv.begin(), H.levels[l].dinv.end());
-          L->dinv.upload(d);
-          L->r.alloc(L->n);
-          L->t.alloc(L->n);
-          if (l > 0)
-            {
-              L->x.alloc(L->n);
-              L->b.alloc(L->n);
-            }
-          // Chebyshev on [lambda_max / 20, lambda_max] (ML's "smoother: Chebyshev alpha" = 20)
-          const double mx = H.levels[l].lambda_max, mn = mx / 20.0;
-          L->theta = 0.5 * (mx + mn);
-          L->delta = 0.5 * (mx - mn);
-          sizes.push_back({L->n, H.levels[l].A.nnz()});
-          lv.push_back(std::move(L));
-        }
-      coarse_inv.upload(H.coarse_inv);
-    }
-
-    template <int MODE>
-    void
-    spmv(const Mat &A, const T *x, T *y, const T *b = nullptr, const T *xold = nullptr, const T *dinv = nullptr, double f1 = 0, double f2 = 0)
-    {
-      launch_csr_spmv<T>(ctx->stream, MODE, A.lanes, A.n_rows, A.ptr.p, A.col.p, A.val.p, x, y, b, xold, dinv, f1, f2);
-    }
-    // Chebyshev of degree `degree` in D^-1 A, zero start (deal.II / ML recurrences): result in x (t: scratch)
-    void
-    smooth_zero(Lvl &L, T *x, T *t, const T *b)
-    {
-      T *cur = (degree % 2 == 1) ? x : t, *oth = (cur == x) ? t : x;
-      hipLaunchKernelGGL(vec_scaled_product_kernel<T>, grid_for(L.n), 256, 0, ctx->stream, cur, T(1.0 / L.theta), L.dinv.p, b, (size_t)L.n);
-      double rhok = L.delta / L.theta;
-      const double sigma = L.theta / L.delta;
-      for (unsigned j = 0; j + 1 < degree; ++j)
-        {
-          const double rhokp = 1.0 / (2.0 * sigma - rhok);
-          spmv<SPMV_CHEB>(L.A, cur, oth, b, j == 0 ? nullptr : oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta); // x_old in place
-          rhok = rhokp;
-          std::swap(cur, oth);
-        }
-      // (degree - 1 swaps from the buffer chosen above: cur == x)
-    }
-    // general start x0 in x: result in x again
-    void
-    smooth_step(Lvl &L, T *x, T *t, const T *b)
-    {
-      T *cur = x, *oth = t;
-      spmv<SPMV_CHEB>(L.A, cur, oth, b, nullptr, L.dinv.p, 0.0, 1.0 / L.theta);
-      std::swap(cur, oth);
-      double rhok = L.delta / L.theta;
-      const double sigma = L.theta / L.delta;
-      for (unsigned j = 0; j + 1 < degree; ++j)
-        {
-          const double rhokp = 1.0 / (2.0 * sigma - rhok);
-          spmv<SPMV_CHEB>(L.A, cur, oth, b, oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
-          rhok = rhokp;
-          std::swap(cur, oth);
-        }
-      if (cur != x)
-        HIP_CHECK(hipMemcpyAsync(x, cur, (size_t)L.n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    void
-    cycle(size_t l, T *x, const T *b)
-    {
-      Lvl &L = *lv[l];
-      if (l + 1 == lv.size())
-        {
-          hipLaunchKernelGGL(dense_matvec_kernel<T>, (int)std::min<uint32_t>(L.n, 1024), 256, 0, ctx->stream, coarse_inv.p, b, x, (int)L.n);
-          return;
-        }
-      Lvl &C = *lv[l + 1];
-      smooth_zero(L, x, L.t.p, b);
-      spmv<SPMV_RESID>(L.A, x, L.r.p, b);
-      spmv<SPMV_PLAIN>(L.R, L.r.p, C.b.p);
-      cycle(l + 1, C.x.p, C.b.p);
-      spmv<SPMV_ADD>(L.P, C.x.p, x);
-      smooth_step(L, x, L.t.p, b);
-    }
-    // z = V(r): one V-cycle from a zero initial guess; z and r have the level's n_dofs entries
-    void
-    vcycle(T *z, const T *r)
-    {
-      cycle(0, z, r);
-      HIP_CHECK(hipGetLastError());
-    }
-  };
-
-  // K7 on the rows [row_begin, row_end) (csr_spmv_range_kernel): the launcher of the sharded AMG cycle
-  template <typename T>
-  void
-  launch_csr_spmv_range(hipStream_t stream, int mode, int lanes, uint32_t row_begin, uint32_t row_end, const uint32_t *ptr, const uint32_t *col,
-                        const T *val, const T *x, T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
-  {
-    if (row_end <= row_begin)
-      return;
-    const uint32_t n_rows = row_end - row_begin;
-    auto           launch = [&](auto mode_tag, auto lanes_tag) {
-      constexpr int MODE  = decltype(mode_tag)::value;
-      constexpr int LANES = decltype(lanes_tag)::value;
-      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
-      hipLaunchKernelGGL((csr_spmv_range_kernel<T, MODE, LANES>), grid, 256, 0, stream, row_begin, row_end, ptr, col, val, x, y, b, xold,
-                         dinv, T(f1), T(f2));
-    };
-    auto with_lanes = [&](auto mode_tag) {
-      switch (lanes)
-        {
-          case 4:
-            launch(mode_tag, std::integral_constant<int, 4>());
-            break;
-          case 8:
-            launch(mode_tag, std::integral_constant<int, 8>());
-            break;
-          case 16:
-            launch(mode_tag, std::integral_constant<int, 16>());
-            break;
-          case 32:
-            launch(mode_tag, std::integral_constant<int, 32>());
-            break;
-          default:
-            throw std::invalid_argument("csr_spmv: lanes must be 4, 8, 16 or 32");
-        }
-    };
-    switch (mode)
-      {
-        case SPMV_PLAIN:
-          with_lanes(std::integral_constant<int, SPMV_PLAIN>());
-          break;
-        case SPMV_ADD:
-          with_lanes(std::integral_constant<int, SPMV_ADD>());
-          break;
-        case SPMV_RESID:
-          with_lanes(std::integral_constant<int, SPMV_RESID>());
-          break;
-        case SPMV_CHEB:
-          with_lanes(std::integral_constant<int, SPMV_CHEB>());
-          break;
-        default:
-          throw std::invalid_argument("csr_spmv: unknown mode");
-      }
-    HIP_CHECK(hipGetLastError());
-  }
-
-  // ------------------------------------------------------------------------------------------
-  // The same V-cycle on a SHARDED coarse level (amg_shard.hpp: replicated setup, sharded cycle).  Every rank builds the one-rank
-  // hierarchy from the global tables of the coarse space and keeps its rows of A, P and R; a product is: interior rows, ghost
-  // import on ctx->side underneath them, boundary rows (the level operator's scheme, MGAMD_NO_HALO_OVERLAP=1: one launch after the
-  // import).  The level-0 vectors of the multigrid are consistent copies in the local [I|T|D|H] numbering: the owned rows are
-  // gathered on entry; on exit the owned results are scattered, the copies of other ranks' DoFs are zero and the level
-  // operator's exchange_add completes them (exact: it adds zeros).
-  // ------------------------------------------------------------------------------------------
-  template <typename T>
-  struct AmgSharded
-  {
-    using Mat = typename AmgDevice<T>::Mat;
     struct Lvl
     {
       Mat                   A, P, R;
@@ -1295,23 +1144,100 @@ namespace mgamd
       std::vector<uint32_t> peer_offset;
     };
     Ctx                              *ctx = nullptr;
-    LevelOperator<T>                 *op0 = nullptr;
+    LevelOperator<T>                 *op0 = nullptr; // sharded: level 0 of the multigrid; one rank: null, the cycle runs on its vectors
     std::shared_ptr<Comm>             comm;
     std::vector<std::unique_ptr<Lvl>> lv;
     DBuf<double>                      coarse_inv;
-    unsigned                          degree  = 2;
+    unsigned                          degree  = 2; // Chebyshev smoother degree (MGAMD_AMG_SMOOTHER_DEGREE: development)
     bool                              overlap = true;
     // level 0 <-> geometric vector
     DBuf<uint32_t> in_amg, in_geo, out_amg, out_geo;
     uint32_t       n_in = 0, n_out = 0;
 
-    AmgSharded(Ctx *c, LevelOperator<T> *op, const LevelTables &global, uint32_t min_sharded_rows)
+    AmgHierarchyHost
+    build_hierarchy(const LevelTables &tables)
+    {
+      if (const char *e = getenv("MGAMD_AMG_SMOOTHER_DEGREE"))
+        degree = std::max(1, atoi(e));
+      AmgHierarchyHost H = build_smoothed_aggregation(assemble_level_matrix(tables)); // (refuses local-smoothing levels)
+      if (H.levels.back().A.n_rows > 4096)
+        throw std::runtime_error("AMG: coarsening stalled at " + std::to_string(H.levels.back().A.n_rows) + " rows");
+      coarse_inv.upload(H.coarse_inv);
+      return H;
+    }
+    // level G of the hierarchy, cut as P says (null: whole)
+    void
+    add_level(const AmgLevelHost &G, const AmgShardLevel *P, bool last)
+    {
+      const bool whole = !P || P->replicated;
+      auto       L     = std::make_unique<Lvl>();
+      L->n_global = L->n = L->n_int = L->n_owned = G.A.n_rows;
+      if (P)
+        {
+          L->replicated  = P->replicated;
+          L->n_global    = P->n_global;
+          L->n           = P->n_rows;
+          L->n_int       = P->replicated ? P->n_rows : P->launch_interior();
+          L->n_recv      = P->n_recv;
+          L->n_owned     = P->n_owned();
+          L->n_ghost     = P->n_ghost;
+          L->peers       = P->peers;
+          L->peer_offset = P->peer_offset;
+        }
+      L->A.upload(whole ? G.A : P->A);
+      L->A.lanes = csr_spmv_lanes(G.A.n_rows, G.A.nnz()); // the whole matrix's lanes: the same additions per row however it is cut
+      if (!last)
+        {
+          L->P.upload(whole ? G.P : P->P);
+          L->R.upload(whole ? G.R : P->R);
+          L->P.lanes = csr_spmv_lanes(G.P.n_rows, G.P.nnz());
+          L->R.lanes = csr_spmv_lanes(G.R.n_rows, G.R.nnz());
+        }
+      std::vector<T> d(std::max<uint32_t>(L->n, 1), T(1));
+      for (uint32_t i = 0; i < L->n; ++i)
+        d[i] = (T)G.dinv[whole ? i : P->rows[i]];
+      L->dinv.upload(d);
+      // x, r, t are read through the columns of a product: room for the ghosts behind the local rows
+      const size_t nv = std::max<size_t>((size_t)L->n + L->n_recv, 1);
+      for (DBuf<T> *v : {&L->r, &L->t})
+        {
+          v->alloc(nv);
+          v->zero(ctx->stream);
+        }
+      if (op0 || !lv.empty()) // (one rank: level 0 works on the caller's vectors)
+        {
+          L->x.alloc(nv);
+          L->x.zero(ctx->stream);
+          L->b.alloc(std::max<uint32_t>(L->n, 1));
+          L->b.zero(ctx->stream);
+        }
+      if (L->n_recv)
+        {
+          L->send.alloc(L->n_recv);
+          L->send_idx.upload(P->send_idx);
+        }
+      // Chebyshev on [lambda_max / 20, lambda_max] (ML's "smoother: Chebyshev alpha" = 20)
+      const double mx = G.lambda_max, mn = mx / 20.0;
+      L->theta = 0.5 * (mx + mn);
+      L->delta = 0.5 * (mx - mn);
+      lv.push_back(std::move(L));
+    }
+
+    // one rank: the hierarchy of the level's own tables, every level whole
+    AmgCycle(Ctx *c, const LevelTables &tables)
+      : ctx(c)
+    {
+      const AmgHierarchyHost H = build_hierarchy(tables);
+      for (size_t l = 0; l < H.levels.size(); ++l)
+        add_level(H.levels[l], nullptr, l + 1 == H.levels.size());
+    }
+
+    // sharded level 0: the hierarchy of the global tables, this rank's rows of it
+    AmgCycle(Ctx *c, LevelOperator<T> *op, const LevelTables &global, uint32_t min_sharded_rows)
       : ctx(c)
       , op0(op)
       , comm(op->comm)
     {
-      if (const char *e = getenv("MGAMD_AMG_SMOOTHER_DEGREE"))
-        degree = std::max(1, atoi(e));
       overlap = getenv("MGAMD_NO_HALO_OVERLAP") == nullptr;
       if (auto *sub = dynamic_cast<SubsetComm *>(comm.get()))
         if (sub->group > 1)
@@ -1321,10 +1247,8 @@ namespace mgamd
       const LevelTables &local   = *op->tables;
       const std::vector<uint32_t> grow = match_rows_by_key(global, local); // (refuses another space)
       const std::vector<uint8_t>  own  = local_dof_owned(local);
-      AmgHierarchyHost            H    = build_smoothed_aggregation(assemble_level_matrix(global)); // (refuses local-smoothing levels)
-      if (H.levels.back().A.n_rows > 4096)
-        throw std::runtime_error("AMG: coarsening stalled at " + std::to_string(H.levels.back().A.n_rows) + " rows");
-      const uint32_t n0 = H.levels[0].A.n_rows;
+      const AmgHierarchyHost      H    = build_hierarchy(global);
+      const uint32_t              n0   = H.levels[0].A.n_rows;
       // owner stamps: one all-reduce builds the owner map of level 0 and checks that every row is owned exactly once
       std::vector<double> stamp(2 * (size_t)n0, 0.0);
       for (uint32_t d = 0; d < local.n_dofs; ++d)
@@ -1358,53 +1282,7 @@ namespace mgamd
       const AmgShardPlan S = build_amg_shard_plan(H, amg_level_owners(H, owner0, n_ranks, n_sharded), mirror0, n_ranks, rank);
 
       for (size_t l = 0; l < H.levels.size(); ++l)
-        {
-          const AmgLevelHost  &G = H.levels[l];
-          const AmgShardLevel &P = S.levels[l];
-          auto                 L = std::make_unique<Lvl>();
-          L->replicated          = P.replicated;
-          L->n_global            = P.n_global;
-          L->n                   = P.n_rows;
-          L->n_int               = P.replicated ? P.n_rows : P.launch_interior();
-          L->n_recv              = P.n_recv;
-          L->n_owned             = P.n_owned();
-          L->n_ghost             = P.n_ghost;
-          L->peers               = P.peers;
-          L->peer_offset         = P.peer_offset;
-          const bool last        = l + 1 == H.levels.size();
-          L->A.upload(P.replicated ? G.A : P.A);
-          L->A.lanes = csr_spmv_lanes(G.A.n_rows, G.A.nnz()); // the one-rank launch's lanes: the same additions per row
-          if (!last)
-            {
-              L->P.upload(P.replicated ? G.P : P.P);
-              L->R.upload(P.replicated ? G.R : P.R);
-              L->P.lanes = csr_spmv_lanes(G.P.n_rows, G.P.nnz());
-              L->R.lanes = csr_spmv_lanes(G.R.n_rows, G.R.nnz());
-            }
-          std::vector<T> d(std::max<uint32_t>(L->n, 1), T(1));
-          for (uint32_t i = 0; i < L->n; ++i)
-            d[i] = (T)G.dinv[P.replicated ? i : P.rows[i]];
-          L->dinv.upload(d);
-          // x, r, t are read through the columns of a product: room for the ghosts behind the local rows
-          const size_t nv = std::max<size_t>((size_t)L->n + L->n_recv, 1);
-          for (DBuf<T> *v : {&L->x, &L->r, &L->t})
-            {
-              v->alloc(nv);
-              v->zero(ctx->stream);
-            }
-          L->b.alloc(std::max<uint32_t>(L->n, 1));
-          L->b.zero(ctx->stream);
-          if (L->n_recv)
-            {
-              L->send.alloc(L->n_recv);
-              L->send_idx.upload(P.send_idx);
-            }
-          const double mx = G.lambda_max, mn = mx / 20.0;
-          L->theta = 0.5 * (mx + mn);
-          L->delta = 0.5 * (mx - mn);
-          lv.push_back(std::move(L));
-        }
-      coarse_inv.upload(H.coarse_inv);
+        add_level(H.levels[l], &S.levels[l], l + 1 == H.levels.size());
 
       std::vector<uint32_t> ia, ig, oa, og;
       if (S.levels[0].replicated)
@@ -1460,14 +1338,14 @@ namespace mgamd
     spmv(const Mat &M, Lvl *in, uint32_t n_int, T *x, T *y, const T *b = nullptr, const T *xold = nullptr, const T *dinv = nullptr,
          double f1 = 0, double f2 = 0)
     {
+      if (!in || in->replicated || !comm)
+        {
+          launch_csr_spmv<T>(ctx->stream, MODE, M.lanes, M.n_rows, M.ptr.p, M.col.p, M.val.p, x, y, b, xold, dinv, f1, f2);
+          return;
+        }
       auto rows = [&](uint32_t r0, uint32_t r1) {
         launch_csr_spmv_range<T>(ctx->stream, MODE, M.lanes, r0, r1, M.ptr.p, M.col.p, M.val.p, x, y, b, xold, dinv, f1, f2);
       };
-      if (!in || in->replicated || !comm)
-        {
-          rows(0, M.n_rows);
-          return;
-        }
       if (overlap && !in->peers.empty() && n_int > 0 && n_int < M.n_rows)
         {
           import_ghosts(*in, x, ctx->side);
@@ -1481,6 +1359,7 @@ namespace mgamd
           rows(0, M.n_rows);
         }
     }
+    // Chebyshev of degree `degree` in D^-1 A, zero start (deal.II / ML recurrences): result in x (t: scratch)
     void
     smooth_zero(Lvl &L, T *x, T *t, const T *b)
     {
@@ -1492,11 +1371,14 @@ namespace mgamd
       for (unsigned j = 0; j + 1 < degree; ++j)
         {
           const double rhokp = 1.0 / (2.0 * sigma - rhok);
+          // (x_old in place)
           spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, j == 0 ? nullptr : oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
           rhok = rhokp;
           std::swap(cur, oth);
         }
+      // (degree - 1 swaps from the buffer chosen above: cur == x)
     }
+    // general start x0 in x: result in x again
     void
     smooth_step(Lvl &L, T *x, T *t, const T *b)
     {
@@ -1540,12 +1422,15 @@ namespace mgamd
       spmv<SPMV_ADD>(L.P, &C, L.n_int, C.x.p, x);
       smooth_step(L, x, L.t.p, b);
     }
-    // z = V(r) on the level-0 vectors of the multigrid (local numbering, consistent copies)
+    // z = V(r): one V-cycle from a zero initial guess on the level-0 vectors of the multigrid (sharded: local numbering,
+    // consistent copies)
     void
     vcycle(T *z, const T *r)
     {
       Lvl &L = *lv[0];
-      if (L.replicated)
+      if (!op0)
+        cycle(0, z, r);
+      else if (L.replicated)
         {
           if (comm)
             L.b.zero(ctx->stream);
@@ -1553,15 +1438,15 @@ namespace mgamd
             hipLaunchKernelGGL(amg_level0_gather_kernel<T>, grid_for(n_in), 256, 0, ctx->stream, L.b.p, in_amg.p, r, in_geo.p, n_in);
           if (comm)
             comm->allreduce_sum(L.b.p, L.n, (int)sizeof(T), ctx->stream);
+          cycle(0, L.x.p, L.b.p);
+          hipLaunchKernelGGL(amg_level0_scatter_kernel<T>, grid_for(n_out), 256, 0, ctx->stream, z, out_geo.p, L.x.p, out_amg.p, n_out);
         }
-      else if (n_in)
-        hipLaunchKernelGGL(amg_level0_gather_kernel<T>, grid_for(n_in), 256, 0, ctx->stream, L.b.p, (const uint32_t *)nullptr, r, in_geo.p,
-                           n_in);
-      cycle(0, L.x.p, L.b.p);
-      if (L.replicated)
-        hipLaunchKernelGGL(amg_level0_scatter_kernel<T>, grid_for(n_out), 256, 0, ctx->stream, z, out_geo.p, L.x.p, out_amg.p, n_out);
       else
         {
+          if (n_in)
+            hipLaunchKernelGGL(amg_level0_gather_kernel<T>, grid_for(n_in), 256, 0, ctx->stream, L.b.p, (const uint32_t *)nullptr, r,
+                               in_geo.p, n_in);
+          cycle(0, L.x.p, L.b.p);
           HIP_CHECK(hipMemsetAsync(z, 0, (size_t)op0->n_dofs() * sizeof(T), ctx->stream));
           if (n_out)
             hipLaunchKernelGGL(amg_level0_scatter_kernel<T>, grid_for(n_out), 256, 0, ctx->stream, z, out_geo.p, L.x.p,
@@ -1683,8 +1568,7 @@ namespace mgamd
     }
 
     uint64_t       coarse_iterations = 0; // inner CG iterations of the coarse solver, accumulated
-    std::unique_ptr<AmgDevice<T>> amg;  // coarse solvers "amg", "cg_with_amg"
-    std::unique_ptr<AmgSharded<T>> amg_sharded; // the same on a sharded level 0 (by request: amg_global)
+    std::unique_ptr<AmgCycle<T>> amg; // coarse solvers "amg", "cg_with_amg": one rank, or a sharded level 0 (by request: amg_global)
     DBuf<T>                       amg_r, amg_z;
     MultigridBase *nested   = nullptr; // coarse solver "gmg_vcycle"
     unsigned       n_cycles = 1;
@@ -1703,12 +1587,8 @@ namespace mgamd
     amg_layout(std::vector<uint32_t> &out) const override
     {
       out.clear();
-      if (amg_sharded)
-        amg_sharded->layout(out);
-      else if (amg)
-        for (const auto &sz : amg->sizes) // one rank: every level whole, no ghosts, no peers
-          for (uint32_t v : {sz.first, sz.first, 0u, 0u, 1u})
-            out.push_back(v);
+      if (amg)
+        amg->layout(out);
     }
     void
     vcycle_level_raw(void *z, const void *r) override
@@ -1777,11 +1657,11 @@ namespace mgamd
       // ONE policy for the reference's Trilinos/PETSc choices ("amg", "cg_with_amg", "amg_petsc"):
       //   coarse level of <= 4096 DoFs (global coarsening ends on one cell): any AMG degenerates to an exact solve -> "direct";
       //   larger coarse level (PMG, HPMG with MinLevel): the library's own smoothed-aggregation AMG on the assembled level matrix
-      //     (amg.hpp, AmgDevice) -> "amg" / "cg_with_amg" (amg_petsc: BoomerAMG's role, the same SA hierarchy -> "amg");
+      //     (amg.hpp, AmgCycle) -> "amg" / "cg_with_amg" (amg_petsc: BoomerAMG's role, the same SA hierarchy -> "amg");
       //   a `nested` geometric multigrid on level 0's space, if the caller supplies one, takes the coarse solver's place as
       //     "gmg_vcycle" (the round-1/2 stand-in, still the DEFAULT on a SHARDED coarse level);
       //   `amg_global` (the global tables of level 0's space), if the caller supplies them, asks for the algebraic multigrid on a
-      //     sharded level 0: replicated setup, sharded cycle (AmgSharded) -> "amg" / "cg_with_amg".
+      //     sharded level 0: replicated setup, sharded cycle (AmgCycle's second set-up) -> "amg" / "cg_with_amg".
       // Never a silent substitution: coarse_used names what runs (harness table column / bench JSON).
       coarse_type = coarse;
       const bool amg_like = coarse == "amg" || coarse == "cg_with_amg" || coarse == "amg_petsc";
@@ -1791,7 +1671,7 @@ namespace mgamd
             throw std::invalid_argument("multigrid: the sharded algebraic multigrid takes the place of the AMG coarse solvers (amg, "
                                         "cg_with_amg, amg_petsc) and excludes a nested multigrid");
           coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
-          amg_sharded = std::make_unique<AmgSharded<T>>(ctx, ops[0], *amg_global, amg_min_sharded_rows);
+          amg         = std::make_unique<AmgCycle<T>>(ctx, ops[0], *amg_global, amg_min_sharded_rows);
         }
       else if (nested)
         {
@@ -1812,7 +1692,7 @@ namespace mgamd
                                          "from one rank's assembled matrix; use the nested geometric multigrid (gmg_vcycle), cg or "
                                          "cg_with_chebyshev");
               coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
-              amg         = std::make_unique<AmgDevice<T>>(ctx, *ops[0]->tables);
+              amg         = std::make_unique<AmgCycle<T>>(ctx, *ops[0]->tables);
             }
         }
       else if (coarse == "gmg_vcycle")
@@ -2005,17 +1885,11 @@ namespace mgamd
     amg_apply(T *z, const T *r, T *rr, T *zz)
     {
       const size_t n = ops[0]->n_dofs();
-      auto         V = [&](T *out, const T *in) {
-        if (amg_sharded)
-          amg_sharded->vcycle(out, in);
-        else
-          amg->vcycle(out, in);
-      };
-      V(z, r);
+      amg->vcycle(z, r);
       for (unsigned c = 1; c < n_cycles; ++c)
         {
           ops[0]->residual_raw(rr, r, z);
-          V(zz, rr);
+          amg->vcycle(zz, rr);
           hipLaunchKernelGGL(vec_sadd_kernel<T>, grid_for(n), 256, 0, ctx->stream, z, T(1), T(1), zz, n);
         }
     }

@@ -1,5 +1,5 @@
 """Independent numpy/scipy restatement of the smoothed-aggregation AMG behind the coarse solvers "amg", "cg_with_amg" and
-"amg_petsc" (DESIGN.md section 9), written from its specification, not from the C++ (csrc/amg.hpp, runtime.hip AmgDevice):
+"amg_petsc" (DESIGN.md section 9), written from its specification, not from the C++ (csrc/amg.hpp, runtime.hip AmgCycle):
 
   strength     j != i strongly coupled to i:  a_ij != 0  and  |a_ij| >= theta sqrt(|a_ii a_jj|),  theta = 1e-4
   aggregates   three greedy passes in row order over the rows with at least one strong connection (the others, the identity

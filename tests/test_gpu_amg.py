@@ -1,4 +1,4 @@
-"""The algebraic multigrid of the coarse solvers "amg", "cg_with_amg" (csrc/amg.hpp, runtime.hip AmgDevice, kernel K7 of
+"""The algebraic multigrid of the coarse solvers "amg", "cg_with_amg" (csrc/amg.hpp, runtime.hip AmgCycle, kernel K7 of
 kernels_amg.hpp) on the GPU against the independent numpy restatement oracle/amg_oracle.py:
   * K7 through its production launcher (mgamd_debug_csr_spmv) against float64 numpy: every mode, 4/8/16/32 lanes and the
     automatic choice, double and float, on CSR matrices with empty, 1-entry and long rows and on one large enough for the
@@ -6,7 +6,7 @@ kernels_amg.hpp) on the GPU against the independent numpy restatement oracle/amg
   * the one-level AMG (a p = 1 PMG hierarchy: a pure application of the coarse solver), with 1 and 2 cycles and Chebyshev degrees
     1-4 (MGAMD_AMG_SMOOTHER_DEGREE: the odd degrees start in the other buffer);
   * cg_with_amg, whole PMG V-cycles and the outer CG with "amg" x 2 on the coarse level;
-  * FP32 levels (AmgDevice<float>) against the FP64 oracle;
+  * FP32 levels (AmgCycle<float>) against the FP64 oracle;
   * "gmg_vcycle" without a nested multigrid.
 Every output vector is filled with NaN before the call that must overwrite it."""
 import copy
@@ -118,7 +118,7 @@ def amg_oracles():
 
 def _one_level(mgamd, ctx, monkeypatch, geo, L, degree, n_cycles, coarse="amg", number_type=None):
     if degree != 2:
-        monkeypatch.setenv("MGAMD_AMG_SMOOTHER_DEGREE", str(degree))  # read when AmgDevice is built
+        monkeypatch.setenv("MGAMD_AMG_SMOOTHER_DEGREE", str(degree))  # read when AmgCycle is built
     kw = {} if number_type is None else dict(number_type=number_type)
     h = mgamd.Hierarchy(ctx, geo, L, 1, "PMG", coarse_solver=coarse, coarse_n_cycles=n_cycles, **kw)
     monkeypatch.delenv("MGAMD_AMG_SMOOTHER_DEGREE", raising=False)
@@ -233,7 +233,7 @@ def test_pmg_vcycle_with_amg_equals_oracle(mgamd, ctx, pmg_oracles, p):
     assert it == itref and err_x <= TOL_SOL, (it, itref, err_x)
 
 
-# ------------------------------------------------------------------ FP32 levels: AmgDevice<float>
+# ------------------------------------------------------------------ FP32 levels: AmgCycle<float>
 def test_one_level_amg_float(mgamd, ctx, amg_oracles, monkeypatch):
     rng = np.random.default_rng(8)
     for n_cycles in (1, 2):

@@ -1,5 +1,5 @@
-"""The AMG coarse solvers on a SHARDED coarse level (csrc/amg_shard.hpp, runtime.hip AmgSharded, the ranged K7 and the level-0
-gather / scatter kernels of kernels_amg.hpp) on simulated ranks: n ranks run as host threads over the in-process communicator
+"""The AMG coarse solvers on a SHARDED coarse level (csrc/amg_shard.hpp, runtime.hip AmgCycle in its sharded set-up, the ranged
+entry point of K7 and the level-0 gather / scatter kernels of kernels_amg.hpp) on simulated ranks: n ranks run as host threads over the in-process communicator
 (as in test_gpu_distributed_sim.py); partition, shard plans, ghost imports, partial restrictions + all-reduce and the level-0
 exchange are the production code.  Compared, through the geometric DoF keys, with the independent numpy restatement
 oracle/amg_oracle.py on the GLOBAL matrix and with the one-rank Hierarchy.  Tolerances: test_gpu_amg.py's own."""
