@@ -10,6 +10,8 @@ follow deal.II as the reference uses it:
   MGTwoLevelTransfer       <-> MGTwoLevelTransfer<3,Vector>                            (ref:multigrid_throughput.cc:1600-1604)
   PreconditionMG           <-> Multigrid + PreconditionMG + MGTransferGlobalCoarsening (ref:multigrid_throughput.cc:1093-1133)
   solve_cg                 <-> SolverCG + ReductionControl                             (ref:multigrid_throughput.cc:1140-1147)
+  SparseMatrix             <-> Operator::get_trilinos_system_matrix on the device      (ref:include/operator.h:244-287)
+  PreconditionAMG          <-> TrilinosWrappers::PreconditionAMG                       (ref:multigrid_throughput.cc:1907-1909)
   solve_with_global_coarsening  (ref:multigrid_throughput.cc:1443-1666)
 
 There is no CPU fallback: every device call raises if the HIP library or a gfx950 GPU is missing.
@@ -499,6 +501,10 @@ class Operator:
         """constraints.distribute(solution): Dirichlet values of `kind`, hanging nodes interpolated"""
         _chk(_lib.mgamd_level_op_distribute(self._h, kind, x._h))
 
+    def get_system_matrix(self) -> "SparseMatrix":
+        """Operator::get_trilinos_system_matrix: the assembled matrix of this operator's DoFs on the device (FP64, one rank)"""
+        return SparseMatrix(self.ctx, self.dofs)
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mgamd_level_op_destroy(self._h)
@@ -647,10 +653,73 @@ class PreconditionMG:
             self._h = None
 
 
-def solve_cg(A: Operator, preconditioner, x: Vector, b: Vector, reltol=1e-4, abstol=1e-20, maxiter=10000):
-    """SolverCG<Vector>(ReductionControl(maxiter, abstol, reltol)).solve(A, x, b, preconditioner) from x = 0."""
+class SparseMatrix:
+    """The assembled system matrix on the device (mgamd_matrix_create): what Operator::get_trilinos_system_matrix returns and
+    Type "AMG" runs CG on (ref:multigrid_throughput.cc:1877-1966).  FP64; refuses distributed and local-smoothing DoFs."""
+
+    def __init__(self, ctx: Context, dofs: DoFs):
+        self.ctx, self.dofs = ctx, dofs
+        self._h = C.c_void_p()
+        _chk(_lib.mgamd_matrix_create(ctx._h, dofs._h, C.byref(self._h)))
+        n, nnz, lanes = C.c_uint64(), C.c_uint64(), C.c_int()
+        _chk(_lib.mgamd_matrix_info(self._h, C.byref(n), C.byref(nnz), C.byref(lanes)))
+        self.n_rows, self.nnz, self.lanes = n.value, nnz.value, lanes.value
+
+    def m(self) -> int:
+        return self.n_rows
+
+    def vmult(self, dst: Vector, src: Vector):
+        _chk(_lib.mgamd_matrix_vmult(self._h, dst._h, src._h))
+
+    def time_spmv(self, mode: int, lanes: int, reps: int = 50) -> float:
+        """measurement (tools/spmv_bench.py): milliseconds per launch of the product in `mode` (SPMV_PLAIN, SPMV_CHEB, SPMV_DOT)
+        at `lanes` lanes per row, HIP events around `reps` launches"""
+        ms = C.c_double()
+        _chk(_lib.mgamd_debug_matrix_time_spmv(self._h, mode, lanes, reps, C.byref(ms)))
+        return ms.value
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mgamd_matrix_destroy(self._h)
+            self._h = None
+
+
+class PreconditionAMG:
+    """TrilinosWrappers::PreconditionAMG on a SparseMatrix (mgamd_amg_create): n_cycles V-cycles of the library's
+    smoothed-aggregation AMG; level 0 works on the matrix's own device arrays."""
+
+    def __init__(self, matrix: SparseMatrix, n_cycles: int = 1):
+        self.matrix, self.n_cycles = matrix, n_cycles
+        self._h = C.c_void_p()
+        _chk(_lib.mgamd_amg_create(matrix._h, n_cycles, C.byref(self._h)))
+
+    def vmult(self, z: Vector, r: Vector):
+        _chk(_lib.mgamd_amg_vmult(self._h, z._h, r._h))
+
+    def layout(self):
+        """rows of every AMG level, finest first"""
+        n, rows = C.c_uint32(), (C.c_uint32 * 32)()
+        _chk(_lib.mgamd_amg_layout(self._h, C.byref(n), rows, 32))
+        return [rows[l] for l in range(min(n.value, 32))]
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mgamd_amg_destroy(self._h)
+            self._h = None
+
+
+def solve_cg(A, preconditioner, x: Vector, b: Vector, reltol=1e-4, abstol=1e-20, maxiter=10000):
+    """SolverCG<Vector>(ReductionControl(maxiter, abstol, reltol)).solve(A, x, b, preconditioner) from x = 0.
+    A: an Operator with a PreconditionMG (or None), or a SparseMatrix with a PreconditionAMG built on it (or None)."""
     it, res = C.c_uint(), C.c_double()
     ph = preconditioner._h if preconditioner is not None else None
+    if isinstance(A, SparseMatrix):
+        if preconditioner is not None and not isinstance(preconditioner, PreconditionAMG):
+            raise MgamdError("solve_cg: a SparseMatrix takes a PreconditionAMG (or None)")
+        _chk(_lib.mgamd_solve_cg_matrix(A._h, ph, x._h, b._h, C.c_double(reltol), C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
+        return it.value, res.value
+    if isinstance(preconditioner, PreconditionAMG):
+        raise MgamdError("solve_cg: a PreconditionAMG goes with the SparseMatrix it was built on")
     _chk(_lib.mgamd_solve_cg(A._h, ph, x._h, b._h, C.c_double(reltol), C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
     return it.value, res.value
 
@@ -722,7 +791,7 @@ class AmgShardPlans:
             self._h = None
 
 
-SPMV_PLAIN, SPMV_ADD, SPMV_RESID, SPMV_CHEB = 0, 1, 2, 3
+SPMV_PLAIN, SPMV_ADD, SPMV_RESID, SPMV_CHEB, SPMV_DOT = 0, 1, 2, 3, 4
 
 
 def debug_csr_spmv(ctx: "Context", number_type, mode, lanes, ptr, col, val, x, y, b=None, xold=None, xold_is_y=False, dinv=None, f1=0.0,
@@ -740,6 +809,40 @@ def debug_csr_spmv(ctx: "Context", number_type, mode, lanes, ptr, col, val, x, y
                                    _ptr(x), _ptr(y), *[None if a is None else _ptr(a) for a in opt[:2]], 1 if xold_is_y else 0,
                                    None if opt[2] is None else _ptr(opt[2]), C.c_double(f1), C.c_double(f2), C.byref(used)))
     return y, used.value
+
+
+def debug_csr_spmv_ex(ctx: "Context", mode, lanes, ptr, col, val, x, y, b=None, xold=None, xold_is_y=False, dinv=None, f1=0.0, f2=0.0,
+                      max_blocks=0, number_type=F64):
+    """debug_csr_spmv with what the assembled operator adds (mgamd_debug_csr_spmv_ex): lanes 64 (one wavefront per row) and
+    SPMV_DOT; max_blocks > 0 caps the grid.  Returns (y, lanes used, blocks launched, x . y or 0.0)"""
+    ptr, col = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(col, np.uint32)
+    val, x, y = (np.ascontiguousarray(a, np.float64) for a in (val, x, y))
+    y = y.copy()
+    opt = [None if a is None else np.ascontiguousarray(a, np.float64) for a in (b, xold, dinv)]
+    n_rows = len(ptr) - 1
+    assert len(y) == n_rows and len(col) == len(val) == ptr[-1]
+    used, blocks, dot = C.c_int(), C.c_int(), C.c_double()
+    _chk(_lib.mgamd_debug_csr_spmv_ex(ctx._h, number_type, mode, lanes, C.c_uint32(n_rows), C.c_uint32(len(x)), _ptr(ptr), _ptr(col),
+                                      _ptr(val), _ptr(x), _ptr(y), *[None if a is None else _ptr(a) for a in opt[:2]],
+                                      1 if xold_is_y else 0, None if opt[2] is None else _ptr(opt[2]), C.c_double(f1), C.c_double(f2),
+                                      max_blocks, C.byref(used), C.byref(blocks), C.byref(dot)))
+    return y, used.value, blocks.value, dot.value
+
+
+def csr_spmv_lanes_long(n_rows: int, nnz: int) -> int:
+    """lanes per row the assembled operator and its AMG choose for a matrix of these sizes (64: one wavefront per row)"""
+    lanes = C.c_int()
+    _chk(_lib.mgamd_debug_csr_spmv_lanes_long(C.c_uint32(n_rows), C.c_uint64(nnz), C.byref(lanes)))
+    return lanes.value
+
+
+def csr_row_pointers(row_counts):
+    """the 32-bit row pointers assemble_level_matrix builds from 64-bit entry counts per row (host only); MgamdError when the
+    matrix would need more than 2^32 - 1 entries"""
+    counts = np.ascontiguousarray(row_counts, np.uint64)
+    ptr = np.zeros(len(counts) + 1, np.uint32)
+    _chk(_lib.mgamd_debug_csr_row_pointers(C.c_uint32(len(counts)), _ptr(counts), _ptr(ptr)))
+    return ptr
 
 
 AMG_COARSE_SOLVERS = ("amg", "cg_with_amg", "amg_petsc")
@@ -785,6 +888,18 @@ class Hierarchy:
         elif mg_type == "HMG-local":
             self._build_local_smoothing(ctx, fine, degree, smoother_degree, smoothing_range, eig_cg_n_iterations, coarse_solver, number_type,
                                         max_brick)
+            return
+        elif mg_type in ("AMG", "AMGPETSc"):
+            # solve_with_amg (ref:multigrid_throughput.cc:1877-1966): no multigrid levels; CG on the assembled matrix of the one
+            # level with the AMG built on it: solve_cg(h.system_matrix, h.amg, x, b).  FP64 whatever number_type says, as in the
+            # reference; coarse_n_cycles: AMG cycles per application.  AMGPETSc (BoomerAMG's role): the same solver.
+            self.trias, self.degrees = [fine], [degree]
+            self.dofs = [DoFs(fine, degree, max_brick)]
+            self.fine_operator = Operator(ctx, self.dofs[0], F64)
+            self.operators, self.transfers, self.smoothers, self.coarse, self.mg = [self.fine_operator], [None], [None], None, None
+            self.system_matrix = self.fine_operator.get_system_matrix()
+            self.amg = PreconditionAMG(self.system_matrix, coarse_n_cycles)
+            self.n_dofs = self.dofs[0].n_dofs
             return
         elif mg_type == "HPMG-local":
             # ref:multigrid_throughput.cc:1685-1695,1846-1860: p-multigrid on the active mesh whose coarse problem (lowest degree)

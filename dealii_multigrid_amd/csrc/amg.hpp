@@ -23,6 +23,8 @@
 #include <algorithm>
 #include <cmath>
 #include <numeric>
+#include <stdexcept>
+#include <string>
 
 namespace mgamd
 {
@@ -37,6 +39,28 @@ namespace mgamd
       return col.size();
     }
   };
+
+  // row pointers from the entries per row.  CSR::ptr is 32-bit: the counts are accumulated in 64 bits and a matrix of more than
+  // 2^32 - 1 entries is refused here, where the sum would otherwise wrap
+  inline std::vector<uint32_t>
+  csr_row_pointers(const std::vector<uint64_t> &row_counts)
+  {
+    std::vector<uint32_t> ptr(row_counts.size() + 1, 0);
+    uint64_t              total = 0;
+    for (size_t i = 0; i < row_counts.size(); ++i)
+      {
+        total += row_counts[i]; // (a count is at most 2^32: n_dofs columns; 2^32 of them cannot wrap 64 bits)
+        if (total > 0xFFFFFFFFull)
+          {
+            for (size_t j = i + 1; j < row_counts.size(); ++j)
+              total += row_counts[j];
+            throw std::length_error("assembled matrix: " + std::to_string(total) + " entries in " + std::to_string(row_counts.size()) +
+                                    " rows, more than the 4294967295 that 32-bit CSR row pointers can address");
+          }
+        ptr[i + 1] = (uint32_t)total;
+      }
+    return ptr;
+  }
 
   // Operator::get_trilinos_system_matrix (ref:include/operator.h:244-287) without Trilinos
   inline CSR
@@ -98,7 +122,7 @@ namespace mgamd
     CSR A;
     A.n_rows = A.n_cols = L.n_dofs;
     // pattern: per row the columns of all touching cells, then sort + unique
-    std::vector<uint32_t> cnt(L.n_dofs + 1, 0);
+    std::vector<uint64_t> cnt(L.n_dofs + 1, 0);
     for (size_t ci = 0; ci < nc; ++ci)
       for (int i = 0; i < n3; ++i)
         if (idx[ci * n3 + i] != INVALID_DOF)
@@ -122,14 +146,16 @@ namespace mgamd
       for (uint32_t i = L.first_constrained(); i < L.n_dofs; ++i)
         cols[fill[i]++] = i;
     }
-    A.ptr.assign(L.n_dofs + 1, 0);
-    for (uint32_t i = 0; i < L.n_dofs; ++i)
-      {
-        auto b = cols.begin() + start[i], e = cols.begin() + start[i + 1];
-        std::sort(b, e);
-        e            = std::unique(b, e);
-        A.ptr[i + 1] = A.ptr[i] + (uint32_t)(e - b);
-      }
+    {
+      std::vector<uint64_t> row_counts(L.n_dofs);
+      for (uint32_t i = 0; i < L.n_dofs; ++i)
+        {
+          auto b = cols.begin() + start[i], e = cols.begin() + start[i + 1];
+          std::sort(b, e);
+          row_counts[i] = (uint64_t)(std::unique(b, e) - b);
+        }
+      A.ptr = csr_row_pointers(row_counts);
+    }
     A.col.resize(A.ptr[L.n_dofs]);
     for (uint32_t i = 0; i < L.n_dofs; ++i)
       std::copy(cols.begin() + start[i], cols.begin() + start[i] + (A.ptr[i + 1] - A.ptr[i]), A.col.begin() + A.ptr[i]);

@@ -1,5 +1,6 @@
 // C ABI, device entry points (include/mgamd.h, section "Device runtime").
 #include "runtime.hpp"
+#include "kernels_amg.hpp"
 #include <cstdio>
 
 using namespace mgamd;
@@ -857,7 +858,8 @@ namespace
   template <typename T>
   void
   debug_csr_spmv(Ctx &c, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr, const uint32_t *col, const double *val,
-                 const double *x, double *y, const double *b, const double *xold, bool xold_is_y, const double *dinv, double f1, double f2)
+                 const double *x, double *y, const double *b, const double *xold, bool xold_is_y, const double *dinv, double f1, double f2,
+                 int max_blocks, double *dot, int *blocks)
   {
     const size_t nnz = ptr[n_rows];
     auto         dev = [&](DBuf<T> &buf, const double *h, size_t n) -> T * {
@@ -877,8 +879,20 @@ namespace
     dev(dval, val, nnz);
     dev(dx, x, n_cols);
     T *yp = dev(dy, y, n_rows);
-    launch_csr_spmv<T>(c.stream, mode, lanes, n_rows, dptr.p, dcol.p, dval.p, dx.p, yp, dev(db, b, n_rows),
-                       xold_is_y ? yp : dev(dxold, xold, n_rows), dev(ddinv, dinv, n_rows), f1, f2);
+    const int g = launch_csr_spmv<T>(c.stream, mode, lanes, n_rows, dptr.p, dcol.p, dval.p, dx.p, yp, dev(db, b, n_rows),
+                                     xold_is_y ? yp : dev(dxold, xold, n_rows), dev(ddinv, dinv, n_rows), f1, f2,
+                                     mode == SPMV_DOT ? c.d_partial : nullptr, max_blocks);
+    if (blocks)
+      *blocks = g;
+    if (mode == SPMV_DOT)
+      {
+        // as the solver finishes the sum
+        hipLaunchKernelGGL(vec_dot_final_kernel<>, 1, 256, 0, c.stream, c.d_partial, g, c.d_result);
+        HIP_CHECK(hipMemcpyAsync(c.h_result, c.d_result, sizeof(double), hipMemcpyDeviceToHost, c.stream));
+        HIP_CHECK(hipStreamSynchronize(c.stream));
+        if (dot)
+          *dot = c.h_result[0];
+      }
     std::vector<T> out(std::max<size_t>(n_rows, 1));
     HIP_CHECK(hipMemcpyAsync(out.data(), yp, (size_t)n_rows * sizeof(T), hipMemcpyDeviceToHost, c.stream));
     HIP_CHECK(hipStreamSynchronize(c.stream));
@@ -889,15 +903,17 @@ namespace
 extern "C" {
 
 int
-mgamd_debug_csr_spmv(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr,
-                     const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold, int xold_is_y,
-                     const double *dinv, double f1, double f2, int *lanes_used)
+mgamd_debug_csr_spmv_ex(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr,
+                        const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold,
+                        int xold_is_y, const double *dinv, double f1, double f2, int max_blocks, int *lanes_used, int *blocks, double *dot)
 {
   MGAMD_TRY
   REQUIRE(ctx && ptr && x && y);
   REQUIRE(number_type == MGAMD_F64 || number_type == MGAMD_F32);
-  REQUIRE(mode >= 0 && mode <= 3);
-  REQUIRE(lanes == 0 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32);
+  REQUIRE(mode >= 0 && mode <= 4);
+  REQUIRE(lanes == 0 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == 64);
+  REQUIRE(number_type == MGAMD_F64 || (mode != 4 && lanes != 64));
+  REQUIRE(max_blocks >= 0);
   // every index the kernel follows is checked here, on the host
   REQUIRE(ptr[0] == 0);
   for (uint32_t i = 0; i < n_rows; ++i)
@@ -907,15 +923,164 @@ mgamd_debug_csr_spmv(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint3
     REQUIRE(col[k] < n_cols);
   REQUIRE(mode != 2 || b);
   REQUIRE(mode != 3 || (b && dinv && n_cols == n_rows));
+  REQUIRE(mode != 4 || n_cols == n_rows);
   REQUIRE(!(xold_is_y && xold));
   if (!lanes)
     lanes = csr_spmv_lanes(n_rows, ptr[n_rows]);
   if (lanes_used)
     *lanes_used = lanes;
+  if (blocks)
+    *blocks = 0;
+  if (dot)
+    *dot = 0.0;
   if (number_type == MGAMD_F64)
-    debug_csr_spmv<double>(*ctx->ctx, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y != 0, dinv, f1, f2);
+    debug_csr_spmv<double>(*ctx->ctx, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y != 0, dinv, f1, f2, max_blocks, dot,
+                           blocks);
   else
-    debug_csr_spmv<float>(*ctx->ctx, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y != 0, dinv, f1, f2);
+    debug_csr_spmv<float>(*ctx->ctx, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y != 0, dinv, f1, f2, max_blocks, dot,
+                          blocks);
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_csr_spmv(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr,
+                     const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold, int xold_is_y,
+                     const double *dinv, double f1, double f2, int *lanes_used)
+{
+  return mgamd_debug_csr_spmv_ex(ctx, number_type, mode, lanes, n_rows, n_cols, ptr, col, val, x, y, b, xold, xold_is_y, dinv, f1, f2, 0,
+                                 lanes_used, nullptr, nullptr);
+}
+
+int
+mgamd_debug_csr_spmv_lanes_long(uint32_t n_rows, uint64_t nnz, int *lanes)
+{
+  MGAMD_TRY
+  REQUIRE(lanes);
+  *lanes = csr_spmv_lanes_long(n_rows, nnz);
+  MGAMD_CATCH
+}
+
+// ---- Type "AMG": the assembled matrix, its AMG, CG on the pair (mgamd.h)
+int
+mgamd_matrix_create(mgamd_ctx *ctx, const mgamd_dofs *dofs, mgamd_matrix **out)
+{
+  MGAMD_TRY
+  REQUIRE(ctx && dofs && out);
+  auto *h = new mgamd_matrix;
+  try
+    {
+      h->A = make_assembled_matrix(ctx->ctx.get(), dofs);
+    }
+  catch (...)
+    {
+      delete h;
+      throw;
+    }
+  *out = h;
+  MGAMD_CATCH
+}
+
+int
+mgamd_matrix_destroy(mgamd_matrix *A)
+{
+  delete A;
+  return MGAMD_OK;
+}
+
+int
+mgamd_matrix_info(const mgamd_matrix *A, uint64_t *n_rows, uint64_t *nnz, int *lanes)
+{
+  MGAMD_TRY
+  REQUIRE(A);
+  if (n_rows)
+    *n_rows = A->A->n_rows;
+  if (nnz)
+    *nnz = A->A->nnz;
+  if (lanes)
+    *lanes = A->A->lanes;
+  MGAMD_CATCH
+}
+
+int
+mgamd_matrix_vmult(mgamd_matrix *A, mgamd_vec *dst, const mgamd_vec *src)
+{
+  MGAMD_TRY
+  REQUIRE(A && dst && src);
+  A->A->vmult(*dst, *src);
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_matrix_time_spmv(mgamd_matrix *A, int mode, int lanes, unsigned reps, double *ms_per_launch)
+{
+  MGAMD_TRY
+  REQUIRE(A && ms_per_launch);
+  REQUIRE(mode == 0 || mode == 3 || mode == 4);
+  *ms_per_launch = A->A->time_spmv(mode, lanes, reps);
+  MGAMD_CATCH
+}
+
+int
+mgamd_amg_create(mgamd_matrix *A, unsigned n_cycles, mgamd_amg **out)
+{
+  MGAMD_TRY
+  REQUIRE(A && out);
+  auto *h = new mgamd_amg;
+  try
+    {
+      h->P.reset(make_amg_preconditioner(A->A, n_cycles));
+    }
+  catch (...)
+    {
+      delete h;
+      throw;
+    }
+  *out = h;
+  MGAMD_CATCH
+}
+
+int
+mgamd_amg_destroy(mgamd_amg *P)
+{
+  delete P;
+  return MGAMD_OK;
+}
+
+int
+mgamd_amg_vmult(mgamd_amg *P, mgamd_vec *z, const mgamd_vec *r)
+{
+  MGAMD_TRY
+  REQUIRE(P && z && r);
+  P->P->vmult(*z, *r);
+  MGAMD_CATCH
+}
+
+int
+mgamd_amg_layout(const mgamd_amg *P, uint32_t *n_levels, uint32_t *rows, uint32_t max_levels)
+{
+  MGAMD_TRY
+  REQUIRE(P && n_levels);
+  std::vector<uint32_t> v;
+  P->P->layout(v);
+  *n_levels = (uint32_t)v.size();
+  if (rows)
+    std::copy(v.begin(), v.begin() + std::min<size_t>(v.size(), max_levels), rows);
+  MGAMD_CATCH
+}
+
+int
+mgamd_solve_cg_matrix(mgamd_matrix *A, mgamd_amg *preconditioner, mgamd_vec *x, const mgamd_vec *b, double reltol, double abstol,
+                      unsigned maxiter, unsigned *n_iterations, double *residual_norm)
+{
+  MGAMD_TRY
+  REQUIRE(A && x && b);
+  unsigned it  = 0;
+  double   res = 0;
+  solve_cg_matrix(*A->A, preconditioner ? preconditioner->P.get() : nullptr, *x, *b, reltol, abstol, maxiter, it, res);
+  if (n_iterations)
+    *n_iterations = it;
+  if (residual_norm)
+    *residual_norm = res;
   MGAMD_CATCH
 }
 

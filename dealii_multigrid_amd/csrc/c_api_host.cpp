@@ -89,6 +89,17 @@ mgamd_dofs_matrix(const mgamd_dofs *d, uint64_t *nnz, uint32_t *row_ptr, uint32_
 }
 
 int
+mgamd_debug_csr_row_pointers(uint32_t n_rows, const uint64_t *row_counts, uint32_t *ptr)
+{
+  MGAMD_TRY
+  if ((n_rows && !row_counts) || !ptr)
+    throw std::invalid_argument("null argument");
+  const std::vector<uint32_t> p = csr_row_pointers(std::vector<uint64_t>(row_counts, row_counts + n_rows));
+  std::copy(p.begin(), p.end(), ptr);
+  MGAMD_CATCH
+}
+
+int
 mgamd_dofs_amg_setup_info(const mgamd_dofs *d, uint32_t *n_levels, uint32_t *rows, uint64_t *nnz, uint32_t max_levels)
 {
   MGAMD_TRY

@@ -446,6 +446,56 @@ namespace mgamd
     std::shared_ptr<mgamd_vec> h;
   };
 
+  // TrilinosWrappers::SparseMatrix as Type "AMG" uses it: Operator::get_system_matrix() (the reference's
+  // get_trilinos_system_matrix / get_petsc_system_matrix, ref:include/operator.h:244-358) on the device, FP64, one rank
+  class SparseMatrix
+  {
+  public:
+    using VectorType = Vector;
+    SparseMatrix() = default;
+    SparseMatrix(const Context &ctx, const DoFHandler &dof_handler)
+    {
+      mgamd_matrix *a = nullptr;
+      check(mgamd_matrix_create(ctx.get(), dof_handler.get(), &a));
+      h.reset(a, mgamd_matrix_destroy);
+    }
+    uint64_t
+    m() const
+    {
+      uint64_t n = 0;
+      check(mgamd_matrix_info(h.get(), &n, nullptr, nullptr));
+      return n;
+    }
+    uint64_t
+    n_nonzero_elements() const
+    {
+      uint64_t n = 0;
+      check(mgamd_matrix_info(h.get(), nullptr, &n, nullptr));
+      return n;
+    }
+    // lanes per row of its products (64: one wavefront per row)
+    int
+    lanes_per_row() const
+    {
+      int l = 0;
+      check(mgamd_matrix_info(h.get(), nullptr, nullptr, &l));
+      return l;
+    }
+    void
+    vmult(Vector &dst, const Vector &src) const
+    {
+      check(mgamd_matrix_vmult(h.get(), dst.get(), src.get()));
+    }
+    mgamd_matrix *
+    get() const
+    {
+      return h.get();
+    }
+
+  private:
+    std::shared_ptr<mgamd_matrix> h;
+  };
+
   // Operator<dim=3, n_components=1, Number> (ref:include/operator.h:11)
   class Operator
   {
@@ -459,6 +509,8 @@ namespace mgamd
       mgamd_level_op *o = nullptr;
       check(mgamd_level_op_create(ctx.get(), dof_handler.get(), number_type, &o));
       h.reset(o, mgamd_level_op_destroy);
+      context = std::make_shared<const Context>(ctx);
+      dofs    = std::make_shared<const DoFHandler>(dof_handler);
     }
     // a level of a sharded hierarchy (DoFHandler(partition, level, rank, ...)): sums of shared DoFs are completed through `comm`
     // (nullptr: replicated level)
@@ -468,6 +520,17 @@ namespace mgamd
       mgamd_level_op *o = nullptr;
       check(mgamd_level_op_create_distributed(ctx.get(), dof_handler.get(), number_type, comm ? comm->get() : nullptr, &o));
       h.reset(o, mgamd_level_op_destroy);
+      context = std::make_shared<const Context>(ctx);
+      dofs    = std::make_shared<const DoFHandler>(dof_handler);
+    }
+    // Operator::get_trilinos_system_matrix / get_petsc_system_matrix (ref:include/operator.h:244-358): the assembled matrix of
+    // this operator's DoFs, on the device (built at every call: keep the result); refuses distributed and local-smoothing levels
+    SparseMatrix
+    get_system_matrix() const
+    {
+      if (!dofs)
+        throw std::runtime_error("Operator::get_system_matrix: reinit first");
+      return SparseMatrix(*context, *dofs);
     }
     // DoFs this rank owns (sums to DoFHandler::n_dofs() over the ranks)
     uint64_t
@@ -538,7 +601,9 @@ namespace mgamd
     }
 
   private:
-    std::shared_ptr<mgamd_level_op> h;
+    std::shared_ptr<mgamd_level_op>   h;
+    std::shared_ptr<const Context>    context;
+    std::shared_ptr<const DoFHandler> dofs;
   };
 
   class PreconditionChebyshev
@@ -830,6 +895,49 @@ namespace mgamd
     double   value = 0;
   };
 
+  // TrilinosWrappers::PreconditionAMG (ref:multigrid_throughput.cc:1907-1909): the library's smoothed-aggregation AMG on the matrix
+  class PreconditionAMG
+  {
+  public:
+    struct AdditionalData
+    {
+      unsigned n_cycles = 1;
+    };
+    void
+    initialize(const SparseMatrix &matrix, const AdditionalData &data)
+    {
+      mgamd_amg *p = nullptr;
+      check(mgamd_amg_create(matrix.get(), data.n_cycles, &p));
+      h.reset(p, mgamd_amg_destroy);
+    }
+    void
+    initialize(const SparseMatrix &matrix)
+    {
+      initialize(matrix, AdditionalData());
+    }
+    void
+    vmult(Vector &dst, const Vector &src) const
+    {
+      check(mgamd_amg_vmult(h.get(), dst.get(), src.get()));
+    }
+    // rows of every AMG level, finest first
+    std::vector<uint32_t>
+    layout() const
+    {
+      uint32_t n = 0, rows[32];
+      check(mgamd_amg_layout(h.get(), &n, rows, 32));
+      return std::vector<uint32_t>(rows, rows + std::min<uint32_t>(n, 32));
+    }
+    mgamd_amg *
+    get() const
+    {
+      return h.get();
+    }
+
+  private:
+    std::shared_ptr<mgamd_amg> h;
+  };
+
   class SolverCG
   {
   public:
@@ -843,6 +951,13 @@ namespace mgamd
     {
       check(mgamd_solve_cg(A.get(), preconditioner.get(), x.get(), b.get(), control.reltol, control.abstol, control.maxiter,
                            &control.steps, &control.value));
+    }
+    // CG on the assembled matrix with the AMG built on it (ref:multigrid_throughput.cc:1911-1915)
+    void
+    solve(const SparseMatrix &A, Vector &x, const Vector &b, const PreconditionAMG &preconditioner)
+    {
+      check(mgamd_solve_cg_matrix(A.get(), preconditioner.get(), x.get(), b.get(), control.reltol, control.abstol, control.maxiter,
+                                  &control.steps, &control.value));
     }
 
   private:

@@ -172,10 +172,13 @@ namespace mgamd
   // the inner products (the owned prefix on a sharded level, all otherwise).  One host read-back per iteration (the
   // residual norm); alpha, beta and the three inner products never leave the device: they live in S (8 doubles, one array per
   // solver instance -- the coarse CG of a V-cycle runs INSIDE the outer CG's preconditioner).
+  // vmult_dot (optional): Ap = A p and S[2] = p . Ap in one pass over the matrix (the assembled operator's SPMV_DOT launch), in
+  // place of vmult and the inner product after it
   template <typename T, typename VMULT, typename PRECOND>
   static void
   device_pcg(Ctx *ctx, Comm *comm, double *S, size_t n, size_t n_dot, T *x, T *r, T *z, T *p, T *Ap, VMULT vmult, PRECOND precond, double reltol,
-             double abstol, unsigned maxiter, unsigned &n_iterations, double &residual)
+             double abstol, unsigned maxiter, unsigned &n_iterations, double &residual,
+             const std::function<void(T *, const T *, double *)> &vmult_dot = nullptr)
   {
     const int g  = grid_for(n);
     const int gd = std::min(g, 1024);
@@ -193,8 +196,13 @@ namespace mgamd
     dot_to_device(ctx, comm, S, r, z, n_dot, cur);
     for (unsigned it = 1; it <= maxiter; ++it)
       {
-        vmult(Ap, p);
-        dot_to_device(ctx, comm, S, p, Ap, n_dot, 2);
+        if (vmult_dot)
+          vmult_dot(Ap, p, S + 2);
+        else
+          {
+            vmult(Ap, p);
+            dot_to_device(ctx, comm, S, p, Ap, n_dot, 2);
+          }
         hipLaunchKernelGGL(cg_update_xr_kernel<T>, gd, 256, 0, ctx->stream, x, r, p, Ap, n, n_dot, S, cur, ctx->d_partial);
         hipLaunchKernelGGL(vec_dot_final_kernel<>, 1, 256, 0, ctx->stream, ctx->d_partial, gd, S + 3);
         if (comm)
@@ -1004,13 +1012,23 @@ namespace mgamd
   }
 
   // ------------------------------------------------------------------------------------------
-  // K7 launchers (kernels_amg.hpp): the one path of the AMG cycle and of mgamd_debug_csr_spmv
+  // K7 / K8 launchers (kernels_amg.hpp): the one path of the AMG cycle, of the assembled operator and of mgamd_debug_csr_spmv
   // ------------------------------------------------------------------------------------------
   int
   csr_spmv_lanes(uint32_t n_rows, size_t nnz)
   {
     const double avg = n_rows ? (double)nnz / n_rows : 0.0;
     return avg <= 6 ? 4 : (avg <= 24 ? 8 : (avg <= 64 ? 16 : 32));
+  }
+  // the assembled operator and its AMG (AssembledMatrix, below) only: K8, a wave per row, above a mean row length of
+  // CSR_SPMV_WAVE_MIN_MEAN_ROW (measured: profiles/amg_solver_spmv.txt), K7's choice below it
+  int
+  csr_spmv_lanes_long(uint32_t n_rows, size_t nnz)
+  {
+    const double avg       = n_rows ? (double)nnz / n_rows : 0.0;
+    const char  *e         = getenv("MGAMD_SPMV_WAVE_MIN_MEAN_ROW");
+    const double threshold = e ? atof(e) : CSR_SPMV_WAVE_MIN_MEAN_ROW;
+    return avg > threshold ? 64 : csr_spmv_lanes(n_rows, nnz);
   }
 
   // f(mode tag, lanes tag) with the run-time mode and lane count as compile-time constants
@@ -1033,8 +1051,11 @@ namespace mgamd
           case 32:
             f(mode_tag, std::integral_constant<int, 32>());
             break;
+          case 64:
+            f(mode_tag, std::integral_constant<int, 64>());
+            break;
           default:
-            throw std::invalid_argument("csr_spmv: lanes must be 4, 8, 16 or 32");
+            throw std::invalid_argument("csr_spmv: lanes must be 4, 8, 16, 32 or 64");
         }
     };
     switch (mode)
@@ -1051,33 +1072,55 @@ namespace mgamd
         case SPMV_CHEB:
           with_lanes(std::integral_constant<int, SPMV_CHEB>());
           break;
+        case SPMV_DOT:
+          with_lanes(std::integral_constant<int, SPMV_DOT>());
+          break;
         default:
           throw std::invalid_argument("csr_spmv: unknown mode");
       }
   }
 
-  // all rows of the matrix (csr_spmv_kernel)
+  // all rows of the matrix (csr_spmv_kernel; lanes 64: csr_spmv_wave_kernel); returns the blocks launched.  SPMV_DOT leaves one
+  // partial sum per block in `partial` (Ctx::d_partial: 1024 doubles, hence its cap of 1024 blocks).  max_blocks > 0 lowers the
+  // cap (tests: a row's result does not depend on the grid).  SPMV_DOT and 64 lanes exist in FP64 only.
   template <typename T>
-  void
+  int
   launch_csr_spmv(hipStream_t stream, int mode, int lanes, uint32_t n_rows, const uint32_t *ptr, const uint32_t *col, const T *val, const T *x,
-                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2)
+                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2, double *partial, int max_blocks)
   {
     if (!n_rows)
-      return;
+      return 0;
+    if (mode == SPMV_DOT && !partial)
+      throw std::invalid_argument("csr_spmv: SPMV_DOT needs the buffer of the block partials");
+    int grid = 0;
     dispatch_spmv(mode, lanes, [&](auto mode_tag, auto lanes_tag) {
       constexpr int MODE  = decltype(mode_tag)::value;
       constexpr int LANES = decltype(lanes_tag)::value;
-      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
-      hipLaunchKernelGGL((csr_spmv_kernel<T, MODE, LANES>), grid, 256, 0, stream, n_rows, ptr, col, val, x, y, b, xold, dinv, T(f1), T(f2));
+      if constexpr ((MODE == SPMV_DOT || LANES == 64) && !std::is_same<T, double>::value)
+        throw std::invalid_argument("csr_spmv: SPMV_DOT and 64 lanes per row are FP64 only");
+      else
+        {
+          size_t g = std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, MODE == SPMV_DOT ? 1024 : 4096);
+          if (max_blocks > 0)
+            g = std::min<size_t>(g, (size_t)max_blocks);
+          grid = (int)g;
+          if constexpr (LANES == 64)
+            hipLaunchKernelGGL((csr_spmv_wave_kernel<T, MODE>), grid, 256, 0, stream, n_rows, ptr, col, val, x, y, b, xold, dinv, T(f1), T(f2),
+                               partial);
+          else
+            hipLaunchKernelGGL((csr_spmv_kernel<T, MODE, LANES>), grid, 256, 0, stream, n_rows, ptr, col, val, x, y, b, xold, dinv, T(f1),
+                               T(f2), partial);
+        }
     });
     HIP_CHECK(hipGetLastError());
+    return grid;
   }
-  template void
+  template int
   launch_csr_spmv<double>(hipStream_t, int, int, uint32_t, const uint32_t *, const uint32_t *, const double *, const double *, double *,
-                          const double *, const double *, const double *, double, double);
-  template void
+                          const double *, const double *, const double *, double, double, double *, int);
+  template int
   launch_csr_spmv<float>(hipStream_t, int, int, uint32_t, const uint32_t *, const uint32_t *, const float *, const float *, float *,
-                         const float *, const float *, const float *, double, double);
+                         const float *, const float *, const float *, double, double, double *, int);
 
   // the rows [row_begin, row_end) only (csr_spmv_range_kernel): the interior and boundary launches of a sharded level
   template <typename T>
@@ -1087,13 +1130,18 @@ namespace mgamd
   {
     if (row_end <= row_begin)
       return;
+    if (mode == SPMV_DOT || lanes == 64)
+      throw std::invalid_argument("csr_spmv: a range of rows has neither SPMV_DOT nor 64 lanes per row");
     const uint32_t n_rows = row_end - row_begin;
     dispatch_spmv(mode, lanes, [&](auto mode_tag, auto lanes_tag) {
       constexpr int MODE  = decltype(mode_tag)::value;
       constexpr int LANES = decltype(lanes_tag)::value;
-      const int     grid  = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
-      hipLaunchKernelGGL((csr_spmv_range_kernel<T, MODE, LANES>), grid, 256, 0, stream, row_begin, row_end, ptr, col, val, x, y, b, xold,
-                         dinv, T(f1), T(f2));
+      if constexpr (MODE != SPMV_DOT && LANES != 64)
+        {
+          const int grid = (int)std::min<size_t>(((size_t)n_rows * LANES + 255) / 256, 4096);
+          hipLaunchKernelGGL((csr_spmv_range_kernel<T, MODE, LANES>), grid, 256, 0, stream, row_begin, row_end, ptr, col, val, x, y, b, xold,
+                             dinv, T(f1), T(f2));
+        }
     });
     HIP_CHECK(hipGetLastError());
   }
@@ -1134,7 +1182,8 @@ namespace mgamd
     };
     struct Lvl
     {
-      Mat                   A, P, R;
+      std::shared_ptr<Mat>  A; // (level 0 of the assembled operator's AMG: the operator's own device matrix)
+      Mat                   P, R;
       DBuf<T>               dinv, x, b, r, t, send;
       DBuf<uint32_t>        send_idx;
       double                theta = 1, delta = 0;
@@ -1150,16 +1199,23 @@ namespace mgamd
     DBuf<double>                      coarse_inv;
     unsigned                          degree  = 2; // Chebyshev smoother degree (MGAMD_AMG_SMOOTHER_DEGREE: development)
     bool                              overlap = true;
+    bool                              long_rows = false; // lanes per row by csr_spmv_lanes_long (the assembled operator's AMG)
+    std::shared_ptr<Mat>              shared0;           // that operator's device matrix: level 0's A, not uploaded again
     // level 0 <-> geometric vector
     DBuf<uint32_t> in_amg, in_geo, out_amg, out_geo;
     uint32_t       n_in = 0, n_out = 0;
 
+    int
+    lanes_for(const CSR &M) const
+    {
+      return long_rows ? csr_spmv_lanes_long(M.n_rows, M.nnz()) : csr_spmv_lanes(M.n_rows, M.nnz());
+    }
     AmgHierarchyHost
-    build_hierarchy(const LevelTables &tables)
+    build_hierarchy(CSR A0)
     {
       if (const char *e = getenv("MGAMD_AMG_SMOOTHER_DEGREE"))
         degree = std::max(1, atoi(e));
-      AmgHierarchyHost H = build_smoothed_aggregation(assemble_level_matrix(tables)); // (refuses local-smoothing levels)
+      AmgHierarchyHost H = build_smoothed_aggregation(std::move(A0));
       if (H.levels.back().A.n_rows > 4096)
         throw std::runtime_error("AMG: coarsening stalled at " + std::to_string(H.levels.back().A.n_rows) + " rows");
       coarse_inv.upload(H.coarse_inv);
@@ -1184,14 +1240,20 @@ namespace mgamd
           L->peers       = P->peers;
           L->peer_offset = P->peer_offset;
         }
-      L->A.upload(whole ? G.A : P->A);
-      L->A.lanes = csr_spmv_lanes(G.A.n_rows, G.A.nnz()); // the whole matrix's lanes: the same additions per row however it is cut
+      if (lv.empty() && shared0)
+        L->A = shared0;
+      else
+        {
+          L->A = std::make_shared<Mat>();
+          L->A->upload(whole ? G.A : P->A);
+          L->A->lanes = lanes_for(G.A); // the whole matrix's lanes: the same additions per row however it is cut
+        }
       if (!last)
         {
           L->P.upload(whole ? G.P : P->P);
           L->R.upload(whole ? G.R : P->R);
-          L->P.lanes = csr_spmv_lanes(G.P.n_rows, G.P.nnz());
-          L->R.lanes = csr_spmv_lanes(G.R.n_rows, G.R.nnz());
+          L->P.lanes = lanes_for(G.P);
+          L->R.lanes = lanes_for(G.R);
         }
       std::vector<T> d(std::max<uint32_t>(L->n, 1), T(1));
       for (uint32_t i = 0; i < L->n; ++i)
@@ -1227,9 +1289,22 @@ namespace mgamd
     AmgCycle(Ctx *c, const LevelTables &tables)
       : ctx(c)
     {
-      const AmgHierarchyHost H = build_hierarchy(tables);
+      const AmgHierarchyHost H = build_hierarchy(assemble_level_matrix(tables)); // (refuses local-smoothing levels)
       for (size_t l = 0; l < H.levels.size(); ++l)
         add_level(H.levels[l], nullptr, l + 1 == H.levels.size());
+    }
+
+    // one rank, the assembled operator's preconditioner (AssembledMatrix): the hierarchy of its matrix A0, whose device copy
+    // dev0 is level 0's; K8 on the matrices with long rows
+    AmgCycle(Ctx *c, const CSR &A0, std::shared_ptr<Mat> dev0)
+      : ctx(c)
+      , long_rows(true)
+      , shared0(std::move(dev0))
+    {
+      const AmgHierarchyHost H = build_hierarchy(A0);
+      for (size_t l = 0; l < H.levels.size(); ++l)
+        add_level(H.levels[l], nullptr, l + 1 == H.levels.size());
+      ctx->sync();
     }
 
     // sharded level 0: the hierarchy of the global tables, this rank's rows of it
@@ -1247,7 +1322,7 @@ namespace mgamd
       const LevelTables &local   = *op->tables;
       const std::vector<uint32_t> grow = match_rows_by_key(global, local); // (refuses another space)
       const std::vector<uint8_t>  own  = local_dof_owned(local);
-      const AmgHierarchyHost      H    = build_hierarchy(global);
+      const AmgHierarchyHost      H    = build_hierarchy(assemble_level_matrix(global));
       const uint32_t              n0   = H.levels[0].A.n_rows;
       // owner stamps: one all-reduce builds the owner map of level 0 and checks that every row is owned exactly once
       std::vector<double> stamp(2 * (size_t)n0, 0.0);
@@ -1340,7 +1415,7 @@ namespace mgamd
     {
       if (!in || in->replicated || !comm)
         {
-          launch_csr_spmv<T>(ctx->stream, MODE, M.lanes, M.n_rows, M.ptr.p, M.col.p, M.val.p, x, y, b, xold, dinv, f1, f2);
+          launch_csr_spmv<T>(ctx->stream, MODE, M.lanes, M.n_rows, M.ptr.p, M.col.p, M.val.p, x, y, b, xold, dinv, f1, f2, nullptr, 0);
           return;
         }
       auto rows = [&](uint32_t r0, uint32_t r1) {
@@ -1372,7 +1447,7 @@ namespace mgamd
         {
           const double rhokp = 1.0 / (2.0 * sigma - rhok);
           // (x_old in place)
-          spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, j == 0 ? nullptr : oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
+          spmv<SPMV_CHEB>(*L.A, &L, L.n_int, cur, oth, b, j == 0 ? nullptr : oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
           rhok = rhokp;
           std::swap(cur, oth);
         }
@@ -1383,14 +1458,14 @@ namespace mgamd
     smooth_step(Lvl &L, T *x, T *t, const T *b)
     {
       T *cur = x, *oth = t;
-      spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, nullptr, L.dinv.p, 0.0, 1.0 / L.theta);
+      spmv<SPMV_CHEB>(*L.A, &L, L.n_int, cur, oth, b, nullptr, L.dinv.p, 0.0, 1.0 / L.theta);
       std::swap(cur, oth);
       double       rhok  = L.delta / L.theta;
       const double sigma = L.theta / L.delta;
       for (unsigned j = 0; j + 1 < degree; ++j)
         {
           const double rhokp = 1.0 / (2.0 * sigma - rhok);
-          spmv<SPMV_CHEB>(L.A, &L, L.n_int, cur, oth, b, oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
+          spmv<SPMV_CHEB>(*L.A, &L, L.n_int, cur, oth, b, oth, L.dinv.p, rhokp * rhok, 2.0 * rhokp / L.delta);
           rhok = rhokp;
           std::swap(cur, oth);
         }
@@ -1408,7 +1483,7 @@ namespace mgamd
         }
       Lvl &C = *lv[l + 1];
       smooth_zero(L, x, L.t.p, b);
-      spmv<SPMV_RESID>(L.A, &L, L.n_int, x, L.r.p, b);
+      spmv<SPMV_RESID>(*L.A, &L, L.n_int, x, L.r.p, b);
       if (!L.replicated && C.replicated)
         {
           // partial sums over my owned columns, completed over the ranks
@@ -2226,5 +2301,190 @@ namespace mgamd
       solve_cg_T<double>(A, M, x, b, reltol, abstol, maxiter, n_iterations, residual);
     else
       solve_cg_T<float>(A, M, x, b, reltol, abstol, maxiter, n_iterations, residual);
+  }
+
+  // ------------------------------------------------------------------------------------------
+  // Type "AMG": SolverCG on the assembled system matrix, preconditioned by the AMG built on it (solve_with_amg,
+  // ref:multigrid_throughput.cc:1877-1966).  The matrix lives once on the device: the operator's products and level 0 of the
+  // cycle read the same arrays.  Rows of the fine-level matrix at degree 2-4 hold hundreds of entries: K8 above
+  // CSR_SPMV_WAVE_MIN_MEAN_ROW, K7 below (degree 1).  The host copy stays: the AMG setup (amg.hpp) starts from it.
+  // ------------------------------------------------------------------------------------------
+  struct AssembledMatrix : AssembledMatrixBase
+  {
+    using Mat = AmgCycle<double>::Mat;
+    std::shared_ptr<const CSR> host;
+    std::shared_ptr<Mat>       dev;
+    AssembledMatrix(Ctx *c, const mgamd_dofs *dofs)
+    {
+      ctx = c;
+      if (dofs->halo)
+        throw std::invalid_argument("assembled matrix: the level is distributed (one rank only)");
+      host   = std::make_shared<const CSR>(assemble_level_matrix(*dofs->tables)); // (refuses local-smoothing levels)
+      n_rows = host->n_rows;
+      nnz    = host->nnz();
+      lanes  = csr_spmv_lanes_long(n_rows, nnz);
+      dev    = std::make_shared<Mat>();
+      dev->upload(*host);
+      dev->lanes = lanes;
+    }
+    template <int MODE>
+    int
+    spmv(const double *x, double *y, const double *b = nullptr, double *partial = nullptr) const
+    {
+      return launch_csr_spmv<double>(ctx->stream, MODE, lanes, n_rows, dev->ptr.p, dev->col.p, dev->val.p, x, y, b, nullptr, nullptr, 0, 0,
+                                     partial);
+    }
+    void
+    check(const mgamd_vec &v) const
+    {
+      if (v.n != n_rows)
+        throw std::invalid_argument("assembled matrix: vector size mismatch");
+      if (v.type != MGAMD_F64)
+        throw std::invalid_argument("assembled matrix: vectors must be MGAMD_F64 (the reference runs this path in double)");
+    }
+    void
+    vmult(mgamd_vec &dst, const mgamd_vec &src) override
+    {
+      check(dst);
+      check(src);
+      if (dst.data == src.data)
+        throw std::invalid_argument("assembled matrix: vmult in place");
+      spmv<SPMV_PLAIN>(src.as<double>(), dst.as<double>());
+    }
+    double
+    time_spmv(int mode, int lanes_, unsigned reps) override
+    {
+      if (!reps || !n_rows)
+        throw std::invalid_argument("time_spmv: nothing to time");
+      std::vector<double> h(n_rows);
+      for (uint32_t i = 0; i < n_rows; ++i)
+        h[i] = 1.0 / (1.0 + (double)(i % 7));
+      DBuf<double> x, y, b, dinv;
+      for (DBuf<double> *v : {&x, &y, &b, &dinv})
+        v->upload(h);
+      auto launch = [&] {
+        launch_csr_spmv<double>(ctx->stream, mode, lanes_, n_rows, dev->ptr.p, dev->col.p, dev->val.p, x.p, y.p, b.p, nullptr, dinv.p, 0.25, 0.5,
+                                ctx->d_partial);
+      };
+      hipEvent_t e0, e1;
+      HIP_CHECK(hipEventCreate(&e0));
+      HIP_CHECK(hipEventCreate(&e1));
+      launch();
+      HIP_CHECK(hipEventRecord(e0, ctx->stream));
+      for (unsigned r = 0; r < reps; ++r)
+        launch();
+      HIP_CHECK(hipEventRecord(e1, ctx->stream));
+      HIP_CHECK(hipEventSynchronize(e1));
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      return (double)ms / reps;
+    }
+    // Ap = A p, *out = p . Ap: one pass over the matrix, the block partials summed by vec_dot_final_kernel
+    void
+    vmult_dot(double *Ap, const double *p, double *out) const
+    {
+      const int g = spmv<SPMV_DOT>(p, Ap, nullptr, ctx->d_partial);
+      hipLaunchKernelGGL(vec_dot_final_kernel<>, 1, 256, 0, ctx->stream, ctx->d_partial, g, out);
+    }
+  };
+
+  struct AmgPreconditioner : AmgPreconditionerBase
+  {
+    std::shared_ptr<AssembledMatrix> A;
+    AmgCycle<double>                 cycle;
+    unsigned                         n_cycles;
+    DBuf<double>                     rr, zz; // n_cycles > 1: residual and correction
+    AmgPreconditioner(std::shared_ptr<AssembledMatrix> a, unsigned n)
+      : A(std::move(a))
+      , cycle(A->ctx, *A->host, A->dev)
+      , n_cycles(n)
+    {
+      if (n_cycles > 1)
+        {
+          rr.alloc(A->n_rows);
+          zz.alloc(A->n_rows);
+        }
+    }
+    // z = V(r), then n_cycles - 1 corrections z += V(r - A z) (ML's `cycle applications`)
+    void
+    apply_raw(double *z, const double *r)
+    {
+      cycle.vcycle(z, r);
+      for (unsigned c = 1; c < n_cycles; ++c)
+        {
+          A->spmv<SPMV_RESID>(z, rr.p, r);
+          cycle.vcycle(zz.p, rr.p);
+          hipLaunchKernelGGL(vec_sadd_kernel<double>, grid_for(A->n_rows), 256, 0, A->ctx->stream, z, 1.0, 1.0, zz.p, (size_t)A->n_rows);
+        }
+      HIP_CHECK(hipGetLastError());
+    }
+    void
+    vmult(mgamd_vec &z, const mgamd_vec &r) override
+    {
+      A->check(z);
+      A->check(r);
+      if (z.data == r.data)
+        throw std::invalid_argument("AMG preconditioner: vmult in place");
+      apply_raw(z.as<double>(), r.as<double>());
+    }
+    void
+    layout(std::vector<uint32_t> &rows_per_level) const override
+    {
+      rows_per_level.clear();
+      for (const auto &L : cycle.lv)
+        rows_per_level.push_back(L->n_global);
+    }
+  };
+
+  std::shared_ptr<AssembledMatrixBase>
+  make_assembled_matrix(Ctx *ctx, const mgamd_dofs *dofs)
+  {
+    return std::make_shared<AssembledMatrix>(ctx, dofs);
+  }
+  AmgPreconditionerBase *
+  make_amg_preconditioner(const std::shared_ptr<AssembledMatrixBase> &A, unsigned n_cycles)
+  {
+    if (n_cycles == 0)
+      throw std::invalid_argument("AMG preconditioner: n_cycles must be at least 1");
+    return new AmgPreconditioner(std::static_pointer_cast<AssembledMatrix>(A), n_cycles);
+  }
+
+  void
+  solve_cg_matrix(AssembledMatrixBase &Ab, AmgPreconditionerBase *Mb, mgamd_vec &x, const mgamd_vec &b, double reltol, double abstol,
+                  unsigned maxiter, unsigned &n_iterations, double &residual)
+  {
+    auto &A = static_cast<AssembledMatrix &>(Ab);
+    auto *M = static_cast<AmgPreconditioner *>(Mb);
+    A.check(x);
+    A.check(b);
+    if (M && M->A.get() != &A)
+      throw std::invalid_argument("SolverCG::solve: the AMG preconditioner was built on another matrix");
+    Ctx         *ctx = A.ctx;
+    const size_t n   = A.n_rows;
+    if (!n)
+      {
+        n_iterations = 0;
+        residual     = 0;
+        return;
+      }
+    DBuf<double> g, h, d, Ad;
+    for (DBuf<double> *v : {&g, &h, &d, &Ad})
+      v->alloc(n);
+    HIP_CHECK(hipMemcpyAsync(g.p, b.data, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    std::function<void(double *, const double *, double *)> fused;
+    if (getenv("MGAMD_NO_FUSED_DOT") == nullptr)
+      fused = [&](double *Ap, const double *p, double *out) { A.vmult_dot(Ap, p, out); };
+    device_pcg<double>(
+      ctx, nullptr, ctx->d_cg, n, n, x.as<double>(), g.p, h.p, d.p, Ad.p, [&](double *Ap, const double *p) { A.spmv<SPMV_PLAIN>(p, Ap); },
+      [&](double *z, const double *r) {
+        if (M)
+          M->apply_raw(z, r);
+        else
+          HIP_CHECK(hipMemcpyAsync(z, r, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      },
+      reltol, abstol, maxiter, n_iterations, residual, fused);
+    ctx->sync();
   }
 } // namespace mgamd

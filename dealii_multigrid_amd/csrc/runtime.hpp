@@ -333,10 +333,55 @@ namespace mgamd
   // (grid-stride above); mode: SpmvMode; lanes 0 = csr_spmv_lanes
   int
   csr_spmv_lanes(uint32_t n_rows, size_t nnz);
+  // K8 (one wave64 per row, lanes = 64) above this mean row length, K7's choice below: the assembled operator and its AMG only
+  // (between the measured 102, where K8 loses, and 185, where it wins: profiles/amg_solver_spmv.txt; MGAMD_SPMV_WAVE_MIN_MEAN_ROW
+  // in the environment replaces it: development and tests)
+  constexpr double CSR_SPMV_WAVE_MIN_MEAN_ROW = 144.0;
+  int
+  csr_spmv_lanes_long(uint32_t n_rows, size_t nnz);
+  // returns the blocks launched; mode SPMV_DOT: one partial of x . y per block in `partial` (at most 1024); max_blocks > 0: a
+  // lower cap on the grid
   template <typename T>
-  void
+  int
   launch_csr_spmv(hipStream_t stream, int mode, int lanes, uint32_t n_rows, const uint32_t *ptr, const uint32_t *col, const T *val, const T *x,
-                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2);
+                  T *y, const T *b, const T *xold, const T *dinv, double f1, double f2, double *partial = nullptr, int max_blocks = 0);
+
+  // ---- CG on the assembled matrix with the AMG preconditioner: the reference's Type "AMG" / "AMGPETSc", solve_with_amg
+  // (ref:multigrid_throughput.cc:1877-1966).  FP64, one rank, global-coarsening levels.
+  // Operator::get_trilinos_system_matrix (ref:include/operator.h:244-287) on the device: vmult is a plain CSR product
+  struct AssembledMatrixBase
+  {
+    virtual ~AssembledMatrixBase() = default;
+    Ctx     *ctx    = nullptr;
+    uint32_t n_rows = 0;
+    uint64_t nnz    = 0;
+    int      lanes  = 0; // lanes per row of its products (csr_spmv_lanes_long)
+    virtual void
+    vmult(mgamd_vec &dst, const mgamd_vec &src) = 0;
+    // measurement (tools/spmv_bench.py): milliseconds per launch of the product in `mode` at `lanes` lanes per row, HIP events
+    // around `reps` launches after one warm-up launch, on scratch vectors
+    virtual double
+    time_spmv(int mode, int lanes, unsigned reps) = 0;
+  };
+  // TrilinosWrappers::PreconditionAMG on that matrix (ref:multigrid_throughput.cc:1907-1909): n_cycles V-cycles of the library's
+  // smoothed-aggregation AMG (amg.hpp); level 0 works on the operator's device matrix, which it keeps alive
+  struct AmgPreconditionerBase
+  {
+    virtual ~AmgPreconditionerBase() = default;
+    virtual void
+    vmult(mgamd_vec &z, const mgamd_vec &r) = 0;
+    virtual void
+    layout(std::vector<uint32_t> &rows_per_level) const = 0;
+  };
+  std::shared_ptr<AssembledMatrixBase>
+  make_assembled_matrix(Ctx *ctx, const mgamd_dofs *dofs);
+  AmgPreconditionerBase *
+  make_amg_preconditioner(const std::shared_ptr<AssembledMatrixBase> &A, unsigned n_cycles);
+  // SolverCG on the matrix (ref:multigrid_throughput.cc:1911-1915); M null: no preconditioner.  A p and p . A p come from one
+  // SPMV_DOT launch (MGAMD_NO_FUSED_DOT=1 in the environment: the product, then the inner product, as the other solvers do)
+  void
+  solve_cg_matrix(AssembledMatrixBase &A, AmgPreconditionerBase *M, mgamd_vec &x, const mgamd_vec &b, double reltol, double abstol,
+                  unsigned maxiter, unsigned &n_iterations, double &residual);
 } // namespace mgamd
 
 struct mgamd_level_op
@@ -354,4 +399,12 @@ struct mgamd_transfer2
 struct mgamd_mg
 {
   std::unique_ptr<mgamd::MultigridBase> mg;
+};
+struct mgamd_matrix
+{
+  std::shared_ptr<mgamd::AssembledMatrixBase> A;
+};
+struct mgamd_amg
+{
+  std::unique_ptr<mgamd::AmgPreconditionerBase> P;
 };

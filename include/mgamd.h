@@ -40,6 +40,8 @@ typedef struct mgamd_level_op  mgamd_level_op;  /* Operator<3,1,Number>  (ref:in
 typedef struct mgamd_cheb      mgamd_cheb;      /* PreconditionChebyshev<Operator,Vector,DiagonalMatrix> */
 typedef struct mgamd_transfer2 mgamd_transfer2; /* MGTwoLevelTransfer<3,Vector>                          */
 typedef struct mgamd_mg        mgamd_mg;        /* Multigrid + PreconditionMG + MGTransferGlobalCoarsening */
+typedef struct mgamd_matrix    mgamd_matrix;    /* TrilinosWrappers::SparseMatrix: Operator::get_trilinos_system_matrix, on the device */
+typedef struct mgamd_amg       mgamd_amg;       /* TrilinosWrappers::PreconditionAMG on that matrix                                    */
 typedef struct mgamd_partition mgamd_partition; /* domain decomposition of the level hierarchy (one rank per GPU) */
 typedef struct mgamd_comm      mgamd_comm;      /* communicator: RCCL over xGMI, or the in-process simulator      */
 typedef struct mgamd_sim_group mgamd_sim_group; /* the ranks of one in-process simulation                         */
@@ -364,6 +366,37 @@ int mgamd_mg_time_vcycles(mgamd_mg *mg, mgamd_vec *z, const mgamd_vec *r, unsign
  * 1625-1635): solves A x = b from x = 0; returns last_step() and the final residual norm. */
 int mgamd_solve_cg(mgamd_level_op *A, mgamd_mg *preconditioner, mgamd_vec *x, const mgamd_vec *b, double reltol, double abstol,
                    unsigned maxiter, unsigned *n_iterations, double *residual_norm);
+
+/* ---------------------------------------------------------------------------------------------
+ * Type "AMG" / "AMGPETSc": CG on the assembled system matrix with an AMG preconditioner built on it (solve_with_amg,
+ * ref:multigrid_throughput.cc:1877-1966, called at :2337-2338) -- the baseline the reference measures its matrix-free multigrid
+ * against.  FP64 only (the reference runs this path in double whatever MGNumberType says), one rank.  Every entry below returns
+ * MGAMD_ERR_INVALID, with the reason in mgamd_last_error(), for a distributed level (mgamd_dofs_create_local), a local-smoothing
+ * level (mgamd_dofs_create_level) and MGAMD_F32 vectors.
+ * ------------------------------------------------------------------------------------------- */
+/* Operator::get_trilinos_system_matrix() (ref:include/operator.h:244-287): the matrix of mgamd_dofs_matrix, assembled on the host
+ * and held on the device as CSR.  The host setup bounds the usable size (32-bit row pointers: < 2^32 entries). */
+int mgamd_matrix_create(mgamd_ctx *ctx, const mgamd_dofs *dofs, mgamd_matrix **out);
+int mgamd_matrix_destroy(mgamd_matrix *A);
+/* rows, stored entries and the lanes per row of its products (64: one wavefront per row, the long rows of degree >= 2; 4-32: the
+ * coarse solver's kernel).  Any pointer may be NULL. */
+int mgamd_matrix_info(const mgamd_matrix *A, uint64_t *n_rows, uint64_t *nnz, int *lanes);
+/* SparseMatrix::vmult as SolverCG calls it (ref:multigrid_throughput.cc:1913-1914): dst = A src, dst != src */
+int mgamd_matrix_vmult(mgamd_matrix *A, mgamd_vec *dst, const mgamd_vec *src);
+/* TrilinosWrappers::PreconditionAMG::initialize(matrix, AdditionalData()) (ref:multigrid_throughput.cc:1907-1909; defaults: 1 cycle,
+ * aggregation threshold 1e-4, 2 smoother sweeps): the library's own smoothed-aggregation AMG (see mgamd_mg_create) on A, n_cycles
+ * cycles per application (>= 1).  Level 0 works on A's device arrays: the matrix is on the device once; P keeps it alive. */
+int mgamd_amg_create(mgamd_matrix *A, unsigned n_cycles, mgamd_amg **out);
+int mgamd_amg_destroy(mgamd_amg *P);
+/* PreconditionAMG::vmult: z = n_cycles V-cycles applied to r, z != r */
+int mgamd_amg_vmult(mgamd_amg *P, mgamd_vec *z, const mgamd_vec *r);
+/* rows of every AMG level, finest first (`rows` may be NULL; at most max_levels entries are written) */
+int mgamd_amg_layout(const mgamd_amg *P, uint32_t *n_levels, uint32_t *rows, uint32_t max_levels);
+/* SolverCG<VectorType>(ReductionControl).solve(op.get_trilinos_system_matrix(), dst, src, preconditioner)
+ * (ref:multigrid_throughput.cc:1911-1915) from x = 0; preconditioner NULL: PreconditionIdentity.  A p and p . A p come from one pass
+ * over the matrix. */
+int mgamd_solve_cg_matrix(mgamd_matrix *A, mgamd_amg *preconditioner, mgamd_vec *x, const mgamd_vec *b, double reltol, double abstol,
+                          unsigned maxiter, unsigned *n_iterations, double *residual_norm);
 
 #ifdef __cplusplus
 }

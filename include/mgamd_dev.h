@@ -72,6 +72,23 @@ int mgamd_debug_csr_spmv(mgamd_ctx *ctx, int number_type, int mode, int lanes, u
                          const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold,
                          int xold_is_y, const double *dinv, double f1, double f2, int *lanes_used);
 
+/* the same with what the assembled operator (mgamd_matrix_create) adds: lanes 64 (K8: one wavefront per row, FP64 only) and mode 4,
+ * y = A x with x . y in the same pass (FP64, n_cols == n_rows; at K7's lane counts too), the sum finished as the solver does and
+ * returned in *dot.  max_blocks > 0 caps the grid below the launcher's own cap (a row's result must not depend on it); *blocks: the
+ * grid launched.  lanes_used, blocks, dot may be null. */
+int mgamd_debug_csr_spmv_ex(mgamd_ctx *ctx, int number_type, int mode, int lanes, uint32_t n_rows, uint32_t n_cols, const uint32_t *ptr,
+                            const uint32_t *col, const double *val, const double *x, double *y, const double *b, const double *xold,
+                            int xold_is_y, const double *dinv, double f1, double f2, int max_blocks, int *lanes_used, int *blocks,
+                            double *dot);
+/* the assembled operator's lane choice: 64 above its mean-row-length threshold, the coarse solver's choice below */
+int mgamd_debug_csr_spmv_lanes_long(uint32_t n_rows, uint64_t nnz, int *lanes);
+/* measurement (tools/spmv_bench.py): milliseconds per launch of A's product in mode 0 (plain), 3 (Chebyshev) or 4 (with the dot) at
+ * `lanes` lanes per row (4-64), HIP events around `reps` launches after a warm-up launch, on scratch vectors */
+int mgamd_debug_matrix_time_spmv(mgamd_matrix *A, int mode, int lanes, unsigned reps, double *ms_per_launch);
+/* the row pointers assemble_level_matrix builds from its per-row entry counts (accumulated in 64 bits): MGAMD_ERR, with the count
+ * in mgamd_last_error(), when the matrix needs more than 2^32 - 1 entries; ptr has n_rows + 1 entries.  No GPU needed. */
+int mgamd_debug_csr_row_pointers(uint32_t n_rows, const uint64_t *row_counts, uint32_t *ptr);
+
 #ifdef __cplusplus
 }
 #endif
