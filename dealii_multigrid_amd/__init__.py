@@ -144,11 +144,8 @@ def create_geometric_coarsening_sequence(fine: Triangulation):
 
 
 def create_polynomial_coarsening_sequence(degree: int):
-    """...::create_polynomial_coarsening_sequence(degree, bisect): e.g. 4 -> [1, 2, 4]."""
-    seq = [degree]
-    while seq[-1] > 1:
-        seq.append(max(seq[-1] // 2, 1))
-    return seq[::-1]
+    """...::create_polynomial_coarsening_sequence(degree, bisect): e.g. 4 -> [1, 2, 4] (the degrees of the PMG levels)."""
+    return [p for _, p in _level_plan("PMG", 1, degree)[0]]
 
 
 class Partition:
@@ -845,7 +842,54 @@ def csr_row_pointers(row_counts):
     return ptr
 
 
-AMG_COARSE_SOLVERS = ("amg", "cg_with_amg", "amg_petsc")
+COARSE_PLAIN, COARSE_NESTED, COARSE_SHARDED_AMG = 0, 1, 2  # mgamd_coarse_plan: what a coarse solver needs next to the levels
+
+
+def _level_plan(mg_type: str, n_meshes: int, degree: int):
+    """mgamd_level_plan: ([(mesh index, degree)] of the multigrid levels of `mg_type` over n_meshes meshes, coarse -> fine; whether
+    they are local-smoothing levels).  MgamdError for a type without levels."""
+    n, ls, mesh, deg = C.c_uint(), C.c_int(), (C.c_uint * 64)(), (C.c_uint * 64)()
+    _chk(_lib.mgamd_level_plan(mg_type.encode(), n_meshes, degree, 64, C.byref(n), mesh, deg, C.byref(ls)))
+    return [(mesh[l], deg[l]) for l in range(n.value)], bool(ls.value)
+
+
+def _coarse_plan(coarse_solver: str, n_level0_dofs_global: int, level0_distributed=False, sharded_amg_requested=False) -> int:
+    """mgamd_coarse_plan: COARSE_PLAIN | COARSE_NESTED (the geometric stand-in) | COARSE_SHARDED_AMG"""
+    plan = C.c_int()
+    _chk(_lib.mgamd_coarse_plan(coarse_solver.encode(), C.c_uint64(n_level0_dofs_global), int(level0_distributed),
+                                int(sharded_amg_requested), C.byref(plan)))
+    return plan.value
+
+
+def _partition_defaults(n_ranks: int, p_low: int = 1):
+    """mgamd_partition_defaults: (rank group of the two-tier partition, cells from which a level is cut over all ranks, over groups);
+    at p_low = 1 the thresholds are DoFs: the defaults of DistributedHierarchy's min_root_dofs and min_subset_dofs"""
+    group, root, sub = C.c_uint(), C.c_uint64(), C.c_uint64()
+    _chk(_lib.mgamd_partition_defaults(n_ranks, p_low, C.byref(group), C.byref(root), C.byref(sub)))
+    return group.value, root.value, sub.value
+
+
+_, MIN_ROOT_DOFS_DEFAULT, MIN_SUBSET_DOFS_DEFAULT = _partition_defaults(1)
+
+
+def _build_levels(ctx, meshes, plan, number_type, max_brick, smoother, partition=None, rank=0, level_comm=None, local_smoothing=False,
+                  first_dofs=None, shared_last=None):
+    """(DoFs, operators, transfers, smoothers) of the levels plan = [(mesh index, degree)], coarse -> fine.
+    smoother: (degree, smoothing_range, eig_cg_n_iterations) of every PreconditionChebyshev
+    partition, rank, level_comm: one rank's share of a sharded hierarchy; level_comm(mesh index) is the communicator of a distributed
+    mesh, None on a replicated one
+    local_smoothing: the meshes are Triangulation.level_mesh(l)
+    first_dofs: existing DoFs that are level 0's (HPMG-local: the ones the local-smoothing cycle underneath acts on)
+    shared_last: (dofs, operator, smoother) of another hierarchy's level that is the finest one here (the coarse stand-in)
+    max_brick=-1: bricks on large levels, single-cell slots on the latency-bound small ones (level_tables.hpp)"""
+    shared = [] if shared_last is None else [shared_last]
+    lo, hi = int(first_dofs is not None), len(plan) - len(shared)
+    dofs = [first_dofs][:lo] + [DoFs(meshes[mi], p, max_brick, partition, mi, rank, local_smoothing) for mi, p in plan[lo:hi]]
+    ops = [Operator(ctx, d, number_type, level_comm(mi) if level_comm else None) for d, (mi, _) in zip(dofs, plan)]
+    dofs, ops = dofs + [s[0] for s in shared], ops + [s[1] for s in shared]
+    transfers = [None] + [MGTwoLevelTransfer(ops[l], ops[l - 1]) for l in range(1, len(ops))]
+    smoothers = [PreconditionChebyshev(op, *smoother) for op in ops[:hi]] + [s[2] for s in shared]
+    return dofs, ops, transfers, smoothers
 
 
 class CoarseHierarchy:
@@ -854,17 +898,15 @@ class CoarseHierarchy:
 
     def __init__(self, ctx, tria, dofs0, op0, smoother0, smoother_degree, smoothing_range, eig_cg_n_iterations, number_type, max_brick):
         self.trias = create_geometric_coarsening_sequence(tria)
-        p0 = dofs0.degree
-        self.dofs = [DoFs(t, p0, max_brick) for t in self.trias[:-1]] + [dofs0]
-        self.operators = [Operator(ctx, d, number_type) for d in self.dofs[:-1]] + [op0]
-        self.transfers = [None] + [MGTwoLevelTransfer(self.operators[l], self.operators[l - 1]) for l in range(1, len(self.dofs))]
-        self.smoothers = [PreconditionChebyshev(op, smoother_degree, smoothing_range, eig_cg_n_iterations) for op in self.operators[:-1]]
-        self.smoothers.append(smoother0)
+        plan, _ = _level_plan("HMG-global", len(self.trias), dofs0.degree)
+        self.dofs, self.operators, self.transfers, self.smoothers = _build_levels(
+            ctx, self.trias, plan, number_type, max_brick, (smoother_degree, smoothing_range, eig_cg_n_iterations),
+            shared_last=(dofs0, op0, smoother0))
         self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, "amg")
 
 
 class Hierarchy:
-    """What solve_with_global_coarsening builds (ref:multigrid_throughput.cc:1443-1666)."""
+    """What solve_with_global_coarsening and solve_with_local_smoothing build (ref:multigrid_throughput.cc:1443-1666, 1670-1873)."""
 
     def __init__(self, ctx: Context, geometry="quadrant", n_ref_global=3, degree=1, mg_type="HMG-global", n_ref_local=0,
                  smoother_degree=3, smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64,
@@ -872,24 +914,7 @@ class Hierarchy:
         self.ctx = ctx
         # `geometry` may also be a caller-built Triangulation (Triangulation.from_leaves)
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global, n_ref_local)
-        if mg_type == "HMG-global":
-            self.trias = create_geometric_coarsening_sequence(fine)
-            self.degrees = [degree] * len(self.trias)
-        elif mg_type == "PMG":
-            self.degrees = create_polynomial_coarsening_sequence(degree)
-            self.trias = [fine] * len(self.degrees)
-        elif mg_type == "HPMG":
-            # h-levels at the lowest degree of the bisection sequence, then the p-levels on the finest mesh
-            # (ref:multigrid_throughput.cc:1518-1519, 1551-1553, 1569-1571)
-            pseq = create_polynomial_coarsening_sequence(degree)
-            hseq = create_geometric_coarsening_sequence(fine)
-            self.trias = hseq + [fine] * (len(pseq) - 1)
-            self.degrees = [pseq[0]] * len(hseq) + pseq[1:]
-        elif mg_type == "HMG-local":
-            self._build_local_smoothing(ctx, fine, degree, smoother_degree, smoothing_range, eig_cg_n_iterations, coarse_solver, number_type,
-                                        max_brick)
-            return
-        elif mg_type in ("AMG", "AMGPETSc"):
+        if mg_type in ("AMG", "AMGPETSc"):
             # solve_with_amg (ref:multigrid_throughput.cc:1877-1966): no multigrid levels; CG on the assembled matrix of the one
             # level with the AMG built on it: solve_cg(h.system_matrix, h.amg, x, b).  FP64 whatever number_type says, as in the
             # reference; coarse_n_cycles: AMG cycles per application.  AMGPETSc (BoomerAMG's role): the same solver.
@@ -901,63 +926,50 @@ class Hierarchy:
             self.amg = PreconditionAMG(self.system_matrix, coarse_n_cycles)
             self.n_dofs = self.dofs[0].n_dofs
             return
-        elif mg_type == "HPMG-local":
+        smoother = (smoother_degree, smoothing_range, eig_cg_n_iterations)
+        if mg_type == "HMG-local":
+            self._build_local_smoothing(ctx, fine, degree, smoother, coarse_solver, number_type, max_brick)
+            return
+        # the meshes the levels live on: the coarsening sequence of the h-levels; the p-levels of PMG and HPMG-local need the one mesh
+        meshes = create_geometric_coarsening_sequence(fine) if mg_type in ("HMG-global", "HPMG") else [fine]
+        plan, _ = _level_plan(mg_type, len(meshes), degree)
+        first_dofs, nested = None, None
+        if mg_type == "HPMG-local":
             # ref:multigrid_throughput.cc:1685-1695,1846-1860: p-multigrid on the active mesh whose coarse problem (lowest degree)
             # is handed to ONE local-smoothing V-cycle (MGCoarseGridApplyPreconditioner of the intermediate PreconditionMG)
-            pseq = create_polynomial_coarsening_sequence(degree)
-            self._build_local_smoothing(ctx, fine, pseq[0], smoother_degree, smoothing_range, eig_cg_n_iterations, coarse_solver, number_type,
-                                        max_brick)
-            if len(pseq) == 1:
+            self._build_local_smoothing(ctx, fine, plan[0][1], smoother, coarse_solver, number_type, max_brick)
+            if len(plan) == 1:
                 return
             self.ls = dict(trias=self.trias, dofs=self.dofs, operators=self.operators, transfers=self.transfers, smoothers=self.smoothers,
                            mg=self.mg)
-            self.trias = [fine] * len(pseq)
-            self.degrees = pseq
-            self.dofs = [self.active_dofs] + [DoFs(fine, p, max_brick) for p in pseq[1:]]
-            self.operators = [Operator(ctx, d, number_type) for d in self.dofs]
-            self.transfers = [None] + [MGTwoLevelTransfer(self.operators[l], self.operators[l - 1]) for l in range(1, len(self.dofs))]
-            self.smoothers = [PreconditionChebyshev(op, smoother_degree, smoothing_range, eig_cg_n_iterations) for op in self.operators]
-            self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, "gmg_vcycle", self.ls["mg"], 1)
-            self.fine_operator = self.operators[-1] if number_type == F64 else Operator(ctx, self.dofs[-1], F64)
-            self.n_dofs = self.dofs[-1].n_dofs
-            return
-        else:
-            raise MgamdError(f"Type '{mg_type}' not implemented")
-        # max_brick=-1: bricks on large levels, single-cell slots on the latency-bound small ones (level_tables.hpp)
-        self.dofs = [DoFs(t, p, max_brick) for t, p in zip(self.trias, self.degrees)]
-        self.operators = [Operator(ctx, d, number_type) for d in self.dofs]
-        self.transfers = [None] + [MGTwoLevelTransfer(self.operators[l], self.operators[l - 1]) for l in range(1, len(self.dofs))]
-        self.smoothers = [PreconditionChebyshev(op, smoother_degree, smoothing_range, eig_cg_n_iterations) for op in self.operators]
+            first_dofs, nested, coarse_solver, coarse_n_cycles = self.active_dofs, self.mg, "gmg_vcycle", 1
+        self.trias, self.degrees = [meshes[mi] for mi, _ in plan], [p for _, p in plan]
+        self.dofs, self.operators, self.transfers, self.smoothers = _build_levels(ctx, meshes, plan, number_type, max_brick, smoother,
+                                                                                  first_dofs=first_dofs)
         self.coarse = None
-        if coarse_solver == "gmg_vcycle" and self.dofs[0].n_dofs > 4096:
-            # the geometric stand-in for the AMG coarse solvers on a large coarse level (PMG), now by explicit request only:
-            # V-cycles of the h-multigrid on level 0 ("amg", "cg_with_amg" run the library's smoothed-aggregation AMG)
-            self.coarse = CoarseHierarchy(ctx, self.trias[0], self.dofs[0], self.operators[0], self.smoothers[0], smoother_degree,
-                                          smoothing_range, eig_cg_n_iterations, number_type, max_brick)
-        self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver,
-                                 self.coarse.mg if self.coarse else None, coarse_n_cycles)
+        if nested is None and _coarse_plan(coarse_solver, self.dofs[0].n_dofs) == COARSE_NESTED:
+            # the geometric stand-in for the AMG coarse solvers on a large coarse level (PMG), on one rank by explicit request only
+            # ("gmg_vcycle"): V-cycles of the h-multigrid on level 0 ("amg", "cg_with_amg" run the library's smoothed-aggregation AMG)
+            self.coarse = CoarseHierarchy(ctx, self.trias[0], self.dofs[0], self.operators[0], self.smoothers[0], *smoother, number_type,
+                                          max_brick)
+            nested = self.coarse.mg
+        self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, nested, coarse_n_cycles)
         self.fine_operator = self.operators[-1] if number_type == F64 else Operator(ctx, self.dofs[-1], F64)
         self.n_dofs = self.dofs[-1].n_dofs
 
-
-def _hierarchy_build_local_smoothing(self, ctx, fine, degree, smoother_degree, smoothing_range, eig_cg_n_iterations, coarse_solver,
-                                     number_type, max_brick):
-    """solve_with_local_smoothing (ref:multigrid_throughput.cc:1670-1873): operators on the refinement levels 0..L of the
-    octree, MGTransferMatrixFree between them, edge matrices, the outer operator on the active mesh"""
-    self.active_dofs = DoFs(fine, degree, max_brick)
-    self.trias = [fine.level_mesh(l) for l in range(fine.n_levels)]
-    self.degrees = [degree] * len(self.trias)
-    self.dofs = [DoFs(t, degree, max_brick, local_smoothing_level=True) for t in self.trias]
-    self.operators = [Operator(ctx, d, number_type) for d in self.dofs]
-    self.transfers = [None] + [MGTwoLevelTransfer(self.operators[l], self.operators[l - 1]) for l in range(1, len(self.dofs))]
-    self.smoothers = [PreconditionChebyshev(op, smoother_degree, smoothing_range, eig_cg_n_iterations) for op in self.operators]
-    self.coarse = None
-    self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, local_smoothing=self.active_dofs)
-    self.fine_operator = Operator(ctx, self.active_dofs, F64)
-    self.n_dofs = self.active_dofs.n_dofs
-
-
-Hierarchy._build_local_smoothing = _hierarchy_build_local_smoothing
+    def _build_local_smoothing(self, ctx, fine, degree, smoother, coarse_solver, number_type, max_brick):
+        """solve_with_local_smoothing (ref:multigrid_throughput.cc:1670-1873): operators on the refinement levels 0..L of the
+        octree, MGTransferMatrixFree between them, edge matrices, the outer operator on the active mesh"""
+        self.active_dofs = DoFs(fine, degree, max_brick)
+        meshes = [fine.level_mesh(l) for l in range(fine.n_levels)]
+        plan, local_smoothing = _level_plan("HMG-local", len(meshes), degree)
+        self.trias, self.degrees = [meshes[mi] for mi, _ in plan], [p for _, p in plan]
+        self.dofs, self.operators, self.transfers, self.smoothers = _build_levels(ctx, meshes, plan, number_type, max_brick, smoother,
+                                                                                  local_smoothing=local_smoothing)
+        self.coarse = None
+        self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, local_smoothing=self.active_dofs)
+        self.fine_operator = Operator(ctx, self.active_dofs, F64)
+        self.n_dofs = self.active_dofs.n_dofs
 
 
 class DistributedHierarchy:
@@ -969,75 +981,58 @@ class DistributedHierarchy:
 
     def __init__(self, ctx: Context, comm: Communicator, geometry="quadrant", n_ref_global=3, degree=1, smoother_degree=3,
                  smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64, hanging_weight=2.0, max_brick=-1,
-                 min_root_dofs=4_000_000, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None, min_subset_dofs=1_000_000,
-                 sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT):
+                 min_root_dofs=MIN_ROOT_DOFS_DEFAULT, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None,
+                 min_subset_dofs=MIN_SUBSET_DOFS_DEFAULT, sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT):
         """sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
         smoothed-aggregation AMG cut into rows over the ranks (replicated setup, sharded cycle; levels of at most
         amg_min_sharded_rows rows replicated) instead of the geometric stand-in "gmg_vcycle".  Off by default."""
         self.ctx, self.comm = ctx, comm
+        if mg_type not in ("HMG-global", "PMG", "HPMG"):
+            raise MgamdError(f"Type '{mg_type}' not implemented")
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global)
         self.mesh_sequence = create_geometric_coarsening_sequence(fine)
-        nm = len(self.mesh_sequence)
         # (mesh index, degree) of every multigrid level, coarse -> fine (ref:multigrid_throughput.cc:1506-1571)
-        if mg_type == "HMG-global":
-            plan = [(l, degree) for l in range(nm)]
-        elif mg_type == "PMG":
-            plan = [(nm - 1, p) for p in create_polynomial_coarsening_sequence(degree)]
-        elif mg_type == "HPMG":
-            pseq = create_polynomial_coarsening_sequence(degree)
-            plan = [(l, pseq[0]) for l in range(nm)] + [(nm - 1, p) for p in pseq[1:]]
-        else:
-            raise MgamdError(f"Type '{mg_type}' not implemented")
-        # levels below ~4 M DoFs stay replicated: their single-GPU time (latency-bound: 0.34 ms for 2.3 M DoFs at p=4,
-        # 0.33 ms for 2.2 M at p=1) is below what a distributed level pays for its 8 halo exchanges per cycle on top of its
-        # own (also latency-bound) kernels
-        # (round 3) levels between min_subset_dofs and min_root_dofs are cut into n_ranks / subset_group parts, each held by a
-        # group of ranks (Partition tiers): default groups of 4 from 8 ranks on, of 2 for 4-7 ranks
-        p_low = min(p for _, p in plan)
+        self.plan, _ = _level_plan(mg_type, len(self.mesh_sequence), degree)
+        # levels below ~4 M DoFs stay replicated: their single-GPU time (latency-bound: 0.34 ms for 2.3 M DoFs at p=4, 0.33 ms for
+        # 2.2 M at p=1) is below what a distributed level pays for its 8 halo exchanges per cycle on top of its own kernels; levels
+        # between min_subset_dofs and min_root_dofs are cut into n_ranks / subset_group parts, each held by a group of ranks
+        # (Partition tiers); the default group is mgamd_partition_defaults'
+        p_low = min(p for _, p in self.plan)
         if subset_group is None:
-            subset_group = 4 if comm.n_ranks % 4 == 0 and comm.n_ranks >= 8 else (2 if comm.n_ranks % 2 == 0 and comm.n_ranks >= 4 else 1)
+            subset_group = _partition_defaults(comm.n_ranks)[0]
         self.partition = Partition(self.mesh_sequence, comm.n_ranks, hanging_weight, min_root_dofs // p_low ** 3, subset_group,
                                    min_subset_dofs // p_low ** 3)
-        sharded = comm.n_ranks > 1
         sub_comm = comm.subset(self.partition.group) if self.partition.group > 1 else comm
         self.level_comm = lambda mi: comm if mi >= self.partition.root_level else sub_comm
+        smoother = (smoother_degree, smoothing_range, eig_cg_n_iterations)
 
-        def build(levels, shared_level0=None):
-            """levels: list of (mesh index, degree); shared_level0: (dofs, operator, smoother) reused as the LAST level"""
-            dofs = [DoFs(self.mesh_sequence[mi], p, max_brick, self.partition, mi, comm.rank) for mi, p in levels]
-            dist = [sharded and mi >= self.partition.sub_root_level for mi, _ in levels]
-            if shared_level0 is not None:
-                dofs[-1] = shared_level0[0]
-            ops = [Operator(ctx, d, number_type, self.level_comm(levels[l][0]) if dist[l] else None) for l, d in enumerate(dofs)]
-            if shared_level0 is not None:
-                ops[-1] = shared_level0[1]
-            tr = [None] + [MGTwoLevelTransfer(ops[l], ops[l - 1]) for l in range(1, len(ops))]
-            sm = [PreconditionChebyshev(op, smoother_degree, smoothing_range, eig_cg_n_iterations) for op in ops]
-            if shared_level0 is not None:
-                sm[-1] = shared_level0[2]
-            return dofs, dist, ops, tr, sm
+        def mesh_comm(mi):
+            return self.level_comm(mi) if comm.n_ranks > 1 and mi >= self.partition.sub_root_level else None
 
-        self.trias = [self.mesh_sequence[mi] for mi, _ in plan]
-        self.degrees = [p for _, p in plan]
-        self.dofs, self.distributed, self.operators, self.transfers, self.smoothers = build(plan)
-        self.coarse = None
-        self.plan = plan
-        n0 = self.global_level_dofs(ctx)[0]
-        self.amg_global_dofs = None
-        if sharded_amg and coarse_solver in AMG_COARSE_SOLVERS and n0 > 4096:
+        def build(plan, shared_last=None):
+            return _build_levels(ctx, self.mesh_sequence, plan, number_type, max_brick, smoother, self.partition, comm.rank, mesh_comm,
+                                 shared_last=shared_last)
+
+        self.trias = [self.mesh_sequence[mi] for mi, _ in self.plan]
+        self.degrees = [p for _, p in self.plan]
+        self.distributed = [mesh_comm(mi) is not None for mi, _ in self.plan]
+        self.dofs, self.operators, self.transfers, self.smoothers = build(self.plan)
+        self.coarse, self.amg_global_dofs = None, None
+        mi0, p0 = self.plan[0]
+        extra = _coarse_plan(coarse_solver, self.global_level_dofs(ctx)[0], self.distributed[0], sharded_amg)
+        if extra == COARSE_SHARDED_AMG:
             # every rank builds the one-rank AMG from the global tables of level 0's space and keeps its rows (amg_shard.hpp)
-            mi0, p0 = plan[0]
             self.amg_global_dofs = DoFs(self.mesh_sequence[mi0], p0, max_brick)
             self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, None, coarse_n_cycles,
                                      sharded_amg=self.amg_global_dofs, amg_min_sharded_rows=amg_min_sharded_rows)
-        elif (coarse_solver == "gmg_vcycle" or (coarse_solver in AMG_COARSE_SOLVERS and self.distributed[0])) and n0 > 4096:
-            # geometric stand-in for the AMG coarse solvers: the h-multigrid on level 0's space (mgamd.h, "gmg_vcycle"); the
-            # algebraic multigrid is built from ONE rank's assembled matrix, so a sharded coarse level takes the stand-in
-            mi0, p0 = plan[0]
-            cd, cdist, cops, ctr, csm = build([(l, p0) for l in range(mi0 + 1)], (self.dofs[0], self.operators[0], self.smoothers[0]))
-            self.coarse = PreconditionMG(ctx, cops, ctr, csm, "amg")
-            self.coarse.parts = (cd, cdist)
-        if self.amg_global_dofs is None:
+        else:
+            if extra == COARSE_NESTED:
+                # geometric stand-in for the AMG coarse solvers: the h-multigrid on level 0's space (mgamd.h, "gmg_vcycle"); the
+                # algebraic multigrid is built from ONE rank's assembled matrix, so a sharded coarse level takes the stand-in
+                cplan, _ = _level_plan("HMG-global", mi0 + 1, p0)
+                cd, cops, ctr, csm = build(cplan, (self.dofs[0], self.operators[0], self.smoothers[0]))
+                self.coarse = PreconditionMG(ctx, cops, ctr, csm, "amg")
+                self.coarse.parts = (cd, [mesh_comm(mi) is not None for mi, _ in cplan])
             self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, self.coarse, coarse_n_cycles)
         self.fine_operator = self.operators[-1]
         self.n_local = self.dofs[-1].n_dofs

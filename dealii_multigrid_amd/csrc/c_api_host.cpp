@@ -34,6 +34,81 @@ mgamd_version(void)
   return "mgamd 0.1 (gfx950)";
 }
 
+// ---- hierarchy policy (mgamd.h, "Hierarchy policy") ----------------------------------------------------------
+int
+mgamd_level_plan(const char *type, unsigned n_meshes, unsigned degree, unsigned max_levels, unsigned *n_levels, unsigned *mesh_index,
+                 unsigned *degrees, int *local_smoothing)
+{
+  MGAMD_TRY
+  if (!type || !n_levels || !mesh_index || !degrees || !local_smoothing)
+    throw std::invalid_argument("null argument");
+  if (n_meshes == 0 || degree == 0)
+    throw std::invalid_argument("level plan: needs a mesh and a degree >= 1");
+  const std::string t = type;
+  // create_polynomial_coarsening_sequence(degree, bisect) (ref:multigrid_throughput.cc:1506-1510), lowest degree first
+  std::vector<unsigned> pseq{degree};
+  while (pseq.back() > 1)
+    pseq.push_back(pseq.back() / 2);
+  std::reverse(pseq.begin(), pseq.end());
+  std::vector<std::pair<unsigned, unsigned>> plan;
+  if (t == "HMG-global" || t == "HMG-local")
+    for (unsigned l = 0; l < n_meshes; ++l)
+      plan.emplace_back(l, degree);
+  else if (t == "PMG" || t == "HPMG" || t == "HPMG-local")
+    {
+      // HPMG: h-levels at the lowest degree first (ref:multigrid_throughput.cc:1518-1519,1551-1553,1569-1571)
+      for (unsigned l = 0; t == "HPMG" && l + 1 < n_meshes; ++l)
+        plan.emplace_back(l, pseq.front());
+      for (const unsigned p : pseq)
+        plan.emplace_back(n_meshes - 1, p);
+    }
+  else
+    throw std::runtime_error("Type '" + t + "': not implemented");
+  if (plan.size() > max_levels)
+    throw std::invalid_argument("level plan: " + std::to_string(plan.size()) + " levels, room for " + std::to_string(max_levels));
+  for (size_t l = 0; l < plan.size(); ++l)
+    mesh_index[l] = plan[l].first, degrees[l] = plan[l].second;
+  *n_levels        = (unsigned)plan.size();
+  *local_smoothing = t == "HMG-local";
+  MGAMD_CATCH
+}
+
+// (the GLOBAL DoF count of level 0: every rank of a sharded run, and a one-rank run of the same problem, decide alike)
+int
+mgamd_coarse_plan(const char *coarse_name, uint64_t n_level0_dofs_global, int level0_distributed, int sharded_amg_requested, int *plan)
+{
+  MGAMD_TRY
+  if (!coarse_name || !plan)
+    throw std::invalid_argument("null argument");
+  const std::string c   = coarse_name;
+  const bool        amg = c == "amg" || c == "cg_with_amg" || c == "amg_petsc";
+  if (n_level0_dofs_global <= MGAMD_DIRECT_COARSE_MAX_DOFS)
+    *plan = MGAMD_COARSE_PLAIN;
+  else if (amg && sharded_amg_requested)
+    *plan = MGAMD_COARSE_SHARDED_AMG;
+  else if (c == "gmg_vcycle" || (amg && level0_distributed)) // the AMG is built from ONE rank's assembled matrix
+    *plan = MGAMD_COARSE_NESTED;
+  else
+    *plan = MGAMD_COARSE_PLAIN;
+  MGAMD_CATCH
+}
+
+int
+mgamd_partition_defaults(unsigned n_ranks, unsigned p_low, unsigned *group, uint64_t *min_root_cells, uint64_t *min_sub_root_cells)
+{
+  MGAMD_TRY
+  if (p_low == 0)
+    throw std::invalid_argument("partition defaults: degree 0");
+  const uint64_t p3 = (uint64_t)p_low * p_low * p_low;
+  if (group)
+    *group = (n_ranks >= 8 && n_ranks % 4 == 0) ? 4 : ((n_ranks >= 4 && n_ranks % 2 == 0) ? 2 : 1);
+  if (min_root_cells)
+    *min_root_cells = (uint64_t)4000000 / p3;
+  if (min_sub_root_cells)
+    *min_sub_root_cells = (uint64_t)1000000 / p3;
+  MGAMD_CATCH
+}
+
 int
 mgamd_tria_create(const char *geometry, unsigned n_ref_global, unsigned n_ref_local, mgamd_tria **out)
 {

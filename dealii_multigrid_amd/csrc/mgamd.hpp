@@ -18,6 +18,7 @@
 
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <fstream>
 #include <thread>
@@ -148,14 +149,34 @@ namespace mgamd
     return out;
   }
 
-  // ...::create_polynomial_coarsening_sequence(degree, bisect) (ref:multigrid_throughput.cc:1506-1510)
+  // The multigrid levels of `type` as (mesh index, degree), coarse -> fine, over n_meshes meshes, and whether they are local-smoothing
+  // levels (mgamd_level_plan: the one place that knows the level structure of HMG-global, PMG, HPMG, HMG-local and HPMG-local)
+  struct LevelPlan
+  {
+    std::vector<std::pair<unsigned, unsigned>> levels;
+    bool                                       local_smoothing = false;
+  };
+  inline LevelPlan
+  level_plan(const std::string &type, unsigned n_meshes, unsigned degree)
+  {
+    unsigned n = 0, mesh[64], deg[64];
+    int      ls = 0;
+    check(mgamd_level_plan(type.c_str(), n_meshes, degree, 64, &n, mesh, deg, &ls));
+    LevelPlan plan;
+    for (unsigned l = 0; l < n; ++l)
+      plan.levels.emplace_back(mesh[l], deg[l]);
+    plan.local_smoothing = ls != 0;
+    return plan;
+  }
+
+  // ...::create_polynomial_coarsening_sequence(degree, bisect) (ref:multigrid_throughput.cc:1506-1510): the degrees of the PMG levels
   inline std::vector<unsigned>
   create_polynomial_coarsening_sequence(unsigned degree)
   {
-    std::vector<unsigned> seq{degree};
-    while (seq.back() > 1)
-      seq.push_back(std::max(seq.back() / 2, 1u));
-    return {seq.rbegin(), seq.rend()};
+    std::vector<unsigned> seq;
+    for (const auto &level : level_plan("PMG", 1, degree).levels)
+      seq.push_back(level.second);
+    return seq;
   }
 
   // Domain decomposition of a level hierarchy, one rank per GPU (the reference partitions with p4est + RepartitioningPolicyTools,
@@ -673,6 +694,84 @@ namespace mgamd
     std::shared_ptr<mgamd_transfer2> h;
   };
 
+  // The levels of one multigrid hierarchy, coarse -> fine: what solve_with_global_coarsening / solve_with_local_smoothing build level
+  // by level (DoFHandler + constraints, Operator, MGTwoLevelTransfer, PreconditionChebyshev; ref:multigrid_throughput.cc:1540-1621),
+  // from the (mesh index, degree) list of level_plan()
+  class LevelStack
+  {
+  public:
+    // a sharded run: the levels are this rank's share of the partition's meshes; `comm` spans all ranks, `sub_comm` the parts of the
+    // subset tier (Communicator::subset(partition->group()))
+    struct Sharding
+    {
+      const Partition    *partition;
+      const Communicator *comm, *sub_comm;
+      const Communicator *
+      mesh_comm(unsigned mesh) const // of a distributed mesh; nullptr: the mesh is replicated
+      {
+        if (comm->n_ranks() <= 1 || mesh < partition->sub_root_level())
+          return nullptr;
+        return mesh >= partition->root_level() ? comm : sub_comm;
+      }
+    };
+    // a level that exists already: its DoFs (HPMG-local: level 0 acts on the DoFs of the local-smoothing cycle underneath) and, if the
+    // whole level is another stack's, its operator and smoother too (the coarse stand-in ends on the level it stands in for)
+    struct Given
+    {
+      unsigned                     level;
+      const DoFHandler            *dofs;
+      const Operator              *op       = nullptr;
+      const PreconditionChebyshev *smoother = nullptr;
+    };
+    LevelStack() = default;
+    // meshes: coarsest first (with `sharding`: the partition's); local_smoothing: they are Triangulation::level_mesh(l)
+    LevelStack(const Context &ctx, const std::vector<std::shared_ptr<const Triangulation>> &meshes,
+               const std::vector<std::pair<unsigned, unsigned>> &levels, int number_type, const PreconditionChebyshev::AdditionalData &smoother_data,
+               const Sharding *sharding = nullptr, bool local_smoothing = false, const Given *given = nullptr)
+      : operators(levels.size())
+      , transfers(levels.size())
+      , smoothers(levels.size())
+      , comms(levels.size(), nullptr)
+    {
+      const unsigned n = levels.size();
+      for (unsigned l = 0; l < n; ++l)
+        if (given && given->level == l)
+          dof_handlers.push_back(*given->dofs);
+        else if (sharding)
+          dof_handlers.emplace_back(*sharding->partition, levels[l].first, sharding->comm->rank(), levels[l].second);
+        else
+          dof_handlers.emplace_back(meshes[levels[l].first], levels[l].second, -1, local_smoothing);
+      for (unsigned l = 0; l < n; ++l)
+        {
+          comms[l] = sharding ? sharding->mesh_comm(levels[l].first) : nullptr;
+          if (given && given->level == l && given->op)
+            operators[l] = *given->op;
+          else if (sharding)
+            operators[l].reinit(ctx, dof_handlers[l], number_type, comms[l]);
+          else
+            operators[l].reinit(ctx, dof_handlers[l], number_type);
+        }
+      for (unsigned l = 1; l < n; ++l)
+        transfers[l].reinit(operators[l], operators[l - 1]);
+      for (unsigned l = 0; l < n; ++l)
+        if (given && given->level == l && given->smoother)
+          smoothers[l] = *given->smoother;
+        else
+          smoothers[l].initialize(operators[l], smoother_data);
+    }
+    // DoFHandler::n_dofs() of the GLOBAL level: the owned DoFs summed over the pieces of a distributed level
+    uint64_t
+    n_dofs_global(const Context &ctx, unsigned l) const
+    {
+      return comms[l] ? (uint64_t)std::llround(comms[l]->allreduce_sum(ctx, (double)operators[l].n_owned())) : dof_handlers[l].n_dofs();
+    }
+    std::vector<DoFHandler>            dof_handlers;
+    std::vector<Operator>              operators;
+    std::vector<MGTwoLevelTransfer>    transfers; // transfers[l]: levels l - 1 and l; transfers[0] unused
+    std::vector<PreconditionChebyshev> smoothers;
+    std::vector<const Communicator *>  comms; // per level; nullptr: replicated (or one rank)
+  };
+
   // Multigrid<VectorType> + PreconditionMG<dim,VectorType,MGTransferGlobalCoarsening> in one object
   class PreconditionMG
   {
@@ -686,32 +785,20 @@ namespace mgamd
                    const std::vector<PreconditionChebyshev> &smoothers, const std::string &coarse_grid_solver_type,
                    const PreconditionMG *coarse_mg = nullptr, unsigned n_cycles = 1, const DoFHandler *active_mesh_dofs = nullptr)
     {
-      const unsigned                 n = mg_matrices.size();
-      std::vector<mgamd_level_op *>  L(n);
-      std::vector<mgamd_transfer2 *> T(n, nullptr);
-      std::vector<mgamd_cheb *>      S(n);
-      for (unsigned l = 0; l < n; ++l)
-        {
-          L[l] = mg_matrices[l].get();
-          S[l] = smoothers[l].get();
-          if (l > 0)
-            T[l] = transfers[l].get();
-        }
-      mgamd_mg *m = nullptr;
+      const unsigned n = mg_matrices.size();
+      const auto     L = handles<mgamd_level_op>(mg_matrices, n);
+      const auto     T = handles<mgamd_transfer2>(transfers, n, 1);
+      const auto     S = handles<mgamd_cheb>(smoothers, n);
+      mgamd_mg      *m = nullptr;
       if (active_mesh_dofs)
         check(mgamd_mg_create_local_smoothing(ctx.get(), n, L.data(), T.data(), S.data(), active_mesh_dofs->get(),
                                               coarse_grid_solver_type.c_str(), &m));
-      else if (coarse_mg)
-        {
-          check(mgamd_mg_create_nested(ctx.get(), n, L.data(), T.data(), S.data(), coarse_grid_solver_type.c_str(), coarse_mg->get(),
-                                       n_cycles, &m));
-          nested = coarse_mg->h; // keep the nested hierarchy's handle alive
-        }
-      else // (n_cycles = CoarseSolverNCycles of the algebraic coarse solvers "amg" / "cg_with_amg")
-        check(mgamd_mg_create_nested(ctx.get(), n, L.data(), T.data(), S.data(), coarse_grid_solver_type.c_str(), nullptr, n_cycles, &m));
-      h.reset(m, mgamd_mg_destroy);
-      slots.resize(9);
-      n_levels = n;
+      else // (n_cycles = CoarseSolverNCycles, also of the algebraic coarse solvers "amg" / "cg_with_amg")
+        check(mgamd_mg_create_nested(ctx.get(), n, L.data(), T.data(), S.data(), coarse_grid_solver_type.c_str(),
+                                     coarse_mg ? coarse_mg->get() : nullptr, n_cycles, &m));
+      if (coarse_mg)
+        nested = coarse_mg->h; // keep the nested hierarchy's handle alive
+      adopt(m, n);
     }
     // The AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a SHARDED mg_matrices[0] (mgamd_mg_create_sharded_amg): replicated
     // setup from `global_coarse_dofs` (the DoFHandler of level 0's space on the whole mesh, built as a one-rank hierarchy builds
@@ -726,25 +813,16 @@ namespace mgamd
                    const std::vector<PreconditionChebyshev> &smoothers, const std::string &coarse_grid_solver_type, const ShardedAMG &amg,
                    unsigned n_cycles = 1)
     {
-      const unsigned                 n = mg_matrices.size();
-      std::vector<mgamd_level_op *>  L(n);
-      std::vector<mgamd_transfer2 *> T(n, nullptr);
-      std::vector<mgamd_cheb *>      S(n);
-      for (unsigned l = 0; l < n; ++l)
-        {
-          L[l] = mg_matrices[l].get();
-          S[l] = smoothers[l].get();
-          if (l > 0)
-            T[l] = transfers[l].get();
-        }
       if (!amg.global_coarse_dofs)
         throw std::invalid_argument("PreconditionMG: ShardedAMG needs the global DoFs of level 0's space");
-      mgamd_mg *m = nullptr;
+      const unsigned n = mg_matrices.size();
+      const auto     L = handles<mgamd_level_op>(mg_matrices, n);
+      const auto     T = handles<mgamd_transfer2>(transfers, n, 1);
+      const auto     S = handles<mgamd_cheb>(smoothers, n);
+      mgamd_mg      *m = nullptr;
       check(mgamd_mg_create_sharded_amg(ctx.get(), n, L.data(), T.data(), S.data(), coarse_grid_solver_type.c_str(),
                                         amg.global_coarse_dofs->get(), n_cycles, amg.min_sharded_rows, &m));
-      h.reset(m, mgamd_mg_destroy);
-      slots.resize(9);
-      n_levels = n;
+      adopt(m, n);
     }
     // the levels of the algebraic coarse solver that runs, finest first (mgamd_mg_amg_layout); empty: no AMG runs
     struct AmgLevelLayout
@@ -853,6 +931,23 @@ namespace mgamd
     }
 
   private:
+    // a handle array of the C entry points: n entries, those below `from` null (transfers[0] is unused)
+    template <typename Handle, typename Object>
+    static std::vector<Handle *>
+    handles(const std::vector<Object> &objects, unsigned n, unsigned from = 0)
+    {
+      std::vector<Handle *> out(n, nullptr);
+      for (unsigned l = from; l < n; ++l)
+        out[l] = objects[l].get();
+      return out;
+    }
+    void
+    adopt(mgamd_mg *m, unsigned n)
+    {
+      h.reset(m, mgamd_mg_destroy);
+      slots.resize(9);
+      n_levels = n;
+    }
     void
     connect(int stage, StageSlot s)
     {

@@ -1730,13 +1730,16 @@ namespace mgamd
           tview[l] = Tb[l]->p;
         }
       // ONE policy for the reference's Trilinos/PETSc choices ("amg", "cg_with_amg", "amg_petsc"):
-      //   coarse level of <= 4096 DoFs (global coarsening ends on one cell): any AMG degenerates to an exact solve -> "direct";
+      //   coarse level of <= MGAMD_DIRECT_COARSE_MAX_DOFS DoFs (global coarsening ends on one cell): any AMG degenerates to an
+      //     exact solve -> "direct";
       //   larger coarse level (PMG, HPMG with MinLevel): the library's own smoothed-aggregation AMG on the assembled level matrix
       //     (amg.hpp, AmgCycle) -> "amg" / "cg_with_amg" (amg_petsc: BoomerAMG's role, the same SA hierarchy -> "amg");
       //   a `nested` geometric multigrid on level 0's space, if the caller supplies one, takes the coarse solver's place as
       //     "gmg_vcycle" (the round-1/2 stand-in, still the DEFAULT on a SHARDED coarse level);
       //   `amg_global` (the global tables of level 0's space), if the caller supplies them, asks for the algebraic multigrid on a
       //     sharded level 0: replicated setup, sharded cycle (AmgCycle's second set-up) -> "amg" / "cg_with_amg".
+      // Whether a caller builds `nested` or `amg_global` is decided by mgamd_coarse_plan (c_api_host.cpp), for the harness and the
+      // Python hierarchies alike; this constructor validates what it is given.
       // Never a silent substitution: coarse_used names what runs (harness table column / bench JSON).
       coarse_type = coarse;
       const bool amg_like = coarse == "amg" || coarse == "cg_with_amg" || coarse == "amg_petsc";
@@ -1758,7 +1761,7 @@ namespace mgamd
         }
       else if (amg_like)
         {
-          if (ops[0]->n_dofs() <= 4096)
+          if (ops[0]->n_dofs() <= MGAMD_DIRECT_COARSE_MAX_DOFS)
             coarse_type = "direct";
           else
             {
@@ -1773,9 +1776,9 @@ namespace mgamd
       else if (coarse == "gmg_vcycle")
         {
           // no nested multigrid to hand the coarse problem to: a small level is solved exactly, a large one is an error
-          if (ops[0]->n_dofs() > 4096)
-            throw std::invalid_argument("multigrid: CoarseGridSolverType 'gmg_vcycle' on a level of more than 4096 DoFs needs a nested "
-                                        "multigrid");
+          if (ops[0]->n_dofs() > MGAMD_DIRECT_COARSE_MAX_DOFS)
+            throw std::invalid_argument("multigrid: CoarseGridSolverType 'gmg_vcycle' on a level of more than " +
+                                        std::to_string(MGAMD_DIRECT_COARSE_MAX_DOFS) + " DoFs needs a nested multigrid");
           coarse_type = "direct";
         }
       coarse_used = coarse_type;
@@ -1859,7 +1862,7 @@ namespace mgamd
     setup_direct()
     {
       const size_t n = ops[0]->n_dofs();
-      if (n > 4096)
+      if (n > MGAMD_DIRECT_COARSE_MAX_DOFS)
         throw std::runtime_error("coarse level too large for the direct solver (" + std::to_string(n) +
                                  " DoFs): use CoarseGridSolverType cg or cg_with_chebyshev");
       // dense A_0 column by column through the level operator

@@ -278,220 +278,127 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
 
   auto tria = std::make_shared<const Triangulation>(params.geometry_type, params.n_ref_global, params.n_ref_local);
 
-  // ---- level hierarchy (ref:multigrid_throughput.cc:2219-2260, 1506-1596)
-  std::vector<std::shared_ptr<const Triangulation>> triangulations;
-  std::vector<unsigned>                             degrees;
-  if (params.type == "HMG-global")
+  // ---- level hierarchy (ref:multigrid_throughput.cc:2219-2260, 1506-1596): the meshes here, the levels on them from the library
+  // (mgamd_level_plan), which also refuses the Types without levels
+  const bool local_smoothing = params.type == "HMG-local", hp_local = params.type == "HPMG-local";
+  auto       level_meshes    = [&]() { // the refinement levels of the mesh (solve_with_local_smoothing, ref:multigrid_throughput.cc:1670-1873)
+    std::vector<std::shared_ptr<const Triangulation>> m;
+    for (unsigned l = 0; l < tria->n_global_levels(); ++l)
+      m.push_back(tria->level_mesh(l));
+    return m;
+  };
+  std::vector<std::shared_ptr<const Triangulation>> meshes{tria}; // PMG, HPMG-local on one rank: p-levels on the one mesh
+  if (local_smoothing)
+    meshes = level_meshes();
+  else if (params.type == "HMG-global" || params.type == "HPMG" || (comm && params.type == "PMG"))
+    meshes = create_geometric_coarsening_sequence(tria); // (sharded PMG: the meshes the partition is built on)
+  if (params.type == "HMG-global" && meshes.size() > 1)
     {
-      triangulations = create_geometric_coarsening_sequence(tria);
-      if (triangulations.size() > 1)
-        {
-          auto ptr = std::find_if(triangulations.begin(), triangulations.end() - 1, [&](const auto &t) {
-            if (params.min_level != -1)
-              return params.min_level <= (int)t->n_global_levels();
-            if (params.min_n_cells != -1)
-              return (int)t->n_global_active_cells() >= params.min_n_cells;
-            return true;
-          });
-          triangulations.erase(triangulations.begin(), ptr);
-        }
-      degrees.assign(triangulations.size(), params.fe_degree_fine);
+      auto ptr = std::find_if(meshes.begin(), meshes.end() - 1, [&](const auto &t) {
+        if (params.min_level != -1)
+          return params.min_level <= (int)t->n_global_levels();
+        if (params.min_n_cells != -1)
+          return (int)t->n_global_active_cells() >= params.min_n_cells;
+        return true;
+      });
+      meshes.erase(meshes.begin(), ptr);
     }
-  else if (params.type == "PMG")
-    {
-      degrees = create_polynomial_coarsening_sequence(params.fe_degree_fine);
-      triangulations.assign(degrees.size(), tria);
-    }
-  else if (params.type == "HPMG")
-    {
-      // ref:multigrid_throughput.cc:1518-1519,1551-1553,1569-1571: h-levels at the lowest degree, then p-levels
-      const auto pseq = create_polynomial_coarsening_sequence(params.fe_degree_fine);
-      triangulations  = create_geometric_coarsening_sequence(tria);
-      degrees.assign(triangulations.size(), pseq.front());
-      for (size_t i = 1; i < pseq.size(); ++i)
-        {
-          triangulations.push_back(tria);
-          degrees.push_back(pseq[i]);
-        }
-    }
-  else if (params.type == "HPMG-local")
-    {
-      // ref:multigrid_throughput.cc:1685-1695,1846-1860: p-multigrid on the active mesh; its coarse problem (lowest degree) is
-      // handed to one local-smoothing V-cycle, built below
-      degrees = create_polynomial_coarsening_sequence(params.fe_degree_fine);
-      triangulations.assign(degrees.size(), tria);
-    }
-  else if (params.type == "HMG-local")
-    {
-      // solve_with_local_smoothing (ref:multigrid_throughput.cc:1670-1873): the levels are the refinement levels of the mesh
-      for (unsigned l = 0; l < tria->n_global_levels(); ++l)
-        triangulations.push_back(tria->level_mesh(l));
-      degrees.assign(triangulations.size(), params.fe_degree_fine);
-    }
-  else
-    throw std::runtime_error("Type '" + params.type + "': not implemented");
-  const bool local_smoothing = params.type == "HMG-local";
+  const LevelPlan plan     = level_plan(params.type, meshes.size(), params.fe_degree_fine);
+  const unsigned  n_levels = plan.levels.size();
   if (comm && !(params.type == "HMG-global" || params.type == "PMG" || params.type == "HPMG"))
     throw std::runtime_error("sharded harness: Type '" + params.type + "' is not implemented (HMG-global, PMG and HPMG are)");
-  // the geometric meshes the partition is built on, and the mesh of every multigrid level: the p-levels of PMG / HPMG live on the
-  // finest mesh and inherit its partition (ref:multigrid_throughput.cc:1506-1571)
-  std::vector<std::shared_ptr<const Triangulation>> mesh_sequence = triangulations;
-  std::vector<unsigned>                             mesh_index(triangulations.size());
-  for (unsigned l = 0; l < mesh_index.size(); ++l)
-    mesh_index[l] = l;
-  if (comm && (params.type == "PMG" || params.type == "HPMG"))
-    {
-      mesh_sequence = create_geometric_coarsening_sequence(tria);
-      for (unsigned l = 0; l < mesh_index.size(); ++l)
-        mesh_index[l] = params.type == "PMG" ? (unsigned)mesh_sequence.size() - 1 : std::min<unsigned>(l, (unsigned)mesh_sequence.size() - 1);
-    }
   // levels of >= ~4 M DoFs are cut into one chunk per rank, those of >= ~1 M DoFs into n_ranks / group parts that a group of ranks
-  // holds together (groups of 4 from 8 ranks on, of 2 from 4 on), the others are replicated (the counterpart
-  // of the reference's min_level / min_n_cells_per_process agglomeration, ref:multigrid_throughput.cc:379-418,1464-1501)
+  // holds together, the others are replicated (mgamd_partition_defaults; the counterpart of the reference's
+  // min_level / min_n_cells_per_process agglomeration, ref:multigrid_throughput.cc:379-418,1464-1501)
   std::unique_ptr<Partition> partition;
   Communicator               sub_comm;
+  LevelStack::Sharding       sharding{nullptr, comm, &sub_comm};
   if (comm)
     {
-      const uint64_t p_low = *std::min_element(degrees.begin(), degrees.end());
-      const uint64_t p3    = p_low * p_low * p_low;
-      const unsigned nr    = comm->n_ranks();
-      const unsigned group = (nr >= 8 && nr % 4 == 0) ? 4 : ((nr >= 4 && nr % 2 == 0) ? 2 : 1);
-      partition            = std::make_unique<Partition>(mesh_sequence, nr, 2.0, (uint64_t)4000000 / p3, group, (uint64_t)1000000 / p3);
-      sub_comm             = comm->subset(partition->group());
+      unsigned p_low = params.fe_degree_fine, group = 1;
+      uint64_t min_root_cells = 0, min_sub_root_cells = 0;
+      for (const auto &level : plan.levels)
+        p_low = std::min(p_low, level.second);
+      check(mgamd_partition_defaults(comm->n_ranks(), p_low, &group, &min_root_cells, &min_sub_root_cells));
+      partition          = std::make_unique<Partition>(meshes, comm->n_ranks(), 2.0, min_root_cells, group, min_sub_root_cells);
+      sub_comm           = comm->subset(partition->group());
+      sharding.partition = partition.get();
     }
-  // (by mesh index: what the partition knows)
-  auto mesh_distributed = [&](unsigned mi) { return comm && comm->n_ranks() > 1 && mi >= partition->sub_root_level(); };
-  auto mesh_comm        = [&](unsigned mi) -> const Communicator        *{ return mi >= partition->root_level() ? comm : &sub_comm; };
-  auto distributed      = [&](unsigned l) { return mesh_distributed(mesh_index[l]); };
-  auto level_comm       = [&](unsigned l) { return mesh_comm(mesh_index[l]); };
+  const LevelStack::Sharding *shards = comm ? &sharding : nullptr;
 
-  const bool hp_local        = params.type == "HPMG-local";
   PreconditionChebyshev::AdditionalData sd;
   sd.smoothing_range     = params.mg_data.smoother.smoothing_range;
   sd.degree              = params.mg_data.smoother.degree;
   sd.eig_cg_n_iterations = params.mg_data.smoother.eig_cg_n_iterations;
-  // HPMG-local: the local-smoothing hierarchy of the lowest degree (the coarse solver of the p-levels)
-  std::vector<DoFHandler>            ls_dof_handlers;
-  std::vector<Operator>              ls_operators;
-  std::vector<MGTwoLevelTransfer>    ls_transfers;
-  std::vector<PreconditionChebyshev> ls_smoothers;
-  std::unique_ptr<DoFHandler>        ls_active;
-  std::unique_ptr<PreconditionMG>    ls_mg;
+  // local smoothing: the DoFs of the active mesh, which the outer vectors live on
+  std::unique_ptr<DoFHandler> active_dof_handler;
+  if (local_smoothing || hp_local)
+    active_dof_handler = std::make_unique<DoFHandler>(tria, plan.levels.front().second);
+  // HPMG-local (ref:multigrid_throughput.cc:1685-1695,1846-1860): the coarse problem of the p-levels (lowest degree) is handed to one
+  // local-smoothing V-cycle; level 0 acts on the SAME DoFs as that cycle
+  LevelStack                      ls;
+  std::unique_ptr<PreconditionMG> ls_mg;
   if (hp_local)
     {
-      const unsigned nls = tria->n_global_levels();
-      ls_operators.resize(nls);
-      ls_transfers.resize(nls);
-      ls_smoothers.resize(nls);
-      for (unsigned l = 0; l < nls; ++l)
-        ls_dof_handlers.emplace_back(tria->level_mesh(l), degrees.front(), -1, true);
-      ls_active = std::make_unique<DoFHandler>(tria, degrees.front());
-      for (unsigned l = 0; l < nls; ++l)
-        ls_operators[l].reinit(ctx, ls_dof_handlers[l], level_number_type);
-      for (unsigned l = 1; l < nls; ++l)
-        ls_transfers[l].reinit(ls_operators[l], ls_operators[l - 1]);
-      for (unsigned l = 0; l < nls; ++l)
-        ls_smoothers[l].initialize(ls_operators[l], sd);
-      ls_mg = std::make_unique<PreconditionMG>(ctx, ls_operators, ls_transfers, ls_smoothers, params.mg_data.coarse_solver.type, nullptr, 1,
-                                               ls_active.get());
+      const auto ls_meshes = level_meshes();
+      const auto ls_plan   = level_plan("HMG-local", ls_meshes.size(), plan.levels.front().second);
+      ls    = LevelStack(ctx, ls_meshes, ls_plan.levels, level_number_type, sd, nullptr, ls_plan.local_smoothing);
+      ls_mg = std::make_unique<PreconditionMG>(ctx, ls.operators, ls.transfers, ls.smoothers, params.mg_data.coarse_solver.type, nullptr, 1,
+                                               active_dof_handler.get());
     }
-
-  const unsigned                  n_levels = degrees.size();
-  std::vector<DoFHandler>         dof_handlers;
-  std::vector<Operator>           operators(n_levels);
-  std::vector<MGTwoLevelTransfer> transfers(n_levels);
-  std::vector<PreconditionChebyshev> smoothers(n_levels);
-  for (unsigned l = 0; l < n_levels; ++l)
-    if (hp_local && l == 0)
-      dof_handlers.push_back(*ls_active); // the SAME DoFs as the local-smoothing cycle acts on
-    else if (comm)
-      dof_handlers.emplace_back(*partition, mesh_index[l], comm->rank(), degrees[l]);
-    else
-      dof_handlers.emplace_back(triangulations[l], degrees[l], -1, local_smoothing);
-  std::unique_ptr<DoFHandler> active_dof_handler;
-  if (local_smoothing)
-    active_dof_handler = std::make_unique<DoFHandler>(tria, params.fe_degree_fine);
-  const DoFHandler &fine_dof_handler = local_smoothing ? *active_dof_handler : dof_handlers.back();
-  for (unsigned l = 0; l < n_levels; ++l)
-    if (comm)
-      operators[l].reinit(ctx, dof_handlers[l], level_number_type, distributed(l) ? level_comm(l) : nullptr);
-    else
-      operators[l].reinit(ctx, dof_handlers[l], level_number_type);
-  for (unsigned l = 1; l < n_levels; ++l)
-    transfers[l].reinit(operators[l], operators[l - 1]);
-  for (unsigned l = 0; l < n_levels; ++l)
-    smoothers[l].initialize(operators[l], sd);
+  const LevelStack::Given ls_level0{0, active_dof_handler.get()};
+  const LevelStack        stack(ctx, meshes, plan.levels, level_number_type, sd, shards, plan.local_smoothing, hp_local ? &ls_level0 : nullptr);
+  const DoFHandler       &fine_dof_handler = local_smoothing ? *active_dof_handler : stack.dof_handlers.back();
 
   // coarse solver (library policy, include/mgamd.h): the Trilinos/PETSc AMG options are an exact solve on the one-cell coarse
   // level of global coarsening and, on a large coarse level (PMG, MinLevel), the library's own smoothed-aggregation AMG.
   // CoarseGridSolverType "gmg_vcycle" (this project's extension) selects the geometric stand-in of rounds 1-2 instead: V-cycles
   // of the h-multigrid on that level.  The table says what ran in its `coarse_solver` column.
+  // What has to be built for it is mgamd_coarse_plan's decision: the stand-in ("gmg_vcycle", and the AMG choices on a SHARDED coarse
+  // level: the AMG is built from one rank's matrix) or, with "ShardedAMG": true (sharded runs), the global DoFs of the coarse space,
+  // from which every rank sets the AMG up and keeps its rows of the cycle.  HPMG-local has its nested multigrid already.
   const std::string coarse = hp_local ? std::string("gmg_vcycle") : params.mg_data.coarse_solver.type;
-  // (a SHARDED coarse level takes the geometric stand-in for the AMG choices too: the AMG is built from one rank's matrix)
-  const bool amg_name = coarse == "amg" || coarse == "cg_with_amg" || coarse == "amg_petsc";
-  // "ShardedAMG": true (sharded runs): the AMG itself, set up from the global tables of the coarse space on every rank, its
-  // cycle cut into rows over the ranks
-  const bool sharded_amg = comm && !hp_local && amg_name && params.sharded_amg && dof_handlers[0].n_dofs() > 4096;
-  const bool amg_like    = !hp_local && !sharded_amg && (coarse == "gmg_vcycle" || (comm && distributed(0) && amg_name));
-  std::vector<DoFHandler>            c_dof_handlers;
-  std::vector<Operator>              c_operators;
-  std::vector<MGTwoLevelTransfer>    c_transfers;
-  std::vector<PreconditionChebyshev> c_smoothers;
-  std::unique_ptr<PreconditionMG>    coarse_mg;
-  if (amg_like && dof_handlers[0].n_dofs() > 4096)
+  int               extra  = MGAMD_COARSE_PLAIN;
+  if (!hp_local)
+    check(mgamd_coarse_plan(coarse.c_str(), stack.n_dofs_global(ctx, 0), stack.comms[0] != nullptr, comm && params.sharded_amg, &extra));
+  const unsigned                  mesh0 = plan.levels.front().first, degree0 = plan.levels.front().second;
+  LevelStack                      c_stack;
+  std::unique_ptr<PreconditionMG> coarse_mg;
+  if (extra == MGAMD_COARSE_NESTED)
     {
-      const auto c_trias = create_geometric_coarsening_sequence(triangulations[0]);
-      const unsigned nc  = c_trias.size();
-      c_operators.resize(nc);
-      c_transfers.resize(nc);
-      c_smoothers.resize(nc);
-      if (comm && nc != mesh_index[0] + 1)
+      const auto c_meshes = create_geometric_coarsening_sequence(meshes[mesh0]);
+      if (comm && c_meshes.size() != mesh0 + 1)
         throw std::runtime_error("sharded harness: the coarse level's mesh is not the end of the partition's mesh sequence");
-      for (unsigned l = 0; l + 1 < nc; ++l)
-        if (comm)
-          c_dof_handlers.emplace_back(*partition, l, comm->rank(), degrees[0]); // (mesh index = level of the coarse hierarchy)
-        else
-          c_dof_handlers.emplace_back(c_trias[l], degrees[0]);
-      for (unsigned l = 0; l + 1 < nc; ++l)
-        if (comm)
-          c_operators[l].reinit(ctx, c_dof_handlers[l], level_number_type, mesh_distributed(l) ? mesh_comm(l) : nullptr);
-        else
-          c_operators[l].reinit(ctx, c_dof_handlers[l], level_number_type);
-      c_operators[nc - 1] = operators[0];
-      for (unsigned l = 1; l < nc; ++l)
-        c_transfers[l].reinit(c_operators[l], c_operators[l - 1]);
-      for (unsigned l = 0; l + 1 < nc; ++l)
-        c_smoothers[l].initialize(c_operators[l], sd);
-      c_smoothers[nc - 1] = smoothers[0];
-      coarse_mg           = std::make_unique<PreconditionMG>(ctx, c_operators, c_transfers, c_smoothers, "amg");
-      std::cout << "note: CoarseGridSolverType '" << coarse << "' on the " << dof_handlers[0].n_dofs() << "-DoF coarse level: "
+      const LevelStack::Given top{(unsigned)c_meshes.size() - 1, &stack.dof_handlers[0], &stack.operators[0], &stack.smoothers[0]};
+      c_stack   = LevelStack(ctx, c_meshes, level_plan("HMG-global", c_meshes.size(), degree0).levels, level_number_type, sd, shards, false, &top);
+      coarse_mg = std::make_unique<PreconditionMG>(ctx, c_stack.operators, c_stack.transfers, c_stack.smoothers, "amg");
+      std::cout << "note: CoarseGridSolverType '" << coarse << "' on the " << stack.dof_handlers[0].n_dofs() << "-DoF coarse level: "
                 << params.mg_data.coarse_solver.n_cycles << " V-cycle(s) of the geometric multigrid on that level" << std::endl;
     }
   std::unique_ptr<DoFHandler> amg_global_dofs;
-  if (sharded_amg)
+  if (extra == MGAMD_COARSE_SHARDED_AMG)
     {
-      amg_global_dofs = std::make_unique<DoFHandler>(mesh_sequence[mesh_index[0]], degrees[0]);
+      amg_global_dofs = std::make_unique<DoFHandler>(meshes[mesh0], degree0);
       std::cout << "note: CoarseGridSolverType '" << coarse << "' on the sharded " << amg_global_dofs->n_dofs() << "-DoF coarse level: "
                 << params.mg_data.coarse_solver.n_cycles << " cycle(s) of the smoothed-aggregation AMG, rows cut over the ranks (levels of <= "
                 << params.amg_min_sharded_rows << " rows replicated)" << std::endl;
     }
   PreconditionMG preconditioner =
-    sharded_amg ? PreconditionMG(ctx, operators, transfers, smoothers, coarse, PreconditionMG::ShardedAMG{amg_global_dofs.get(), params.amg_min_sharded_rows},
-                                 params.mg_data.coarse_solver.n_cycles) :
-                  PreconditionMG(ctx, operators, transfers, smoothers, coarse, hp_local ? ls_mg.get() : coarse_mg.get(),
-                                 hp_local ? 1u : params.mg_data.coarse_solver.n_cycles, active_dof_handler.get());
+    amg_global_dofs ? PreconditionMG(ctx, stack.operators, stack.transfers, stack.smoothers, coarse,
+                                     PreconditionMG::ShardedAMG{amg_global_dofs.get(), params.amg_min_sharded_rows}, params.mg_data.coarse_solver.n_cycles) :
+                      PreconditionMG(ctx, stack.operators, stack.transfers, stack.smoothers, coarse, hp_local ? ls_mg.get() : coarse_mg.get(),
+                                     hp_local ? 1u : params.mg_data.coarse_solver.n_cycles, local_smoothing ? active_dof_handler.get() : nullptr);
 
   // fine (outer, double) operator, right-hand side (ref:multigrid_throughput.cc:2262-2324)
   Operator op;
   if (level_number_type == MGAMD_F64 && !local_smoothing)
-    op = operators.back();
+    op = stack.operators.back();
   else if (comm)
-    op.reinit(ctx, fine_dof_handler, MGAMD_F64, distributed(n_levels - 1) ? level_comm(n_levels - 1) : nullptr);
+    op.reinit(ctx, fine_dof_handler, MGAMD_F64, stack.comms.back());
   else
     op.reinit(ctx, fine_dof_handler, MGAMD_F64);
   // DoFHandler::n_dofs() of the GLOBAL problem
-  const uint64_t n_dofs_global = (comm && distributed(n_levels - 1)) ? (uint64_t)std::llround(level_comm(n_levels - 1)->allreduce_sum(ctx, (double)op.n_owned())) :
-                                                                       fine_dof_handler.n_dofs();
+  const uint64_t n_dofs_global = local_smoothing ? fine_dof_handler.n_dofs() : stack.n_dofs_global(ctx, n_levels - 1);
   Vector solution, rhs;
   op.initialize_dof_vector(solution);
   op.initialize_dof_vector(rhs);
@@ -513,8 +420,8 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
       ConvergenceTable t;
       for (unsigned l = 0; l < n_levels; ++l)
         {
-          t.add_value("cells", triangulations[l]->n_global_active_cells());
-          t.add_value("dofs", dof_handlers[l].n_dofs());
+          t.add_value("cells", meshes[plan.levels[l].first]->n_global_active_cells());
+          t.add_value("dofs", stack.dof_handlers[l].n_dofs());
         }
       t.write_text(std::cout);
     }
@@ -581,22 +488,13 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
     {
       // partition statistics of the level meshes (ref:multigrid_throughput.cc:1657-1665, ref:include/mg_tools.h:267-512); the
       // p-levels of PMG/HPMG repeat the finest mesh: every distinct mesh once, coarse -> fine
-      std::vector<std::shared_ptr<const Triangulation>> meshes;
-      for (const auto &t : triangulations)
-        if (meshes.empty() || meshes.back().get() != t.get())
-          meshes.push_back(t);
       // local smoothing: the reference calls the single-triangulation overload (ref:multigrid_throughput.cc:1862-1872,
-      // ref:include/mg_tools.h:39-61,85,195), which counts ALL cells of each refinement level of the one mesh: `triangulations`
-      // holds exactly those level meshes here.  PMG (one mesh, several degrees): its coarsening sequence.
-      if (!local_smoothing && meshes.size() == 1)
-        meshes = create_geometric_coarsening_sequence(tria);
-      if (hp_local)
-        {
-          meshes.clear();
-          for (unsigned l = 0; l < tria->n_global_levels(); ++l)
-            meshes.push_back(tria->level_mesh(l));
-        }
-      for (const auto &stat : print_multigrid_statistics(meshes, comm ? comm->n_ranks() : 1))
+      // ref:include/mg_tools.h:39-61,85,195), which counts ALL cells of each refinement level of the one mesh (HPMG-local: of the
+      // cycle underneath).  PMG on its one mesh: the coarsening sequence.
+      auto stat_meshes = hp_local ? level_meshes() : meshes;
+      if (!local_smoothing && !hp_local && stat_meshes.size() == 1)
+        stat_meshes = create_geometric_coarsening_sequence(tria);
+      for (const auto &stat : print_multigrid_statistics(stat_meshes, comm ? comm->n_ranks() : 1))
         table.add_value(stat.first, stat.second, true);
     }
   // this project's additions (after the reference's columns): DoF/s per V-cycle = n_dofs / (sum of the nine stage columns)

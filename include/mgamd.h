@@ -185,6 +185,44 @@ int mgamd_transfer_tables_get(const mgamd_dofs *fine, const mgamd_dofs *coarse, 
                               uint16_t *coarse_mask, uint32_t *fine_idx);
 
 /* ---------------------------------------------------------------------------------------------
+ * Hierarchy policy (plain integer functions, no GPU): what the harness, the C++ layer and the Python module build is decided
+ * here and nowhere else.
+ * ------------------------------------------------------------------------------------------- */
+
+/* most DoFs of a coarse level that is solved exactly ("direct": a dense inverse) */
+#define MGAMD_DIRECT_COARSE_MAX_DOFS 4096u
+
+/* The multigrid levels of `type`, coarse -> fine, as (mesh_index[l], degrees[l]) over the caller's n_meshes meshes (coarsest first;
+ * ref:multigrid_throughput.cc:1506-1571, 1685-1695).  The degrees of the p-levels are create_polynomial_coarsening_sequence(degree)
+ * (bisection: 7 -> 1, 3, 7):
+ *   "HMG-global"  (l, degree) on every mesh
+ *   "PMG"         the p-levels on the LAST mesh (one rank passes its one mesh, a sharded run the partition's mesh sequence)
+ *   "HPMG"        every mesh at the lowest degree, then the remaining p-levels on the last mesh
+ *   "HMG-local"   (l, degree) on every mesh, the meshes being the refinement levels (mgamd_tria_level_mesh): *local_smoothing = 1
+ *   "HPMG-local"  as "PMG"; its coarse solver is the "HMG-local" hierarchy at the lowest degree, which the caller plans separately
+ * Any other type: MGAMD_ERR, "Type '...': not implemented".  MGAMD_ERR_INVALID if the levels exceed max_levels. */
+int mgamd_level_plan(const char *type, unsigned n_meshes, unsigned degree, unsigned max_levels, unsigned *n_levels, unsigned *mesh_index,
+                     unsigned *degrees, int *local_smoothing);
+
+/* What the coarse solver `coarse_name` needs next to the levels, given the GLOBAL number of DoFs of level 0, whether level 0 is
+ * distributed and whether the caller asked for the sharded AMG:
+ *   at most MGAMD_DIRECT_COARSE_MAX_DOFS DoFs                                          -> MGAMD_COARSE_PLAIN
+ *   else, "amg" | "cg_with_amg" | "amg_petsc" with the sharded AMG requested            -> MGAMD_COARSE_SHARDED_AMG
+ *   else, "gmg_vcycle", or one of those three names on a distributed level 0            -> MGAMD_COARSE_NESTED
+ *   else                                                                                -> MGAMD_COARSE_PLAIN
+ * NESTED: build the h-multigrid on level 0's space and pass it to mgamd_mg_create_nested; SHARDED_AMG: build the global DoFs of
+ * that space and call mgamd_mg_create_sharded_amg. */
+#define MGAMD_COARSE_PLAIN 0
+#define MGAMD_COARSE_NESTED 1
+#define MGAMD_COARSE_SHARDED_AMG 2
+int mgamd_coarse_plan(const char *coarse_name, uint64_t n_level0_dofs_global, int level0_distributed, int sharded_amg_requested, int *plan);
+
+/* Defaults of mgamd_partition_create_tiered for n_ranks ranks and a hierarchy whose lowest degree is p_low: *group = 4 from 8 ranks
+ * on if 4 divides n_ranks, 2 from 4 ranks on if 2 does, else 1; levels of >= 4 000 000 / p_low^3 cells (~4 M DoFs) are cut over all
+ * ranks (*min_root_cells), those of >= 1 000 000 / p_low^3 cells over the groups (*min_sub_root_cells).  Any pointer may be NULL. */
+int mgamd_partition_defaults(unsigned n_ranks, unsigned p_low, unsigned *group, uint64_t *min_root_cells, uint64_t *min_sub_root_cells);
+
+/* ---------------------------------------------------------------------------------------------
  * Device runtime
  * ------------------------------------------------------------------------------------------- */
 int mgamd_ctx_create(int device, mgamd_ctx **out);
@@ -279,20 +317,20 @@ int mgamd_transfer2_n_fused_bricks(const mgamd_transfer2 *t, uint64_t *n);
  * 1618-1621).  levels[0] is the coarsest; transfers[l] connects levels l-1 and l (transfers[0] unused,
  * may be NULL); smoothers[0] is only used by coarse solver "cg_with_chebyshev".
  * coarse_solver (CoarseGridSolverType, ref:multigrid_throughput.cc:909-1077):
- *   "direct"             dense inverse (coarse levels up to 4096 DoFs)
+ *   "direct"             dense inverse (coarse levels up to MGAMD_DIRECT_COARSE_MAX_DOFS DoFs)
  *   "cg", "cg_with_chebyshev"   SolverCG to reltol 1e-4, unpreconditioned / with the level-0 Chebyshev smoother (:911-944)
  *   "amg", "cg_with_amg", "amg_petsc"   the reference applies Trilinos ML / BoomerAMG to Operator::get_trilinos_system_matrix
- *                        (:945-1077).  Here: on a coarse level of <= 4096 DoFs (global coarsening ends on one cell) an exact solve
- *                        ("direct"); on a larger one (PMG: the p = 1 space on the finest mesh) the library's OWN
- *                        smoothed-aggregation AMG on the assembled level matrix (mgamd_dofs_matrix; Chebyshev(2) smoothing, dense
- *                        coarsest solve), applied CoarseSolverNCycles times as the coarse solver ("amg") or as the preconditioner
- *                        of the coarse CG ("cg_with_amg").  Same role and inputs as ML, not the same aggregates: its iteration
- *                        counts cannot be parity-checked against ML.
+ *                        (:945-1077).  Here: on a coarse level of at most MGAMD_DIRECT_COARSE_MAX_DOFS DoFs (global coarsening ends
+ *                        on one cell) an exact solve ("direct"); on a larger one (PMG: the p = 1 space on the finest mesh) the
+ *                        library's OWN smoothed-aggregation AMG on the assembled level matrix (mgamd_dofs_matrix; Chebyshev(2)
+ *                        smoothing, dense coarsest solve), applied CoarseSolverNCycles times as the coarse solver ("amg") or as the
+ *                        preconditioner of the coarse CG ("cg_with_amg").  Same role and inputs as ML, not the same aggregates: its
+ *                        iteration counts cannot be parity-checked against ML.
  * mgamd_mg_create_nested additionally takes n_cycles (CoarseSolverNCycles) and, optionally, `coarse_mg`: a geometric multigrid
- * whose finest level IS levels[0]; if given, it takes the AMG's place ("gmg_vcycle": x = V(b), x += V(b - A x) ...; the default
- * on a sharded coarse level, where mgamd_mg_create_sharded_amg is the alternative); "gmg_vcycle" without `coarse_mg` is "direct" on a level of <= 4096 DoFs and MGAMD_ERR_INVALID on a
- * larger one.  mgamd_mg_coarse_solver_used returns what runs: "direct" | "cg" | "cg_with_chebyshev" | "amg" |
- * "cg_with_amg" | "gmg_vcycle". */
+ * whose finest level IS levels[0]; if given, it takes the AMG's place ("gmg_vcycle": x = V(b), x += V(b - A x) ...).  Whether a
+ * caller has to build one, or the global DoFs for mgamd_mg_create_sharded_amg, is mgamd_coarse_plan's decision; "gmg_vcycle"
+ * without `coarse_mg` is "direct" on a level of at most MGAMD_DIRECT_COARSE_MAX_DOFS DoFs and MGAMD_ERR_INVALID on a larger one.
+ * mgamd_mg_coarse_solver_used returns what runs: "direct" | "cg" | "cg_with_chebyshev" | "amg" | "cg_with_amg" | "gmg_vcycle". */
 int mgamd_mg_create(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
                     mgamd_cheb *const *smoothers, const char *coarse_solver, mgamd_mg **out);
 int mgamd_mg_create_nested(mgamd_ctx *ctx, unsigned n_levels, mgamd_level_op *const *levels, mgamd_transfer2 *const *transfers,
