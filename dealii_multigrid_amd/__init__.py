@@ -203,6 +203,16 @@ class DoFs:
         self.degree = degree
         self.n_dofs = self.info.n_dofs
 
+    def set_mass_coefficient(self, sigma: float):
+        """the mass term: operators, matrices and right-hand sides built from these DoFs AFTER the call represent K + sigma M
+        (-Laplace u + sigma u).  sigma >= 0 and finite; local-smoothing levels only take 0 (mgamd_dofs_set_mass_coefficient)"""
+        _chk(_lib.mgamd_dofs_set_mass_coefficient(self._h, C.c_double(sigma)))
+
+    def mass_coefficient(self) -> float:
+        s = C.c_double()
+        _chk(_lib.mgamd_dofs_mass_coefficient(self._h, C.byref(s)))
+        return s.value
+
     def keys(self):
         k = np.zeros((self.n_dofs, 5), np.int32)
         _chk(_lib.mgamd_dofs_get_keys(self._h, _ptr(k)))
@@ -466,6 +476,12 @@ class Operator:
         _chk(_lib.mgamd_level_op_m(self._h, C.byref(n)))
         return n.value
 
+    def mass_coefficient(self) -> float:
+        """the mass coefficient the operator was built with (DoFs.set_mass_coefficient before its construction)"""
+        s = C.c_double()
+        _chk(_lib.mgamd_level_op_mass_coefficient(self._h, C.byref(s)))
+        return s.value
+
     def initialize_dof_vector(self) -> Vector:
         h = C.c_void_p()
         _chk(_lib.mgamd_level_op_init_vector(self._h, C.byref(h)))
@@ -500,6 +516,9 @@ class Operator:
 
     def get_system_matrix(self) -> "SparseMatrix":
         """Operator::get_trilinos_system_matrix: the assembled matrix of this operator's DoFs on the device (FP64, one rank)"""
+        if self.dofs.mass_coefficient() != self.mass_coefficient():  # the matrix is assembled from the DoFs' tables
+            raise MgamdError(f"get_system_matrix: the mass coefficient of the DoFs ({self.dofs.mass_coefficient()}) was changed after this "
+                             f"operator was built with {self.mass_coefficient()}; the assembled matrix would be another operator's")
         return SparseMatrix(self.ctx, self.dofs)
 
     def __del__(self):
@@ -833,6 +852,14 @@ def csr_spmv_lanes_long(n_rows: int, nnz: int) -> int:
     return lanes.value
 
 
+def amg_shard_match_rows(global_dofs: "DoFs", local_dofs: "DoFs"):
+    """the first step of the sharded AMG's plans (development entry, mgamd_dev.h): the global row of every DoF of local_dofs in
+    global_dofs; MgamdError if the two are not the same space (another degree, another mass coefficient)"""
+    rows = np.zeros(local_dofs.n_dofs, np.uint32)
+    _chk(_lib.mgamd_debug_amg_shard_match_rows(global_dofs._h, local_dofs._h, _ptr(rows)))
+    return rows
+
+
 def csr_row_pointers(row_counts):
     """the 32-bit row pointers assemble_level_matrix builds from 64-bit entry counts per row (host only); MgamdError when the
     matrix would need more than 2^32 - 1 entries"""
@@ -873,7 +900,7 @@ _, MIN_ROOT_DOFS_DEFAULT, MIN_SUBSET_DOFS_DEFAULT = _partition_defaults(1)
 
 
 def _build_levels(ctx, meshes, plan, number_type, max_brick, smoother, partition=None, rank=0, level_comm=None, local_smoothing=False,
-                  first_dofs=None, shared_last=None):
+                  first_dofs=None, shared_last=None, mass_coefficient=0.0):
     """(DoFs, operators, transfers, smoothers) of the levels plan = [(mesh index, degree)], coarse -> fine.
     smoother: (degree, smoothing_range, eig_cg_n_iterations) of every PreconditionChebyshev
     partition, rank, level_comm: one rank's share of a sharded hierarchy; level_comm(mesh index) is the communicator of a distributed
@@ -881,10 +908,13 @@ def _build_levels(ctx, meshes, plan, number_type, max_brick, smoother, partition
     local_smoothing: the meshes are Triangulation.level_mesh(l)
     first_dofs: existing DoFs that are level 0's (HPMG-local: the ones the local-smoothing cycle underneath acts on)
     shared_last: (dofs, operator, smoother) of another hierarchy's level that is the finest one here (the coarse stand-in)
-    max_brick=-1: bricks on large levels, single-cell slots on the latency-bound small ones (level_tables.hpp)"""
+    max_brick=-1: bricks on large levels, single-cell slots on the latency-bound small ones (level_tables.hpp)
+    mass_coefficient: sigma of K + sigma M, set on every level's DoFs before its operator is built"""
     shared = [] if shared_last is None else [shared_last]
     lo, hi = int(first_dofs is not None), len(plan) - len(shared)
     dofs = [first_dofs][:lo] + [DoFs(meshes[mi], p, max_brick, partition, mi, rank, local_smoothing) for mi, p in plan[lo:hi]]
+    for d in dofs:
+        d.set_mass_coefficient(mass_coefficient)
     ops = [Operator(ctx, d, number_type, level_comm(mi) if level_comm else None) for d, (mi, _) in zip(dofs, plan)]
     dofs, ops = dofs + [s[0] for s in shared], ops + [s[1] for s in shared]
     transfers = [None] + [MGTwoLevelTransfer(ops[l], ops[l - 1]) for l in range(1, len(ops))]
@@ -896,12 +926,13 @@ class CoarseHierarchy:
     """Geometric stand-in for the reference's AMG coarse solvers (mgamd.h: "gmg_vcycle"): the h-multigrid on the coarse
     level of a PMG hierarchy (the lowest-degree space on the finest mesh); its finest level shares that level's objects."""
 
-    def __init__(self, ctx, tria, dofs0, op0, smoother0, smoother_degree, smoothing_range, eig_cg_n_iterations, number_type, max_brick):
+    def __init__(self, ctx, tria, dofs0, op0, smoother0, smoother_degree, smoothing_range, eig_cg_n_iterations, number_type, max_brick,
+                 mass_coefficient=0.0):
         self.trias = create_geometric_coarsening_sequence(tria)
         plan, _ = _level_plan("HMG-global", len(self.trias), dofs0.degree)
         self.dofs, self.operators, self.transfers, self.smoothers = _build_levels(
             ctx, self.trias, plan, number_type, max_brick, (smoother_degree, smoothing_range, eig_cg_n_iterations),
-            shared_last=(dofs0, op0, smoother0))
+            shared_last=(dofs0, op0, smoother0), mass_coefficient=mass_coefficient)
         self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, "amg")
 
 
@@ -910,8 +941,11 @@ class Hierarchy:
 
     def __init__(self, ctx: Context, geometry="quadrant", n_ref_global=3, degree=1, mg_type="HMG-global", n_ref_local=0,
                  smoother_degree=3, smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64,
-                 max_brick=-1, coarse_n_cycles=1):
+                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0):
+        """mass_coefficient: sigma >= 0 of the operator K + sigma M (-Laplace u + sigma u) on every level, the stand-in and nested
+        hierarchies included; the local-smoothing types refuse a non-zero value"""
         self.ctx = ctx
+        self.mass_coefficient = mass_coefficient
         # `geometry` may also be a caller-built Triangulation (Triangulation.from_leaves)
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global, n_ref_local)
         if mg_type in ("AMG", "AMGPETSc"):
@@ -920,6 +954,7 @@ class Hierarchy:
             # reference; coarse_n_cycles: AMG cycles per application.  AMGPETSc (BoomerAMG's role): the same solver.
             self.trias, self.degrees = [fine], [degree]
             self.dofs = [DoFs(fine, degree, max_brick)]
+            self.dofs[0].set_mass_coefficient(mass_coefficient)
             self.fine_operator = Operator(ctx, self.dofs[0], F64)
             self.operators, self.transfers, self.smoothers, self.coarse, self.mg = [self.fine_operator], [None], [None], None, None
             self.system_matrix = self.fine_operator.get_system_matrix()
@@ -945,13 +980,13 @@ class Hierarchy:
             first_dofs, nested, coarse_solver, coarse_n_cycles = self.active_dofs, self.mg, "gmg_vcycle", 1
         self.trias, self.degrees = [meshes[mi] for mi, _ in plan], [p for _, p in plan]
         self.dofs, self.operators, self.transfers, self.smoothers = _build_levels(ctx, meshes, plan, number_type, max_brick, smoother,
-                                                                                  first_dofs=first_dofs)
+                                                                                  first_dofs=first_dofs, mass_coefficient=mass_coefficient)
         self.coarse = None
         if nested is None and _coarse_plan(coarse_solver, self.dofs[0].n_dofs) == COARSE_NESTED:
             # the geometric stand-in for the AMG coarse solvers on a large coarse level (PMG), on one rank by explicit request only
             # ("gmg_vcycle"): V-cycles of the h-multigrid on level 0 ("amg", "cg_with_amg" run the library's smoothed-aggregation AMG)
             self.coarse = CoarseHierarchy(ctx, self.trias[0], self.dofs[0], self.operators[0], self.smoothers[0], *smoother, number_type,
-                                          max_brick)
+                                          max_brick, mass_coefficient)
             nested = self.coarse.mg
         self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, nested, coarse_n_cycles)
         self.fine_operator = self.operators[-1] if number_type == F64 else Operator(ctx, self.dofs[-1], F64)
@@ -960,6 +995,9 @@ class Hierarchy:
     def _build_local_smoothing(self, ctx, fine, degree, smoother, coarse_solver, number_type, max_brick):
         """solve_with_local_smoothing (ref:multigrid_throughput.cc:1670-1873): operators on the refinement levels 0..L of the
         octree, MGTransferMatrixFree between them, edge matrices, the outer operator on the active mesh"""
+        if self.mass_coefficient != 0.0:
+            raise MgamdError(f"mass coefficient {self.mass_coefficient} with local smoothing: not implemented (the refinement-edge "
+                             "matrices have no mass term)")
         self.active_dofs = DoFs(fine, degree, max_brick)
         meshes = [fine.level_mesh(l) for l in range(fine.n_levels)]
         plan, local_smoothing = _level_plan("HMG-local", len(meshes), degree)
@@ -982,7 +1020,8 @@ class DistributedHierarchy:
     def __init__(self, ctx: Context, comm: Communicator, geometry="quadrant", n_ref_global=3, degree=1, smoother_degree=3,
                  smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64, hanging_weight=2.0, max_brick=-1,
                  min_root_dofs=MIN_ROOT_DOFS_DEFAULT, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None,
-                 min_subset_dofs=MIN_SUBSET_DOFS_DEFAULT, sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT):
+                 min_subset_dofs=MIN_SUBSET_DOFS_DEFAULT, sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT,
+                 mass_coefficient=0.0):
         """sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
         smoothed-aggregation AMG cut into rows over the ranks (replicated setup, sharded cycle; levels of at most
         amg_min_sharded_rows rows replicated) instead of the geometric stand-in "gmg_vcycle".  Off by default."""
@@ -1011,7 +1050,7 @@ class DistributedHierarchy:
 
         def build(plan, shared_last=None):
             return _build_levels(ctx, self.mesh_sequence, plan, number_type, max_brick, smoother, self.partition, comm.rank, mesh_comm,
-                                 shared_last=shared_last)
+                                 shared_last=shared_last, mass_coefficient=mass_coefficient)
 
         self.trias = [self.mesh_sequence[mi] for mi, _ in self.plan]
         self.degrees = [p for _, p in self.plan]
@@ -1023,6 +1062,7 @@ class DistributedHierarchy:
         if extra == COARSE_SHARDED_AMG:
             # every rank builds the one-rank AMG from the global tables of level 0's space and keeps its rows (amg_shard.hpp)
             self.amg_global_dofs = DoFs(self.mesh_sequence[mi0], p0, max_brick)
+            self.amg_global_dofs.set_mass_coefficient(mass_coefficient)
             self.mg = PreconditionMG(ctx, self.operators, self.transfers, self.smoothers, coarse_solver, None, coarse_n_cycles,
                                      sharded_amg=self.amg_global_dofs, amg_min_sharded_rows=amg_min_sharded_rows)
         else:

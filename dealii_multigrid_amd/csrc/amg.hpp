@@ -81,9 +81,23 @@ namespace mgamd
                 Kref[(size_t)((c * n + b) * n + a) * n3 + (c2 * n + b2) * n + a2] =
                   fe.K[a * n + a2] * fe.M[b * n + b2] * fe.M[c * n + c2] + fe.M[a * n + a2] * fe.K[b * n + b2] * fe.M[c * n + c2] +
                   fe.M[a * n + a2] * fe.M[b * n + b2] * fe.K[c * n + c2];
-    // element matrices of hanging configurations, cached by mask: I^T K_ref I
-    std::map<uint16_t, std::vector<double>> cache;
-    auto                                    element = [&](uint16_t mask) -> const std::vector<double> & {
+    // the mass term of K + sigma M (LevelTables::sigma): reference mass matrix M (x) M (x) M, only built if sigma != 0
+    const double        sigma = L.sigma;
+    std::vector<double> Mref;
+    if (sigma != 0.0)
+      {
+        Mref.resize((size_t)n3 * n3);
+        for (int c = 0; c < n; ++c)
+          for (int b = 0; b < n; ++b)
+            for (int a = 0; a < n; ++a)
+              for (int c2 = 0; c2 < n; ++c2)
+                for (int b2 = 0; b2 < n; ++b2)
+                  for (int a2 = 0; a2 < n; ++a2)
+                    Mref[(size_t)((c * n + b) * n + a) * n3 + (c2 * n + b2) * n + a2] = fe.M[a * n + a2] * fe.M[b * n + b2] * fe.M[c * n + c2];
+      }
+    // element matrices of hanging configurations, cached by mask: I^T K_ref I (and I^T M_ref I)
+    std::map<uint16_t, std::vector<double>> cache, cache_mass;
+    auto element_of = [&](const std::vector<double> &Kref, std::map<uint16_t, std::vector<double>> &cache, uint16_t mask) -> const std::vector<double> & {
       if (!(mask >> MASK_FACE_SHIFT))
         return Kref;
       auto it = cache.find(mask);
@@ -170,13 +184,23 @@ namespace mgamd
       {
         if (!L.cell_is_local(ci))
           continue;
-        const std::vector<double> &Ke = element(L.tria->masks[ci]);
+        const std::vector<double> &Ke = element_of(Kref, cache, L.tria->masks[ci]);
         const double               h  = 2.0 / (double)(1u << L.tria->cells[ci].level);
         for (int i = 0; i < n3; ++i)
           if (idx[ci * n3 + i] != INVALID_DOF)
             for (int j = 0; j < n3; ++j)
               if (idx[ci * n3 + j] != INVALID_DOF)
                 at(idx[ci * n3 + i], idx[ci * n3 + j]) += h * Ke[(size_t)i * n3 + j];
+        if (sigma != 0.0)
+          {
+            const std::vector<double> &Me = element_of(Mref, cache_mass, L.tria->masks[ci]);
+            const double               s3 = sigma * h * h * h;
+            for (int i = 0; i < n3; ++i)
+              if (idx[ci * n3 + i] != INVALID_DOF)
+                for (int j = 0; j < n3; ++j)
+                  if (idx[ci * n3 + j] != INVALID_DOF)
+                    at(idx[ci * n3 + i], idx[ci * n3 + j]) += s3 * Me[(size_t)i * n3 + j];
+          }
       }
     for (uint32_t i = L.first_constrained(); i < L.n_dofs; ++i)
       at(i, i) = 1.0;

@@ -66,10 +66,14 @@ namespace mgamd
 
   // global row (index in `global`) of every DoF of `local`, matched through the geometric keys
   inline std::vector<uint32_t>
-  match_rows_by_key(const LevelTables &global, const LevelTables &local)
+  match_rows_by_key(const LevelTables &global, const LevelTables &local, double local_sigma)
   {
     if (global.p != local.p)
       throw std::invalid_argument("sharded AMG: the global coarse DoFs must have the degree of the hierarchy's level 0");
+    // (local_sigma: the mass coefficient the local level's OPERATOR was built with, or of its tables where there is no operator)
+    if (global.sigma != local_sigma)
+      throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the mass coefficient " + std::to_string(global.sigma) +
+                                  ", the local level " + std::to_string(local_sigma) + ": the assembled matrix would be another operator's");
     std::vector<DofKey> kg, kl;
     global.export_dof_keys(kg);
     local.export_dof_keys(kl);

@@ -346,6 +346,15 @@ mgamd_level_op_m(const mgamd_level_op *op, uint64_t *n)
 }
 
 int
+mgamd_level_op_mass_coefficient(const mgamd_level_op *op, double *sigma)
+{
+  MGAMD_TRY
+  REQUIRE(op && sigma);
+  *sigma = op->op->sigma;
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_init_vector(const mgamd_level_op *op, mgamd_vec **out)
 {
   MGAMD_TRY

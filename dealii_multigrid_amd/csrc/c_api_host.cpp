@@ -164,6 +164,38 @@ mgamd_dofs_matrix(const mgamd_dofs *d, uint64_t *nnz, uint32_t *row_ptr, uint32_
 }
 
 int
+mgamd_dofs_set_mass_coefficient(mgamd_dofs *d, double sigma)
+{
+  MGAMD_TRY
+  if (!d)
+    throw std::invalid_argument("null argument");
+  d->tables->set_mass_coefficient(sigma); // (refuses negative and non-finite values, and non-zero ones on local-smoothing levels)
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_mass_coefficient(const mgamd_dofs *d, double *sigma)
+{
+  MGAMD_TRY
+  if (!d || !sigma)
+    throw std::invalid_argument("null argument");
+  *sigma = d->tables->sigma;
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_amg_shard_match_rows(const mgamd_dofs *global, const mgamd_dofs *local, uint32_t *rows)
+{
+  MGAMD_TRY
+  if (!global || !local)
+    throw std::invalid_argument("null argument");
+  const std::vector<uint32_t> r = match_rows_by_key(*global->tables, *local->tables, local->tables->sigma);
+  if (rows)
+    std::copy(r.begin(), r.end(), rows);
+  MGAMD_CATCH
+}
+
+int
 mgamd_debug_csr_row_pointers(uint32_t n_rows, const uint64_t *row_counts, uint32_t *ptr)
 {
   MGAMD_TRY
@@ -303,7 +335,7 @@ mgamd_debug_amg_shard_create(const mgamd_partition *p, unsigned level, int degre
         if (mgamd_dofs_create_local(p, level, (unsigned)r, degree, max_brick, &ld) != MGAMD_OK)
           throw std::runtime_error(g_last_error);
         std::unique_ptr<mgamd_dofs> local(ld);
-        const auto                  grow = match_rows_by_key(*global->tables, *local->tables);
+        const auto                  grow = match_rows_by_key(*global->tables, *local->tables, local->tables->sigma);
         const auto                  own  = local_dof_owned(*local->tables);
         for (uint32_t d = 0; d < local->tables->n_dofs; ++d)
           if (own[d])

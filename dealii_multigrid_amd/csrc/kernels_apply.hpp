@@ -24,6 +24,38 @@ namespace mgamd
 #define MGAMD_ABLATED(bit) false
 #endif
 
+  // Closed-form diagonal of a slot-interior lattice node of TYPE t (t = lattice coordinate mod P per direction: 0 = node shared
+  // by two cells, a = a-th interior node of a cell), without the cell size:  d = h (s_K + c s_M),  c = sigma h^2, with
+  // s_K = k_x m_y m_z + m_x k_y m_z + m_x m_y k_z and s_M = m_x m_y m_z of the assembled 1D diagonals.
+  template <typename T, int P>
+  __device__ __forceinline__ void
+  interior_diag_terms(const Mats<P, T> &mats, const int t, T &s_K, T &s_M)
+  {
+    const int tt[3] = {t % P, (t / P) % P, t / (P * P)};
+    T         m[3], k[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      {
+        T dm = T(0), dk = T(0);
+        if (tt[d] == 0)
+          { // last node of one cell + first node of the next
+            dm = T(mats.M[P * (P + 1) + P]) + T(mats.M[0]);
+            dk = T(mats.K[P * (P + 1) + P]) + T(mats.K[0]);
+          }
+#pragma unroll
+        for (int q = 1; q < P; ++q)
+          if (q == tt[d])
+            {
+              dm = T(mats.M[q * (P + 1) + q]);
+              dk = T(mats.K[q * (P + 1) + q]);
+            }
+        m[d] = dm;
+        k[d] = dk;
+      }
+    s_K = k[0] * m[1] * m[2] + m[0] * k[1] * m[2] + m[0] * m[1] * k[2];
+    s_M = m[0] * m[1] * m[2];
+  }
+
   // waves per SIMD: 2 for the 17^3 lattices (<= 256 VGPRs); 6 for single-cell slots (<= 80 VGPRs, measured 5 % faster at
   // p = 4 than unconstrained with 110 VGPRs)
   // the work of workgroup `block` of `nblocks` on the slots of args.g (kernels below)
@@ -34,7 +66,9 @@ namespace mgamd
   // workgroup-scoped kernel: 5-7 of the 9 us a workgroup lives are spent between those barriers).
   // NTHREADS: the threads of the workgroup if they are more than the lattice's own block (lattice_apply_small_kernel runs the
   // 13-point bricks of p = 6, whose 169 lines make a 192-thread block, in its 256-thread workgroups); 0: Geo's ABLOCK
-  template <typename T, int P, int B, int MODE, bool CONSTR = false, bool WAVE = false, int NTHREADS = 0>
+  // MASS = false compiles the mass term out (lattice_sweeps); only kernels whose register budget has no room for it come in
+  // both forms (small_slots_mass_compiled), every other caller leaves MASS = true and sigma decides at run time
+  template <typename T, int P, int B, int MODE, bool CONSTR = false, bool WAVE = false, int NTHREADS = 0, bool MASS = true>
   __device__ __forceinline__ void
   lattice_apply_body(const ApplyArgs<T, P> &args, const uint32_t block, const uint32_t nblocks, unsigned char *smem_raw)
   {
@@ -81,39 +115,26 @@ namespace mgamd
     // Used at P = 1 (one node type: the look-up is a broadcast, -11 % on the 17^3 kernel); at P = 4 the 64-entry look-up
     // per entry pushes the 17^3 kernel over its 256 VGPRs (measured 1113 -> 1829 us), so D^-1 is read from memory there.
     constexpr bool CLOSED_DINV = P == 1 || (P == 4 && B == 4);
-    T *dtab = bufB + G::SPW * G::N3; // [P^3] s, [P^3] 1/s, [SPW] 1/h
+    // With the mass term  d = h (s_K + c s_M), c = sigma h^2 of the slot: the table is PER SLOT (TS entries; at P = 1 that is one
+    // entry per slot, apply_lds_bytes), formed once per workgroup; the epilogue stays  rh * table.  sigma = 0: s_K + 0 = s_K.
+    constexpr int TS = CLOSED_DINV ? P * P * P * (P == 1 ? G::SPW : 1) : P * P * P;
+    static_assert(!(CLOSED_DINV && G::N_INT > 0) || P == 1 || G::SPW == 1, "one D^-1 table per slot");
+    T *dtab = bufB + G::SPW * G::N3; // [TS] s, [TS] 1/s, [SPW] 1/h
     if (CLOSED_DINV && is_cheb(MODE) && G::N_INT > 0)
       {
         constexpr int P3 = P * P * P;
-        for (int t = tid; t < P3; t += BLOCK)
+        for (int i = tid; i < nslots * P3; i += BLOCK)
           {
-            const int tt[3] = {t % P, (t / P) % P, t / (P * P)};
-            T         m[3], k[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-              {
-                T dm = T(0), dk = T(0);
-                if (tt[d] == 0)
-                  { // last node of one cell + first node of the next
-                    dm = T(args.m.M[P * (P + 1) + P]) + T(args.m.M[0]);
-                    dk = T(args.m.K[P * (P + 1) + P]) + T(args.m.K[0]);
-                  }
-#pragma unroll
-                for (int q = 1; q < P; ++q)
-                  if (q == tt[d])
-                    {
-                      dm = T(args.m.M[q * (P + 1) + q]);
-                      dk = T(args.m.K[q * (P + 1) + q]);
-                    }
-                m[d] = dm;
-                k[d] = dk;
-              }
-            const T sv   = k[0] * m[1] * m[2] + m[0] * k[1] * m[2] + m[0] * m[1] * k[2];
-            dtab[t]      = sv;
-            dtab[P3 + t] = T(1) / sv;
+            const int t = i % P3, s2 = i / P3;
+            const T   hs = T(args.g.h[slot0 + s2]);
+            T         s_K, s_M;
+            interior_diag_terms<T, P>(args.m, t, s_K, s_M);
+            const T sv   = s_K + (T(args.sigma) * hs * hs) * s_M;
+            dtab[i]      = sv;
+            dtab[TS + i] = T(1) / sv;
           }
         for (int t = tid; t < nslots; t += BLOCK)
-          dtab[2 * P3 + t] = T(1) / T(args.g.h[slot0 + t]);
+          dtab[2 * TS + t] = T(1) / T(args.g.h[slot0 + t]);
         slot_sync<WAVE>();
       }
 
@@ -200,9 +221,10 @@ namespace mgamd
     auto interior_dinv = [&](int it) -> T {
       constexpr int P3 = P * P * P;
       const int     gl = glds[it] >= 0 ? glds[it] : 0, t = (gl >> 16) & 0xFF, s2 = (gl >> 24) & 0x7F;
-      const T       rh = dtab[2 * P3 + s2];
+      const T       rh = dtab[2 * TS + s2];
+      const int     e  = s2 * P3 + t; // this slot's table
       // |d| > 1e-10 ? 1/d : 1 with d = h s  (ref:include/operator.h:228-242)
-      return fabs((double)dtab[t]) > 1.0e-10 * fabs((double)rh) ? rh * dtab[P3 + t] : T(1);
+      return fabs((double)dtab[e]) > 1.0e-10 * fabs((double)rh) ? rh * dtab[TS + e] : T(1);
     };
     // ---- epilogue operands, requested now, consumed after the sweeps ----------------------------------------
     T xo[ITER], bv[ITER], dvm[CLOSED_DINV ? 1 : ITER]; // dvm: D^-1 from memory
@@ -275,7 +297,7 @@ namespace mgamd
     MGAMD_STAMP(5)
 
     if (!MGAMD_ABLATED(1))
-      lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true);
+      lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE, MASS>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true, args.sigma);
     MGAMD_STAMP(6)
 
     if (B == 1 && any_hanging)
@@ -354,7 +376,10 @@ namespace mgamd
   //               x (shell entries that an un-fused patch owns arrive corrected already); x + P x_c is stored once (interior in
   //               place, owned shell entries to a scratch vector that tail_kernel folds in) and never re-read by this pass.
   // Slots that are not flagged as fused (no brick patch, halo slots of a sharded level) take the base mode's path.
-  template <typename T, int P, int B, int MODE_, bool CONSTR = false>
+  // MASS: the operator carries the mass term (args.sigma != 0, checked by the host, which picks the instantiation): the sweeps
+  // shift b by c a, and the closed-form D^-1 table is formed for every slot.  MASS = false is the Laplace kernel, unchanged.
+  // (no default for MASS, here or on the kernels: a launch site that forgot it would apply the Laplace operator under sigma != 0)
+  template <typename T, int P, int B, int MODE_, bool CONSTR, bool MASS>
   __device__ __forceinline__ void
   lattice_apply_persistent_body(const ApplyArgs<T, P> &args, const uint32_t w, const uint32_t stride, unsigned char *smem_raw)
   {
@@ -386,28 +411,8 @@ namespace mgamd
       {
         for (int t = tid; t < P3; t += BLOCK)
           {
-            const int tt[3] = {t % P, (t / P) % P, t / (P * P)};
-            T         m[3], k[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-              {
-                T dm = T(0), dk = T(0);
-                if (tt[d] == 0)
-                  { // last node of one cell + first node of the next
-                    dm = T(args.m.M[P * (P + 1) + P]) + T(args.m.M[0]);
-                    dk = T(args.m.K[P * (P + 1) + P]) + T(args.m.K[0]);
-                  }
-#pragma unroll
-                for (int q = 1; q < P; ++q)
-                  if (q == tt[d])
-                    {
-                      dm = T(args.m.M[q * (P + 1) + q]);
-                      dk = T(args.m.K[q * (P + 1) + q]);
-                    }
-                m[d] = dm;
-                k[d] = dk;
-              }
-            const T sv   = k[0] * m[1] * m[2] + m[0] * k[1] * m[2] + m[0] * m[1] * k[2];
+            T sv, s_M;
+            interior_diag_terms<T, P>(args.m, t, sv, s_M);
             dtab[t]      = sv;
             dtab[P3 + t] = T(1) / sv;
           }
@@ -539,6 +544,24 @@ namespace mgamd
         const bool     has_next = vn < n;
         MGAMD_STAMP(0)
         const T rh = T(1) / T(hcur);
+        // Mass term: d = h (s_K + c s_M) with c = sigma h^2 of THIS slot, so the table is formed anew for every slot by its first
+        // P^3 threads.  The barrier at the end of the slot loop (or the one before the loop) has every reader of the previous
+        // table behind it; the first reader of this one is the epilogue, behind the barriers of the sweeps -- except where x is
+        // formed from b on the fly (x_from_b), which takes one more barrier.  MASS = false: the table built above.
+        if constexpr (MASS && is_cheb(MODE))
+          {
+            const T c = T(args.sigma) * T(hcur) * T(hcur);
+            for (int t = tid; t < P3; t += BLOCK)
+              {
+                T s_K, s_M;
+                interior_diag_terms<T, P>(args.m, t, s_K, s_M);
+                const T sv   = s_K + c * s_M;
+                dtab[t]      = sv;
+                dtab[P3 + t] = T(1) / sv;
+              }
+            if (x_from_b)
+              __syncthreads();
+          }
         // D^-1 of this thread's interior entry `it`: |d| > 1e-10 ? 1/d : 1 with d = h s  (ref:include/operator.h:228-242)
         auto interior_dinv = [&](int t) -> T { // t: node type (InteriorWalk::type)
           return fabs((double)dtab[t]) > 1.0e-10 * fabs((double)rh) ? rh * dtab[P3 + t] : T(1);
@@ -665,7 +688,8 @@ namespace mgamd
               brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, false, &fmcur);
           }
         // cell prefetch in the streamed sweeps (-4 % on the 2-4-word passes); the 5-word mode has no registers left for it
-        lattice_sweeps<T, P, B, BLOCK, NoHook, true, (MODE != MODE_CHEB || sizeof(T) == 4)>(bufA, bufB, args.m, tid, 1, &hcur);
+        lattice_sweeps<T, P, B, BLOCK, NoHook, true, (MODE != MODE_CHEB || sizeof(T) == 4), false, MASS>(
+          bufA, bufB, args.m, tid, 1, &hcur, NoHook(), false, args.sigma);
         if constexpr (brick_may_be_constrained(B, CONSTR))
           if (any_hanging)
             brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, true, &fmcur);
@@ -812,6 +836,8 @@ namespace mgamd
   cell_wave_lds()
   {
     using G = Geo<P, 1, 64>;
+    // (the D^-1 tables of lattice_apply_body are laid out as in apply_lds_bytes: per slot at P = 1, where no wave-scoped kernel exists)
+    static_assert(P >= 2, "wave-scoped cells: P >= 2 (at P = 1 the closed-form D^-1 table of lattice_apply_body is per slot, apply_lds_bytes)");
     return (((2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T) + 15) / 16) * 16;
   }
 
@@ -917,12 +943,12 @@ namespace mgamd
   {
     return 2;
   }
-  template <typename T, int P, int B, int MODE, bool CONSTR = false>
+  template <typename T, int P, int B, int MODE, bool CONSTR, bool MASS>
   __global__ void
   __launch_bounds__((Geo<P, B>::ABLOCK), (persistent_wgs_per_cu<T, P>())) lattice_apply_persistent_kernel(const ApplyArgs<T, P> args)
   {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    lattice_apply_persistent_body<T, P, B, MODE, CONSTR>(args, blockIdx.x, gridDim.x, smem_raw);
+    lattice_apply_persistent_body<T, P, B, MODE, CONSTR, MASS>(args, blockIdx.x, gridDim.x, smem_raw);
   }
 
   // The plain and the constrained bricks of one size in ONE launch (same lattice, same LDS, same block size): the
@@ -956,7 +982,7 @@ namespace mgamd
   // are 19 % faster (tools/sweep_probe.hip), the kernel is not: vmult 950 -> 964 us per pass, and the Chebyshev modes spill.)
   // the pair launch with persistent workgroups.  n_wg_plain > 0 (all slots resident at once): the first n_wg_plain workgroups
   // take one plain brick each, the others one constrained brick each; n_wg_plain == 0: see below
-  template <typename T, int P, int B, int MODE>
+  template <typename T, int P, int B, int MODE, bool MASS>
   __global__ void
   __launch_bounds__((Geo<P, B>::ABLOCK), 2) lattice_apply_persistent_pair_kernel(const BrickPairArgs<T, P> args)
   {
@@ -969,18 +995,18 @@ namespace mgamd
         ApplyArgs<T, P> a = args.a;
         a.g               = args.g_constrained;
         a.stamps          = nullptr;
-        lattice_apply_persistent_body<T, P, B, base_mode(MODE), true>(a, blockIdx.x, gridDim.x, smem_raw);
+        lattice_apply_persistent_body<T, P, B, base_mode(MODE), true, MASS>(a, blockIdx.x, gridDim.x, smem_raw);
         __syncthreads(); // the lattice of the last constrained brick has been read by every thread
-        lattice_apply_persistent_body<T, P, B, MODE, false>(args.a, blockIdx.x, gridDim.x, smem_raw);
+        lattice_apply_persistent_body<T, P, B, MODE, false, MASS>(args.a, blockIdx.x, gridDim.x, smem_raw);
       }
     else if (blockIdx.x < args.n_wg_plain)
-      lattice_apply_persistent_body<T, P, B, MODE, false>(args.a, blockIdx.x, args.n_wg_plain, smem_raw);
+      lattice_apply_persistent_body<T, P, B, MODE, false, MASS>(args.a, blockIdx.x, args.n_wg_plain, smem_raw);
     else
       {
         ApplyArgs<T, P> a = args.a;
         a.g               = args.g_constrained;
         a.stamps          = nullptr;
-        lattice_apply_persistent_body<T, P, B, base_mode(MODE), true>(a, blockIdx.x - args.n_wg_plain, gridDim.x - args.n_wg_plain, smem_raw);
+        lattice_apply_persistent_body<T, P, B, base_mode(MODE), true, MASS>(a, blockIdx.x - args.n_wg_plain, gridDim.x - args.n_wg_plain, smem_raw);
       }
   }
 
@@ -995,13 +1021,22 @@ namespace mgamd
     uint32_t        n_wg_bricks;
   };
   static_assert(sizeof(SmallSlotsArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "SmallSlotsArgs exceeds the kernel-argument segment");
-  template <typename T, int P, int MODE>
+  // The float kernel of p = 7 sits at the 128 VGPRs of its four workgroups per CU: with a run-time sigma its Chebyshev mode
+  // spills (tools/kernel_resources.sh: 127 -> 128 VGPRs + 8 bytes of scratch), so that one comes with the mass term compiled in
+  // and compiled out (the brick half; the cells keep the run-time sigma) and the host picks by sigma != 0.
+  template <typename T, int P>
+  constexpr bool
+  small_slots_mass_compiled()
+  {
+    return sizeof(T) == 4 && P == 7;
+  }
+  template <typename T, int P, int MODE, bool MASS = true>
   __global__ void
   __launch_bounds__(256, (small_slots_wgs_per_cu<T, P>())) lattice_apply_small_kernel(const SmallSlotsArgs<T, P> args)
   {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     if (blockIdx.x < args.n_wg_bricks)
-      lattice_apply_body<T, P, 2, MODE, false, false, 256>(args.a, blockIdx.x, args.n_wg_bricks, smem_raw);
+      lattice_apply_body<T, P, 2, MODE, false, false, 256, MASS>(args.a, blockIdx.x, args.n_wg_bricks, smem_raw);
     else
       {
         ApplyArgs<T, P> a = args.a;
@@ -1043,6 +1078,7 @@ namespace mgamd
     T        c0;
     int      from_b;
     uint32_t cluster_offset; // first cluster of this launch (the halo / interior split of sharded levels)
+    double   sigma = 0.0;    // mass coefficient of K + sigma M (ApplyArgs::sigma)
   };
   static_assert(sizeof(ClusterArgs<double>) <= KERNARG_LIMIT, "ClusterArgs exceeds the kernel-argument segment");
 
@@ -1177,6 +1213,7 @@ namespace mgamd
     // three sweeps of the 2x2x2 lattice, as in lattice_sweeps
     const T M0 = T(a.m.M[0]), M1 = T(a.m.M[1]), M2 = T(a.m.M[2]), M3 = T(a.m.M[3]);
     const T K0 = T(a.m.K[0]), K1 = T(a.m.K[1]), K2 = T(a.m.K[2]), K3 = T(a.m.K[3]);
+    const T cm = T(a.sigma) * h * h; // sigma h^2: h (K a + M (b + c a)) adds sigma h^3 M (x) M (x) M
     T       A[8], Bv[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -1199,8 +1236,8 @@ namespace mgamd
       }
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      { // x lines: nodes 2q, 2q + 1
-        const T a0 = A[2 * q], a1 = A[2 * q + 1], b0 = Bv[2 * q], b1 = Bv[2 * q + 1];
+      { // x lines: nodes 2q, 2q + 1; the mass term as in lattice_sweeps: b += c a
+        const T a0 = A[2 * q], a1 = A[2 * q + 1], b0 = Bv[2 * q] + cm * a0, b1 = Bv[2 * q + 1] + cm * a1;
         x[2 * q]     = h * (K0 * a0 + K1 * a1 + M0 * b0 + M1 * b1);
         x[2 * q + 1] = h * (K2 * a0 + K3 * a1 + M2 * b0 + M3 * b1);
       }
@@ -1251,7 +1288,7 @@ namespace mgamd
       cell_cluster_body<T>(args.c, blockIdx.x - args.n_wg_bricks, gridDim.x - args.n_wg_bricks, smem_raw);
   }
 
-  // Diagonal of C^T K C.  Slots without hanging nodes: closed tensor form; single cells with hanging
+  // Diagonal of C^T (K + sigma M) C.  Slots without hanging nodes: closed tensor form; single cells with hanging
   // faces/edges: one unit vector per local node through interpolation, sweeps and transpose.
   template <typename T, int P, int B, bool CONSTR = false>
   __global__ void
@@ -1294,7 +1331,8 @@ namespace mgamd
               dM[c * P + a] += T(args.m.M[a * (P + 1) + a]);
               dK[c * P + a] += T(args.m.K[a * (P + 1) + a]);
             }
-        T mx = T(0), kx = T(0), my = T(0), ky = T(0);
+        const T sh3 = T(args.sigma) * h * h * h; // d = h s_K + sigma h^3 s_M
+        T       mx = T(0), kx = T(0), my = T(0), ky = T(0);
 #pragma unroll
         for (int i = 0; i < G::N; ++i)
           {
@@ -1311,7 +1349,7 @@ namespace mgamd
           }
 #pragma unroll
         for (int i = 0; i < G::N; ++i)
-          bufD[sl * G::N3 + (i * G::N + v) * G::N + u] = h * (kx * my * dM[i] + mx * ky * dM[i] + mx * my * dK[i]);
+          bufD[sl * G::N3 + (i * G::N + v) * G::N + u] = h * (kx * my * dM[i] + mx * ky * dM[i] + mx * my * dK[i]) + sh3 * (mx * my * dM[i]);
       }
     __syncthreads();
     if (B == 1)
@@ -1325,7 +1363,7 @@ namespace mgamd
                 bufA[idx] = (idx % G::N3) == j ? T(1) : T(0);
               __syncthreads();
               hanging_passes<T, P>(bufA, args.m, sl, u, v, act, mask, false);
-              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0);
+              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0, NoHook(), false, args.sigma);
               hanging_passes<T, P>(bufA, args.m, sl, u, v, act, mask, true);
               if (act && ln == 0 && (mask >> 3))
                 bufD[sl * G::N3 + j] = bufA[sl * G::N3 + j];
@@ -1348,7 +1386,7 @@ namespace mgamd
                 bufA[idx] = (idx % G::N3) == j ? T(1) : T(0);
               __syncthreads();
               brick_constraint_passes<T, P, B, G::BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, false);
-              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0);
+              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0, NoHook(), false, args.sigma);
               brick_constraint_passes<T, P, B, G::BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, true);
               if (act && ln == 0 && args.g.fmask[slot0 + sl])
                 bufD[sl * G::N3 + j] = bufA[sl * G::N3 + j];

@@ -95,14 +95,15 @@ namespace mgamd
     return 16 % p == 0 ? 16 / p : 0;
   }
   // dynamic LDS of the operator kernels of Geo<P, B> (lattice_apply_body, lattice_apply_persistent_body): two lattices per
-  // slot, the closed-form D^-1 tables [P^3] s and [P^3] 1/s, and 1/h per slot
+  // slot, the closed-form D^-1 tables s and 1/s, and 1/h per slot.  The tables have P^3 entries; at P = 1 (one entry)
+  // lattice_apply_body keeps one PER SLOT, because the mass term makes s depend on the slot's h
   template <typename T, int P, int B>
   constexpr size_t
   apply_lds_bytes()
   {
     using G = Geo<P, B>;
     static_assert(persistent_lattice(G::N) == (G::SPW == 1 && G::N_INT > 0 && G::ROUNDS > 1), "persistent_lattice() and Geo disagree");
-    return (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P + G::SPW) * sizeof(T);
+    return (2 * (size_t)G::SPW * G::N3 + 2 * P * P * P * (P == 1 ? G::SPW : 1) + G::SPW) * sizeof(T);
   }
 
   struct SlotGroupDev
@@ -374,17 +375,20 @@ namespace mgamd
   // P nodes stored (the first one with the carry of the previous cell), its last node carried on.  Same arithmetic as
   // line_MK / line_M_KM / line_KM on whole lines, but ~35 instead of ~70 doubles in registers per thread: what lets the
   // persistent kernel keep its epilogue operands and the next slot's tables in flight across the sweeps.
-  // KIND 0: A <- M a, Bb <- K a;  1: A <- M a, Bb <- K a + M b;  2: A <- scale (K a + M b)     (a from A, b from Bb)
+  // KIND 0: A <- M a, Bb <- K a;  1: A <- M a, Bb <- K a + M b;  2: A <- scale (K a + M (b + shift a))     (a from A, b from Bb)
+  // shift (KIND 2 with MASS only): c = sigma h^2 of the mass term (lattice_sweeps); every b is shifted once, as it arrives
   // PREFETCH: the inputs of the next cell are requested before this cell's products (LDS latency under the arithmetic; 8
   // more doubles in registers: measured -4 % on the 2-4-word passes, but the 5-word Chebyshev pass then spills)
-  template <typename T, int P, int B, int KIND, bool PREFETCH>
+  template <typename T, int P, int B, int KIND, bool PREFETCH, bool MASS = false>
   __device__ __forceinline__ void
-  line_stream(const Mats<P, T> &m, T *__restrict__ A, T *__restrict__ Bb, const int stride, const T scale)
+  line_stream(const Mats<P, T> &m, T *__restrict__ A, T *__restrict__ Bb, const int stride, const T scale, const T shift = T(0))
   {
     constexpr int n = P + 1;
     T             a[n], b[n], an[n], bn[n], c1 = T(0), c2 = T(0);
     a[0] = A[0];
     b[0] = KIND == 0 ? T(0) : Bb[0];
+    if (KIND == 2 && MASS)
+      b[0] += shift * a[0];
     if (PREFETCH)
       {
 #pragma unroll
@@ -415,6 +419,12 @@ namespace mgamd
                 an[j] = A[((c + 1) * P + j) * stride];
                 bn[j] = KIND == 0 ? T(0) : Bb[((c + 1) * P + j) * stride];
               }
+          }
+        if (KIND == 2 && MASS)
+          { // (b[0] is the carried, already shifted, last node of the previous cell)
+#pragma unroll
+            for (int j = 1; j < n; ++j)
+              b[j] += shift * a[j];
           }
         T o1[n], o2[n];
 #pragma unroll
@@ -577,10 +587,18 @@ namespace mgamd
   };
   // before_x: called between the y and the x sweep (the x sweep holds one line less in registers than the y sweep: the
   // persistent kernel requests its epilogue operands there)
-  template <typename T, int P, int B, int BLOCK, typename Hook = NoHook, bool STREAMED = false, bool PREFETCH = false, bool WAVE = false>
+  // sigma: mass coefficient of  K + sigma M.  The cell's mass matrix is h^3 M (x) M (x) M and the x sweep forms
+  // h (K a + M b) from a = My Mz u, b = (Ky Mz + My Kz) u, so the mass term is  b += c a  with c = sigma h^2 of the line's slot
+  // on the inputs of the x sweep: one multiply-add per lattice point, no further matrix, no further LDS traffic.  sigma = 0
+  // leaves b as it is, bit for bit (b is a sum that started from +0, and +0 a is +0 or -0).
+  // MASS = false compiles the term out: the persistent 17-point kernels, whose 5-word modes have no register left for c
+  // (DESIGN.md "Mass term"), come in both forms and the host picks one by sigma != 0; every other kernel takes sigma at run time.
+  template <typename T, int P, int B, int BLOCK, typename Hook = NoHook, bool STREAMED = false, bool PREFETCH = false, bool WAVE = false,
+            bool MASS = true>
   __device__ __forceinline__ void
   lattice_sweeps(T *__restrict__ bufA, T *__restrict__ bufB, const Mats<P, T> &m, int tid, int nslots, const double *__restrict__ hslot,
-                 const Hook &before_x = Hook(), const bool h_is_mine = false) // h_is_mine: hslot[0] is the h of THIS thread's line
+                 const Hook &before_x = Hook(), const bool h_is_mine = false, // h_is_mine: hslot[0] is the h of THIS thread's line
+                 const double sigma = 0.0)
   {
     using G              = Geo<P, B, WAVE ? 64 : 256>;
     constexpr int N      = G::N;
@@ -699,9 +717,10 @@ namespace mgamd
         if (l < TOT && sl < nslots)
           {
             const T   h    = T(h_is_mine ? hslot[0] : hslot[sl]);
+            const T   c    = MASS ? T(sigma) * h * h : T(0);
             const int base = sl * N3 + (v * N + u) * N;
             if constexpr (STREAM)
-              line_stream<T, P, B, 2, PREFETCH>(m, bufA + base, bufB + base, 1, h);
+              line_stream<T, P, B, 2, PREFETCH, MASS>(m, bufA + base, bufB + base, 1, h, c);
             else
               {
 #pragma unroll
@@ -709,7 +728,7 @@ namespace mgamd
                   r0[i] = bufA[base + i];
 #pragma unroll
                 for (int i = 0; i < N; ++i)
-                  r1[i] = bufB[base + i];
+                  r1[i] = MASS ? bufB[base + i] + c * r0[i] : bufB[base + i];
                 line_KM<T, P, B>(m, r0, r1, r2);
 #pragma unroll
                 for (int i = 0; i < N; ++i)
@@ -721,6 +740,7 @@ namespace mgamd
       if (sg)
         {
           const T   h    = T(hslot[0]);
+          const T   c    = MASS ? T(sigma) * h * h : T(0);
           const int base = (sg_v * N + sg_u) * N + 4 * sg_s;
           T         a[P + 5], b[P + 5], o1[5], o2[5];
 #pragma unroll
@@ -730,6 +750,12 @@ namespace mgamd
               b[i] = (sg_s > 0 || i >= P) ? bufB[base + (i - P)] : T(0);
             }
           seg_fence();
+          if constexpr (MASS)
+            {
+#pragma unroll
+              for (int i = 0; i < P + 5; ++i)
+                b[i] += c * a[i];
+            }
           seg_products<T, P, 2>(m, a, b, sg_s > 0, o1, o2);
 #pragma unroll
           for (int i = 0; i < 5; ++i)
@@ -1041,6 +1067,7 @@ namespace mgamd
     // residual scatters to their rows, the edge matrix gathers and scatters them (runtime.hip, EdgeMode).
     uint32_t gather_limit, scatter_limit;
     FusedTransferDev<T, P> fused; // MODE_RESIDUAL_RESTRICT / MODE_CHEB_PROLONGATE only
+    double sigma = 0.0; // mass coefficient of K + sigma M (lattice_sweeps); 0: the Laplace operator
   };
   static_assert(sizeof(ApplyArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "ApplyArgs exceeds the kernel-argument segment");
 

@@ -133,8 +133,11 @@ namespace mgamd
       // one-slot-per-workgroup lattices (17^3): persistent workgroups with a software pipeline over their slots
       // (kernels.hpp, lattice_apply_persistent_body).  Two workgroups fit a CU (LDS); the grid is a multiple of 8 so
       // that a workgroup stays inside the Morton range of its XCD.
-      launch_persistent(ctx, st, lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR>, grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK,
-                        apply_lds_bytes<T, P, B>(), a);
+      // (the mass term is compiled in or out of these kernels: kernels.hpp, lattice_apply_persistent_body)
+      launch_persistent(ctx, st,
+                        a.sigma != 0.0 ? lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, true> :
+                                         lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, false>,
+                        grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
     else
       launch_lds(ctx, st, lattice_apply_kernel<T, P, B, MODE, CONSTR>, grid, G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
     HIP_CHECK(hipGetLastError());
@@ -299,6 +302,10 @@ namespace mgamd
       tables = dofs->tables;
       tria   = dofs->tria;
       p      = tables->p;
+      sigma  = tables->sigma;
+      if (tables->ls_level && sigma != 0.0)
+        throw std::invalid_argument("level operator: mass coefficient " + std::to_string(sigma) +
+                                    " on a local-smoothing level: not implemented (refinement-edge matrices have no mass term)");
       if (cm && dofs->halo)
         {
           comm      = cm;
@@ -536,6 +543,7 @@ namespace mgamd
       c.c0         = a.epi.c0;
       c.from_b     = first ? 1 : 0;
       c.cluster_offset = 0;
+      c.sigma          = a.sigma;
       return c;
     }
 
@@ -566,7 +574,10 @@ namespace mgamd
         {
           if (n_wg > resident_workgroups(ctx))
             pa.n_wg_plain = 0; // every workgroup walks both kinds (kernels.hpp)
-          launch_persistent(ctx, st, lattice_apply_persistent_pair_kernel<T, P, B, MODE>, n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
+          launch_persistent(ctx, st,
+                            a.sigma != 0.0 ? lattice_apply_persistent_pair_kernel<T, P, B, MODE, true> :
+                                             lattice_apply_persistent_pair_kernel<T, P, B, MODE, false>,
+                            n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
         }
       else if constexpr (MODE != base_mode(MODE))
         throw std::runtime_error("fused transfers need the persistent brick kernel");
@@ -604,8 +615,10 @@ namespace mgamd
                 return launch_pair<P, B, MODE>(st, a, partner_constrained);
               throw std::runtime_error("brick pair launch: size not instantiated");
             }
-          launch_persistent(ctx, st, lattice_apply_persistent_kernel<T, P, B, MODE>, (int)a.g.n_slots, persistent_wgs_per_cu<T, P>(),
-                            G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
+          launch_persistent(ctx, st,
+                            a.sigma != 0.0 ? lattice_apply_persistent_kernel<T, P, B, MODE, false, true> :
+                                             lattice_apply_persistent_kernel<T, P, B, MODE, false, false>,
+                            (int)a.g.n_slots, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
           HIP_CHECK(hipGetLastError());
         }
       else
@@ -644,7 +657,10 @@ namespace mgamd
       const uint32_t n_wg_cells = (n_w + CELL_WAVES - 1) / CELL_WAVES;
       constexpr size_t lds      = small_slots_lds_bytes<T, P>();
       static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit the launch has to go through launch_lds");
-      hipLaunchKernelGGL((lattice_apply_small_kernel<T, P, MODE>), sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
+      // (kernels.hpp: MASS = false exists only where the kernel has no room for a run-time sigma; elsewhere both names are one kernel)
+      constexpr bool laplace_form = !small_slots_mass_compiled<T, P>();
+      hipLaunchKernelGGL((a.sigma == 0.0 ? lattice_apply_small_kernel<T, P, MODE, laplace_form> : lattice_apply_small_kernel<T, P, MODE, true>),
+                         sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
       HIP_CHECK(hipGetLastError());
     }
 

@@ -22,6 +22,7 @@ namespace mgamd
     a.ablate     = ablate;
     a.stamps     = nullptr;
     a.epi        = epi;
+    a.sigma      = sigma;
     // Sharded level: the slots that touch shared DoFs first, then the halo exchange on the side queue UNDERNEATH the remaining
     // slots (ref: MatrixFree::cell_loop overlaps its ghost exchange with the interior cell ranges, ref:include/operator.h:166-167).
     if (!diag && !plan.interior_slots.empty())

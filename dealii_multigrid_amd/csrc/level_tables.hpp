@@ -365,6 +365,21 @@ namespace mgamd
     // are INVALID = 0xFFFFFFFF, above every limit).
     bool     ls_level = false;
     uint32_t n_edge   = 0;
+    // Mass coefficient sigma >= 0 of the shifted operator  K + sigma M  (weak form of -Laplace u + sigma u; DESIGN.md "Mass
+    // term").  Everything built FROM the tables (level operators, assembled matrices, the Gaussian right-hand side) reads it at
+    // its construction and keeps its own copy; 0 = the Laplace operator.  Local-smoothing levels refuse a non-zero value (their
+    // refinement-edge matrices carry no mass term).
+    double sigma = 0.0;
+    void
+    set_mass_coefficient(double s)
+    {
+      if (!(s >= 0.0) || !std::isfinite(s))
+        throw std::invalid_argument("mass coefficient " + std::to_string(s) + " refused: it must be finite and >= 0");
+      if (ls_level && s != 0.0)
+        throw std::invalid_argument("mass coefficient " + std::to_string(s) +
+                                    " refused: local-smoothing level tables only take 0 (refinement-edge matrices have no mass term)");
+      sigma = s;
+    }
     static constexpr int      CLS_SHIFT = 29;
     static constexpr uint32_t CLS_MASK  = (1u << CLS_SHIFT) - 1;
     // distributed runs: the tail is [owned | copies of DoFs owned by a lower rank]; *_owned count each DoF once globally
@@ -646,9 +661,33 @@ namespace mgamd
             y[i] += h * t3[i];
         }
     }
+    // y += sigma M_cell x,  M_cell = h^3 M (x) M (x) M
+    void
+    cell_mass_add(double h, double sigma, const double *x, double *y) const
+    {
+      const int           n = p + 1, n3 = n * n * n;
+      std::vector<double> t1(n3), t2(n3);
+      for (int d = 0; d < 3; ++d)
+        {
+          const int     st = d == 0 ? 1 : (d == 1 ? n : n * n);
+          const double *in = d == 0 ? x : (d == 1 ? t1.data() : t2.data());
+          double       *out = d == 1 ? t2.data() : t1.data();
+          for (int i = 0; i < n3; ++i)
+            {
+              const int id = (i / st) % n;
+              double    s  = 0;
+              for (int b = 0; b < n; ++b)
+                s += fe.M[id * n + b] * in[i + (b - id) * st];
+              out[i] = s;
+            }
+        }
+      for (int i = 0; i < n3; ++i)
+        y[i] += sigma * h * h * h * t1[i];
+    }
 
     // right-hand side for data `kind` (ref:include/operator.h:362-447): load vector by QGauss(p+1) quadrature of f,
     // minus the operator without Dirichlet constraints applied to the boundary interpolant of g; constrained rows 0.
+    // With a mass coefficient the manufactured load is -Laplace u_g + sigma u_g and the lifting uses K + sigma M.
     void
     compute_rhs_function(int kind, std::vector<double> &b) const
     {
@@ -674,7 +713,8 @@ namespace mgamd
               for (int qx = 0; qx < n; ++qx)
                 {
                   const double x[3] = {o[0] + h * fe.xq[qx], o[1] + h * fe.xq[qy], o[2] + h * fe.xq[qz]};
-                  fq[(qz * n + qy) * n + qx] = data_f(kind, x) * h * h * h * fe.wq[qx] * fe.wq[qy] * fe.wq[qz];
+                  const double f    = sigma != 0.0 ? data_f(kind, x) + sigma * data_g(kind, x) : data_f(kind, x);
+                  fq[(qz * n + qy) * n + qx] = f * h * h * h * fe.wq[qx] * fe.wq[qy] * fe.wq[qz];
                 }
           // integrate against the shape functions: load[a] = sum_q S[q][a] ... per direction
           auto integrate = [&](int d, const double *in, double *out) {
@@ -714,6 +754,8 @@ namespace mgamd
             {
               interpolate_hanging(fe, mask, xg.data(), false);
               cell_stiffness_apply(h, xg.data(), lift.data());
+              if (sigma != 0.0)
+                cell_mass_add(h, sigma, xg.data(), lift.data());
               for (int t = 0; t < n3; ++t)
                 load[t] -= lift[t];
             }

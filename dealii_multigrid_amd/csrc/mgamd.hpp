@@ -274,6 +274,21 @@ namespace mgamd
     {
       return h.get();
     }
+    // The mass term: operators, matrices and right-hand sides built from this handler AFTER the call represent K + sigma M
+    // (mgamd_dofs_set_mass_coefficient).  sigma >= 0; local-smoothing levels (mg_level) only take 0.  The handle is shared by the
+    // copies of this object, so the method is const like the handle's other uses.
+    void
+    set_mass_coefficient(double sigma) const
+    {
+      check(mgamd_dofs_set_mass_coefficient(h.get(), sigma));
+    }
+    double
+    mass_coefficient() const
+    {
+      double s = 0.0;
+      check(mgamd_dofs_mass_coefficient(h.get(), &s));
+      return s;
+    }
     mgamd_dofs_info_t info;
 
   private:
@@ -551,6 +566,11 @@ namespace mgamd
     {
       if (!dofs)
         throw std::runtime_error("Operator::get_system_matrix: reinit first");
+      // the matrix is assembled from the handler's tables, which may have taken another mass coefficient since reinit
+      if (dofs->mass_coefficient() != mass_coefficient())
+        throw std::invalid_argument("Operator::get_system_matrix: the mass coefficient of the DoFHandler (" + std::to_string(dofs->mass_coefficient()) +
+                                    ") was changed after this operator was built with " + std::to_string(mass_coefficient()) +
+                                    "; the assembled matrix would be another operator's");
       return SparseMatrix(*context, *dofs);
     }
     // DoFs this rank owns (sums to DoFHandler::n_dofs() over the ranks)
@@ -567,6 +587,14 @@ namespace mgamd
       uint64_t n = 0;
       check(mgamd_level_op_m(h.get(), &n));
       return n;
+    }
+    // the mass coefficient this operator was built with (DoFHandler::set_mass_coefficient before reinit)
+    double
+    mass_coefficient() const
+    {
+      double s = 0.0;
+      check(mgamd_level_op_mass_coefficient(h.get(), &s));
+      return s;
     }
     void
     initialize_dof_vector(Vector &vec) const
@@ -727,7 +755,7 @@ namespace mgamd
     // meshes: coarsest first (with `sharding`: the partition's); local_smoothing: they are Triangulation::level_mesh(l)
     LevelStack(const Context &ctx, const std::vector<std::shared_ptr<const Triangulation>> &meshes,
                const std::vector<std::pair<unsigned, unsigned>> &levels, int number_type, const PreconditionChebyshev::AdditionalData &smoother_data,
-               const Sharding *sharding = nullptr, bool local_smoothing = false, const Given *given = nullptr)
+               const Sharding *sharding = nullptr, bool local_smoothing = false, const Given *given = nullptr, double mass_coefficient = 0.0)
       : operators(levels.size())
       , transfers(levels.size())
       , smoothers(levels.size())
@@ -741,6 +769,10 @@ namespace mgamd
           dof_handlers.emplace_back(*sharding->partition, levels[l].first, sharding->comm->rank(), levels[l].second);
         else
           dof_handlers.emplace_back(meshes[levels[l].first], levels[l].second, -1, local_smoothing);
+      // the mass term of K + sigma M, on every level's handler before its operator is built (local-smoothing levels refuse sigma != 0)
+      for (unsigned l = 0; l < n; ++l)
+        if (!(given && given->level == l && given->op))
+          dof_handlers[l].set_mass_coefficient(mass_coefficient);
       for (unsigned l = 0; l < n; ++l)
         {
           comms[l] = sharding ? sharding->mesh_comm(levels[l].first) : nullptr;

@@ -1320,7 +1320,7 @@ namespace mgamd
                                       "algebraic multigrid needs a level 0 that is cut over all ranks");
       const int          n_ranks = comm ? comm->n_ranks : 1, rank = comm ? comm->rank : 0;
       const LevelTables &local   = *op->tables;
-      const std::vector<uint32_t> grow = match_rows_by_key(global, local); // (refuses another space)
+      const std::vector<uint32_t> grow = match_rows_by_key(global, local, op->sigma); // (refuses another space, another operator)
       const std::vector<uint8_t>  own  = local_dof_owned(local);
       const AmgHierarchyHost      H    = build_hierarchy(assemble_level_matrix(global));
       const uint32_t              n0   = H.levels[0].A.n_rows;
@@ -1770,6 +1770,10 @@ namespace mgamd
                                          "from one rank's assembled matrix; use the nested geometric multigrid (gmg_vcycle), cg or "
                                          "cg_with_chebyshev");
               coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
+              if (ops[0]->tables->sigma != ops[0]->sigma)
+                throw std::invalid_argument("multigrid: the mass coefficient of level 0's tables (" + std::to_string(ops[0]->tables->sigma) +
+                                            ") was changed after its operator was built with " + std::to_string(ops[0]->sigma) +
+                                            "; the AMG coarse solver assembles its matrix from the tables");
               amg         = std::make_unique<AmgCycle<T>>(ctx, *ops[0]->tables);
             }
         }

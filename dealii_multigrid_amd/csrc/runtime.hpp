@@ -172,6 +172,9 @@ namespace mgamd
     std::shared_ptr<Tria>        tria;
     std::shared_ptr<Comm>        comm; // sharded runs: set when this level is distributed
     std::shared_ptr<HaloPlan>    halo_plan;
+    // mass coefficient of K + sigma M: the operator's OWN copy of tables->sigma, taken at construction (a time-stepping caller
+    // changes it on the tables and builds new operators)
+    double sigma = 0.0;
     virtual ~LevelOperatorBase() = default;
     // inner product counting every DoF once across ranks (copies of DoFs owned by other ranks are skipped)
     virtual double

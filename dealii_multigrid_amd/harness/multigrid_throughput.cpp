@@ -137,6 +137,9 @@ struct RunParameters
   // library's smoothed-aggregation AMG cut into rows over the ranks instead of the geometric stand-in; default false
   bool         sharded_amg          = false;
   unsigned     amg_min_sharded_rows = MGAMD_AMG_MIN_SHARDED_ROWS_DEFAULT;
+  // this project's extension: "MassCoefficient": sigma >= 0 solves -Laplace u + sigma u = f (the operator K + sigma M); default 0,
+  // the reference's Laplace problem.  The local-smoothing Types have no mass term: a non-zero value is "not implemented" there.
+  double       mass_coefficient     = 0.0;
   MultigridParameters mg_data;
 
   void
@@ -175,6 +178,7 @@ struct RunParameters
     get("MGNumberType", mg_number_type);
     get("ShardedAMG", sharded_amg);
     get("AMGMinShardedRows", amg_min_sharded_rows);
+    get("MassCoefficient", mass_coefficient);
     get("SimulationType", simulation_type); // unknown keys are ignored (skip_undefined = true)
   }
 };
@@ -281,6 +285,10 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
   // ---- level hierarchy (ref:multigrid_throughput.cc:2219-2260, 1506-1596): the meshes here, the levels on them from the library
   // (mgamd_level_plan), which also refuses the Types without levels
   const bool local_smoothing = params.type == "HMG-local", hp_local = params.type == "HPMG-local";
+  const double sigma         = params.mass_coefficient;
+  if ((local_smoothing || hp_local) && sigma != 0.0)
+    throw std::runtime_error("MassCoefficient " + std::to_string(sigma) + " with Type '" + params.type +
+                             "': not implemented (the refinement-edge matrices of local smoothing have no mass term)");
   auto       level_meshes    = [&]() { // the refinement levels of the mesh (solve_with_local_smoothing, ref:multigrid_throughput.cc:1670-1873)
     std::vector<std::shared_ptr<const Triangulation>> m;
     for (unsigned l = 0; l < tria->n_global_levels(); ++l)
@@ -347,7 +355,7 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
                                                active_dof_handler.get());
     }
   const LevelStack::Given ls_level0{0, active_dof_handler.get()};
-  const LevelStack        stack(ctx, meshes, plan.levels, level_number_type, sd, shards, plan.local_smoothing, hp_local ? &ls_level0 : nullptr);
+  const LevelStack        stack(ctx, meshes, plan.levels, level_number_type, sd, shards, plan.local_smoothing, hp_local ? &ls_level0 : nullptr, sigma);
   const DoFHandler       &fine_dof_handler = local_smoothing ? *active_dof_handler : stack.dof_handlers.back();
 
   // coarse solver (library policy, include/mgamd.h): the Trilinos/PETSc AMG options are an exact solve on the one-cell coarse
@@ -370,7 +378,7 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
       if (comm && c_meshes.size() != mesh0 + 1)
         throw std::runtime_error("sharded harness: the coarse level's mesh is not the end of the partition's mesh sequence");
       const LevelStack::Given top{(unsigned)c_meshes.size() - 1, &stack.dof_handlers[0], &stack.operators[0], &stack.smoothers[0]};
-      c_stack   = LevelStack(ctx, c_meshes, level_plan("HMG-global", c_meshes.size(), degree0).levels, level_number_type, sd, shards, false, &top);
+      c_stack   = LevelStack(ctx, c_meshes, level_plan("HMG-global", c_meshes.size(), degree0).levels, level_number_type, sd, shards, false, &top, sigma);
       coarse_mg = std::make_unique<PreconditionMG>(ctx, c_stack.operators, c_stack.transfers, c_stack.smoothers, "amg");
       std::cout << "note: CoarseGridSolverType '" << coarse << "' on the " << stack.dof_handlers[0].n_dofs() << "-DoF coarse level: "
                 << params.mg_data.coarse_solver.n_cycles << " V-cycle(s) of the geometric multigrid on that level" << std::endl;
@@ -379,6 +387,7 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
   if (extra == MGAMD_COARSE_SHARDED_AMG)
     {
       amg_global_dofs = std::make_unique<DoFHandler>(meshes[mesh0], degree0);
+      amg_global_dofs->set_mass_coefficient(sigma);
       std::cout << "note: CoarseGridSolverType '" << coarse << "' on the sharded " << amg_global_dofs->n_dofs() << "-DoF coarse level: "
                 << params.mg_data.coarse_solver.n_cycles << " cycle(s) of the smoothed-aggregation AMG, rows cut over the ranks (levels of <= "
                 << params.amg_min_sharded_rows << " rows replicated)" << std::endl;
@@ -557,6 +566,8 @@ main(int argc, char **argv)
             std::cout << std::string(argv[i]) << std::endl;
           RunParameters params;
           params.parse(std::string(argv[i]));
+          if (rank == 0 && params.mass_coefficient != 0.0)
+            std::cout << "MassCoefficient: " << params.mass_coefficient << std::endl;
           run(ctx, params, table, sharded ? &comm : nullptr);
           if (rank == 0)
             table.write_text(std::cout);

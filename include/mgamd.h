@@ -120,6 +120,23 @@ int mgamd_dofs_rhs_constant(const mgamd_dofs *d, double *out);
  * (ref:include/operator.h:362-447); and AffineConstraints::distribute on a host vector of n_dofs values */
 int mgamd_dofs_rhs(const mgamd_dofs *d, int kind, double *out);
 int mgamd_dofs_distribute(const mgamd_dofs *d, int kind, double *x);
+/* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
+ * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
+ * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
+ * built and keeps its own copy: mgamd_level_op_create[_distributed] (and with them smoothers, the "direct" coarse inverse and the
+ * collapsed coarse levels), mgamd_dofs_matrix, mgamd_matrix_create, the AMG coarse solvers, mgamd_amg_*, and mgamd_dofs_rhs /
+ * mgamd_level_op_rhs_kind for kind 1 (load -Laplace u_g + sigma u_g, Dirichlet lifting with K + sigma M; kind 0, f = 1 and g = 0, does
+ * not depend on sigma).  Transfers and partitions do not depend on it.  A time-stepping caller sets the new sigma on the tables of
+ * every level and re-creates operators, smoothers and the multigrid object; tables, transfer plans and partitions are reused.
+ * MGAMD_ERR_INVALID, with the value in mgamd_last_error(), for sigma < 0 (indefinite Helmholtz), for NaN and infinity, and for a
+ * non-zero sigma on local-smoothing level tables (mgamd_dofs_create_level: the refinement-edge matrices have no mass term).
+ * mgamd_mg_create_sharded_amg refuses a global_coarse_dofs whose sigma differs from level 0's.
+ * What takes mgamd_dofs alone (mgamd_dofs_matrix, mgamd_matrix_create, mgamd_dofs_rhs, mgamd_dofs_amg_setup_info) follows the
+ * CURRENT sigma of the tables; what is handed an operator next to them checks that the two agree: the AMG coarse solver of
+ * mgamd_mg_create*, and Operator::get_system_matrix of the C++ and Python layers, refuse tables whose sigma was changed after the
+ * operator was built.  The "direct" inverse and the collapsed levels are formed through the operator itself. */
+int mgamd_dofs_set_mass_coefficient(mgamd_dofs *d, double sigma);
+int mgamd_dofs_mass_coefficient(const mgamd_dofs *d, double *sigma);
 
 /* Operator::get_trilinos_system_matrix / get_petsc_system_matrix (ref:include/operator.h:244-358: MatrixFreeTools::compute_matrix of
  * the cell kernel with the constraints): the assembled level matrix C^T K C + identity on the constrained rows, CSR with sorted
@@ -279,6 +296,8 @@ int mgamd_level_op_exchange_add_tail(mgamd_level_op *op, mgamd_vec *v);
 /* number of DoFs this rank owns (sums to DoFHandler::n_dofs() over the ranks) */
 int mgamd_level_op_n_owned(const mgamd_level_op *op, uint64_t *n);
 int mgamd_level_op_m(const mgamd_level_op *op, uint64_t *n); /* Operator::m (ref:include/operator.h:123) */
+/* the mass coefficient the operator was BUILT with (mgamd_dofs_set_mass_coefficient; later changes of the tables do not reach it) */
+int mgamd_level_op_mass_coefficient(const mgamd_level_op *op, double *sigma);
 /* Operator::initialize_dof_vector (ref:include/operator.h:140) */
 int mgamd_level_op_init_vector(const mgamd_level_op *op, mgamd_vec **out);
 /* Operator::vmult: dst = A src, identity on constrained rows (ref:include/operator.h:152-183) */

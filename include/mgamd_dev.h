@@ -48,6 +48,9 @@ typedef struct mgamd_amg_shard mgamd_amg_shard;
 int mgamd_debug_amg_shard_create(const mgamd_partition *partition, unsigned level, int degree, int max_brick, uint32_t min_sharded_rows,
                                  mgamd_amg_shard **out);
 int mgamd_debug_amg_shard_destroy(mgamd_amg_shard *h);
+/* the first step of every shard plan, on its own: the global row of every DoF of `local` in `global` (rows[n_dofs of local], may be
+ * null).  MGAMD_ERR_INVALID if the two are not the same space: another degree, or another mass coefficient. */
+int mgamd_debug_amg_shard_match_rows(const mgamd_dofs *global, const mgamd_dofs *local, uint32_t *rows);
 int mgamd_debug_amg_shard_n_levels(const mgamd_amg_shard *h, uint32_t *n_levels, uint32_t *n_sharded_levels);
 /* info[12] of one rank's level: replicated, global rows, local rows, mirror rows (identity rows of constrained DoFs computed here
  * but owned elsewhere; local rows are [mirror | owned interior | owned boundary]), owned interior rows, ghosts, length of the padded
