@@ -9,8 +9,9 @@ LIB        := $(LIBDIR)/libmgamd.so
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/mgamd.h include/mgamd_dev.h
 
 BIN        := dealii_multigrid_amd/bin/multigrid_throughput
+EXAMPLE    := bin/heat_equation
 
-all: $(LIB) $(BIN) oracle
+all: $(LIB) $(BIN) $(EXAMPLE) oracle
 
 $(LIBDIR)/runtime.o: $(CSRC)/runtime.hip $(HDRS)
 	@mkdir -p $(LIBDIR)
@@ -39,6 +40,11 @@ $(LIB): $(LIBDIR)/runtime.o $(APPLY_OBJS) $(LIBDIR)/c_api_device.o $(LIBDIR)/c_a
 $(BIN): dealii_multigrid_amd/harness/multigrid_throughput.cpp $(CSRC)/mgamd.hpp include/mgamd.h $(LIB)
 	@mkdir -p dealii_multigrid_amd/bin
 	g++ -O2 -std=c++17 -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lmgamd -Wl,-rpath,'$$ORIGIN/../lib'
+
+# the time-stepping example of INTEGRATION.md (examples/heat_equation.cpp)
+$(EXAMPLE): examples/heat_equation.cpp $(CSRC)/mgamd.hpp include/mgamd.h $(LIB)
+	@mkdir -p bin
+	g++ -O2 -std=c++17 -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lmgamd -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'
 
 oracle:
 	$(MAKE) -C oracle

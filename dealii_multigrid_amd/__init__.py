@@ -490,6 +490,11 @@ class Operator:
     def vmult(self, dst: Vector, src: Vector):
         _chk(_lib.mgamd_level_op_vmult(self._h, dst._h, src._h))
 
+    def vmult_mass(self, dst: Vector, src: Vector):
+        """dst = C^T M C src: the mass matrix of this operator's space; rows and columns of constrained DoFs are zero, the
+        mass coefficient plays no role (mgamd_level_op_vmult_mass)"""
+        _chk(_lib.mgamd_level_op_vmult_mass(self._h, dst._h, src._h))
+
     def vmult_interface_up(self, dst: Vector, src: Vector):
         """local-smoothing level: the edge matrix, A with the refinement-edge DoFs unconstrained applied to src|edge"""
         _chk(_lib.mgamd_level_op_vmult_interface_up(self._h, dst._h, src._h))
@@ -738,6 +743,46 @@ def solve_cg(A, preconditioner, x: Vector, b: Vector, reltol=1e-4, abstol=1e-20,
         raise MgamdError("solve_cg: a PreconditionAMG goes with the SparseMatrix it was built on")
     _chk(_lib.mgamd_solve_cg(A._h, ph, x._h, b._h, C.c_double(reltol), C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
     return it.value, res.value
+
+
+class TimeStepper:
+    """theta-scheme for the heat equation M u' + K u = M f with constant step dt (mgamd_time_stepper).  op: the FP64 operator
+    K + sigma M of a hierarchy built with mass_coefficient=TimeStepper.mass_coefficient(theta, dt) (Hierarchy.fine_operator,
+    DistributedHierarchy.fine_operator), mg: its multigrid.  step() advances u in place, with u as the initial guess: the CG
+    solves for the increment and reltol acts on the increment's residual."""
+
+    def __init__(self, op: Operator, mg: "PreconditionMG", theta: float, dt: float):
+        self.op, self.mg = op, mg  # (kept alive)
+        self._h = C.c_void_p()
+        _chk(_lib.mgamd_time_stepper_create(op._h, mg._h if mg is not None else None, C.c_double(theta), C.c_double(dt), C.byref(self._h)))
+
+    @staticmethod
+    def mass_coefficient(theta: float, dt: float) -> float:
+        """sigma = 1 / (theta dt)"""
+        return 1.0 / (theta * dt)
+
+    def step(self, u: Vector, f_old: Vector = None, f_new: Vector = None, reltol=1e-4, abstol=1e-20, maxiter=10000):
+        """one step; f_old / f_new: nodal source values at t and t + dt (both None: f = 0).  Returns the CG's iterations and
+        final residual norm.  Constrained entries of u are not read and are 0 on return."""
+        it, res = C.c_uint(), C.c_double()
+        _chk(_lib.mgamd_time_stepper_step(self._h, u._h, f_old._h if f_old is not None else None, f_new._h if f_new is not None else None,
+                                          C.c_double(reltol), C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
+        return it.value, res.value
+
+    def time(self) -> float:
+        t = C.c_double()
+        _chk(_lib.mgamd_time_stepper_time(self._h, C.byref(t), None))
+        return t.value
+
+    def n_steps(self) -> int:
+        n = C.c_uint64()
+        _chk(_lib.mgamd_time_stepper_time(self._h, None, C.byref(n)))
+        return n.value
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mgamd_time_stepper_destroy(self._h)
+            self._h = None
 
 
 class AmgHostHierarchy:

@@ -17,6 +17,7 @@ namespace mgamd
   MGAMD_INST(MODE_CHEB)
   MGAMD_INST(MODE_CHEB_FIRST)
   MGAMD_INST(MODE_CHEB_SECOND)
+  MGAMD_INST(MODE_MASS)
   // the passes with fused level transfers: degrees with a persistent 17-point lattice kernel
 #if MGAMD_INST_P == 1 || MGAMD_INST_P == 2 || MGAMD_INST_P == 4
   MGAMD_INST(MODE_RESIDUAL_RESTRICT)

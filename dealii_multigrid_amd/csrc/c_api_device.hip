@@ -373,6 +373,15 @@ mgamd_level_op_vmult(mgamd_level_op *op, mgamd_vec *dst, const mgamd_vec *src)
 }
 
 int
+mgamd_level_op_vmult_mass(mgamd_level_op *op, mgamd_vec *dst, const mgamd_vec *src)
+{
+  MGAMD_TRY
+  REQUIRE(op && dst && src);
+  op->op->vmult_mass(*dst, *src);
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_inverse_diagonal(mgamd_level_op *op, mgamd_vec *diagonal)
 {
   MGAMD_TRY
@@ -808,6 +817,51 @@ mgamd_solve_cg(mgamd_level_op *A, mgamd_mg *preconditioner, mgamd_vec *x, const 
   if (residual_norm)
     *residual_norm = res;
   MGAMD_CATCH
+}
+
+int
+mgamd_time_stepper_create(mgamd_level_op *A, mgamd_mg *preconditioner, double theta, double dt, mgamd_time_stepper **out)
+{
+  MGAMD_TRY
+  REQUIRE(A && out);
+  auto ts = std::make_unique<mgamd_time_stepper>();
+  ts->ts.reset(make_theta_stepper(*A->op, preconditioner ? preconditioner->mg.get() : nullptr, theta, dt));
+  *out = ts.release();
+  MGAMD_CATCH
+}
+
+int
+mgamd_time_stepper_step(mgamd_time_stepper *ts, mgamd_vec *u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol, double abstol,
+                        unsigned maxiter, unsigned *n_iterations, double *residual_norm)
+{
+  MGAMD_TRY
+  REQUIRE(ts && u);
+  unsigned it  = 0;
+  double   res = 0;
+  ts->ts->step(*u, f_old, f_new, reltol, abstol, maxiter, it, res);
+  if (n_iterations)
+    *n_iterations = it;
+  if (residual_norm)
+    *residual_norm = res;
+  MGAMD_CATCH
+}
+
+int
+mgamd_time_stepper_time(const mgamd_time_stepper *ts, double *t, uint64_t *n_steps)
+{
+  MGAMD_TRY
+  REQUIRE(ts);
+  if (t)
+    *t = ts->ts->t;
+  if (n_steps)
+    *n_steps = ts->ts->n_steps;
+  MGAMD_CATCH
+}
+
+void
+mgamd_time_stepper_destroy(mgamd_time_stepper *ts)
+{
+  delete ts;
 }
 
 int

@@ -18,6 +18,8 @@
 //   A_brick = h (K (x) M (x) M + M (x) K (x) M + M (x) M (x) K)
 // with 1D matrices assembled over the B cells of a lattice line; each 1D product is evaluated
 // cell by cell with the dense (p+1)^2 reference matrices held in SGPRs (kernel arguments).
+// The same kernels in MODE_MASS apply the mass matrix h^3 M (x) M (x) M of the brick instead: three mass products on one lattice
+// (mass_sweeps), zero rows on constrained DoFs.
 //
 // K7  csr_spmv_kernel        CSR products of the algebraic coarse solver, fused with the Chebyshev update; one body
 //                            (csr_spmv_rows), two entry points: all rows, and csr_spmv_range_kernel for a sharded level's rows.

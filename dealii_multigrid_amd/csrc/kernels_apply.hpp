@@ -297,7 +297,12 @@ namespace mgamd
     MGAMD_STAMP(5)
 
     if (!MGAMD_ABLATED(1))
-      lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE, MASS>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true, args.sigma);
+      {
+        if constexpr (MODE == MODE_MASS) // three mass products on the first lattice; the second is not touched
+          mass_sweeps<T, P, B, BLOCK, false, false, WAVE>(bufA, args.m, tid, nslots, &h_mine, true);
+        else
+          lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE, MASS>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true, args.sigma);
+      }
     MGAMD_STAMP(6)
 
     if (B == 1 && any_hanging)
@@ -316,7 +321,7 @@ namespace mgamd
             {
               const T ax = bufA[e.l];
               T       r;
-              if (MODE == MODE_VMULT)
+              if (MODE == MODE_VMULT || MODE == MODE_MASS)
                 r = ax;
               else if (MODE == MODE_RESIDUAL)
                 r = bv[it] - ax;
@@ -390,6 +395,7 @@ namespace mgamd
     constexpr bool FUSE_R = MODE_ == MODE_RESIDUAL_RESTRICT, FUSE_P = MODE_ == MODE_CHEB_PROLONGATE, FUSE = FUSE_R || FUSE_P;
     static_assert(!FUSE || (!CONSTR && B >= 2 && G::ABLOCK == 256), "fused transfers: plain bricks, 256 threads");
     static_assert(!CONSTR || P == 1, "constrained bricks larger than a family: p = 1 only (LevelTables::build)");
+    static_assert(MODE_ != MODE_MASS || !MASS, "the mass pass has no mass TERM: one instantiation, MASS = false");
     constexpr int BC = B >= 2 ? B / 2 : 1, NC = P * BC + 1, NC3 = NC * NC * NC; // coarse lattice under the brick
     T *bufA = reinterpret_cast<T *>(smem_raw);
     T *bufB = bufA + G::N3;
@@ -688,8 +694,11 @@ namespace mgamd
               brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, false, &fmcur);
           }
         // cell prefetch in the streamed sweeps (-4 % on the 2-4-word passes); the 5-word mode has no registers left for it
-        lattice_sweeps<T, P, B, BLOCK, NoHook, true, (MODE != MODE_CHEB || sizeof(T) == 4), false, MASS>(
-          bufA, bufB, args.m, tid, 1, &hcur, NoHook(), false, args.sigma);
+        if constexpr (MODE == MODE_MASS) // (streamed like the operator's sweeps, with the cell prefetch; the second lattice is not touched)
+          mass_sweeps<T, P, B, BLOCK, true, true, false>(bufA, args.m, tid, 1, &hcur, false);
+        else
+          lattice_sweeps<T, P, B, BLOCK, NoHook, true, (MODE != MODE_CHEB || sizeof(T) == 4), false, MASS>(
+            bufA, bufB, args.m, tid, 1, &hcur, NoHook(), false, args.sigma);
         if constexpr (brick_may_be_constrained(B, CONSTR))
           if (any_hanging)
             brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, true, &fmcur);
@@ -771,7 +780,7 @@ namespace mgamd
                   const uint32_t g  = base + (uint32_t)(tid + it * BLOCK);
                   const T        ax = bufA[wk.pos()];
                   T              r;
-                  if (MODE == MODE_VMULT)
+                  if (MODE == MODE_VMULT || MODE == MODE_MASS)
                     r = ax;
                   else if (MODE == MODE_RESIDUAL)
                     r = bv[it] - ax;
@@ -1140,7 +1149,8 @@ namespace mgamd
       }
   }
 
-  template <typename T>
+  // MASS_ONLY (MODE_MASS): the cell's mass matrix h^3 M (x) M (x) M instead of the operator
+  template <typename T, bool MASS_ONLY = false>
   __device__ __forceinline__ void
   cell_cluster_body(const ClusterArgs<T> &a, const uint32_t block, const uint32_t nblocks, unsigned char *smem_raw)
   {
@@ -1215,31 +1225,60 @@ namespace mgamd
     const T K0 = T(a.m.K[0]), K1 = T(a.m.K[1]), K2 = T(a.m.K[2]), K3 = T(a.m.K[3]);
     const T cm = T(a.sigma) * h * h; // sigma h^2: h (K a + M (b + c a)) adds sigma h^3 M (x) M (x) M
     T       A[8], Bv[8];
+    if constexpr (MASS_ONLY)
+      { // three mass products of the 2x2x2 lattice in place (mass_sweeps): z, y, x; x scales by h^3
+        const T h3 = h * h * h;
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      { // z lines: nodes q, q + 4
-        const T r0 = x[q], r1 = x[q + 4];
-        A[q]       = M0 * r0 + M1 * r1;
-        A[q + 4]   = M2 * r0 + M3 * r1;
-        Bv[q]      = K0 * r0 + K1 * r1;
-        Bv[q + 4]  = K2 * r0 + K3 * r1;
+        for (int q = 0; q < 4; ++q)
+          {
+            const T r0 = x[q], r1 = x[q + 4];
+            A[q]       = M0 * r0 + M1 * r1;
+            A[q + 4]   = M2 * r0 + M3 * r1;
+          }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          {
+            const int i0 = (q & 1) + 4 * (q >> 1);
+            const T   a0 = A[i0], a1 = A[i0 + 2];
+            A[i0]        = M0 * a0 + M1 * a1;
+            A[i0 + 2]    = M2 * a0 + M3 * a1;
+          }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          {
+            const T a0 = A[2 * q], a1 = A[2 * q + 1];
+            x[2 * q]     = h3 * (M0 * a0 + M1 * a1);
+            x[2 * q + 1] = h3 * (M2 * a0 + M3 * a1);
+          }
       }
+    else
+      {
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      { // y lines: nodes i0, i0 + 2 with i0 = x + 4z
-        const int i0 = (q & 1) + 4 * (q >> 1);
-        const T   a0 = A[i0], a1 = A[i0 + 2], b0 = Bv[i0], b1 = Bv[i0 + 2];
-        A[i0]        = M0 * a0 + M1 * a1;
-        A[i0 + 2]    = M2 * a0 + M3 * a1;
-        Bv[i0]       = K0 * a0 + K1 * a1 + M0 * b0 + M1 * b1;
-        Bv[i0 + 2]   = K2 * a0 + K3 * a1 + M2 * b0 + M3 * b1;
-      }
+        for (int q = 0; q < 4; ++q)
+          { // z lines: nodes q, q + 4
+            const T r0 = x[q], r1 = x[q + 4];
+            A[q]       = M0 * r0 + M1 * r1;
+            A[q + 4]   = M2 * r0 + M3 * r1;
+            Bv[q]      = K0 * r0 + K1 * r1;
+            Bv[q + 4]  = K2 * r0 + K3 * r1;
+          }
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      { // x lines: nodes 2q, 2q + 1; the mass term as in lattice_sweeps: b += c a
-        const T a0 = A[2 * q], a1 = A[2 * q + 1], b0 = Bv[2 * q] + cm * a0, b1 = Bv[2 * q + 1] + cm * a1;
-        x[2 * q]     = h * (K0 * a0 + K1 * a1 + M0 * b0 + M1 * b1);
-        x[2 * q + 1] = h * (K2 * a0 + K3 * a1 + M2 * b0 + M3 * b1);
+        for (int q = 0; q < 4; ++q)
+          { // y lines: nodes i0, i0 + 2 with i0 = x + 4z
+            const int i0 = (q & 1) + 4 * (q >> 1);
+            const T   a0 = A[i0], a1 = A[i0 + 2], b0 = Bv[i0], b1 = Bv[i0 + 2];
+            A[i0]        = M0 * a0 + M1 * a1;
+            A[i0 + 2]    = M2 * a0 + M3 * a1;
+            Bv[i0]       = K0 * a0 + K1 * a1 + M0 * b0 + M1 * b1;
+            Bv[i0 + 2]   = K2 * a0 + K3 * a1 + M2 * b0 + M3 * b1;
+          }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          { // x lines: nodes 2q, 2q + 1; the mass term as in lattice_sweeps: b += c a
+            const T a0 = A[2 * q], a1 = A[2 * q + 1], b0 = Bv[2 * q] + cm * a0, b1 = Bv[2 * q + 1] + cm * a1;
+            x[2 * q]     = h * (K0 * a0 + K1 * a1 + M0 * b0 + M1 * b1);
+            x[2 * q + 1] = h * (K2 * a0 + K3 * a1 + M2 * b0 + M3 * b1);
+          }
       }
     if (mask >> 3)
       hanging_in_registers_p1<T, true>(x, mask, a.m);
@@ -1267,6 +1306,14 @@ namespace mgamd
     extern __shared__ __align__(16) unsigned char smem_raw[];
     cell_cluster_body<T>(a, blockIdx.x, gridDim.x, smem_raw);
   }
+  // MODE_MASS (a kernel of its own: the operator's cluster kernel is the same for every other mode and keeps its name)
+  template <typename T>
+  __global__ void
+  __launch_bounds__(CLUSTER_CELLS) cell_cluster_mass_kernel(const ClusterArgs<T> a)
+  {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    cell_cluster_body<T, true>(a, blockIdx.x, gridDim.x, smem_raw);
+  }
 
   // p = 1: the 8^3 bricks and the cell clusters of a level in one launch (same reason as lattice_apply_small_kernel)
   template <typename T>
@@ -1285,7 +1332,7 @@ namespace mgamd
     if (blockIdx.x < args.n_wg_bricks)
       lattice_apply_body<T, 1, 8, MODE>(args.a, blockIdx.x, args.n_wg_bricks, smem_raw);
     else
-      cell_cluster_body<T>(args.c, blockIdx.x - args.n_wg_bricks, gridDim.x - args.n_wg_bricks, smem_raw);
+      cell_cluster_body<T, MODE == MODE_MASS>(args.c, blockIdx.x - args.n_wg_bricks, gridDim.x - args.n_wg_bricks, smem_raw);
   }
 
   // Diagonal of C^T (K + sigma M) C.  Slots without hanging nodes: closed tensor form; single cells with hanging
@@ -1412,7 +1459,7 @@ namespace mgamd
   }
 
   // Epilogue for the tail (accumulated shell sums) and the constrained DoFs (identity rows:
-  // ref:include/operator.h:170-172); re-zeroes the accumulator for the next application.
+  // ref:include/operator.h:170-172; MODE_MASS: zero rows); re-zeroes the accumulator for the next application.
   template <typename T, int MODE_>
   __global__ void
   __launch_bounds__(256) tail_kernel(T *__restrict__ tail_acc, uint32_t n_interior, uint32_t n_tail, uint32_t n_rest, Epilogue<T> epi)
@@ -1440,7 +1487,7 @@ namespace mgamd
             ax[u] = xv[u] = xo[u] = bv[u] = dv[u] = T(0);
             if (i < total)
               {
-                if (MODE != MODE_INVDIAG && MODE != MODE_CHEB_FIRST && (is_cheb(MODE) || i >= n_tail))
+                if (MODE != MODE_INVDIAG && MODE != MODE_CHEB_FIRST && MODE != MODE_MASS && (is_cheb(MODE) || i >= n_tail))
                   {
                     if (FUSE_P && i < n_tail && NT_LOAD(&epi.xs_flag[i]))
                       { // x + P x_c as the owning fused brick left it: folded into x here, after every brick has gathered x
@@ -1450,7 +1497,7 @@ namespace mgamd
                     else
                       xv[u] = NT_LOAD(&epi.x[gi]);
                   }
-                ax[u] = i < n_tail ? tail_acc[i] : xv[u];
+                ax[u] = i < n_tail ? tail_acc[i] : xv[u]; // (MODE_MASS: x is not read and the rows of constrained DoFs are zero)
                 if (MODE == MODE_RESIDUAL || is_cheb(MODE))
                   bv[u] = NT_LOAD(&epi.b[gi]);
                 if (is_cheb(MODE))
@@ -1488,7 +1535,7 @@ namespace mgamd
                     else
                       xo[u] = x1;
                   }
-                if (MODE == MODE_VMULT)
+                if (MODE == MODE_VMULT || MODE == MODE_MASS)
                   NT_STORE(ax[u], &epi.out[gi]);
                 else if (MODE == MODE_RESIDUAL)
                   NT_STORE(bv[u] - ax[u], &epi.out[gi]);

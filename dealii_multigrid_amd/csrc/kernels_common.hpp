@@ -1,6 +1,6 @@
 // Shared pieces of the HIP kernels (overview: kernels.hpp): non-temporal access macros, XCD-contiguous work mapping, the 1D
 // reference matrices (Mats) and lattice geometry (Geo), argument structs, 1D line products (dense and even-odd), the three lattice
-// sweeps (whole lines, streamed, segment tasks), hanging-node and brick-constraint passes, the 1D h-embedding.
+// sweeps (whole lines, streamed, segment tasks) and their mass-only form, hanging-node and brick-constraint passes, the 1D h-embedding.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -130,8 +130,11 @@ namespace mgamd
     // every other kernel of such a pass runs the base mode):
     MODE_RESIDUAL_RESTRICT = 6, // MODE_RESIDUAL; bricks flagged as fused restrict their part of b - A x into the coarse defect
                                 // (interior rows complete, shell rows as partial sums) instead of storing it
-    MODE_CHEB_PROLONGATE = 7    // MODE_CHEB (x_old = 0: first pass of a smoothing step) on x + P x_c: fused bricks add the
+    MODE_CHEB_PROLONGATE = 7,   // MODE_CHEB (x_old = 0: first pass of a smoothing step) on x + P x_c: fused bricks add the
                                 // coarse correction on their lattice while gathering x and store x + P x_c once
+    // the MASS matrix of the level's space instead of the operator: gather, constraint passes, scatter and launches are the
+    // operator's own, the sweeps are mass_sweeps, and the rows of constrained DoFs are ZERO (tail_kernel), not identity
+    MODE_MASS = 8 // out = C^T M C x
   };
   constexpr int
   base_mode(int mode)
@@ -763,6 +766,196 @@ namespace mgamd
               bufA[base + i] = h * o2[i];
         }
     slot_sync<WAVE>();
+  }
+
+  // ---- The MASS form of the sweeps (MODE_MASS): the cell's mass matrix is h^3 M (x) M (x) M, so the pass is three 1D mass
+  // products in place on ONE lattice, z, y, x, the last one scaled by h^3: half of lattice_sweeps' six products and none of its
+  // second lattice.  The line forms are the M-only variants of the four above (whole lines, streamed lines, segment tasks; the
+  // 2x2x2 product of the cell clusters is in cell_cluster_body); lines, rounds, segments and barriers are lattice_sweeps' own.
+  // out = M a
+  template <typename T, int P, int B>
+  __device__ __forceinline__ void
+  line_M(const Mats<P, T> &m, const T (&a)[P * B + 1], T (&out)[P * B + 1])
+  {
+    if constexpr (P < 4)
+      {
+        line_mult<T, P, B>(m.M, a, out);
+        return;
+      }
+#pragma unroll
+    for (int i = 0; i < P * B + 1; ++i)
+      out[i] = T(0);
+#pragma unroll
+    for (int c = 0; c < B; ++c)
+      {
+        EvenOdd<T, P> xa, y;
+        xa.split(&a[c * P]);
+        y.template apply<false>(m.Me, m.Mo, xa);
+        y.add_to(&out[c * P]);
+      }
+  }
+  // one lattice line in place, cell by cell (line_stream): A <- scale M a
+  template <typename T, int P, int B, bool PREFETCH>
+  __device__ __forceinline__ void
+  line_stream_M(const Mats<P, T> &m, T *__restrict__ A, const int stride, const T scale)
+  {
+    constexpr int n = P + 1;
+    T             a[n], an[n], c1 = T(0);
+    a[0] = A[0];
+    if (PREFETCH)
+      {
+#pragma unroll
+        for (int j = 1; j < n; ++j)
+          a[j] = A[j * stride];
+      }
+#pragma unroll
+    for (int c = 0; c < B; ++c)
+      {
+        if (!PREFETCH)
+          {
+#pragma unroll
+            for (int j = 1; j < n; ++j)
+              a[j] = A[(c * P + j) * stride];
+          }
+        else if (c + 1 < B)
+          {
+#pragma unroll
+            for (int j = 1; j < n; ++j)
+              an[j] = A[((c + 1) * P + j) * stride];
+          }
+        T o1[n];
+#pragma unroll
+        for (int i = 0; i < n; ++i)
+          o1[i] = T(0);
+        if constexpr (P < 4)
+          {
+#pragma unroll
+            for (int i = 0; i < n; ++i)
+#pragma unroll
+              for (int j = 0; j < n; ++j)
+                o1[i] += T(m.M[i * n + j]) * a[j];
+          }
+        else
+          {
+            EvenOdd<T, P> xa, y;
+            xa.split(a);
+            y.template apply<false>(m.Me, m.Mo, xa);
+            y.add_to(o1);
+          }
+        o1[0] += c1;
+#pragma unroll
+        for (int j = 0; j < P; ++j)
+          A[(c * P + j) * stride] = scale * o1[j];
+        c1   = o1[P];
+        a[0] = a[P];
+        if (PREFETCH)
+          {
+#pragma unroll
+            for (int j = 1; j < n; ++j)
+              a[j] = an[j];
+          }
+      }
+    A[P * B * stride] = scale * c1;
+  }
+  // segment task (seg_products): o = M a on the 5 own nodes.   a: [P left nodes | 5 own nodes]
+  template <typename T, int P>
+  __device__ __forceinline__ void
+  seg_products_M(const Mats<P, T> &m, const T (&a)[P + 5], const bool has_left, T (&o)[5])
+  {
+    static_assert(4 % P == 0, "segments of 5 nodes need P in {1, 2, 4}");
+    constexpr int CPS = 4 / P; // cells per segment
+    T             oa[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+      oa[i] = a[P + i];
+    line_M<T, P, CPS>(m, oa, o);
+    // left cell [4 s - P, 4 s]: its last row acts on node 4 s
+    T l = T(0);
+#pragma unroll
+    for (int j = 0; j <= P; ++j)
+      l += T(m.M[P * (P + 1) + j]) * a[j];
+    if (has_left)
+      o[0] += l;
+  }
+  // one of the three mass sweeps: direction D = 2 (z), 1 (y), 0 (x); the lines of the workgroup are lattice_sweeps'.  x scales by h^3.
+  template <typename T, int P, int B, int BLOCK, int D, bool STREAMED, bool PREFETCH, bool WAVE>
+  __device__ __forceinline__ void
+  mass_sweep(T *__restrict__ buf, const Mats<P, T> &m, const int tid, const int nslots, const double *__restrict__ hslot, const bool h_is_mine)
+  {
+    using G                 = Geo<P, B, WAVE ? 64 : 256>;
+    constexpr int  N        = G::N;
+    constexpr int  N3       = G::N3;
+    constexpr int  TOT      = G::SPW * G::LINES;
+    constexpr bool SEGMENTS = N == 17 && G::SPW == 1 && TOT > BLOCK && 4 * (TOT - BLOCK) <= BLOCK && (4 % P == 0);
+    constexpr int  ROUNDS   = SEGMENTS ? 1 : (TOT + BLOCK - 1) / BLOCK;
+    constexpr int  NSEG     = SEGMENTS ? 4 * (TOT - BLOCK) : 0;
+    // line (u, v): z lines (x = u, y = v), y lines (x = u, z = v), x lines (y = u, z = v)
+    constexpr int STRIDE = D == 2 ? N * N : (D == 1 ? N : 1);
+    constexpr int SU = D == 0 ? N : 1, SV = D == 2 ? N : N * N;
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r)
+      {
+        const int l = tid + r * BLOCK, sl = l / G::LINES, ln = l % G::LINES, u = ln % N, v = ln / N;
+        if (l < TOT && sl < nslots)
+          {
+            T scale = T(1);
+            if (D == 0)
+              {
+                const T h = T(h_is_mine ? hslot[0] : hslot[sl]);
+                scale     = h * h * h;
+              }
+            const int base = sl * N3 + v * SV + u * SU;
+            if constexpr (STREAMED)
+              line_stream_M<T, P, B, PREFETCH>(m, buf + base, STRIDE, scale);
+            else
+              {
+                T r0[N], r1[N];
+#pragma unroll
+                for (int i = 0; i < N; ++i)
+                  r0[i] = buf[base + i * STRIDE];
+                line_M<T, P, B>(m, r0, r1);
+#pragma unroll
+                for (int i = 0; i < N; ++i)
+                  buf[base + i * STRIDE] = D == 0 ? scale * r1[i] : r1[i];
+              }
+          }
+      }
+    if constexpr (SEGMENTS)
+      {
+        // segment task of this thread: line BLOCK + tid / 4, segment tid % 4 (in place: see the segment tasks above)
+        const int sg_l = BLOCK + (tid >> 2), sg_s = tid & 3, sg_u = sg_l % N, sg_v = sg_l / N;
+        if (tid < NSEG)
+          {
+            T scale = T(1);
+            if (D == 0)
+              {
+                const T h = T(hslot[0]);
+                scale     = h * h * h;
+              }
+            const int base = sg_v * SV + sg_u * SU + 4 * sg_s * STRIDE;
+            T         a[P + 5], o[5];
+#pragma unroll
+            for (int i = 0; i < P + 5; ++i)
+              a[i] = (sg_s > 0 || i >= P) ? buf[base + (i - P) * STRIDE] : T(0);
+            seg_fence();
+            seg_products_M<T, P>(m, a, sg_s > 0, o);
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+              if (i < 4 || sg_s == 3)
+                buf[base + i * STRIDE] = D == 0 ? scale * o[i] : o[i];
+          }
+      }
+    slot_sync<WAVE>();
+  }
+  // buf <- h^3 (Mx My Mz) buf on every slot of the workgroup.  Ends with a barrier.
+  template <typename T, int P, int B, int BLOCK, bool STREAMED = false, bool PREFETCH = false, bool WAVE = false>
+  __device__ __forceinline__ void
+  mass_sweeps(T *__restrict__ buf, const Mats<P, T> &m, const int tid, const int nslots, const double *__restrict__ hslot,
+              const bool h_is_mine = false)
+  {
+    mass_sweep<T, P, B, BLOCK, 2, STREAMED, PREFETCH, WAVE>(buf, m, tid, nslots, hslot, h_is_mine);
+    mass_sweep<T, P, B, BLOCK, 1, STREAMED, PREFETCH, WAVE>(buf, m, tid, nslots, hslot, h_is_mine);
+    mass_sweep<T, P, B, BLOCK, 0, STREAMED, PREFETCH, WAVE>(buf, m, tid, nslots, hslot, h_is_mine);
   }
 
   // In-cell hanging-node interpolation (transpose = false, before the sweeps) or its transpose

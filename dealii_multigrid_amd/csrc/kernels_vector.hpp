@@ -106,6 +106,37 @@ namespace mgamd
       y[i] = a * d[i] * b[i];
   }
 
+  // The theta time stepper's own vector updates (runtime.hip, ThetaStepper); element-wise.
+  // n_free = the first constrained DoF: the entries [n_free, n) are Dirichlet and hanging DoFs.
+  // w = theta f_new + (1 - theta) f_old + sigma u;   f_new == nullptr: w = sigma u
+  template <typename T>
+  __global__ void
+  __launch_bounds__(256) theta_source_kernel(T *__restrict__ w, const T *__restrict__ u, const T *__restrict__ f_old,
+                                             const T *__restrict__ f_new, T theta, T sigma, size_t n)
+  {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+      w[i] = f_new ? theta * f_new[i] + (T(1) - theta) * f_old[i] + sigma * u[i] : sigma * u[i];
+  }
+  // r <- r / theta on the free DoFs, 0 on the constrained ones (the residual pass leaves -u there: identity rows)
+  template <typename T>
+  __global__ void
+  __launch_bounds__(256) theta_rhs_kernel(T *__restrict__ r, T theta, size_t n_free, size_t n)
+  {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+      r[i] = i < n_free ? r[i] / theta : T(0);
+  }
+  // u <- u + delta on the free DoFs, 0 on the constrained ones
+  template <typename T>
+  __global__ void
+  __launch_bounds__(256) theta_update_kernel(T *__restrict__ u, const T *__restrict__ delta, size_t n_free, size_t n)
+  {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+      u[i] = i < n_free ? u[i] + delta[i] : T(0);
+  }
+
   __device__ __forceinline__ double
   wave_reduce_sum(double v)
   {

@@ -133,11 +133,15 @@ namespace mgamd
       // one-slot-per-workgroup lattices (17^3): persistent workgroups with a software pipeline over their slots
       // (kernels.hpp, lattice_apply_persistent_body).  Two workgroups fit a CU (LDS); the grid is a multiple of 8 so
       // that a workgroup stays inside the Morton range of its XCD.
-      // (the mass term is compiled in or out of these kernels: kernels.hpp, lattice_apply_persistent_body)
-      launch_persistent(ctx, st,
-                        a.sigma != 0.0 ? lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, true> :
-                                         lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, false>,
-                        grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
+      // (the mass term is compiled in or out of these kernels: kernels.hpp, lattice_apply_persistent_body; the mass PASS has no
+      // such term and one form)
+      {
+        void (*kern)(ApplyArgs<T, P>) = lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, false>;
+        if constexpr (MODE != MODE_MASS)
+          if (a.sigma != 0.0)
+            kern = lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, true>;
+        launch_persistent(ctx, st, kern, grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
+      }
     else
       launch_lds(ctx, st, lattice_apply_kernel<T, P, B, MODE, CONSTR>, grid, G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
     HIP_CHECK(hipGetLastError());
@@ -548,14 +552,14 @@ namespace mgamd
     }
 
     // the clusters that hold the cells [begin, end) of g
-    template <int P>
+    template <int P, bool MASS_ONLY = false>
     void
     launch_clusters(hipStream_t st, const GroupDev<T> &g, const ApplyArgs<T, P> &a, bool first, size_t begin, size_t end)
     {
       ClusterArgs<T> c    = cluster_args(g, a, first);
       c.cluster_offset    = (uint32_t)(begin / CLUSTER_CELLS);
       const uint32_t grid = (uint32_t)((end + CLUSTER_CELLS - 1) / CLUSTER_CELLS) - c.cluster_offset;
-      hipLaunchKernelGGL(cell_cluster_apply_kernel<T>, grid, CLUSTER_CELLS, g.cluster_lds_bytes(), st, c);
+      hipLaunchKernelGGL((MASS_ONLY ? cell_cluster_mass_kernel<T> : cell_cluster_apply_kernel<T>), grid, CLUSTER_CELLS, g.cluster_lds_bytes(), st, c);
       HIP_CHECK(hipGetLastError());
     }
 
@@ -574,10 +578,11 @@ namespace mgamd
         {
           if (n_wg > resident_workgroups(ctx))
             pa.n_wg_plain = 0; // every workgroup walks both kinds (kernels.hpp)
-          launch_persistent(ctx, st,
-                            a.sigma != 0.0 ? lattice_apply_persistent_pair_kernel<T, P, B, MODE, true> :
-                                             lattice_apply_persistent_pair_kernel<T, P, B, MODE, false>,
-                            n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
+          void (*kern)(BrickPairArgs<T, P>) = lattice_apply_persistent_pair_kernel<T, P, B, MODE, false>;
+          if constexpr (MODE != MODE_MASS) // (launch_lattice)
+            if (a.sigma != 0.0)
+              kern = lattice_apply_persistent_pair_kernel<T, P, B, MODE, true>;
+          launch_persistent(ctx, st, kern, n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
         }
       else if constexpr (MODE != base_mode(MODE))
         throw std::runtime_error("fused transfers need the persistent brick kernel");
@@ -658,7 +663,8 @@ namespace mgamd
       constexpr size_t lds      = small_slots_lds_bytes<T, P>();
       static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit the launch has to go through launch_lds");
       // (kernels.hpp: MASS = false exists only where the kernel has no room for a run-time sigma; elsewhere both names are one kernel)
-      constexpr bool laplace_form = !small_slots_mass_compiled<T, P>();
+      // (the mass pass has no mass term either way: the one name)
+      constexpr bool laplace_form = !small_slots_mass_compiled<T, P>() || MODE == MODE_MASS;
       hipLaunchKernelGGL((a.sigma == 0.0 ? lattice_apply_small_kernel<T, P, MODE, laplace_form> : lattice_apply_small_kernel<T, P, MODE, true>),
                          sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
       HIP_CHECK(hipGetLastError());
@@ -708,7 +714,7 @@ namespace mgamd
               launch_bricks_and_clusters<MODE>(st, a, *s.partner);
             break;
           case K::CLUSTERS:
-            launch_clusters(st, *g, a, MODE == MODE_CHEB_FIRST, s.begin, s.end);
+            launch_clusters<P, MODE == MODE_MASS>(st, *g, a, MODE == MODE_CHEB_FIRST, s.begin, s.end);
             break;
         }
     }
@@ -917,6 +923,28 @@ namespace mgamd
       if (dst.data == src.data)
         throw std::invalid_argument("vmult: dst and src must differ");
       vmult_raw(dst.as<T>(), src.as<T>());
+    }
+
+    // dst = C^T M C src: the mass matrix of the level's space (kernels.hpp MODE_MASS); rows and columns of constrained DoFs are
+    // zero, and sigma plays no role
+    void
+    vmult_mass_raw(T *dst, const T *src)
+    {
+      if (tables->ls_level)
+        throw std::invalid_argument("vmult_mass: the operator of a local-smoothing level has refinement-edge DoFs, for which the mass "
+                                    "matrix is not defined; use the active-mesh operator");
+      Epilogue<T> e{dst, src, nullptr, nullptr, nullptr, T(0), T(0), T(0)};
+      apply<MODE_MASS>(src, e);
+    }
+    void
+    vmult_mass(mgamd_vec &dst, const mgamd_vec &src) override
+    {
+      if (dst.n != n_dofs() || src.n != n_dofs())
+        throw std::invalid_argument("vmult_mass: vector size mismatch (" + std::to_string(dst.n) + ", " + std::to_string(src.n) +
+                                    " for " + std::to_string(n_dofs()) + " DoFs)");
+      if (dst.data == src.data)
+        throw std::invalid_argument("vmult_mass: dst and src must differ");
+      vmult_mass_raw(dst.as<T>(), src.as<T>());
     }
 
     size_t

@@ -608,6 +608,12 @@ namespace mgamd
     {
       check(mgamd_level_op_vmult(h.get(), dst.get(), src.get()));
     }
+    // dst = C^T M C src: the mass matrix of this operator's space, zero rows and columns on constrained DoFs (mgamd_level_op_vmult_mass)
+    void
+    vmult_mass(Vector &dst, const Vector &src) const
+    {
+      check(mgamd_level_op_vmult_mass(h.get(), dst.get(), src.get()));
+    }
     void
     Tvmult(Vector &dst, const Vector &src) const
     {
@@ -1089,5 +1095,65 @@ namespace mgamd
 
   private:
     ReductionControl &control;
+  };
+
+  // theta-scheme for the heat equation M u' + K u = M f with constant step dt (mgamd_time_stepper): A is the operator K + sigma M
+  // with sigma = mass_coefficient(theta, dt) on every level of its hierarchy (LevelStack's mass_coefficient), mg its multigrid.
+  // Both must outlive the stepper.
+  class ThetaTimeStepper
+  {
+  public:
+    ThetaTimeStepper(const Operator &A, const PreconditionMG &mg, double theta, double dt)
+    {
+      mgamd_time_stepper *t = nullptr;
+      check(mgamd_time_stepper_create(A.get(), mg.get(), theta, dt, &t));
+      h.reset(t, mgamd_time_stepper_destroy);
+    }
+    // sigma = 1 / (theta dt)
+    static double
+    mass_coefficient(double theta, double dt)
+    {
+      return 1.0 / (theta * dt);
+    }
+    // one step without a source, u in place; returns the CG iterations of the increment
+    unsigned
+    step(Vector &u, double reltol, double abstol = 1e-20, unsigned maxiter = 10000)
+    {
+      unsigned it = 0;
+      check(mgamd_time_stepper_step(h.get(), u.get(), nullptr, nullptr, reltol, abstol, maxiter, &it, &residual));
+      return it;
+    }
+    // one step with the nodal source values at t (f_old) and t + dt (f_new)
+    unsigned
+    step(Vector &u, const Vector &f_old, const Vector &f_new, double reltol, double abstol = 1e-20, unsigned maxiter = 10000)
+    {
+      unsigned it = 0;
+      check(mgamd_time_stepper_step(h.get(), u.get(), f_old.get(), f_new.get(), reltol, abstol, maxiter, &it, &residual));
+      return it;
+    }
+    double
+    time() const
+    {
+      double t = 0;
+      check(mgamd_time_stepper_time(h.get(), &t, nullptr));
+      return t;
+    }
+    uint64_t
+    n_steps() const
+    {
+      uint64_t n = 0;
+      check(mgamd_time_stepper_time(h.get(), nullptr, &n));
+      return n;
+    }
+    // residual norm of the last step's CG
+    double
+    last_residual() const
+    {
+      return residual;
+    }
+
+  private:
+    std::shared_ptr<mgamd_time_stepper> h;
+    double                              residual = 0;
   };
 } // namespace mgamd

@@ -2311,6 +2311,89 @@ namespace mgamd
   }
 
   // ------------------------------------------------------------------------------------------
+  // theta time stepper (runtime.hpp, ThetaStepperBase).  The outer solve is FP64, as in solve_cg.
+  // ------------------------------------------------------------------------------------------
+  struct ThetaStepper : ThetaStepperBase
+  {
+    LevelOperator<double>     *op;
+    MultigridBase             *M;
+    std::unique_ptr<mgamd_vec> g, h, d, Ad, delta; // the PCG's r, z, p, A p and x; d and Ad also hold t and w before the solve
+
+    ThetaStepper(LevelOperatorBase &A, MultigridBase *mg, double theta_, double dt_)
+      : M(mg)
+    {
+      theta = theta_;
+      dt    = dt_;
+      if (!(theta > 0.0 && theta <= 1.0) || !std::isfinite(theta))
+        throw std::invalid_argument("time stepper: theta = " + std::to_string(theta) + " is not in (0, 1]");
+      if (!(dt > 0.0) || !std::isfinite(dt))
+        throw std::invalid_argument("time stepper: dt = " + std::to_string(dt) + " is not a positive finite step");
+      if (A.type != MGAMD_F64)
+        throw std::invalid_argument("time stepper: the operator is not FP64 (the outer solve is FP64; FP32 belongs to the levels of the "
+                                    "multigrid)");
+      if (A.tables->ls_level)
+        throw std::invalid_argument("time stepper: the operator of a local-smoothing level has no mass matrix (vmult_mass)");
+      if (std::fabs(A.sigma * theta * dt - 1.0) > 1e-12)
+        {
+          char buf[256];
+          snprintf(buf, sizeof buf,
+                   "time stepper: the operator's mass coefficient sigma = %.17g is not 1 / (theta dt) for theta = %.17g, dt = %.17g "
+                   "(build the hierarchy with mass_coefficient(theta, dt))",
+                   A.sigma, theta, dt);
+          throw std::invalid_argument(buf);
+        }
+      op             = static_cast<LevelOperator<double> *>(&A);
+      const size_t n = A.n_dofs();
+      for (auto *v : {&g, &h, &d, &Ad, &delta})
+        v->reset(vec_create(A.ctx, n, MGAMD_F64));
+    }
+
+    void
+    step(mgamd_vec &u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol, double abstol, unsigned maxiter, unsigned &n_iterations,
+         double &residual) override
+    {
+      Ctx         *ctx = op->ctx;
+      const size_t n   = op->n_dofs();
+      if ((f_old == nullptr) != (f_new == nullptr))
+        throw std::invalid_argument("time stepper: exactly one of f_old / f_new is given (both, or neither for f = 0)");
+      for (const mgamd_vec *v : {(const mgamd_vec *)&u, f_old, f_new})
+        if (v && (v->n != n || v->type != MGAMD_F64))
+          throw std::invalid_argument("time stepper: a vector of " + std::to_string(v->n) + " entries of " + std::to_string(v->type) +
+                                      " bytes where the operator has " + std::to_string(n) + " FP64 DoFs");
+      const size_t n_free = (size_t)op->tables->n_interior + op->tables->n_tail; // the constrained DoFs are numbered last
+      const size_t nd     = op->comm ? (size_t)op->tables->n_interior + op->tables->n_tail_owned : n;
+      const int    grid   = grid_for(n);
+      double      *up     = u.as<double>();
+      hipLaunchKernelGGL(theta_source_kernel<double>, grid, 256, 0, ctx->stream, Ad->as<double>(), up, f_old ? f_old->as<double>() : nullptr,
+                         f_new ? f_new->as<double>() : nullptr, theta, op->sigma, n);
+      op->vmult_mass_raw(d->as<double>(), Ad->as<double>());
+      op->residual_raw(g->as<double>(), d->as<double>(), up);
+      hipLaunchKernelGGL(theta_rhs_kernel<double>, grid, 256, 0, ctx->stream, g->as<double>(), theta, n_free, n);
+      device_pcg<double>(
+        ctx, op->comm.get(), ctx->d_cg, n, nd, delta->as<double>(), g->as<double>(), h->as<double>(), d->as<double>(), Ad->as<double>(),
+        [&](double *Ap, const double *p) { op->vmult_raw(Ap, p); },
+        [&](double *, const double *) {
+          if (M)
+            M->vcycle(*h, *g);
+          else
+            vec_copy(*h, *g);
+        },
+        reltol, abstol, maxiter, n_iterations, residual);
+      hipLaunchKernelGGL(theta_update_kernel<double>, grid, 256, 0, ctx->stream, up, delta->as<double>(), n_free, n);
+      HIP_CHECK(hipGetLastError());
+      ctx->sync();
+      t += dt;
+      ++n_steps;
+    }
+  };
+
+  ThetaStepperBase *
+  make_theta_stepper(LevelOperatorBase &A, MultigridBase *M, double theta, double dt)
+  {
+    return new ThetaStepper(A, M, theta, dt);
+  }
+
+  // ------------------------------------------------------------------------------------------
   // Type "AMG": SolverCG on the assembled system matrix, preconditioned by the AMG built on it (solve_with_amg,
   // ref:multigrid_throughput.cc:1877-1966).  The matrix lives once on the device: the operator's products and level 0 of the
   // cycle read the same arrays.  Rows of the fine-level matrix at degree 2-4 hold hundreds of entries: K8 above

@@ -194,6 +194,10 @@ namespace mgamd
     }
     virtual void
     vmult(mgamd_vec &dst, const mgamd_vec &src) = 0;
+    // dst = C^T M C src: the mass matrix of the level's space; rows and columns of constrained DoFs are zero (not on the
+    // operator of a local-smoothing level)
+    virtual void
+    vmult_mass(mgamd_vec &dst, const mgamd_vec &src) = 0;
     virtual void
     compute_inverse_diagonal(mgamd_vec &d) = 0;
     virtual void
@@ -332,6 +336,24 @@ namespace mgamd
   void
   solve_cg(LevelOperatorBase &A, MultigridBase *M, mgamd_vec &x, const mgamd_vec &b, double reltol, double abstol, unsigned maxiter,
            unsigned &n_iterations, double &residual);
+  // theta-scheme for  M u' + K u = M f  (homogeneous Dirichlet data, constraints eliminated) with constant step dt on the
+  // operator A = K + sigma M, sigma = 1 / (theta dt), and its multigrid.  One step, written for the increment delta = u_new - u:
+  //     w = theta f_new + (1 - theta) f_old + sigma u;   t = M w (vmult_mass);   r = t - A u (residual pass), 0 on constrained rows;
+  //     A delta = r / theta by solve_cg's device PCG from delta = 0 (reltol acts on the increment's residual);   u += delta
+  // Work vectors are allocated once, here; every launch goes to the context's stream; the host read-backs are the PCG's.
+  struct ThetaStepperBase
+  {
+    virtual ~ThetaStepperBase() = default;
+    double   theta = 1, dt = 0, t = 0;
+    uint64_t n_steps = 0;
+    // f_old, f_new: nodal source values at t and t + dt, both null for f = 0.  u is advanced in place; its constrained entries
+    // are not read and are 0 on return
+    virtual void
+    step(mgamd_vec &u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol, double abstol, unsigned maxiter, unsigned &n_iterations,
+         double &residual) = 0;
+  };
+  ThetaStepperBase *
+  make_theta_stepper(LevelOperatorBase &A, MultigridBase *M, double theta, double dt);
   // K7 (kernels_amg.hpp) as the AMG cycle launches it: lanes per row from the average row length, a grid of at most 4096 blocks
   // (grid-stride above); mode: SpmvMode; lanes 0 = csr_spmv_lanes
   int
@@ -402,6 +424,10 @@ struct mgamd_transfer2
 struct mgamd_mg
 {
   std::unique_ptr<mgamd::MultigridBase> mg;
+};
+struct mgamd_time_stepper
+{
+  std::unique_ptr<mgamd::ThetaStepperBase> ts;
 };
 struct mgamd_matrix
 {

@@ -302,6 +302,13 @@ int mgamd_level_op_mass_coefficient(const mgamd_level_op *op, double *sigma);
 int mgamd_level_op_init_vector(const mgamd_level_op *op, mgamd_vec **out);
 /* Operator::vmult: dst = A src, identity on constrained rows (ref:include/operator.h:152-183) */
 int mgamd_level_op_vmult(mgamd_level_op *op, mgamd_vec *dst, const mgamd_vec *src);
+/* dst = C^T M C src: the mass matrix of the level's space; rows and columns of constrained DoFs are zero.  The same launches as
+ * mgamd_level_op_vmult (one-rank and sharded) with three 1D mass products per lattice in place of the operator's six.  Entries of
+ * src on constrained DoFs (Dirichlet, hanging) are never read; the result does not depend on the operator's mass coefficient.
+ * M src is what a source f(t) contributes to a time step, the right-hand side of an L2 projection, and x^T M x the squared L2 norm.
+ * MGAMD_ERR_INVALID for dst == src, vectors of the wrong size or number type, and the operator of a local-smoothing level
+ * (mgamd_dofs_create_level); the active-mesh operator of a local-smoothing hierarchy is an ordinary operator and works. */
+int mgamd_level_op_vmult_mass(mgamd_level_op *op, mgamd_vec *dst, const mgamd_vec *src);
 /* Operator::compute_inverse_diagonal (ref:include/operator.h:228-242) */
 int mgamd_level_op_inverse_diagonal(mgamd_level_op *op, mgamd_vec *diagonal);
 /* Operator::rhs with f == 1, g == 0 (ref:include/operator.h:362-447) */
@@ -423,6 +430,32 @@ int mgamd_mg_time_vcycles(mgamd_mg *mg, mgamd_vec *z, const mgamd_vec *r, unsign
  * 1625-1635): solves A x = b from x = 0; returns last_step() and the final residual norm. */
 int mgamd_solve_cg(mgamd_level_op *A, mgamd_mg *preconditioner, mgamd_vec *x, const mgamd_vec *b, double reltol, double abstol,
                    unsigned maxiter, unsigned *n_iterations, double *residual_norm);
+
+/* -------------------------------------------------------------------------------------------
+ * theta-scheme for the heat equation  M u' + K u = M f  (homogeneous Dirichlet data, f a vector of nodal values) with constant
+ * step dt on the operator A = K + sigma M, sigma = 1 / (theta dt), and its multigrid; 0 < theta <= 1 (1: implicit Euler, 0.5:
+ * Crank-Nicolson).  The caller sets sigma on every level (mgamd_dofs_set_mass_coefficient) before building operators and
+ * multigrid.  One step solves for the increment delta = u_new - u:
+ *     w = theta f_new + (1 - theta) f_old + sigma u;   r = M w - A u, zero on constrained rows;   A delta = r / theta;   u += delta
+ * with mgamd_solve_cg's CG from delta = 0, so u is the initial guess and reltol acts on the residual of the INCREMENT.
+ * The stepper owns its work vectors (allocated at creation, none per step); all work is enqueued on the context's stream and the
+ * host read-backs are those of the CG.  Constrained entries of u are never read and are 0 on return: a vector that
+ * mgamd_level_op_distribute filled for output may be passed back in.  One rank or sharded (A and the multigrid distributed alike).
+ * MGAMD_ERR_INVALID, with the values in mgamd_last_error(): theta outside (0, 1], dt <= 0, NaN or infinity;
+ * |sigma theta dt - 1| > 1e-12 for A's mass coefficient sigma; an operator that is not MGAMD_F64 (the outer solve is FP64 as in
+ * mgamd_solve_cg; the levels of the multigrid may be FP32); a local-smoothing level operator; in a step: vectors of the wrong size
+ * or number type, exactly one of f_old / f_new.  A refused step changes neither u nor the time.
+ * The operator and the multigrid must outlive the stepper.  Changing dt or theta: new sigma, new operators, multigrid and stepper.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mgamd_time_stepper mgamd_time_stepper;
+int mgamd_time_stepper_create(mgamd_level_op *A, mgamd_mg *preconditioner, double theta, double dt, mgamd_time_stepper **out);
+/* one step in place; f_old / f_new: nodal source values at t and t + dt, both NULL for f = 0; n_iterations, residual_norm: of the
+ * CG for the increment (may be NULL) */
+int mgamd_time_stepper_step(mgamd_time_stepper *ts, mgamd_vec *u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol,
+                            double abstol, unsigned maxiter, unsigned *n_iterations, double *residual_norm);
+/* the time reached (n_steps dt, starting at 0) and the number of steps taken; either may be NULL */
+int  mgamd_time_stepper_time(const mgamd_time_stepper *ts, double *t, uint64_t *n_steps);
+void mgamd_time_stepper_destroy(mgamd_time_stepper *ts);
 
 /* ---------------------------------------------------------------------------------------------
  * Type "AMG" / "AMGPETSc": CG on the assembled system matrix with an AMG preconditioner built on it (solve_with_amg,
