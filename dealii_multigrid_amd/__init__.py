@@ -129,18 +129,66 @@ class Triangulation:
         _chk(_lib.mgamd_tria_get_cells(self._h, _ptr(lev), _ptr(i), _ptr(j), _ptr(k), _ptr(mask)))
         return lev, i, j, k, mask
 
+    def cell_centres(self):
+        """the centres of the leaves in [-1, 1]^3, (n_cells, 3), in the order of cells()"""
+        lev, i, j, k, _ = self.cells()
+        h = 2.0 / (1 << lev.astype(np.int64))
+        return np.stack([-1.0 + h * (c.astype(np.float64) + 0.5) for c in (i, j, k)], axis=1)
+
+    def set_coefficient(self, values):
+        """the diffusion coefficient a > 0 of -div(a grad u) + sigma u, one value per leaf in the order of cells(); None resets to
+        a = 1.  coarsen() carries it down as the mean over each coarse leaf; DoFs copy it when they are built
+        (mgamd_tria_set_coefficient).  MgamdError for a value that is <= 0, NaN or infinite."""
+        if values is None:
+            _chk(_lib.mgamd_tria_set_coefficient(self._h, None))
+            return
+        a = np.ascontiguousarray(values, np.float64)
+        if a.shape != (self.n_cells,):
+            raise ValueError(f"set_coefficient: {a.shape} values for {self.n_cells} cells")
+        _chk(_lib.mgamd_tria_set_coefficient(self._h, _ptr(a)))
+
+    def set_coefficient_function(self, f):
+        """set_coefficient with f(x, y, z) evaluated at the leaf centres (arrays in, array out)"""
+        c = self.cell_centres()
+        self.set_coefficient(np.broadcast_to(np.asarray(f(c[:, 0], c[:, 1], c[:, 2]), np.float64), (self.n_cells,)))
+
+    def coefficient(self):
+        """one value per leaf (ones if none is set)"""
+        a = np.zeros(self.n_cells, np.float64)
+        _chk(_lib.mgamd_tria_get_coefficient(self._h, _ptr(a)))
+        return a
+
+    def has_coefficient(self) -> bool:
+        has = C.c_int()
+        _chk(_lib.mgamd_tria_has_coefficient(self._h, C.byref(has)))
+        return bool(has.value)
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mgamd_tria_destroy(self._h)
             self._h = None
 
 
-def create_geometric_coarsening_sequence(fine: Triangulation):
-    """MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence: coarsest first."""
+def create_geometric_coarsening_sequence(fine: Triangulation, coarse_coefficient=None):
+    """MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence: coarsest first.  A diffusion coefficient on `fine`
+    goes down mesh by mesh (Triangulation.coarsen: the mean over each coarse leaf); coarse_coefficient(tria) -> values, if given,
+    overwrites every coarse mesh's values as soon as it exists (e.g. with a harmonic mean)."""
     seq = [fine]
     while seq[-1].n_cells > 1:
         seq.append(seq[-1].coarsen())
+        if coarse_coefficient is not None:
+            seq[-1].set_coefficient(coarse_coefficient(seq[-1]))
     return seq[::-1]
+
+
+def _apply_coefficient(fine: Triangulation, coefficient):
+    """Hierarchy(coefficient=...): a function f(x, y, z) of the leaf centres or one value per leaf of the finest mesh"""
+    if coefficient is None:
+        return
+    if callable(coefficient):
+        fine.set_coefficient_function(coefficient)
+    else:
+        fine.set_coefficient(coefficient)
 
 
 def create_polynomial_coarsening_sequence(degree: int):
@@ -212,6 +260,12 @@ class DoFs:
         s = C.c_double()
         _chk(_lib.mgamd_dofs_mass_coefficient(self._h, C.byref(s)))
         return s.value
+
+    def coefficient_range(self):
+        """(min, max) of the diffusion coefficient these DoFs were built with (their mesh's at that time)"""
+        lo, hi = C.c_double(), C.c_double()
+        _chk(_lib.mgamd_dofs_coefficient_range(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
 
     def keys(self):
         k = np.zeros((self.n_dofs, 5), np.int32)
@@ -986,13 +1040,26 @@ class Hierarchy:
 
     def __init__(self, ctx: Context, geometry="quadrant", n_ref_global=3, degree=1, mg_type="HMG-global", n_ref_local=0,
                  smoother_degree=3, smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64,
-                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0):
+                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0, coefficient=None, coarse_coefficient=None):
         """mass_coefficient: sigma >= 0 of the operator K + sigma M (-Laplace u + sigma u) on every level, the stand-in and nested
-        hierarchies included; the local-smoothing types refuse a non-zero value"""
+        hierarchies included; the local-smoothing types refuse a non-zero value
+        coefficient: the diffusion coefficient a of -div(a grad u) + sigma u: f(x, y, z), evaluated at the leaf centres of the
+        finest mesh before the coarsening sequence is built, or one value per leaf; None keeps what the mesh carries (a = 1 for
+        a named geometry).  If `geometry` is a Triangulation of the caller's, the values are SET ON IT (Triangulation.set_coefficient):
+        the mesh is the carrier of the coefficient, and the caller's object shows them afterwards.
+        coarse_coefficient: g(tria) -> values, called for every coarse mesh of the coarsening sequence in place of the mean over each
+        leaf (create_geometric_coarsening_sequence); refused for the types without coarse meshes (PMG, HPMG-local, AMG, AMGPETSc),
+        where it would have no effect.  The local-smoothing types refuse a coefficient."""
         self.ctx = ctx
         self.mass_coefficient = mass_coefficient
         # `geometry` may also be a caller-built Triangulation (Triangulation.from_leaves)
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global, n_ref_local)
+        if mg_type in ("HMG-local", "HPMG-local") and (coefficient is not None or fine.has_coefficient()):
+            raise MgamdError(f"Type '{mg_type}' with a diffusion coefficient: not implemented (local smoothing: the refinement-edge "
+                             "matrices have no coefficient)")
+        if coarse_coefficient is not None and mg_type not in ("HMG-global", "HPMG"):
+            raise MgamdError(f"Type '{mg_type}' has no coarse meshes: coarse_coefficient would have no effect")
+        _apply_coefficient(fine, coefficient)
         if mg_type in ("AMG", "AMGPETSc"):
             # solve_with_amg (ref:multigrid_throughput.cc:1877-1966): no multigrid levels; CG on the assembled matrix of the one
             # level with the AMG built on it: solve_cg(h.system_matrix, h.amg, x, b).  FP64 whatever number_type says, as in the
@@ -1011,7 +1078,7 @@ class Hierarchy:
             self._build_local_smoothing(ctx, fine, degree, smoother, coarse_solver, number_type, max_brick)
             return
         # the meshes the levels live on: the coarsening sequence of the h-levels; the p-levels of PMG and HPMG-local need the one mesh
-        meshes = create_geometric_coarsening_sequence(fine) if mg_type in ("HMG-global", "HPMG") else [fine]
+        meshes = create_geometric_coarsening_sequence(fine, coarse_coefficient) if mg_type in ("HMG-global", "HPMG") else [fine]
         plan, _ = _level_plan(mg_type, len(meshes), degree)
         first_dofs, nested = None, None
         if mg_type == "HPMG-local":
@@ -1066,15 +1133,18 @@ class DistributedHierarchy:
                  smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64, hanging_weight=2.0, max_brick=-1,
                  min_root_dofs=MIN_ROOT_DOFS_DEFAULT, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None,
                  min_subset_dofs=MIN_SUBSET_DOFS_DEFAULT, sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT,
-                 mass_coefficient=0.0):
-        """sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
+                 mass_coefficient=0.0, coefficient=None, coarse_coefficient=None):
+        """coefficient, coarse_coefficient: the diffusion coefficient, as for Hierarchy (every rank passes the same; set on the
+        caller's Triangulation if one is passed; the coarsening sequence exists for every type here, so coarse_coefficient always acts)
+        sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
         smoothed-aggregation AMG cut into rows over the ranks (replicated setup, sharded cycle; levels of at most
         amg_min_sharded_rows rows replicated) instead of the geometric stand-in "gmg_vcycle".  Off by default."""
         self.ctx, self.comm = ctx, comm
         if mg_type not in ("HMG-global", "PMG", "HPMG"):
             raise MgamdError(f"Type '{mg_type}' not implemented")
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global)
-        self.mesh_sequence = create_geometric_coarsening_sequence(fine)
+        _apply_coefficient(fine, coefficient)
+        self.mesh_sequence = create_geometric_coarsening_sequence(fine, coarse_coefficient)
         # (mesh index, degree) of every multigrid level, coarse -> fine (ref:multigrid_throughput.cc:1506-1571)
         self.plan, _ = _level_plan(mg_type, len(self.mesh_sequence), degree)
         # levels below ~4 M DoFs stay replicated: their single-GPU time (latency-bound: 0.34 ms for 2.3 M DoFs at p=4, 0.33 ms for

@@ -186,11 +186,12 @@ namespace mgamd
           continue;
         const std::vector<double> &Ke = element_of(Kref, cache, L.tria->masks[ci]);
         const double               h  = 2.0 / (double)(1u << L.tria->cells[ci].level);
+        const double               ah = L.coefficient_of(ci) * h; // diffusion coefficient of the cell (LevelTables::coefficient)
         for (int i = 0; i < n3; ++i)
           if (idx[ci * n3 + i] != INVALID_DOF)
             for (int j = 0; j < n3; ++j)
               if (idx[ci * n3 + j] != INVALID_DOF)
-                at(idx[ci * n3 + i], idx[ci * n3 + j]) += h * Ke[(size_t)i * n3 + j];
+                at(idx[ci * n3 + i], idx[ci * n3 + j]) += ah * Ke[(size_t)i * n3 + j];
         if (sigma != 0.0)
           {
             const std::vector<double> &Me = element_of(Mref, cache_mass, L.tria->masks[ci]);

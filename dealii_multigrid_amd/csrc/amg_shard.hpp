@@ -74,6 +74,17 @@ namespace mgamd
     if (global.sigma != local_sigma)
       throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the mass coefficient " + std::to_string(global.sigma) +
                                   ", the local level " + std::to_string(local_sigma) + ": the assembled matrix would be another operator's");
+    // the same holds for the diffusion coefficient of the cells this rank works on
+    // (cell by cell: both tables must describe the same mesh; another mesh is refused here, before the keys are matched)
+    if (global.tria->cells.size() != local.tria->cells.size())
+      throw std::invalid_argument("sharded AMG: the global coarse DoFs live on a mesh of " + std::to_string(global.tria->cells.size()) +
+                                  " cells, the local level on one of " + std::to_string(local.tria->cells.size()) + ": not the same space");
+    if (!global.coefficient.empty() || !local.coefficient.empty())
+      for (size_t ci = 0; ci < local.tria->cells.size(); ++ci)
+        if (local.cell_is_local(ci) && global.coefficient_of(ci) != local.coefficient_of(ci))
+          throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the diffusion coefficient " +
+                                      std::to_string(global.coefficient_of(ci)) + " on cell " + std::to_string(ci) + ", the local level " +
+                                      std::to_string(local.coefficient_of(ci)) + ": the assembled matrix would be another operator's");
     std::vector<DofKey> kg, kl;
     global.export_dof_keys(kg);
     local.export_dof_keys(kl);

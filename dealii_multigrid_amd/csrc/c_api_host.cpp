@@ -479,6 +479,47 @@ mgamd_tria_get_cells(const mgamd_tria *t, uint8_t *level, uint32_t *i, uint32_t 
   MGAMD_CATCH
 }
 
+int
+mgamd_tria_set_coefficient(mgamd_tria *t, const double *a)
+{
+  MGAMD_TRY
+  if (!t)
+    throw std::invalid_argument("null argument");
+  t->tria->set_coefficient(a); // (refuses values that are not finite and > 0, by index)
+  MGAMD_CATCH
+}
+
+int
+mgamd_tria_get_coefficient(const mgamd_tria *t, double *a)
+{
+  MGAMD_TRY
+  if (!t || !a)
+    throw std::invalid_argument("null argument");
+  for (size_t n = 0; n < t->tria->cells.size(); ++n)
+    a[n] = t->tria->coefficient_of(n);
+  MGAMD_CATCH
+}
+
+int
+mgamd_tria_has_coefficient(const mgamd_tria *t, int *has)
+{
+  MGAMD_TRY
+  if (!t || !has)
+    throw std::invalid_argument("null argument");
+  *has = t->tria->coefficient.empty() ? 0 : 1;
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_coefficient_range(const mgamd_dofs *d, double *min, double *max)
+{
+  MGAMD_TRY
+  if (!d || !min || !max)
+    throw std::invalid_argument("null argument");
+  d->tables->coefficient_range(*min, *max);
+  MGAMD_CATCH
+}
+
 static size_t
 n_nonempty_groups(const LevelTables &L)
 {

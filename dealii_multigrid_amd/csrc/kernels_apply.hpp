@@ -66,8 +66,8 @@ namespace mgamd
   // workgroup-scoped kernel: 5-7 of the 9 us a workgroup lives are spent between those barriers).
   // NTHREADS: the threads of the workgroup if they are more than the lattice's own block (lattice_apply_small_kernel runs the
   // 13-point bricks of p = 6, whose 169 lines make a 192-thread block, in its 256-thread workgroups); 0: Geo's ABLOCK
-  // MASS = false compiles the mass term out (lattice_sweeps); only kernels whose register budget has no room for it come in
-  // both forms (small_slots_mass_compiled), every other caller leaves MASS = true and sigma decides at run time
+  // MASS = false compiles the mass term out (lattice_sweeps); the small-slot kernels come in both forms and the host picks by
+  // sigma != 0 (lattice_apply_small_kernel), every other caller leaves MASS = true and sigma decides at run time
   template <typename T, int P, int B, int MODE, bool CONSTR = false, bool WAVE = false, int NTHREADS = 0, bool MASS = true>
   __device__ __forceinline__ void
   lattice_apply_body(const ApplyArgs<T, P> &args, const uint32_t block, const uint32_t nblocks, unsigned char *smem_raw)
@@ -126,10 +126,9 @@ namespace mgamd
         for (int i = tid; i < nslots * P3; i += BLOCK)
           {
             const int t = i % P3, s2 = i / P3;
-            const T   hs = T(args.g.h[slot0 + s2]);
             T         s_K, s_M;
             interior_diag_terms<T, P>(args.m, t, s_K, s_M);
-            const T sv   = s_K + (T(args.sigma) * hs * hs) * s_M;
+            const T sv   = s_K + (T(args.sigma) * T(args.g.q[slot0 + s2])) * s_M;
             dtab[i]      = sv;
             dtab[TS + i] = T(1) / sv;
           }
@@ -301,7 +300,7 @@ namespace mgamd
         if constexpr (MODE == MODE_MASS) // three mass products on the first lattice; the second is not touched
           mass_sweeps<T, P, B, BLOCK, false, false, WAVE>(bufA, args.m, tid, nslots, &h_mine, true);
         else
-          lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE, MASS>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true, args.sigma);
+          lattice_sweeps<T, P, B, BLOCK, NoHook, false, false, WAVE, MASS>(bufA, bufB, args.m, tid, nslots, &h_mine, NoHook(), true, args.sigma, args.g.q + slot0);
       }
     MGAMD_STAMP(6)
 
@@ -556,7 +555,7 @@ namespace mgamd
         // formed from b on the fly (x_from_b), which takes one more barrier.  MASS = false: the table built above.
         if constexpr (MASS && is_cheb(MODE))
           {
-            const T c = T(args.sigma) * T(hcur) * T(hcur);
+            const T c = T(args.sigma) * T(args.g.q[slot]); // (h^2 / a is read where it is used: these kernels have no register to carry it)
             for (int t = tid; t < P3; t += BLOCK)
               {
                 T s_K, s_M;
@@ -698,7 +697,7 @@ namespace mgamd
           mass_sweeps<T, P, B, BLOCK, true, true, false>(bufA, args.m, tid, 1, &hcur, false);
         else
           lattice_sweeps<T, P, B, BLOCK, NoHook, true, (MODE != MODE_CHEB || sizeof(T) == 4), false, MASS>(
-            bufA, bufB, args.m, tid, 1, &hcur, NoHook(), false, args.sigma);
+            bufA, bufB, args.m, tid, 1, &hcur, NoHook(), false, args.sigma, args.g.q + slot);
         if constexpr (brick_may_be_constrained(B, CONSTR))
           if (any_hanging)
             brick_constraint_passes<T, P, B, BLOCK>(bufA, args.m, tid, 1, args.g.fmask + slot, true, &fmcur);
@@ -924,7 +923,7 @@ namespace mgamd
     extern __shared__ __align__(16) unsigned char smem_raw[];
     lattice_apply_body<T, P, B, MODE, CONSTR>(args, blockIdx.x, gridDim.x, smem_raw);
   }
-  template <typename T, int P, int MODE>
+  template <typename T, int P, int MODE, bool MASS = true>
   __device__ __forceinline__ void
   cell_waves_body(const ApplyArgs<T, P> &args, const uint32_t block, const uint32_t nblocks, unsigned char *smem_raw)
   {
@@ -933,7 +932,7 @@ namespace mgamd
     // workgroups in XCD-contiguous (Morton) ranges like every other kernel, the four wavefronts of one on neighbouring cells
     const uint32_t vb = xcd_contiguous(block, nblocks) * CELL_WAVES + wave;
     if (vb < n_w)
-      lattice_apply_body<T, P, 1, MODE, false, true>(args, vb, n_w, smem_raw + wave * cell_wave_lds<T, P>());
+      lattice_apply_body<T, P, 1, MODE, false, true, 0, MASS>(args, vb, n_w, smem_raw + wave * cell_wave_lds<T, P>());
   }
   template <typename T, int P, int MODE>
   __global__ void
@@ -1030,15 +1029,11 @@ namespace mgamd
     uint32_t        n_wg_bricks;
   };
   static_assert(sizeof(SmallSlotsArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "SmallSlotsArgs exceeds the kernel-argument segment");
-  // The float kernel of p = 7 sits at the 128 VGPRs of its four workgroups per CU: with a run-time sigma its Chebyshev mode
-  // spills (tools/kernel_resources.sh: 127 -> 128 VGPRs + 8 bytes of scratch), so that one comes with the mass term compiled in
-  // and compiled out (the brick half; the cells keep the run-time sigma) and the host picks by sigma != 0.
-  template <typename T, int P>
-  constexpr bool
-  small_slots_mass_compiled()
-  {
-    return sizeof(T) == 4 && P == 7;
-  }
+  // The kernel comes with the mass term compiled in and compiled out (MASS, both halves), for every degree and number type, and
+  // the host picks by sigma != 0 (launch_bricks_and_cells).  First the float kernel of p = 7, which sits at the 128 VGPRs of its
+  // four workgroups per CU and spilled with a run-time sigma; with the diffusion coefficient every degree: the mass term reads
+  // h^2 / a of the slot at the x sweep (lattice_sweeps), a load that the sigma = 0 cycle of the flagship paid with +0.2 ... +0.7 %
+  // per V-cycle when sigma was a run-time value here (DESIGN.md "Diffusion coefficient"); MASS = false never reads it.
   template <typename T, int P, int MODE, bool MASS = true>
   __global__ void
   __launch_bounds__(256, (small_slots_wgs_per_cu<T, P>())) lattice_apply_small_kernel(const SmallSlotsArgs<T, P> args)
@@ -1051,7 +1046,7 @@ namespace mgamd
         ApplyArgs<T, P> a = args.a;
         a.g               = args.g_cells;
         a.stamps          = nullptr;
-        cell_waves_body<T, P, MODE>(a, blockIdx.x - args.n_wg_bricks, gridDim.x - args.n_wg_bricks, smem_raw);
+        cell_waves_body<T, P, MODE, MASS>(a, blockIdx.x - args.n_wg_bricks, gridDim.x - args.n_wg_bricks, smem_raw);
       }
   }
 
@@ -1067,9 +1062,10 @@ namespace mgamd
     const uint32_t *uniq_idx; // global DoF index of every cluster-local node (ascending within a cluster)
     const uint16_t *loc;      // [n_slots * 8] cluster-local id of lattice node x + 2y + 4z; 0xFFFF = constrained (zero, no scatter)
     const uint16_t *mask;
-    const double   *h;
+    const double   *h; // the scale of the pass, as SlotGroupDev::h
     uint32_t        n_slots;
     uint32_t        max_uniq; // LDS: 2 * max_uniq values
+    const double   *q;        // h^2 / a, as SlotGroupDev::q
   };
   constexpr int CLUSTER_CELLS = 256;
   constexpr int CLUSTER_ITERS = 8; // 256 cells x 8 nodes / 256 threads: the worst case, nothing shared
@@ -1223,7 +1219,10 @@ namespace mgamd
     // three sweeps of the 2x2x2 lattice, as in lattice_sweeps
     const T M0 = T(a.m.M[0]), M1 = T(a.m.M[1]), M2 = T(a.m.M[2]), M3 = T(a.m.M[3]);
     const T K0 = T(a.m.K[0]), K1 = T(a.m.K[1]), K2 = T(a.m.K[2]), K3 = T(a.m.K[3]);
-    const T cm = T(a.sigma) * h * h; // sigma h^2: h (K a + M (b + c a)) adds sigma h^3 M (x) M (x) M
+    // sigma h^2 / a: (a h) (K x + M (b + c x)) adds sigma h^3 M (x) M (x) M  (MASS_ONLY: no mass term, h is the cell size)
+    T cm = T(0);
+    if (!MASS_ONLY && act && a.sigma != 0.0)
+      cm = T(a.sigma) * T(a.c.q[slot]);
     T       A[8], Bv[8];
     if constexpr (MASS_ONLY)
       { // three mass products of the 2x2x2 lattice in place (mass_sweeps): z, y, x; x scales by h^3
@@ -1356,10 +1355,11 @@ namespace mgamd
     const bool act = tid < G::SPW * G::LINES && sl < nslots;
 
     uint32_t mask = 0;
-    T        h    = T(0);
+    T        h    = T(0), q = T(0);
     if (act)
       {
-        h = T(args.g.h[slot0 + sl]);
+        h = T(args.g.h[slot0 + sl]); // a h
+        q = T(args.g.q[slot0 + sl]); // h^2 / a
         if (B == 1)
           mask = args.g.mask[slot0 + sl];
       }
@@ -1378,7 +1378,7 @@ namespace mgamd
               dM[c * P + a] += T(args.m.M[a * (P + 1) + a]);
               dK[c * P + a] += T(args.m.K[a * (P + 1) + a]);
             }
-        const T sh3 = T(args.sigma) * h * h * h; // d = h s_K + sigma h^3 s_M
+        const T sh3 = T(args.sigma) * q * h; // d = a h s_K + sigma h^3 s_M,  h^3 = (h^2 / a) (a h)
         T       mx = T(0), kx = T(0), my = T(0), ky = T(0);
 #pragma unroll
         for (int i = 0; i < G::N; ++i)
@@ -1410,7 +1410,7 @@ namespace mgamd
                 bufA[idx] = (idx % G::N3) == j ? T(1) : T(0);
               __syncthreads();
               hanging_passes<T, P>(bufA, args.m, sl, u, v, act, mask, false);
-              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0, NoHook(), false, args.sigma);
+              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0, NoHook(), false, args.sigma, args.g.q + slot0);
               hanging_passes<T, P>(bufA, args.m, sl, u, v, act, mask, true);
               if (act && ln == 0 && (mask >> 3))
                 bufD[sl * G::N3 + j] = bufA[sl * G::N3 + j];
@@ -1433,7 +1433,7 @@ namespace mgamd
                 bufA[idx] = (idx % G::N3) == j ? T(1) : T(0);
               __syncthreads();
               brick_constraint_passes<T, P, B, G::BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, false);
-              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0, NoHook(), false, args.sigma);
+              lattice_sweeps<T, P, B, G::BLOCK>(bufA, bufB, args.m, tid, nslots, args.g.h + slot0, NoHook(), false, args.sigma, args.g.q + slot0);
               brick_constraint_passes<T, P, B, G::BLOCK>(bufA, args.m, tid, nslots, args.g.fmask + slot0, true);
               if (act && ln == 0 && args.g.fmask[slot0 + sl])
                 bufD[sl * G::N3 + j] = bufA[sl * G::N3 + j];

@@ -111,10 +111,11 @@ namespace mgamd
     const uint32_t *interior_base;
     const uint32_t *shell_idx;
     const uint16_t *mask;
-    const double   *h;
+    const double   *h; // per slot: the scale of the pass: a h for the operator, the cell size h itself for MODE_MASS
     const uint16_t *shell_pos;
     uint32_t        n_slots;
     const uint32_t *fmask; // bricks: masks of the constrained ones (level_tables.hpp), nullptr if the group has none
+    const double   *q;     // per slot: h^2 / a, the factor of sigma in the mass term (lattice_sweeps)
   };
 
   enum ApplyMode
@@ -592,6 +593,12 @@ namespace mgamd
   // persistent kernel requests its epilogue operands there)
   // sigma: mass coefficient of  K + sigma M.  The cell's mass matrix is h^3 M (x) M (x) M and the x sweep forms
   // h (K a + M b) from a = My Mz u, b = (Ky Mz + My Kz) u, so the mass term is  b += c a  with c = sigma h^2 of the line's slot
+  // Diffusion coefficient a of the slot (DESIGN.md "Diffusion coefficient"): hslot holds the SCALE a h of the stiffness part and
+  // qslot the ratio q = h^2 / a, so the result is  (a h) (S_K x + (sigma q) S_M x)  and c = sigma q.  a = 1: hslot = h, q = h^2
+  // exactly (h is a power of two), so c has the bits of sigma h h.  qslot is indexed by the slot of the workgroup (never "mine")
+  // and only read under MASS with sigma != 0, at the x sweep: held from the gather on, it cost every non-persistent kernel
+  // two VGPRs and some of them an occupancy step or spilled VGPRs (DESIGN.md "Diffusion coefficient").  Kernels that cannot afford
+  // the load at sigma = 0 come with MASS = false as well (the persistent kernels, the small-slot kernels).
   // on the inputs of the x sweep: one multiply-add per lattice point, no further matrix, no further LDS traffic.  sigma = 0
   // leaves b as it is, bit for bit (b is a sum that started from +0, and +0 a is +0 or -0).
   // MASS = false compiles the term out: the persistent 17-point kernels, whose 5-word modes have no register left for c
@@ -600,8 +607,9 @@ namespace mgamd
             bool MASS = true>
   __device__ __forceinline__ void
   lattice_sweeps(T *__restrict__ bufA, T *__restrict__ bufB, const Mats<P, T> &m, int tid, int nslots, const double *__restrict__ hslot,
-                 const Hook &before_x = Hook(), const bool h_is_mine = false, // h_is_mine: hslot[0] is the h of THIS thread's line
-                 const double sigma = 0.0)
+                 const Hook &before_x, const bool h_is_mine, // h_is_mine: hslot[0] is the h of THIS thread's line
+                 const double sigma, const double *__restrict__ qslot) // qslot: h^2 / a of the workgroup's slots (no defaults: a
+                                                                       // caller that forgot them would drop the mass term)
   {
     using G              = Geo<P, B, WAVE ? 64 : 256>;
     constexpr int N      = G::N;
@@ -720,7 +728,7 @@ namespace mgamd
         if (l < TOT && sl < nslots)
           {
             const T   h    = T(h_is_mine ? hslot[0] : hslot[sl]);
-            const T   c    = MASS ? T(sigma) * h * h : T(0);
+            const T   c    = MASS ? T(sigma) * T(qslot[sl]) : T(0); // (read here, where it is used: no register held across the sweeps)
             const int base = sl * N3 + (v * N + u) * N;
             if constexpr (STREAM)
               line_stream<T, P, B, 2, PREFETCH, MASS>(m, bufA + base, bufB + base, 1, h, c);
@@ -743,7 +751,7 @@ namespace mgamd
       if (sg)
         {
           const T   h    = T(hslot[0]);
-          const T   c    = MASS ? T(sigma) * h * h : T(0);
+          const T   c    = MASS ? T(sigma) * T(qslot[0]) : T(0);
           const int base = (sg_v * N + sg_u) * N + 4 * sg_s;
           T         a[P + 5], b[P + 5], o1[5], o2[5];
 #pragma unroll

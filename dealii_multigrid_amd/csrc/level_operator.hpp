@@ -156,20 +156,44 @@ namespace mgamd
     size_t         n_slots = 0;
     DBuf<uint32_t> interior_base, shell_idx;
     DBuf<uint16_t> mask, shell_pos;
-    DBuf<double>   h;
+    // Per slot, with the slot's diffusion coefficient a (SlotGroup::a): the operator's scale a h, the mass term's factor
+    // h^2 / a, and the cell size h itself for the mass pass (MODE_MASS; only held where some a != 1, otherwise it is `h`).
+    DBuf<double>   h, q, h_cell;
     DBuf<uint32_t> fmask; // constrained 2^3 bricks, only if the group has any
-    SlotGroupDev
-    view() const
+    void
+    upload_scales(const SlotGroup &g)
     {
-      return SlotGroupDev{interior_base.p, shell_idx.p, mask.p, h.p, shell_pos.p, (uint32_t)n_slots, fmask.p};
+      std::vector<double> ah(g.h.size()), ratio(g.h.size());
+      bool                any = false;
+      for (size_t s = 0; s < g.h.size(); ++s)
+        {
+          ah[s]    = g.a[s] * g.h[s];
+          ratio[s] = g.h[s] * g.h[s] / g.a[s];
+          any |= g.a[s] != 1.0;
+        }
+      h.upload(ah);
+      q.upload(ratio);
+      if (any)
+        h_cell.upload(g.h);
+    }
+    // the scale of a pass: mass_pass = MODE_MASS, whose matrix does not depend on a
+    const double *
+    scale(bool mass_pass) const
+    {
+      return mass_pass && h_cell.p ? h_cell.p : h.p;
+    }
+    SlotGroupDev
+    view(bool mass_pass) const
+    {
+      return SlotGroupDev{interior_base.p, shell_idx.p, mask.p, scale(mass_pass), shell_pos.p, (uint32_t)n_slots, fmask.p, q.p};
     }
     // slots [begin, end) only (sharded levels: halo slots first, then the rest)
     SlotGroupDev
-    view(size_t begin, size_t end) const
+    view(size_t begin, size_t end, bool mass_pass) const
     {
       const size_t n_shell = (size_t)N * N * N - (size_t)(N - 2) * (N - 2) * (N - 2);
-      return SlotGroupDev{interior_base.p + begin, shell_idx.p + begin * n_shell, mask.p + begin, h.p + begin, shell_pos.p,
-                          (uint32_t)(end - begin), fmask.p ? fmask.p + begin : nullptr};
+      return SlotGroupDev{interior_base.p + begin, shell_idx.p + begin * n_shell, mask.p + begin, scale(mass_pass) + begin, shell_pos.p,
+                          (uint32_t)(end - begin), fmask.p ? fmask.p + begin : nullptr, q.p + begin};
     }
     // single cells at p = 1: per-cluster distinct node lists for cell_cluster_apply_kernel
     DBuf<uint32_t> uniq_ptr, uniq_idx;
@@ -181,9 +205,9 @@ namespace mgamd
       return uniq_ptr.p != nullptr;
     }
     CellClusterDev
-    cluster_view() const
+    cluster_view(bool mass_pass) const
     {
-      return CellClusterDev{uniq_ptr.p, uniq_idx.p, loc.p, mask.p, h.p, (uint32_t)n_slots, max_uniq};
+      return CellClusterDev{uniq_ptr.p, uniq_idx.p, loc.p, mask.p, scale(mass_pass), (uint32_t)n_slots, max_uniq, q.p};
     }
     // dynamic LDS of the cluster kernel (cell_cluster_body): the values and the sums of a cluster's distinct nodes
     size_t
@@ -337,7 +361,7 @@ namespace mgamd
               d->interior_base.upload(g.interior_base);
               d->shell_idx.upload(g.shell_idx);
               d->mask.upload(g.mask);
-              d->h.upload(g.h);
+              d->upload_scales(g);
               d->shell_pos.upload(g.shell_pos);
               if (std::any_of(g.fmask.begin(), g.fmask.end(), [](uint32_t m) { return m != 0; }))
                 d->fmask.upload(g.fmask);
@@ -534,10 +558,10 @@ namespace mgamd
     // the cluster kernel's arguments for the single cells g in the pass described by a (clusters exist at p = 1 only)
     template <int P>
     ClusterArgs<T>
-    cluster_args(const GroupDev<T> &g, const ApplyArgs<T, P> &a, bool first)
+    cluster_args(const GroupDev<T> &g, const ApplyArgs<T, P> &a, bool first, bool mass_pass)
     {
       ClusterArgs<T> c;
-      c.c          = g.cluster_view();
+      c.c          = g.cluster_view(mass_pass);
       c.m          = mats<1>();
       c.src        = a.src;
       c.tail_acc   = a.tail_acc;
@@ -556,7 +580,7 @@ namespace mgamd
     void
     launch_clusters(hipStream_t st, const GroupDev<T> &g, const ApplyArgs<T, P> &a, bool first, size_t begin, size_t end)
     {
-      ClusterArgs<T> c    = cluster_args(g, a, first);
+      ClusterArgs<T> c    = cluster_args(g, a, first, MASS_ONLY);
       c.cluster_offset    = (uint32_t)(begin / CLUSTER_CELLS);
       const uint32_t grid = (uint32_t)((end + CLUSTER_CELLS - 1) / CLUSTER_CELLS) - c.cluster_offset;
       hipLaunchKernelGGL((MASS_ONLY ? cell_cluster_mass_kernel<T> : cell_cluster_apply_kernel<T>), grid, CLUSTER_CELLS, g.cluster_lds_bytes(), st, c);
@@ -571,7 +595,7 @@ namespace mgamd
       using G = Geo<P, B>;
       BrickPairArgs<T, P> pa;
       pa.a             = a;
-      pa.g_constrained = g_constrained->view();
+      pa.g_constrained = g_constrained->view(MODE == MODE_MASS);
       pa.n_wg_plain    = (uint32_t)((a.g.n_slots + G::SPW - 1) / G::SPW);
       const int n_wg   = (int)(pa.n_wg_plain + (uint32_t)((g_constrained->n_slots + G::SPW - 1) / G::SPW));
       if constexpr (persistent_lattice(G::N))
@@ -638,7 +662,7 @@ namespace mgamd
       using G8 = Geo<1, 8>;
       P1SmallArgs<T> sa;
       sa.a           = a;
-      sa.c           = cluster_args(gc, a, MODE == MODE_CHEB_FIRST);
+      sa.c           = cluster_args(gc, a, MODE == MODE_CHEB_FIRST, MODE == MODE_MASS);
       sa.n_wg_bricks = (uint32_t)((a.g.n_slots + G8::SPW - 1) / G8::SPW);
       const uint32_t n_wg_cl = (uint32_t)((gc.n_slots + CLUSTER_CELLS - 1) / CLUSTER_CELLS);
       const size_t   lds     = std::max(apply_lds_bytes<T, 1, 8>(), gc.cluster_lds_bytes());
@@ -654,7 +678,7 @@ namespace mgamd
       using G2 = Geo<P, 2>;
       SmallSlotsArgs<T, P> sa;
       sa.a           = a;
-      sa.g_cells     = g1.view();
+      sa.g_cells     = g1.view(MODE == MODE_MASS);
       sa.n_wg_bricks = (uint32_t)((a.g.n_slots + G2::SPW - 1) / G2::SPW);
       // the cells wave-scoped: four wavefronts per workgroup with their own cells (kernels.hpp cell_waves_body)
       using GW = Geo<P, 1, 64>;
@@ -662,10 +686,9 @@ namespace mgamd
       const uint32_t n_wg_cells = (n_w + CELL_WAVES - 1) / CELL_WAVES;
       constexpr size_t lds      = small_slots_lds_bytes<T, P>();
       static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit the launch has to go through launch_lds");
-      // (kernels.hpp: MASS = false exists only where the kernel has no room for a run-time sigma; elsewhere both names are one kernel)
-      // (the mass pass has no mass term either way: the one name)
-      constexpr bool laplace_form = !small_slots_mass_compiled<T, P>() || MODE == MODE_MASS;
-      hipLaunchKernelGGL((a.sigma == 0.0 ? lattice_apply_small_kernel<T, P, MODE, laplace_form> : lattice_apply_small_kernel<T, P, MODE, true>),
+      // (kernels.hpp: the mass term compiled out for sigma = 0 and compiled in otherwise; the mass pass has no mass term: MASS = false)
+      hipLaunchKernelGGL((a.sigma == 0.0 || MODE == MODE_MASS ? lattice_apply_small_kernel<T, P, MODE, false> :
+                                                                 lattice_apply_small_kernel<T, P, MODE, true>),
                          sa.n_wg_bricks + n_wg_cells, 256, lds, st, sa);
       HIP_CHECK(hipGetLastError());
     }
@@ -679,7 +702,7 @@ namespace mgamd
       constexpr int MODE = base_mode(MODE_);
       using K            = LaunchKind;
       GroupDev<T> *g     = s.g;
-      a.g                = g->view(s.begin, s.end);
+      a.g                = g->view(s.begin, s.end, MODE == MODE_MASS);
       a.stamps           = nullptr;
       if constexpr (MODE_ != MODE)
         if (fused && fused->group >= 0 && g == groups[fused->group].get())

@@ -22,6 +22,7 @@
 #include <array>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include "fe1d.hpp"
 #include "octree.hpp"
 
@@ -102,6 +103,7 @@ namespace mgamd
     std::vector<uint16_t> mask;          // per slot: constraint configuration (0 for bricks)
     std::vector<uint32_t> fmask;         // bricks (B >= 2), per slot: hanging faces/edges of the whole brick (family_* helpers), 0 = none
     std::vector<double>   h;             // per slot: cell edge length
+    std::vector<double>   a;             // per slot: diffusion coefficient, the one value all its cells carry (1 if the mesh has none)
     std::vector<uint32_t> first_cell;    // per slot: index of its first cell in Tria::cells
     std::vector<uint16_t> shell_pos;     // n_shell: lattice index (z*N+y)*N+x of each shell entry
     // sharded levels: the first n_halo_slots slots of the group touch DoFs shared with other ranks; the halo exchange of an
@@ -370,6 +372,29 @@ namespace mgamd
     // its construction and keeps its own copy; 0 = the Laplace operator.  Local-smoothing levels refuse a non-zero value (their
     // refinement-edge matrices carry no mass term).
     double sigma = 0.0;
+    // Diffusion coefficient a of  -div(a grad u) + sigma u,  one value per cell: the triangulation's at the time these tables
+    // were built (a later Tria::set_coefficient does not reach them); empty: a = 1.  The slots carry it too (SlotGroup::a): a
+    // brick is only formed of cells with the bit-identical value (DESIGN.md "Diffusion coefficient").
+    std::vector<double> coefficient;
+    double
+    coefficient_of(size_t cell) const
+    {
+      return coefficient.empty() ? 1.0 : coefficient[cell];
+    }
+    // smallest and largest value over this rank's cells
+    void
+    coefficient_range(double &lo, double &hi) const
+    {
+      lo = hi = 1.0;
+      bool first = true;
+      for (size_t ci = 0; ci < coefficient.size(); ++ci)
+        if (cell_is_local(ci))
+          {
+            lo    = first ? coefficient[ci] : std::min(lo, coefficient[ci]);
+            hi    = first ? coefficient[ci] : std::max(hi, coefficient[ci]);
+            first = false;
+          }
+    }
     void
     set_mass_coefficient(double s)
     {
@@ -400,6 +425,10 @@ namespace mgamd
       , shared(shared)
       , my_rank(my_rank)
     {
+      coefficient = t.coefficient;
+      if (ls_level && !coefficient.empty())
+        throw std::invalid_argument("local-smoothing level tables of a triangulation with a diffusion coefficient: not implemented "
+                                    "(the refinement-edge matrices have no coefficient)");
       if (ls_level && (owned || shared))
         throw std::runtime_error("local-smoothing levels are not sharded in this build");
       if (!helpers_only)
@@ -753,7 +782,7 @@ namespace mgamd
           if (any_g)
             {
               interpolate_hanging(fe, mask, xg.data(), false);
-              cell_stiffness_apply(h, xg.data(), lift.data());
+              cell_stiffness_apply(coefficient_of(ci) * h, xg.data(), lift.data()); // (a K_cell: the cell matrix is linear in its scale)
               if (sigma != 0.0)
                 cell_mass_add(h, sigma, xg.data(), lift.data());
               for (int t = 0; t < n3; ++t)
@@ -848,6 +877,13 @@ namespace mgamd
     const std::map<uint64_t, SharedInfo> *shared  = nullptr;
     int                                 my_rank = 0;
 
+    // the two cells carry the bit-identical coefficient (a brick's cells must: one scale per slot)
+    bool
+    same_coefficient(size_t c0, size_t c1) const
+    {
+      return coefficient.empty() || std::memcmp(&coefficient[c0], &coefficient[c1], sizeof(double)) == 0;
+    }
+
     void
     build(int Bmax)
     {
@@ -923,7 +959,7 @@ namespace mgamd
                     {
                       const Cell &d = cells[t + s];
                       ok = d.level == c.level && (d.i >> b) == (c.i >> b) && (d.j >> b) == (c.j >> b) && (d.k >> b) == (c.k >> b) &&
-                           cell_group[t + s] == 0xFF;
+                           cell_group[t + s] == 0xFF && same_coefficient(t, t + s);
                       hanging |= (masks[t + s] >> MASK_FACE_SHIFT) != 0;
                     }
                   if (ok && hanging)
@@ -959,6 +995,7 @@ namespace mgamd
               if (B >= 2)
                 g.fmask.push_back(fm);
               g.h.push_back(2.0 / (double)(1u << c.level));
+              g.a.push_back(coefficient_of(t));
               for (size_t s = 0; s < B3; ++s)
                 {
                   cell_group[t + s] = (uint8_t)gi;
@@ -1179,6 +1216,7 @@ namespace mgamd
               permute(g.mask, 1);
               permute(g.fmask, 1);
               permute(g.h, 1);
+              permute(g.a, 1);
               permute(g.first_cell, 1);
               std::vector<uint32_t> new_of_old(ns);
               for (size_t n2 = 0; n2 < ns; ++n2)

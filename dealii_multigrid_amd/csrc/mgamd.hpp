@@ -73,6 +73,29 @@ namespace mgamd
       r->query();
       return r;
     }
+    // The diffusion coefficient a > 0 of -div(a grad u) + sigma u: one value per leaf in the order of mgamd_tria_get_cells; an empty
+    // vector resets to a = 1.  coarsen() carries it down (the mean over each coarse leaf); DoFs copy it when they are built.
+    void
+    set_coefficient(const std::vector<double> &a)
+    {
+      if (!a.empty() && a.size() != n_cells)
+        throw std::runtime_error("set_coefficient: " + std::to_string(a.size()) + " values for " + std::to_string(n_cells) + " cells");
+      check(mgamd_tria_set_coefficient(h.get(), a.empty() ? nullptr : a.data()));
+    }
+    std::vector<double>
+    coefficient() const
+    {
+      std::vector<double> a(n_cells);
+      check(mgamd_tria_get_coefficient(h.get(), a.data()));
+      return a;
+    }
+    bool
+    has_coefficient() const
+    {
+      int has = 0;
+      check(mgamd_tria_has_coefficient(h.get(), &has));
+      return has != 0;
+    }
     // local smoothing: all cells of refinement level `level`, active or not (the level of DoFHandler::distribute_mg_dofs)
     std::shared_ptr<Triangulation>
     level_mesh(unsigned level) const
@@ -288,6 +311,14 @@ namespace mgamd
       double s = 0.0;
       check(mgamd_dofs_mass_coefficient(h.get(), &s));
       return s;
+    }
+    // smallest and largest diffusion coefficient these DoFs were built with
+    std::pair<double, double>
+    coefficient_range() const
+    {
+      double lo = 1.0, hi = 1.0;
+      check(mgamd_dofs_coefficient_range(h.get(), &lo, &hi));
+      return {lo, hi};
     }
     mgamd_dofs_info_t info;
 

@@ -180,6 +180,29 @@ namespace mgamd
     std::vector<Cell>     cells; // leaves in Morton (p4est) order
     std::vector<uint16_t> masks; // constraint configuration per leaf
     FlatMap               index; // cell_key -> position in `cells`
+    // Diffusion coefficient a > 0 of -div(a grad u), one value per leaf in the order of `cells`; empty: a = 1 everywhere
+    // (DESIGN.md "Diffusion coefficient").  Level tables copy it when they are built.
+    std::vector<double> coefficient;
+    // values == nullptr resets to a = 1; refuses values that are not finite and positive, naming the first one
+    void
+    set_coefficient(const double *values)
+    {
+      if (!values)
+        {
+          coefficient.clear();
+          return;
+        }
+      for (size_t t = 0; t < cells.size(); ++t)
+        if (!(values[t] > 0.0) || !std::isfinite(values[t]))
+          throw std::invalid_argument("diffusion coefficient of cell " + std::to_string(t) + " is " + std::to_string(values[t]) +
+                                      ": refused, every value must be finite and > 0");
+      coefficient.assign(values, values + cells.size());
+    }
+    double
+    coefficient_of(size_t cell) const
+    {
+      return coefficient.empty() ? 1.0 : coefficient[cell];
+    }
 
     static Tria
     create(const std::string &geometry, unsigned n_ref_global, unsigned n_ref_local);
@@ -191,11 +214,14 @@ namespace mgamd
     static Tria
     from_leaves_checked(std::vector<Cell> leaves);
     Tria
-    coarsen_global() const; // one level of the geometric coarsening sequence
+    coarsen_global() const; // one level of the geometric coarsening sequence; the coefficient goes down as the mean over each leaf
     // local smoothing: ALL cells of refinement level `level`, active or not (DoFHandler::distribute_mg_dofs levels)
     Tria
     level_mesh(int level) const
     {
+      if (!coefficient.empty())
+        throw std::invalid_argument("level_mesh: the triangulation carries a diffusion coefficient: local smoothing with a "
+                                    "coefficient is not implemented (the refinement-edge matrices have none)");
       std::vector<Cell> out;
       FlatMap           seen;
       seen.erase_all_and_reserve(cells.size());
@@ -227,6 +253,8 @@ namespace mgamd
     n_cells_with_hanging_nodes() const;
 
   private:
+    Tria
+    coarsen_cells() const; // the cells of coarsen_global()
     void
     finalize(); // sort, index, masks
   };
@@ -636,6 +664,27 @@ namespace mgamd
 
   inline Tria
   Tria::coarsen_global() const
+  {
+    Tria coarse = coarsen_cells();
+    if (!coefficient.empty())
+      {
+        // Re-discretisation, not a Galerkin product: a coarse leaf is one of this mesh's leaves (its own value) or the parent of
+        // eight of them (their arithmetic mean, the volume-weighted mean of equal cubes).  Eighths are exact, so this is sum / 8.
+        coarse.coefficient.assign(coarse.cells.size(), 0.0);
+        for (size_t t = 0; t < cells.size(); ++t)
+          {
+            const Cell &c  = cells[t];
+            const int   at = coarse.find_leaf(c.level, c.i, c.j, c.k);
+            if (at < 0 || (int)coarse.cells[at].level + 1 < (int)c.level)
+              throw std::runtime_error("coarsen: a leaf is not covered by itself or its parent");
+            coarse.coefficient[at] += coarse.cells[at].level == c.level ? coefficient[t] : 0.125 * coefficient[t];
+          }
+      }
+    return coarse;
+  }
+
+  inline Tria
+  Tria::coarsen_cells() const
   {
     using namespace detail;
     // complete families: 8 consecutive leaves (Morton order) of equal level with a common parent

@@ -74,6 +74,22 @@ int mgamd_tria_info(const mgamd_tria *t, uint64_t *n_cells, uint32_t *n_levels, 
 /* leaves in Morton (p4est) order; arrays of n_cells entries, any may be NULL */
 int mgamd_tria_get_cells(const mgamd_tria *t, uint8_t *level, uint32_t *i, uint32_t *j, uint32_t *k, uint16_t *mask);
 
+/* Diffusion coefficient: the operator of every level is  -div(a grad u) + sigma u  with a > 0 constant on each leaf, in the
+ * matrices  K_a + sigma M,  K_a = sum over cells of a_c h_c (K (x) M (x) M + M (x) K (x) M + M (x) M (x) K).
+ * set_coefficient takes n_cells values in the order of mgamd_tria_get_cells; NULL resets to a = 1, which is also the state of a
+ * new triangulation.  MGAMD_ERR_INVALID, with the index and the value in mgamd_last_error(), for a value that is <= 0, NaN or
+ * infinite.  get_coefficient writes n_cells values (ones if none is set).
+ * mgamd_tria_coarsen carries the coefficient down: a coarse leaf gets the volume-weighted arithmetic mean of the fine leaves it
+ * covers (its own value, or the mean of its eight children) -- a re-discretisation, not a Galerkin product; the caller may
+ * overwrite a coarse mesh's values afterwards (e.g. with a harmonic mean).
+ * mgamd_dofs_create and mgamd_dofs_create_local COPY the coefficient of their mesh: a later set_coefficient does not reach
+ * tables that exist, and everything built from the tables (operators, matrices, right-hand sides, AMG) follows that copy.
+ * Local smoothing with a coefficient is not implemented: mgamd_tria_level_mesh of such a triangulation is MGAMD_ERR_INVALID.
+ * mgamd_mg_create_sharded_amg refuses a global_coarse_dofs whose coefficient differs from level 0's. */
+int mgamd_tria_set_coefficient(mgamd_tria *t, const double *a);
+int mgamd_tria_get_coefficient(const mgamd_tria *t, double *a);
+int mgamd_tria_has_coefficient(const mgamd_tria *t, int *has);
+
 typedef struct
 {
   uint32_t degree;
@@ -137,6 +153,8 @@ int mgamd_dofs_distribute(const mgamd_dofs *d, int kind, double *x);
  * operator was built.  The "direct" inverse and the collapsed levels are formed through the operator itself. */
 int mgamd_dofs_set_mass_coefficient(mgamd_dofs *d, double sigma);
 int mgamd_dofs_mass_coefficient(const mgamd_dofs *d, double *sigma);
+/* smallest and largest diffusion coefficient the tables were built with, over this rank's cells (1, 1 if the mesh had none) */
+int mgamd_dofs_coefficient_range(const mgamd_dofs *d, double *min, double *max);
 
 /* Operator::get_trilinos_system_matrix / get_petsc_system_matrix (ref:include/operator.h:244-358: MatrixFreeTools::compute_matrix of
  * the cell kernel with the constraints): the assembled level matrix C^T K C + identity on the constrained rows, CSR with sorted

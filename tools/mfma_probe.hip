@@ -54,7 +54,7 @@ __launch_bounds__(256, 2) valu_kernel(const Mats<P> m, int reps, double *out, do
   init_lattice(bufA, tid, blockIdx.x);
   for (int r = 0; r < reps; ++r)
     {
-      lattice_sweeps<double, P, B, 256>(bufA, bufB, m, tid, 1, &h);
+      lattice_sweeps<double, P, B, 256>(bufA, bufB, m, tid, 1, &h, NoHook(), false, 0.0, &h);
       for (int i = tid; i < N3; i += 256)
         bufA[i] *= 0.25;
       __syncthreads();

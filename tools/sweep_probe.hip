@@ -210,11 +210,11 @@ __launch_bounds__((VARIANT == 3 ? 512 : 256), (VARIANT == 3 ? 4 : 2)) sweep_kern
   for (int r = 0; r < reps; ++r)
     {
       if constexpr (VARIANT == 0)
-        lattice_sweeps<double, P, B, 256>(bufA, bufB, m, tid, 1, &h);
+        lattice_sweeps<double, P, B, 256>(bufA, bufB, m, tid, 1, &h, NoHook(), false, 0.0, &h);
       else if constexpr (VARIANT == 1)
-        lattice_sweeps<double, P, B, 256, NoHook, true, false>(bufA, bufB, m, tid, 1, &h);
+        lattice_sweeps<double, P, B, 256, NoHook, true, false>(bufA, bufB, m, tid, 1, &h, NoHook(), false, 0.0, &h);
       else if constexpr (VARIANT == 2)
-        lattice_sweeps<double, P, B, 256, NoHook, true, true>(bufA, bufB, m, tid, 1, &h);
+        lattice_sweeps<double, P, B, 256, NoHook, true, true>(bufA, bufB, m, tid, 1, &h, NoHook(), false, 0.0, &h);
       else
         lattice_sweeps_wide<double, P>(bufA, bufB, m, tid, h);
       for (int i = tid; i < N3; i += BLOCK)
