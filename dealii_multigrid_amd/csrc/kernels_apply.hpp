@@ -1460,13 +1460,98 @@ namespace mgamd
 
   // Epilogue for the tail (accumulated shell sums) and the constrained DoFs (identity rows:
   // ref:include/operator.h:170-172; MODE_MASS: zero rows); re-zeroes the accumulator for the next application.
+  // tail_rows is the epilogue of the U rows row[u] (tail index; row >= n_tail: a constrained DoF) with live[u]; the two kernels
+  // below differ in the rows they hand it: tail_kernel a contiguous range, tail_runs_kernel a list of runs.
+  constexpr int TAIL_U = 4;
+  template <typename T, int MODE_>
+  __device__ __forceinline__ void
+  tail_rows(T *__restrict__ tail_acc, const uint32_t n_interior, const uint32_t n_tail, const uint32_t (&row)[TAIL_U], const bool (&live)[TAIL_U],
+            const Epilogue<T> &epi, const T *dtable, const bool coded)
+  {
+    constexpr int  MODE   = base_mode(MODE_); // (MODE_RESIDUAL_RESTRICT: plain residual rows for the un-fused restriction)
+    constexpr bool FUSE_P = MODE_ == MODE_CHEB_PROLONGATE;
+    constexpr int  U      = TAIL_U;
+    T ax[U], xv[U], xo[U], bv[U], dv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      {
+        const uint32_t i  = row[u];
+        const uint32_t gi = n_interior + i;
+        ax[u] = xv[u] = xo[u] = bv[u] = dv[u] = T(0);
+        if (live[u])
+          {
+            if (MODE != MODE_INVDIAG && MODE != MODE_CHEB_FIRST && MODE != MODE_MASS && (is_cheb(MODE) || i >= n_tail))
+              {
+                if (FUSE_P && i < n_tail && NT_LOAD(&epi.xs_flag[i]))
+                  { // x + P x_c as the owning fused brick left it: folded into x here, after every brick has gathered x
+                    xv[u] = NT_LOAD(&epi.xs[gi]);
+                    epi.x_inout[gi] = xv[u];
+                  }
+                else
+                  xv[u] = NT_LOAD(&epi.x[gi]);
+              }
+            ax[u] = i < n_tail ? tail_acc[i] : xv[u]; // (MODE_MASS: x is not read and the rows of constrained DoFs are zero)
+            if (MODE == MODE_RESIDUAL || is_cheb(MODE))
+              bv[u] = NT_LOAD(&epi.b[gi]);
+            if (is_cheb(MODE))
+              {
+                if (MODE == MODE_CHEB && epi.xold)
+                  xo[u] = NT_LOAD(&epi.xold[gi]);
+                if (coded)
+                  {
+                    const uint32_t c = NT_LOAD(&epi.dinv_code[i]);
+                    dv[u]            = c != 255u ? dtable[c] : epi.dinv[gi];
+                  }
+                else
+                  dv[u] = epi.dinv[gi];
+              }
+          }
+      }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      {
+        const uint32_t i  = row[u];
+        const uint32_t gi = n_interior + i;
+        if (live[u])
+          {
+            if (i < n_tail)
+              NT_STORE(T(0), &tail_acc[i]);
+            if (MODE == MODE_CHEB_FIRST || MODE == MODE_CHEB_SECOND)
+              {
+                const T x1 = epi.c0 * dv[u] * bv[u];
+                if (MODE == MODE_CHEB_FIRST)
+                  {
+                    xv[u] = x1;
+                    if (i >= n_tail)
+                      ax[u] = x1; // identity row
+                  }
+                else
+                  xo[u] = x1;
+              }
+            if (MODE == MODE_VMULT || MODE == MODE_MASS)
+              NT_STORE(ax[u], &epi.out[gi]);
+            else if (MODE == MODE_RESIDUAL)
+              NT_STORE(bv[u] - ax[u], &epi.out[gi]);
+            else if (is_cheb(MODE))
+              {
+                const T r = xv[u] + epi.f1 * (xv[u] - xo[u]) + epi.f2 * dv[u] * (bv[u] - ax[u]);
+                if (MODE_ == MODE_CHEB)
+                  store_result(epi, gi, r);
+                else
+                  NT_STORE(r, &epi.out[gi]);
+              }
+            else
+              epi.out[gi] = (i < n_tail && fabs((double)ax[u]) > 1.0e-10) ? T(1) / ax[u] : T(1);
+          }
+      }
+  }
+
   template <typename T, int MODE_>
   __global__ void
   __launch_bounds__(256) tail_kernel(T *__restrict__ tail_acc, uint32_t n_interior, uint32_t n_tail, uint32_t n_rest, Epilogue<T> epi)
   {
-    constexpr int  MODE   = base_mode(MODE_); // (MODE_RESIDUAL_RESTRICT: plain residual rows for the un-fused restriction)
-    constexpr bool FUSE_P = MODE_ == MODE_CHEB_PROLONGATE;
-    constexpr int  U      = 4;
+    constexpr int  MODE   = base_mode(MODE_);
+    constexpr int  U      = TAIL_U;
     const uint32_t total  = n_tail + n_rest;
     const uint32_t stride = gridDim.x * blockDim.x;
     __shared__ T   dtable[256];
@@ -1478,80 +1563,47 @@ namespace mgamd
       }
     for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < total; i0 += U * stride)
       {
-        T ax[U], xv[U], xo[U], bv[U], dv[U];
+        uint32_t row[U];
+        bool     live[U];
 #pragma unroll
         for (int u = 0; u < U; ++u)
           {
-            const uint32_t i  = i0 + u * stride;
-            const uint32_t gi = n_interior + i;
-            ax[u] = xv[u] = xo[u] = bv[u] = dv[u] = T(0);
-            if (i < total)
-              {
-                if (MODE != MODE_INVDIAG && MODE != MODE_CHEB_FIRST && MODE != MODE_MASS && (is_cheb(MODE) || i >= n_tail))
-                  {
-                    if (FUSE_P && i < n_tail && NT_LOAD(&epi.xs_flag[i]))
-                      { // x + P x_c as the owning fused brick left it: folded into x here, after every brick has gathered x
-                        xv[u] = NT_LOAD(&epi.xs[gi]);
-                        epi.x_inout[gi] = xv[u];
-                      }
-                    else
-                      xv[u] = NT_LOAD(&epi.x[gi]);
-                  }
-                ax[u] = i < n_tail ? tail_acc[i] : xv[u]; // (MODE_MASS: x is not read and the rows of constrained DoFs are zero)
-                if (MODE == MODE_RESIDUAL || is_cheb(MODE))
-                  bv[u] = NT_LOAD(&epi.b[gi]);
-                if (is_cheb(MODE))
-                  {
-                    if (MODE == MODE_CHEB && epi.xold)
-                      xo[u] = NT_LOAD(&epi.xold[gi]);
-                    if (coded)
-                      {
-                        const uint32_t c = NT_LOAD(&epi.dinv_code[i]);
-                        dv[u]            = c != 255u ? dtable[c] : epi.dinv[gi];
-                      }
-                    else
-                      dv[u] = epi.dinv[gi];
-                  }
-              }
+            row[u]  = i0 + u * stride;
+            live[u] = row[u] < total;
           }
+        tail_rows<T, MODE_>(tail_acc, n_interior, n_tail, row, live, epi, dtable, coded);
+      }
+  }
+
+  // The same epilogue on a list of runs of rows (the fused residual pass, level_operator_apply.hpp: only the rows somebody
+  // reads).  The host has cut the runs into chunks of at most TAIL_CHUNK = 64 rows, chunks[2c] <= row < chunks[2c+1]: a
+  // wavefront takes U consecutive chunks, one row per lane.  Rows >= n_tail are constrained DoFs, as in tail_kernel.
+  constexpr uint32_t TAIL_CHUNK = 64;
+  template <typename T, int MODE_>
+  __global__ void
+  __launch_bounds__(256) tail_runs_kernel(T *__restrict__ tail_acc, uint32_t n_interior, uint32_t n_tail, const uint32_t *__restrict__ chunks,
+                                          uint32_t n_chunks, Epilogue<T> epi)
+  {
+    constexpr int MODE = base_mode(MODE_);
+    constexpr int U    = TAIL_U;
+    static_assert(!is_cheb(MODE), "run-walking epilogue: modes without the D^-1 code table");
+    const uint32_t c0   = (blockIdx.x * (256 / TAIL_CHUNK) + threadIdx.x / TAIL_CHUNK) * U;
+    const uint32_t lane = threadIdx.x % TAIL_CHUNK;
+    uint32_t       row[U];
+    bool           live[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+    for (int u = 0; u < U; ++u)
+      {
+        const uint32_t c = c0 + u;
+        row[u]           = 0;
+        live[u]          = false;
+        if (c < n_chunks)
           {
-            const uint32_t i  = i0 + u * stride;
-            const uint32_t gi = n_interior + i;
-            if (i < total)
-              {
-                if (i < n_tail)
-                  NT_STORE(T(0), &tail_acc[i]);
-                if (MODE == MODE_CHEB_FIRST || MODE == MODE_CHEB_SECOND)
-                  {
-                    const T x1 = epi.c0 * dv[u] * bv[u];
-                    if (MODE == MODE_CHEB_FIRST)
-                      {
-                        xv[u] = x1;
-                        if (i >= n_tail)
-                          ax[u] = x1; // identity row
-                      }
-                    else
-                      xo[u] = x1;
-                  }
-                if (MODE == MODE_VMULT || MODE == MODE_MASS)
-                  NT_STORE(ax[u], &epi.out[gi]);
-                else if (MODE == MODE_RESIDUAL)
-                  NT_STORE(bv[u] - ax[u], &epi.out[gi]);
-                else if (is_cheb(MODE))
-                  {
-                    const T r = xv[u] + epi.f1 * (xv[u] - xo[u]) + epi.f2 * dv[u] * (bv[u] - ax[u]);
-                    if (MODE_ == MODE_CHEB)
-                      store_result(epi, gi, r);
-                    else
-                      NT_STORE(r, &epi.out[gi]);
-                  }
-                else
-                  epi.out[gi] = (i < n_tail && fabs((double)ax[u]) > 1.0e-10) ? T(1) / ax[u] : T(1);
-              }
+            row[u]  = chunks[2 * c] + lane;
+            live[u] = row[u] < chunks[2 * c + 1];
           }
       }
+    tail_rows<T, MODE_>(tail_acc, n_interior, n_tail, row, live, epi, nullptr, false);
   }
 
 } // namespace mgamd

@@ -262,6 +262,10 @@ namespace mgamd
     uint32_t            nc3 = 0;
     std::vector<double> E;                    // 1D h-embedding (2p+1) x (p+1)
     const uint8_t      *tail_flags = nullptr; // [n_tail]: the tail DoF is owned by a fused brick
+    // the rows the fused residual pass finishes (TransferTables::residual_tail_runs and the constrained DoFs) in chunks of at
+    // most TAIL_CHUNK rows for tail_runs_kernel: [begin, end) pairs; nullptr: the whole tail (sharded levels)
+    const uint32_t     *tail_chunks   = nullptr;
+    uint32_t            n_tail_chunks = 0;
     // per call
     T *coarse = nullptr, *scratch = nullptr, *x_inout = nullptr;
   };
@@ -759,6 +763,19 @@ namespace mgamd
       else
         hipLaunchKernelGGL((tail_kernel<T, MODE>), grid_for(n_t), 256, 0, st, tail_acc.p + begin, tables->n_interior + begin, end - begin, n_rest,
                            epi);
+      HIP_CHECK(hipGetLastError());
+    }
+
+    // the tail epilogue on the rows of a chunk list only (FusedTransferHost::tail_chunks)
+    template <int MODE>
+    void
+    launch_tail_runs(hipStream_t st, const uint32_t *chunks, uint32_t n_chunks, const Epilogue<T> &epi)
+    {
+      if (!n_chunks)
+        return;
+      constexpr uint32_t per_wg = 256 / TAIL_CHUNK * TAIL_U;
+      hipLaunchKernelGGL((tail_runs_kernel<T, MODE>), (n_chunks + per_wg - 1) / per_wg, 256, 0, st, tail_acc.p, tables->n_interior, tables->n_tail,
+                         chunks, n_chunks, epi);
       HIP_CHECK(hipGetLastError());
     }
 

@@ -80,6 +80,13 @@ namespace mgamd
       }
     if (halo)
       exchange_add_raw(tail_acc.p); // complete the shared tail sums across ranks before the epilogue
+    // The fused residual pass: the fused bricks write neither t nor the accumulator, so only the rows that a slot outside the
+    // fused set touches are finished (they are the rows of t the un-fused patches restrict, and the accumulator entries to
+    // re-zero), plus the constrained rows.  Measured on octant p=4, level 8: 18 % of the tail, 153 -> 41 us.
+    // A sharded level keeps the whole tail: the exchange adds remote sums to entries outside that set.
+    if constexpr (MODE == MODE_RESIDUAL_RESTRICT)
+      if (!diag && !halo && !tables->n_edge && fused && fused->tail_chunks)
+        return launch_tail_runs<MODE>(main, fused->tail_chunks, fused->n_tail_chunks, epi);
     launch_tail<MODE>(main, 0, tail_end, true, epi, diag);
   }
 

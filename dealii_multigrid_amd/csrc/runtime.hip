@@ -641,6 +641,7 @@ namespace mgamd
     DBuf<uint32_t>       fused_flags;
     DBuf<uint32_t>       fused_coarse_idx;
     DBuf<uint8_t>        fused_tail_flags;
+    DBuf<uint32_t>       fused_tail_chunks;
     size_t               n_fused_bricks = 0;
     bool
     fused_ready() const
@@ -725,6 +726,27 @@ namespace mgamd
               fused.E          = fec.embedding(1, f->tables->p);
               fused.tail_flags = fused_tail_flags.p;
               n_fused_bricks   = bg.n_bricks() - bg.n_unfused;
+              // the rows of the fused residual pass's tail epilogue (apply_P); a sharded level keeps the whole tail
+              if (!f->halo && !f->tables->n_edge)
+                {
+                  std::vector<uint32_t> runs = tt.residual_tail_runs, chunks;
+                  if (f->tables->n_dofs > f->tables->n_interior + f->tables->n_tail) // the constrained rows
+                    {
+                      runs.push_back(f->tables->n_tail);
+                      runs.push_back(f->tables->n_dofs - f->tables->n_interior);
+                    }
+                  for (size_t k = 0; k + 1 < runs.size(); k += 2)
+                    for (uint32_t b0 = runs[k]; b0 < runs[k + 1]; b0 += TAIL_CHUNK)
+                      {
+                        chunks.push_back(b0);
+                        chunks.push_back(std::min(runs[k + 1], b0 + TAIL_CHUNK));
+                      }
+                  fused.n_tail_chunks = (uint32_t)(chunks.size() / 2);
+                  if (chunks.empty())
+                    chunks.push_back(0);
+                  fused_tail_chunks.upload(chunks);
+                  fused.tail_chunks = fused_tail_chunks.p;
+                }
             }
           d->slot.upload(bg.slot);
           d->coarse_idx.upload(bg.coarse_idx);

@@ -304,7 +304,62 @@ namespace mgamd
               for (int t = 0; t < fg.n_shell; ++t)
                 if (bg.shell_flags[q * (size_t)fg.n_shell + t] == BrickTransferGroup::SHELL_OWN)
                   tail_owned_by_fused[bg.own_shell[q * (size_t)fg.n_shell + t] - fine.n_interior] = 1;
+            if (bg.n_bricks() > bg.n_unfused)
+              build_residual_tail_runs(fine, bg);
           }
+    }
+
+    // The tail rows the fused residual pass has to finish (MODE_RESIDUAL_RESTRICT): a fused brick restricts its own partial
+    // sums and writes neither t nor the tail accumulator, so the epilogue is needed only for the tail DoFs that some slot
+    // OUTSIDE the fused set touches -- these are the accumulator entries anything adds to and, by the ownership plan, the rows
+    // of t the un-fused patches restrict (tools/residual_tail_check.cpp).  Tail indices (DoF - n_interior), sorted disjoint
+    // runs [residual_tail_runs[2k], residual_tail_runs[2k+1]); empty without fused bricks.
+    std::vector<uint32_t> residual_tail_runs;
+    size_t
+    residual_tail_size() const
+    {
+      size_t n = 0;
+      for (size_t k = 0; k + 1 < residual_tail_runs.size(); k += 2)
+        n += residual_tail_runs[k + 1] - residual_tail_runs[k];
+      return n;
+    }
+
+  private:
+    void
+    build_residual_tail_runs(const LevelTables &fine, const BrickTransferGroup &fused_bricks)
+    {
+      std::vector<bool> in_s(fine.n_tail, false);
+      for (size_t gi = 0; gi < fine.groups.size(); ++gi)
+        {
+          const SlotGroup  &g = fine.groups[gi];
+          std::vector<bool> slot_fused(g.n_slots(), false);
+          if ((int)gi == fused_bricks.fine_group)
+            for (size_t q = fused_bricks.n_unfused; q < fused_bricks.n_bricks(); ++q)
+              slot_fused[fused_bricks.slot[q]] = true;
+          for (size_t s = 0; s < g.n_slots(); ++s)
+            if (!slot_fused[s])
+              for (int t = 0; t < g.n_shell; ++t)
+                {
+                  const uint32_t idx = g.shell_idx[s * (size_t)g.n_shell + t];
+                  if (idx != INVALID_DOF && idx >= fine.n_interior && idx - fine.n_interior < fine.n_tail)
+                    in_s[idx - fine.n_interior] = true;
+                }
+        }
+      residual_tail_runs.clear();
+      for (uint32_t i = 0; i < fine.n_tail;)
+        {
+          if (!in_s[i])
+            {
+              ++i;
+              continue;
+            }
+          uint32_t e = i;
+          while (e < fine.n_tail && in_s[e])
+            ++e;
+          residual_tail_runs.push_back(i);
+          residual_tail_runs.push_back(e);
+          i = e;
+        }
     }
   };
 } // namespace mgamd
