@@ -59,6 +59,37 @@ def reshift_hierarchy(levels, sigma):
     return [reshift(lv, sigma) for lv in levels]
 
 
+def _renumber(lv, keys):
+    ext = {tuple(int(v) for v in k): i for i, k in enumerate(keys)}
+    assert len(ext) == lv.n, (len(ext), lv.n)
+    perm = np.array([ext[tuple(int(v) for v in k)] for k in lv.keys], dtype=np.int64)  # old -> new
+    inv = np.argsort(perm)
+    Q = sp.csr_matrix((np.ones(lv.n), (perm, np.arange(lv.n))), shape=(lv.n, lv.n))
+    out = copy.copy(lv)
+    out.__dict__.pop("_rounded", None)
+    out.cell_dofs = perm[lv.cell_dofs]
+    out.keys = [lv.keys[o] for o in inv]
+    out.key_to_dof = {k: i for i, k in enumerate(out.keys)}
+    for name in ("dirichlet", "hanging", "constrained", "rhs_constant", "inv_diag"):
+        setattr(out, name, getattr(lv, name)[inv])
+    for name in ("Ch", "C", "Kraw", "K0raw", "Mraw", "A"):
+        setattr(out, name, (Q @ getattr(lv, name) @ Q.T).tocsr())
+    return out, Q
+
+
+def renumber(lv, keys):
+    """the level lv (a HelmholtzLevel) in another numbering of the same space, `keys` being the DoF keys in the new order: what
+    level_class(...)(mesh, p, numbering_keys=keys) builds, without repeating the constraint search.  Every table of the level
+    (cell_dofs, keys, the masks, C, Ch, the raw matrices, A, inv_diag, rhs_constant) is permuted; lv itself is left unchanged"""
+    return _renumber(lv, keys)[0]
+
+
+def renumber_hierarchy(levels, P, keys):
+    """renumber for every level, keys[l] the new order of level l, and the transfers between them permuted to match"""
+    new, Q = zip(*[_renumber(lv, k) for lv, k in zip(levels, keys)])
+    return list(new), [None] + [(Q[l] @ P[l] @ Q[l - 1].T).tocsr() for l in range(1, len(new))]
+
+
 def level(oracle, sigma, dofs, geometry, n_ref, degree, mesh=None):
     """one Level of K + sigma M numbered like the product's `dofs`"""
     if mesh is None:
@@ -68,7 +99,11 @@ def level(oracle, sigma, dofs, geometry, n_ref, degree, mesh=None):
 
 def level_plan(oracle, geometry, n_ref_global, degree, mg_type):
     """(meshes, degrees) coarse -> fine, as mgoracle.build_hierarchy chooses them"""
-    fine = oracle.create_mesh(geometry, n_ref_global)
+    return level_plan_on(oracle, oracle.create_mesh(geometry, n_ref_global), degree, mg_type)
+
+
+def level_plan_on(oracle, fine, degree, mg_type):
+    """the same for a caller's set of leaves (level, i, j, k) as the finest mesh"""
     pseq = [degree]
     while pseq[-1] > 1:
         pseq.append(max(pseq[-1] // 2, 1))
