@@ -987,6 +987,15 @@ def _coarse_plan(coarse_solver: str, n_level0_dofs_global: int, level0_distribut
     return plan.value
 
 
+def _coarse_resolve(coarse_solver: str, n_level0_dofs: int, level0_sharded=False, has_nested=False, has_amg_global=False) -> str:
+    """mgamd_debug_coarse_resolve: the coarse solver a multigrid built from these would report as coarse_solver_used();
+    MgamdError where its construction would fail"""
+    used = C.create_string_buffer(32)
+    _chk(_lib.mgamd_debug_coarse_resolve(coarse_solver.encode(), C.c_uint64(n_level0_dofs), int(level0_sharded), int(has_nested),
+                                         int(has_amg_global), used))
+    return used.value.decode()
+
+
 def _partition_defaults(n_ranks: int, p_low: int = 1):
     """mgamd_partition_defaults: (rank group of the two-tier partition, cells from which a level is cut over all ranks, over groups);
     at p_low = 1 the thresholds are DoFs: the defaults of DistributedHierarchy's min_root_dofs and min_subset_dofs"""

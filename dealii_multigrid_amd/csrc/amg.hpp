@@ -401,14 +401,10 @@ namespace mgamd
     return na;
   }
 
+  // inv = M^-1 (row-major n x n, M is destroyed) by Gauss-Jordan with partial pivoting; `what` is the singular matrix's error text
   inline void
-  dense_inverse(const CSR &A, std::vector<double> &inv)
+  invert_dense(std::vector<double> &M, size_t n, std::vector<double> &inv, const char *what)
   {
-    const size_t        n = A.n_rows;
-    std::vector<double> M(n * n, 0.0);
-    for (uint32_t i = 0; i < n; ++i)
-      for (uint32_t k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
-        M[i * n + A.col[k]] = A.val[k];
     inv.assign(n * n, 0.0);
     for (size_t i = 0; i < n; ++i)
       inv[i * n + i] = 1.0;
@@ -419,7 +415,7 @@ namespace mgamd
           if (std::fabs(M[r * n + c]) > std::fabs(M[piv * n + c]))
             piv = r;
         if (std::fabs(M[piv * n + c]) < 1e-300)
-          throw std::runtime_error("AMG: the coarsest matrix is singular");
+          throw std::runtime_error(what);
         if (piv != c)
           for (size_t k = 0; k < n; ++k)
             {
@@ -444,6 +440,17 @@ namespace mgamd
                   }
             }
       }
+  }
+
+  inline void
+  dense_inverse(const CSR &A, std::vector<double> &inv)
+  {
+    const size_t        n = A.n_rows;
+    std::vector<double> M(n * n, 0.0);
+    for (uint32_t i = 0; i < n; ++i)
+      for (uint32_t k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
+        M[i * n + A.col[k]] = A.val[k];
+    invert_dense(M, n, inv, "AMG: the coarsest matrix is singular");
   }
 
   inline AmgHierarchyHost

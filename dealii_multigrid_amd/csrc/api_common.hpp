@@ -7,6 +7,7 @@
 #include "partition.hpp"
 #include "amg.hpp"
 #include "amg_shard.hpp"
+#include "coarse_policy.hpp"
 
 #include <memory>
 #include <string>

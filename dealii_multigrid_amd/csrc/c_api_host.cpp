@@ -81,7 +81,7 @@ mgamd_coarse_plan(const char *coarse_name, uint64_t n_level0_dofs_global, int le
   if (!coarse_name || !plan)
     throw std::invalid_argument("null argument");
   const std::string c   = coarse_name;
-  const bool        amg = c == "amg" || c == "cg_with_amg" || c == "amg_petsc";
+  const bool        amg = is_amg_name(c);
   if (n_level0_dofs_global <= MGAMD_DIRECT_COARSE_MAX_DOFS)
     *plan = MGAMD_COARSE_PLAIN;
   else if (amg && sharded_amg_requested)
@@ -90,6 +90,17 @@ mgamd_coarse_plan(const char *coarse_name, uint64_t n_level0_dofs_global, int le
     *plan = MGAMD_COARSE_NESTED;
   else
     *plan = MGAMD_COARSE_PLAIN;
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_coarse_resolve(const char *name, uint64_t n_level0_dofs, int level0_sharded, int has_nested, int has_amg_global, char used[32])
+{
+  MGAMD_TRY
+  if (!name || !used)
+    throw std::invalid_argument("null argument");
+  const char *k = coarse_kind_name(resolve_coarse_kind(name, n_level0_dofs, level0_sharded != 0, has_nested != 0, has_amg_global != 0));
+  snprintf(used, 32, "%s", k);
   MGAMD_CATCH
 }
 

@@ -517,12 +517,8 @@ namespace mgamd
     double
     dot_raw_global(const T *x, const T *y)
     {
-      if (!comm)
-        return dot_raw(ctx, x, y, (size_t)n_dofs());
-      // constrained entries are zero in every vector of the sharded solver path (homogeneous data), so the owned
-      // prefix [interior | owned tail] counts every DoF exactly once
-      const double local = dot_raw(ctx, x, y, (size_t)tables->n_interior + tables->n_tail_owned);
-      return comm->allreduce_sum_host(local, ctx->stream);
+      const double local = dot_raw(ctx, x, y, n_dot());
+      return comm ? comm->allreduce_sum_host(local, ctx->stream) : local;
     }
     double
     dot(const mgamd_vec &x, const mgamd_vec &y) override

@@ -415,7 +415,8 @@ namespace mgamd
           // key, identical on every sharing rank), zero on constrained DoFs so that every entry is counted once
           std::vector<DofKey> keys;
           lop->tables->export_dof_keys(keys);
-          const size_t nf = (size_t)lop->tables->n_interior + lop->tables->n_tail, nown = (size_t)lop->tables->n_interior + lop->tables->n_tail_owned;
+          // (one rank, by MGAMD_CHEB_KEY_INIT: every unconstrained DoF is owned; n_dot() there counts the constrained rows too)
+          const size_t nf = (size_t)lop->tables->n_interior + lop->tables->n_tail, nown = lop->comm ? lop->n_dot() : nf;
           double       sum = 0;
           for (size_t i = 0; i < n; ++i)
             {
@@ -1563,6 +1564,184 @@ namespace mgamd
     }
   };
 
+  // x = V(b), then n_cycles - 1 corrections x += V(b - A x) (ML's `cycle applications`, ref CoarseSolverNCycles).
+  // vcycle(z, r): z = V(r); residual(rr, b, x): rr = b - A x; rr, zz: scratch of n entries, touched only for n_cycles > 1
+  template <typename T, typename VCYCLE, typename RESIDUAL>
+  static void
+  repeat_cycles(hipStream_t stream, unsigned n_cycles, VCYCLE vcycle, RESIDUAL residual, T *x, const T *b, T *rr, T *zz, size_t n)
+  {
+    vcycle(x, b);
+    for (unsigned c = 1; c < n_cycles; ++c)
+      {
+        residual(rr, b, x);
+        vcycle(zz, rr);
+        hipLaunchKernelGGL(vec_sadd_kernel<T>, grid_for(n), 256, 0, stream, x, T(1), T(1), zz, n);
+      }
+  }
+
+  // ------------------------------------------------------------------------------------------
+  // The coarse solver of a multigrid: x = (approximately) A_0^-1 b on level 0.  Which one runs is resolve_coarse_kind's decision
+  // (coarse_policy.hpp); every buffer is allocated by the one kind that reads it.
+  // ------------------------------------------------------------------------------------------
+  template <typename T>
+  struct CoarseSolver
+  {
+    Ctx                         *ctx;
+    CoarseKind                   kind;
+    LevelOperator<T>            *op0;
+    Chebyshev<T>                *sm0;              // CgChebyshev: the preconditioner
+    MultigridBase               *nested = nullptr; // Nested
+    std::unique_ptr<AmgCycle<T>> amg;              // Amg, CgAmg: one rank, or a sharded level 0 (by request: amg_global)
+    unsigned                     n_cycles;         // Nested, Amg, CgAmg: cycles per application
+    DBuf<T>                      rep_r, rep_z;     // their residual and correction, n_cycles > 1 only
+    DBuf<double>                 inv;              // Direct: dense inverse
+    DBuf<T>                      cg_r, cg_z, cg_p, cg_Ap; // Cg, CgChebyshev, CgAmg
+    DBuf<double>                 cg_S;             // device scalars of the coarse CG (device_pcg): its own, it runs inside an outer CG
+    uint64_t                     iterations = 0;   // inner CG iterations, accumulated
+
+    CoarseSolver(Ctx *c, LevelOperator<T> *op, Chebyshev<T> *smoother, const std::string &name, MultigridBase *nested_mg,
+                 unsigned nested_cycles, const LevelTables *amg_global, uint32_t amg_min_sharded_rows)
+      : ctx(c)
+      , kind(resolve_coarse_kind(name, op->n_dofs(), op->comm != nullptr, nested_mg != nullptr, amg_global != nullptr))
+      , op0(op)
+      , sm0(smoother)
+      , n_cycles(std::max(1u, nested_cycles))
+    {
+      switch (kind)
+        {
+          case CoarseKind::Direct:
+            setup_direct();
+            break;
+          case CoarseKind::Nested:
+            if (nested_mg->number_type != (int)sizeof(T) || nested_mg->outer_tables() != op0->tables.get())
+              throw std::invalid_argument("multigrid: the nested multigrid must act on the DoFs of this hierarchy's level 0 (same number type)");
+            nested = nested_mg;
+            alloc_repeat();
+            break;
+          case CoarseKind::CgAmg:
+            alloc_cg();
+            [[fallthrough]];
+          case CoarseKind::Amg:
+            if (amg_global)
+              amg = std::make_unique<AmgCycle<T>>(ctx, op0, *amg_global, amg_min_sharded_rows);
+            else if (op0->tables->sigma != op0->sigma)
+              throw std::invalid_argument("multigrid: the mass coefficient of level 0's tables (" + std::to_string(op0->tables->sigma) +
+                                          ") was changed after its operator was built with " + std::to_string(op0->sigma) +
+                                          "; the AMG coarse solver assembles its matrix from the tables");
+            else
+              amg = std::make_unique<AmgCycle<T>>(ctx, *op0->tables);
+            alloc_repeat();
+            break;
+          case CoarseKind::CgChebyshev:
+            if (!sm0)
+              throw std::invalid_argument("multigrid: cg_with_chebyshev needs a smoother on level 0");
+            [[fallthrough]];
+          case CoarseKind::Cg:
+            alloc_cg();
+            break;
+        }
+    }
+    void
+    alloc_repeat() // residual and correction of the cycles after the first
+    {
+      if (n_cycles > 1)
+        rep_r.alloc(op0->n_dofs()), rep_z.alloc(op0->n_dofs());
+    }
+    void
+    alloc_cg()
+    {
+      for (DBuf<T> *v : {&cg_r, &cg_z, &cg_p, &cg_Ap})
+        v->alloc(op0->n_dofs());
+      cg_S.alloc(8);
+    }
+
+    // tabulate A_0 column by column through the level operator, symmetrise, invert
+    void
+    setup_direct()
+    {
+      const size_t n = op0->n_dofs();
+      if (n > MGAMD_DIRECT_COARSE_MAX_DOFS)
+        throw std::runtime_error("coarse level too large for the direct solver (" + std::to_string(n) +
+                                 " DoFs): use CoarseGridSolverType cg or cg_with_chebyshev");
+      std::vector<double> A(n * n, 0.0), Ainv;
+      DBuf<T>             e, col;
+      e.alloc(n);
+      col.alloc(n);
+      std::vector<T> h(n);
+      for (size_t j = 0; j < n; ++j)
+        {
+          e.zero(ctx->stream);
+          const T one = T(1);
+          HIP_CHECK(hipMemcpyAsync(e.p + j, &one, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+          op0->vmult_raw(col.p, e.p);
+          HIP_CHECK(hipMemcpyAsync(h.data(), col.p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+          ctx->sync();
+          for (size_t i = 0; i < n; ++i)
+            A[i * n + j] = (double)h[i];
+        }
+      for (size_t i = 0; i < n; ++i)
+        for (size_t j = i + 1; j < n; ++j)
+          A[i * n + j] = A[j * n + i] = 0.5 * (A[i * n + j] + A[j * n + i]);
+      invert_dense(A, n, Ainv, "coarse matrix is singular");
+      inv.upload(Ainv);
+    }
+
+    void
+    solve(T *x, const T *b)
+    {
+      const size_t n = op0->n_dofs();
+      // z = n_cycles applications of `vcycle` to r
+      auto cycles = [&](auto vcycle, T *z, const T *r) {
+        repeat_cycles<T>(ctx->stream, n_cycles, vcycle, [&](T *rr, const T *bb, const T *xx) { op0->residual_raw(rr, bb, xx); }, z, r,
+                         rep_r.p, rep_z.p, n);
+      };
+      auto amg_cycles = [&](T *z, const T *r) { cycles([&](T *zz, const T *rr) { amg->vcycle(zz, rr); }, z, r); };
+      switch (kind)
+        {
+          case CoarseKind::Direct:
+            hipLaunchKernelGGL(dense_matvec_kernel<T>, (int)std::min<size_t>(n, 1024), 256, 0, ctx->stream, inv.p, b, x, (int)n);
+            return;
+          case CoarseKind::Nested:
+            cycles([&](T *zz, const T *rr) { nested->vcycle_level_raw(zz, rr); }, x, b);
+            return;
+          case CoarseKind::Amg:
+            amg_cycles(x, b);
+            return;
+          case CoarseKind::Cg:
+          case CoarseKind::CgChebyshev:
+          case CoarseKind::CgAmg:
+            break;
+        }
+      // SolverCG + ReductionControl(maxiter 10000, abstol 1e-20, reltol 1e-4): ref:multigrid_throughput.cc:888-895;
+      // device-resident iteration, inner products over the GLOBAL vector (owned prefix + one scalar all-reduce on a
+      // sharded level)
+      HIP_CHECK(hipMemcpyAsync(cg_r.p, b, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+      unsigned its = 0;
+      double   res = 0;
+      device_pcg<T>(
+        ctx, op0->comm.get(), cg_S.p, n, op0->n_dot(), x, cg_r.p, cg_z.p, cg_p.p, cg_Ap.p, [&](T *Ap, const T *p) { op0->vmult_raw(Ap, p); },
+        [&](T *z, const T *r) {
+          if (kind == CoarseKind::CgChebyshev)
+            sm0->vmult_raw(z, sm0->tmp.p, r);
+          else if (kind == CoarseKind::CgAmg)
+            amg_cycles(z, r);
+          else
+            HIP_CHECK(hipMemcpyAsync(z, r, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+        },
+        1e-4, 1e-20, 10000, its, res);
+      iterations += its;
+    }
+
+    // the algebraic coarse solver's levels (AmgCycle::layout); empty: no AMG
+    void
+    layout(std::vector<uint32_t> &out) const
+    {
+      out.clear();
+      if (amg)
+        amg->layout(out);
+    }
+  };
+
   // ------------------------------------------------------------------------------------------
   // Multigrid V-cycle  (deal.II Multigrid::level_v_step + PreconditionMG::vmult)
   // ------------------------------------------------------------------------------------------
@@ -1581,8 +1760,7 @@ namespace mgamd
     // finest defect and z is one of the two smoother buffers (no copy_to_mg / copy_from_mg traffic)
     std::vector<const T *> dview;
     std::vector<T *>       sview, tview;
-    std::string                      coarse_type;
-    DBuf<double>                     coarse_inv; // dense inverse for "direct"
+    std::unique_ptr<CoarseSolver<T>> coarse; // level 0
     // The V-cycle restricted to levels 0..collapse_level is a fixed linear map of that level's defect (zero start): on
     // levels this small every kernel is pure launch latency, so the map is tabulated once (n unit defects through the
     // regular level code) and applied as ONE dense matvec.  Not used while stage callbacks are installed (the
@@ -1607,8 +1785,6 @@ namespace mgamd
       graph_exec = nullptr;
       graph_z = graph_r = nullptr;
     }
-    DBuf<T>                          cg_r, cg_z, cg_p, cg_Ap;
-    DBuf<double>                     cg_S; // device scalars of the coarse CG (device_pcg)
     hipGraphExec_t                   graph_exec = nullptr;
     const void                      *graph_z = nullptr, *graph_r = nullptr;
 
@@ -1630,7 +1806,7 @@ namespace mgamd
     void
     setup_local_smoothing(const LevelTables &active) override
     {
-      if (collapse_level || nested)
+      if (collapse_level || coarse->kind == CoarseKind::Nested)
         throw std::invalid_argument("local smoothing: not combinable with a nested coarse solver");
       ls_copy.clear();
       std::vector<uint32_t> g, l;
@@ -1664,12 +1840,6 @@ namespace mgamd
       return ls_copy.empty() ? (size_t)ops[nl - 1]->n_dofs() : ls_n_global;
     }
 
-    uint64_t       coarse_iterations = 0; // inner CG iterations of the coarse solver, accumulated
-    std::unique_ptr<AmgCycle<T>> amg; // coarse solvers "amg", "cg_with_amg": one rank, or a sharded level 0 (by request: amg_global)
-    DBuf<T>                       amg_r, amg_z;
-    MultigridBase *nested   = nullptr; // coarse solver "gmg_vcycle"
-    unsigned       n_cycles = 1;
-
     LevelOperatorBase *
     finest_operator() const override
     {
@@ -1678,14 +1848,12 @@ namespace mgamd
     uint64_t
     coarse_cg_iterations() const override
     {
-      return coarse_iterations;
+      return coarse->iterations;
     }
     void
     amg_layout(std::vector<uint32_t> &out) const override
     {
-      out.clear();
-      if (amg)
-        amg->layout(out);
+      coarse->layout(out);
     }
     void
     vcycle_level_raw(void *z, const void *r) override
@@ -1694,14 +1862,12 @@ namespace mgamd
     }
 
     MultigridT(Ctx *c, unsigned n_levels, LevelOperatorBase *const *levels, Transfer2Base *const *transfers,
-               ChebyshevBase *const *smoothers, const std::string &coarse, MultigridBase *nested_mg, unsigned nested_cycles,
+               ChebyshevBase *const *smoothers, const std::string &coarse_name, MultigridBase *nested_mg, unsigned nested_cycles,
                const LevelTables *amg_global = nullptr, uint32_t amg_min_sharded_rows = AMG_MIN_SHARDED_ROWS_DEFAULT)
     {
       ctx         = c;
       nl          = n_levels;
       number_type = (int)sizeof(T);
-      nested      = nested_mg;
-      n_cycles    = std::max(1u, nested_cycles);
       if (nl < 1)
         throw std::invalid_argument("multigrid: need at least one level");
       for (unsigned l = 0; l < nl; ++l)
@@ -1751,85 +1917,9 @@ namespace mgamd
           sview[l] = S[l]->p;
           tview[l] = Tb[l]->p;
         }
-      // ONE policy for the reference's Trilinos/PETSc choices ("amg", "cg_with_amg", "amg_petsc"):
-      //   coarse level of <= MGAMD_DIRECT_COARSE_MAX_DOFS DoFs (global coarsening ends on one cell): any AMG degenerates to an
-      //     exact solve -> "direct";
-      //   larger coarse level (PMG, HPMG with MinLevel): the library's own smoothed-aggregation AMG on the assembled level matrix
-      //     (amg.hpp, AmgCycle) -> "amg" / "cg_with_amg" (amg_petsc: BoomerAMG's role, the same SA hierarchy -> "amg");
-      //   a `nested` geometric multigrid on level 0's space, if the caller supplies one, takes the coarse solver's place as
-      //     "gmg_vcycle" (the round-1/2 stand-in, still the DEFAULT on a SHARDED coarse level);
-      //   `amg_global` (the global tables of level 0's space), if the caller supplies them, asks for the algebraic multigrid on a
-      //     sharded level 0: replicated setup, sharded cycle (AmgCycle's second set-up) -> "amg" / "cg_with_amg".
-      // Whether a caller builds `nested` or `amg_global` is decided by mgamd_coarse_plan (c_api_host.cpp), for the harness and the
-      // Python hierarchies alike; this constructor validates what it is given.
-      // Never a silent substitution: coarse_used names what runs (harness table column / bench JSON).
-      coarse_type = coarse;
-      const bool amg_like = coarse == "amg" || coarse == "cg_with_amg" || coarse == "amg_petsc";
-      if (amg_global)
-        {
-          if (nested || !amg_like)
-            throw std::invalid_argument("multigrid: the sharded algebraic multigrid takes the place of the AMG coarse solvers (amg, "
-                                        "cg_with_amg, amg_petsc) and excludes a nested multigrid");
-          coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
-          amg         = std::make_unique<AmgCycle<T>>(ctx, ops[0], *amg_global, amg_min_sharded_rows);
-        }
-      else if (nested)
-        {
-          if (!amg_like && coarse != "gmg_vcycle")
-            throw std::invalid_argument("multigrid: a nested multigrid is the stand-in for the AMG coarse solvers only");
-          if (nested->number_type != (int)sizeof(T) || nested->outer_tables() != ops[0]->tables.get())
-            throw std::invalid_argument("multigrid: the nested multigrid must act on the DoFs of this hierarchy's level 0 (same number type)");
-          coarse_type = "gmg_vcycle";
-        }
-      else if (amg_like)
-        {
-          if (ops[0]->n_dofs() <= MGAMD_DIRECT_COARSE_MAX_DOFS)
-            coarse_type = "direct";
-          else
-            {
-              if (ops[0]->comm)
-                throw std::runtime_error("CoarseGridSolverType '" + coarse + "' on a sharded coarse level: the algebraic multigrid is built "
-                                         "from one rank's assembled matrix; use the nested geometric multigrid (gmg_vcycle), cg or "
-                                         "cg_with_chebyshev");
-              coarse_type = coarse == "cg_with_amg" ? "cg_with_amg" : "amg";
-              if (ops[0]->tables->sigma != ops[0]->sigma)
-                throw std::invalid_argument("multigrid: the mass coefficient of level 0's tables (" + std::to_string(ops[0]->tables->sigma) +
-                                            ") was changed after its operator was built with " + std::to_string(ops[0]->sigma) +
-                                            "; the AMG coarse solver assembles its matrix from the tables");
-              amg         = std::make_unique<AmgCycle<T>>(ctx, *ops[0]->tables);
-            }
-        }
-      else if (coarse == "gmg_vcycle")
-        {
-          // no nested multigrid to hand the coarse problem to: a small level is solved exactly, a large one is an error
-          if (ops[0]->n_dofs() > MGAMD_DIRECT_COARSE_MAX_DOFS)
-            throw std::invalid_argument("multigrid: CoarseGridSolverType 'gmg_vcycle' on a level of more than " +
-                                        std::to_string(MGAMD_DIRECT_COARSE_MAX_DOFS) + " DoFs needs a nested multigrid");
-          coarse_type = "direct";
-        }
-      coarse_used = coarse_type;
-      if (coarse_type == "gmg_vcycle" || coarse_type == "amg")
-        {
-          if (n_cycles > 1)
-            cg_r.alloc(ops[0]->n_dofs()), cg_z.alloc(ops[0]->n_dofs());
-        }
-      else if (coarse_type == "direct")
-        setup_direct();
-      else if (coarse_type == "cg" || coarse_type == "cg_with_chebyshev" || coarse_type == "cg_with_amg")
-        {
-          if (coarse_type == "cg_with_amg" && n_cycles > 1)
-            amg_r.alloc(ops[0]->n_dofs()), amg_z.alloc(ops[0]->n_dofs());
-          const size_t n = ops[0]->n_dofs();
-          cg_r.alloc(n);
-          cg_z.alloc(n);
-          cg_p.alloc(n);
-          cg_Ap.alloc(n);
-          cg_S.alloc(8);
-          if (coarse_type == "cg_with_chebyshev" && !sm[0])
-            throw std::invalid_argument("multigrid: cg_with_chebyshev needs a smoother on level 0");
-        }
-      else
-        throw std::invalid_argument("CoarseGridSolverType '" + coarse + "' not implemented");
+      // what runs on level 0: resolve_coarse_kind (coarse_policy.hpp) from the name and what the caller supplies, built by CoarseSolver
+      coarse = std::make_unique<CoarseSolver<T>>(ctx, ops[0], sm[0], coarse_name, nested_mg, nested_cycles, amg_global, amg_min_sharded_rows);
+      coarse_used = coarse_kind_name(coarse->kind);
       setup_collapse();
     }
 
@@ -1849,7 +1939,7 @@ namespace mgamd
         else
           break;
       // an iterative coarse solver (cg, cg_with_chebyshev) is not a linear map of its right-hand side
-      if (lc == 0 || ops[0]->comm || coarse_type != "direct")
+      if (lc == 0 || ops[0]->comm || coarse->kind != CoarseKind::Direct)
         return;
       const size_t        n = ops[lc]->n_dofs();
       std::vector<T>      col(n);
@@ -1858,14 +1948,9 @@ namespace mgamd
       for (size_t j = 0; j < n; ++j)
         {
           // unit defect on level lc (coarser defects zero), the regular cycle below it
-          if (lc + 1 < nl)
-            defect_slab.zero(ctx->stream);
-          else
-            {
-              HIP_CHECK(hipMemsetAsync(dptr[lc], 0, n * sizeof(T), ctx->stream));
-              if (nl > 1)
-                defect_slab.zero(ctx->stream);
-            }
+          if (lc + 1 == nl) // (the finest defect is not part of the slab)
+            HIP_CHECK(hipMemsetAsync(dptr[lc], 0, n * sizeof(T), ctx->stream));
+          defect_slab.zero(ctx->stream);
           HIP_CHECK(hipMemcpyAsync(dptr[lc] + j, &one, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
           level_v_step(lc);
           HIP_CHECK(hipMemcpyAsync(col.data(), sol[lc], n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
@@ -1880,74 +1965,7 @@ namespace mgamd
     ~MultigridT() override
     {
       release_stage_records();
-      if (graph_exec)
-        (void)hipGraphExecDestroy(graph_exec);
-    }
-
-    void
-    setup_direct()
-    {
-      const size_t n = ops[0]->n_dofs();
-      if (n > MGAMD_DIRECT_COARSE_MAX_DOFS)
-        throw std::runtime_error("coarse level too large for the direct solver (" + std::to_string(n) +
-                                 " DoFs): use CoarseGridSolverType cg or cg_with_chebyshev");
-      // dense A_0 column by column through the level operator
-      std::vector<double> A(n * n, 0.0);
-      DBuf<T>             e, col;
-      e.alloc(n);
-      col.alloc(n);
-      std::vector<T> h(n);
-      for (size_t j = 0; j < n; ++j)
-        {
-          e.zero(ctx->stream);
-          const T one = T(1);
-          HIP_CHECK(hipMemcpyAsync(e.p + j, &one, sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-          ops[0]->vmult_raw(col.p, e.p);
-          HIP_CHECK(hipMemcpyAsync(h.data(), col.p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-          ctx->sync();
-          for (size_t i = 0; i < n; ++i)
-            A[i * n + j] = (double)h[i];
-        }
-      // symmetrise and invert by Gauss-Jordan with partial pivoting
-      for (size_t i = 0; i < n; ++i)
-        for (size_t j = i + 1; j < n; ++j)
-          A[i * n + j] = A[j * n + i] = 0.5 * (A[i * n + j] + A[j * n + i]);
-      std::vector<double> inv(n * n, 0.0);
-      for (size_t i = 0; i < n; ++i)
-        inv[i * n + i] = 1.0;
-      for (size_t c = 0; c < n; ++c)
-        {
-          size_t piv = c;
-          for (size_t r = c + 1; r < n; ++r)
-            if (std::fabs(A[r * n + c]) > std::fabs(A[piv * n + c]))
-              piv = r;
-          if (std::fabs(A[piv * n + c]) < 1e-300)
-            throw std::runtime_error("coarse matrix is singular");
-          if (piv != c)
-            for (size_t k = 0; k < n; ++k)
-              {
-                std::swap(A[c * n + k], A[piv * n + k]);
-                std::swap(inv[c * n + k], inv[piv * n + k]);
-              }
-          const double d = 1.0 / A[c * n + c];
-          for (size_t k = 0; k < n; ++k)
-            {
-              A[c * n + k] *= d;
-              inv[c * n + k] *= d;
-            }
-          for (size_t r = 0; r < n; ++r)
-            if (r != c)
-              {
-                const double f = A[r * n + c];
-                if (f != 0.0)
-                  for (size_t k = 0; k < n; ++k)
-                    {
-                      A[r * n + k] -= f * A[c * n + k];
-                      inv[r * n + k] -= f * inv[c * n + k];
-                    }
-              }
-        }
-      coarse_inv.upload(inv);
+      drop_graph();
     }
 
     void
@@ -1983,47 +2001,6 @@ namespace mgamd
       return nl;
     }
 
-    // z = n_cycles V-cycles of the algebraic multigrid applied to r (x = V(r); x += V(r - A x) ...: ML's `cycle applications`,
-    // CoarseSolverNCycles); rr, zz: scratch of n entries (only used for n_cycles > 1)
-    void
-    amg_apply(T *z, const T *r, T *rr, T *zz)
-    {
-      const size_t n = ops[0]->n_dofs();
-      amg->vcycle(z, r);
-      for (unsigned c = 1; c < n_cycles; ++c)
-        {
-          ops[0]->residual_raw(rr, r, z);
-          amg->vcycle(zz, rr);
-          hipLaunchKernelGGL(vec_sadd_kernel<T>, grid_for(n), 256, 0, ctx->stream, z, T(1), T(1), zz, n);
-        }
-    }
-
-    void
-    coarse_cg(T *x, const T *b, int precond_kind) // 0 identity, 1 Chebyshev smoother of level 0, 2 algebraic multigrid
-    {
-      // SolverCG + ReductionControl(maxiter 10000, abstol 1e-20, reltol 1e-4): ref:multigrid_throughput.cc:888-895;
-      // device-resident iteration, inner products over the GLOBAL vector (owned prefix + one scalar all-reduce on a
-      // sharded level)
-      LevelOperator<T> *op  = ops[0];
-      const size_t      n   = op->n_dofs();
-      const size_t      nd  = op->comm ? (size_t)op->tables->n_interior + op->tables->n_tail_owned : n;
-      HIP_CHECK(hipMemcpyAsync(cg_r.p, b, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
-      unsigned its = 0;
-      double   res = 0;
-      device_pcg<T>(
-        ctx, op->comm.get(), cg_S.p, n, nd, x, cg_r.p, cg_z.p, cg_p.p, cg_Ap.p, [&](T *Ap, const T *p) { op->vmult_raw(Ap, p); },
-        [&](T *z, const T *r) {
-          if (precond_kind == 1)
-            sm[0]->vmult_raw(z, sm[0]->tmp.p, r);
-          else if (precond_kind == 2)
-            amg_apply(z, r, amg_r.p, amg_z.p);
-          else
-            HIP_CHECK(hipMemcpyAsync(z, r, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
-        },
-        1e-4, 1e-20, 10000, its, res);
-      coarse_iterations += its;
-    }
-
     // the cycle on level vectors; defect[nl-1] must be set, coarser defects zero.  wide_out (float levels under double outer
     // vectors, finest level only): the last post-smoothing pass stores the level solution there as doubles, see vcycle_raw
     void
@@ -2032,25 +2009,7 @@ namespace mgamd
       if (l == 0)
         {
           stage(3, true, 0);
-          const size_t n = ops[0]->n_dofs();
-          if (coarse_type == "direct")
-            hipLaunchKernelGGL(dense_matvec_kernel<T>, (int)std::min<size_t>(n, 1024), 256, 0, ctx->stream, coarse_inv.p, dptr[0],
-                               S[0]->p, (int)n);
-          else if (coarse_type == "gmg_vcycle")
-            {
-              // x = V(b); then n_cycles - 1 corrections x += V(b - A x)   (AMG applied n_cycles times, ref CoarseSolverNCycles)
-              nested->vcycle_level_raw(S[0]->p, dptr[0]);
-              for (unsigned c = 1; c < n_cycles; ++c)
-                {
-                  ops[0]->residual_raw(cg_r.p, dptr[0], S[0]->p);
-                  nested->vcycle_level_raw(cg_z.p, cg_r.p);
-                  hipLaunchKernelGGL(vec_sadd_kernel<T>, grid_for(n), 256, 0, ctx->stream, S[0]->p, T(1), T(1), cg_z.p, n);
-                }
-            }
-          else if (coarse_type == "amg")
-            amg_apply(S[0]->p, dptr[0], cg_r.p, cg_z.p);
-          else
-            coarse_cg(S[0]->p, dptr[0], coarse_type == "cg_with_chebyshev" ? 1 : (coarse_type == "cg_with_amg" ? 2 : 0));
+          coarse->solve(S[0]->p, dptr[0]);
           sol[0] = S[0]->p;
           stage(3, false, 0);
           return;
@@ -2180,10 +2139,7 @@ namespace mgamd
           dview[L] = defect[L]->p;
           sview[L] = S[L]->p;
           tview[L] = Tb[L]->p;
-          if (sizeof(TO) == sizeof(T))
-            hipLaunchKernelGGL((vec_copy_kernel<T, TO>), grid_for(n), 256, 0, ctx->stream, defect[L]->p, r, n);
-          else
-            hipLaunchKernelGGL((vec_copy_kernel<T, TO>), grid_for(n), 256, 0, ctx->stream, defect[L]->p, r, n);
+          hipLaunchKernelGGL((vec_copy_kernel<T, TO>), grid_for(n), 256, 0, ctx->stream, defect[L]->p, r, n);
         }
       if (nl > 1)
         defect_slab.zero(ctx->stream);
@@ -2221,16 +2177,12 @@ namespace mgamd
         return 0.0;
       if (cb || stage_timing)
         throw std::invalid_argument("time_vcycles: remove the stage callback / stage timing first");
-      const bool graphable = coarse_type == "direct" && !ops[nl - 1]->comm; // (nested cycles are not captured)
+      const bool graphable = coarse->kind == CoarseKind::Direct && !ops[nl - 1]->comm; // (nested cycles are not captured)
       vcycle(z, r); // warm-up: sets kernel attributes, touches memory
       ctx->sync();
       if (use_graph && graphable && (!graph_exec || graph_z != z.data || graph_r != r.data))
         {
-          if (graph_exec)
-            {
-              (void)hipGraphExecDestroy(graph_exec);
-              graph_exec = nullptr;
-            }
+          drop_graph();
           hipGraph_t graph;
           HIP_CHECK(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
           const bool saved = ctx->profile;
@@ -2300,13 +2252,12 @@ namespace mgamd
     Ctx         *ctx = A.ctx;
     const size_t n   = A.n_dofs();
     auto        *op  = static_cast<LevelOperator<T> *>(&A);
-    const size_t nd  = op->comm ? (size_t)op->tables->n_interior + op->tables->n_tail_owned : n;
     std::unique_ptr<mgamd_vec> g(vec_create(ctx, n, A.type)), h(vec_create(ctx, n, A.type)), d(vec_create(ctx, n, A.type)),
       Ad(vec_create(ctx, n, A.type));
     vec_copy(*g, b); // residual r = b - A*0; dst = 0 (ref:multigrid_throughput.cc:1142,1245) is set by device_pcg
     // the V-cycle works on whole vectors (it may alias them as level buffers): hand it the mgamd_vec objects
     device_pcg<T>(
-      ctx, op->comm.get(), ctx->d_cg, n, nd, x.as<T>(), g->as<T>(), h->as<T>(), d->as<T>(), Ad->as<T>(), [&](T *Ap, const T *p) { op->vmult_raw(Ap, p); },
+      ctx, op->comm.get(), ctx->d_cg, n, op->n_dot(), x.as<T>(), g->as<T>(), h->as<T>(), d->as<T>(), Ad->as<T>(), [&](T *Ap, const T *p) { op->vmult_raw(Ap, p); },
       [&](T *z, const T *r) {
         (void)z;
         (void)r;
@@ -2383,7 +2334,6 @@ namespace mgamd
           throw std::invalid_argument("time stepper: a vector of " + std::to_string(v->n) + " entries of " + std::to_string(v->type) +
                                       " bytes where the operator has " + std::to_string(n) + " FP64 DoFs");
       const size_t n_free = (size_t)op->tables->n_interior + op->tables->n_tail; // the constrained DoFs are numbered last
-      const size_t nd     = op->comm ? (size_t)op->tables->n_interior + op->tables->n_tail_owned : n;
       const int    grid   = grid_for(n);
       double      *up     = u.as<double>();
       hipLaunchKernelGGL(theta_source_kernel<double>, grid, 256, 0, ctx->stream, Ad->as<double>(), up, f_old ? f_old->as<double>() : nullptr,
@@ -2392,7 +2342,7 @@ namespace mgamd
       op->residual_raw(g->as<double>(), d->as<double>(), up);
       hipLaunchKernelGGL(theta_rhs_kernel<double>, grid, 256, 0, ctx->stream, g->as<double>(), theta, n_free, n);
       device_pcg<double>(
-        ctx, op->comm.get(), ctx->d_cg, n, nd, delta->as<double>(), g->as<double>(), h->as<double>(), d->as<double>(), Ad->as<double>(),
+        ctx, op->comm.get(), ctx->d_cg, n, op->n_dot(), delta->as<double>(), g->as<double>(), h->as<double>(), d->as<double>(), Ad->as<double>(),
         [&](double *Ap, const double *p) { op->vmult_raw(Ap, p); },
         [&](double *, const double *) {
           if (M)
@@ -2523,13 +2473,9 @@ namespace mgamd
     void
     apply_raw(double *z, const double *r)
     {
-      cycle.vcycle(z, r);
-      for (unsigned c = 1; c < n_cycles; ++c)
-        {
-          A->spmv<SPMV_RESID>(z, rr.p, r);
-          cycle.vcycle(zz.p, rr.p);
-          hipLaunchKernelGGL(vec_sadd_kernel<double>, grid_for(A->n_rows), 256, 0, A->ctx->stream, z, 1.0, 1.0, zz.p, (size_t)A->n_rows);
-        }
+      repeat_cycles<double>(
+        A->ctx->stream, n_cycles, [&](double *zc, const double *rc) { cycle.vcycle(zc, rc); },
+        [&](double *res, const double *b, const double *x) { A->spmv<SPMV_RESID>(x, res, b); }, z, r, rr.p, zz.p, A->n_rows);
       HIP_CHECK(hipGetLastError());
     }
     void

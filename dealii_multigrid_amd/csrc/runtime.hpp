@@ -192,6 +192,14 @@ namespace mgamd
     {
       return tables->n_dofs;
     }
+    // length of this rank's part of an inner product over the GLOBAL vector.  Sharded: the owned prefix [interior | owned tail],
+    // which counts every DoF exactly once over the ranks (constrained entries are zero in every vector of the sharded solver
+    // path: homogeneous data).  One rank: the whole vector, constrained rows included.
+    size_t
+    n_dot() const
+    {
+      return comm ? (size_t)tables->n_interior + tables->n_tail_owned : (size_t)n_dofs();
+    }
     virtual void
     vmult(mgamd_vec &dst, const mgamd_vec &src) = 0;
     // dst = C^T M C src: the mass matrix of the level's space; rows and columns of constrained DoFs are zero (not on the

@@ -25,6 +25,12 @@ int mgamd_ctx_kernel_profile_read(mgamd_ctx *ctx, double *total_ms, uint64_t *n_
  * p = 1 and the persistent 17-point lattice kernels, one word less than SURVEY 8(d)'s figure in `algorithmic_bytes`) */
 int mgamd_ctx_kernel_profile_bytes_moved(mgamd_ctx *ctx, double *bytes_moved);
 
+/* the coarse solver a multigrid runs when asked for `name` on a level 0 of n_level0_dofs DoFs (sharded or not), with or without a
+ * nested multigrid / the global DoFs of the sharded AMG: what mgamd_mg_coarse_solver_used() will report, or the error
+ * mgamd_mg_create* will return for it (the checks of the objects themselves aside).  Host only, no GPU. */
+int mgamd_debug_coarse_resolve(const char *name, uint64_t n_level0_dofs, int level0_sharded, int has_nested, int has_amg_global,
+                               char used[32]);
+
 /* ---- the algebraic multigrid of the "amg" coarse solvers, for tests against an independent restatement ----
  * host hierarchy (amg.hpp) of the smoothed aggregation built on the level's assembled matrix (mgamd_dofs_matrix); level 0 finest */
 typedef struct mgamd_amg_host mgamd_amg_host;

@@ -189,6 +189,16 @@ def test_cg_with_amg_equals_oracle(mgamd, oracle, ctx, amg_oracles, monkeypatch)
     x = ha.fine_operator.initialize_dof_vector()
     it, _ = mgamd.solve_cg(ha.fine_operator, ha.mg, x, b, 1e-4)
     assert it == itref and rel_err(x.to_host(), xref) <= TOL_SOL, (it, itref)
+    # two AMG cycles per application of the coarse CG's preconditioner (annulus L=6, 9 763 rows): the one coarse solver x cycle
+    # count whose residual / correction scratch no other test reaches
+    h2 = _one_level(mgamd, ctx, monkeypatch, "annulus", 6, 2, 2, coarse="cg_with_amg")
+    d2, o2 = amg_oracles(h2, "annulus", 6)
+    b2 = h2.fine_operator.initialize_dof_vector()
+    h2.fine_operator.rhs(b2)
+    xref2, itref2, _ = oracle.pcg(ao.csr(*d2.matrix()), b2.to_host(), o2.precondition(2), 1e-4)
+    err2 = rel_err(_apply(mgamd, ctx, h2.mg, b2.to_host()), xref2)
+    print(f"cg_with_amg x 2, annulus L=6: iterations {h2.mg.coarse_iterations()} (oracle {itref2}), rel. error {err2:.2e}")
+    assert err2 <= TOL_SOL and h2.mg.coarse_iterations() == itref2, (err2, h2.mg.coarse_iterations(), itref2)
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,6 @@
 """The hierarchy policy of the library (include/mgamd.h, "Hierarchy policy"; no GPU): which (mesh, degree) pairs form the levels of
-every multigrid type, what a coarse solver needs next to the levels, and the defaults of the two-tier partition.  The harness, the
-C++ layer and the Python hierarchies all build what these three functions say."""
+every multigrid type, what a coarse solver needs next to the levels, which coarse solver then runs, and the defaults of the two-tier
+partition.  The harness, the C++ layer and the Python hierarchies all build what these functions say."""
 import ctypes as C
 import itertools
 
@@ -60,6 +60,58 @@ def test_coarse_plan(mgamd, name):
         assert mgamd._coarse_plan(name, 4096, distributed, requested) == PLAIN, (distributed, requested)
         assert mgamd._coarse_plan(name, 4097, distributed, requested) == ABOVE[name][i], (distributed, requested)
     assert (mgamd.COARSE_PLAIN, mgamd.COARSE_NESTED, mgamd.COARSE_SHARDED_AMG) == (PLAIN, NESTED, SHARDED_AMG)
+
+
+# What a multigrid RUNS (mgamd_debug_coarse_resolve): coarse_solver_used(), or the error of its construction.  Errors, by the texts
+# the library raises (status: 3 MGAMD_ERR_INVALID, 1 MGAMD_ERR):
+ERRORS = {
+    "G": (3, "multigrid: the sharded algebraic multigrid takes the place of the AMG coarse solvers (amg, cg_with_amg, amg_petsc) and "
+             "excludes a nested multigrid"),
+    "N": (3, "multigrid: a nested multigrid is the stand-in for the AMG coarse solvers only"),
+    "S": (1, "CoarseGridSolverType '{name}' on a sharded coarse level: the algebraic multigrid is built from one rank's assembled "
+             "matrix; use the nested geometric multigrid (gmg_vcycle), cg or cg_with_chebyshev"),
+    "V": (3, "multigrid: CoarseGridSolverType 'gmg_vcycle' on a level of more than 4096 DoFs needs a nested multigrid"),
+    "U": (3, "CoarseGridSolverType '{name}' not implemented"),
+}
+# name -> (at 4096 DoFs, at 4097 DoFs) for (sharded, nested, amg_global) =
+#         (0,0,0)                   (0,0,1)                         (0,1,0)                       (0,1,1)
+#         (1,0,0)                   (1,0,1)                         (1,1,0)                       (1,1,1)
+RESOLVE = {
+    "amg": [("direct", "amg"), ("amg", "amg"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G"),
+            ("direct", "S"), ("amg", "amg"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G")],
+    "amg_petsc": [("direct", "amg"), ("amg", "amg"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G"),
+                  ("direct", "S"), ("amg", "amg"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G")],
+    "cg_with_amg": [("direct", "cg_with_amg"), ("cg_with_amg", "cg_with_amg"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G"),
+                    ("direct", "S"), ("cg_with_amg", "cg_with_amg"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G")],
+    "gmg_vcycle": [("direct", "V"), ("G", "G"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G"),
+                   ("direct", "V"), ("G", "G"), ("gmg_vcycle", "gmg_vcycle"), ("G", "G")],
+    "direct": [("direct", "direct"), ("G", "G"), ("N", "N"), ("G", "G"),
+               ("direct", "direct"), ("G", "G"), ("N", "N"), ("G", "G")],
+    "cg": [("cg", "cg"), ("G", "G"), ("N", "N"), ("G", "G"),
+           ("cg", "cg"), ("G", "G"), ("N", "N"), ("G", "G")],
+    "cg_with_chebyshev": [("cg_with_chebyshev", "cg_with_chebyshev"), ("G", "G"), ("N", "N"), ("G", "G"),
+                          ("cg_with_chebyshev", "cg_with_chebyshev"), ("G", "G"), ("N", "N"), ("G", "G")],
+    "ilu": [("U", "U"), ("G", "G"), ("N", "N"), ("G", "G"),
+            ("U", "U"), ("G", "G"), ("N", "N"), ("G", "G")],
+}
+
+
+@pytest.mark.parametrize("name", sorted(RESOLVE))
+def test_coarse_resolve(mgamd, name):
+    for i, (sharded, nested, amg_global) in enumerate(itertools.product((False, True), repeat=3)):
+        for n_dofs, expected in zip((4096, 4097), RESOLVE[name][i]):
+            case = (n_dofs, sharded, nested, amg_global)
+            used = C.create_string_buffer(32)
+            status = mgamd._lib.mgamd_debug_coarse_resolve(name.encode(), C.c_uint64(n_dofs), int(sharded), int(nested), int(amg_global), used)
+            if expected in ERRORS:
+                code, text = ERRORS[expected]
+                assert status == code, case
+                assert mgamd._lib.mgamd_last_error().decode() == text.format(name=name), case
+                with pytest.raises(mgamd.MgamdError):
+                    mgamd._coarse_resolve(name, *case)
+            else:
+                assert status == 0 and used.value.decode() == expected, case
+                assert mgamd._coarse_resolve(name, *case) == expected, case
 
 
 def test_partition_defaults(mgamd):
