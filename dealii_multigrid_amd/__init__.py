@@ -29,6 +29,8 @@ F64, F32 = 8, 4
 # levels of the sharded AMG with at most this many global rows are replicated (mgamd.h: a guess, unmeasured on multi-GPU hardware)
 AMG_MIN_SHARDED_ROWS_DEFAULT = 20000
 INVALID_DOF = 0xFFFFFFFF
+# Triangulation.set_dirichlet_faces: every face of the cube is Dirichlet (the default, the reference's boundary id 0)
+ALL_DIRICHLET = 0x3F
 
 
 class MgamdError(RuntimeError):
@@ -163,6 +165,19 @@ class Triangulation:
         _chk(_lib.mgamd_tria_has_coefficient(self._h, C.byref(has)))
         return bool(has.value)
 
+    def set_dirichlet_faces(self, mask: int):
+        """which faces of the cube [-1, 1]^3 are Dirichlet: bit f = 2 axis + side (0: x = -1, 1: x = +1, ... 5: z = +1); the other
+        faces are natural (Neumann: zero flux unless rhs_boundary_flux adds one).  Default 0x3F.  coarsen() inherits the mask; DoFs
+        copy it when they are built (mgamd_tria_set_dirichlet_faces).  MgamdError for a mask > 63."""
+        if int(mask) < 0:
+            raise MgamdError(f"dirichlet_faces mask {mask} refused: it is a 6-bit mask, 0 to 63")
+        _chk(_lib.mgamd_tria_set_dirichlet_faces(self._h, C.c_uint(int(mask))))
+
+    def dirichlet_faces(self) -> int:
+        m = C.c_uint()
+        _chk(_lib.mgamd_tria_get_dirichlet_faces(self._h, C.byref(m)))
+        return m.value
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mgamd_tria_destroy(self._h)
@@ -179,6 +194,31 @@ def create_geometric_coarsening_sequence(fine: Triangulation, coarse_coefficient
         if coarse_coefficient is not None:
             seq[-1].set_coefficient(coarse_coefficient(seq[-1]))
     return seq[::-1]
+
+
+def _flux_array(q):
+    """six face fluxes as a contiguous double array: a sequence of 6 values or {face: value}"""
+    if isinstance(q, dict):
+        a = np.zeros(6)
+        for f, v in q.items():
+            if not 0 <= int(f) <= 5:
+                raise MgamdError(f"boundary flux: face {f} refused, the faces are 0 to 5")
+            a[int(f)] = v
+        return a
+    a = np.ascontiguousarray(q, np.float64)
+    if a.shape != (6,):
+        raise ValueError(f"boundary flux: {a.shape} values for the 6 faces")
+    return a
+
+
+def _apply_dirichlet_faces(fine: Triangulation, mg_type: str, dirichlet_faces):
+    """Hierarchy(dirichlet_faces=...): set on the mesh (the carrier, as for the coefficient) before anything is built from it; the
+    local-smoothing types refuse another mask than 63 by name"""
+    if dirichlet_faces is not None:
+        fine.set_dirichlet_faces(dirichlet_faces)
+    if mg_type in ("HMG-local", "HPMG-local") and fine.dirichlet_faces() != ALL_DIRICHLET:
+        raise MgamdError(f"Type '{mg_type}' with the dirichlet_faces mask {fine.dirichlet_faces()}: not implemented (local smoothing "
+                         "takes the mask 63 only)")
 
 
 def _apply_coefficient(fine: Triangulation, coefficient):
@@ -266,6 +306,19 @@ class DoFs:
         lo, hi = C.c_double(), C.c_double()
         _chk(_lib.mgamd_dofs_coefficient_range(self._h, C.byref(lo), C.byref(hi)))
         return lo.value, hi.value
+
+    def dirichlet_faces(self) -> int:
+        """the dirichlet_faces mask these DoFs were built with (their mesh's at that time)"""
+        m = C.c_uint()
+        _chk(_lib.mgamd_dofs_dirichlet_faces(self._h, C.byref(m)))
+        return m.value
+
+    def rhs_boundary_flux(self, q):
+        """boundary load of one constant flux per face, host vector: sum_f q[f] int_{face f} phi_i, through the hanging-node
+        constraints, constrained rows 0.  q: 6 values or {face: value}.  MgamdError for a non-zero flux on a Dirichlet face."""
+        q, b = _flux_array(q), np.zeros(self.n_dofs)
+        _chk(_lib.mgamd_dofs_rhs_boundary_flux(self._h, _ptr(q), _ptr(b)))
+        return b
 
     def keys(self):
         k = np.zeros((self.n_dofs, 5), np.int32)
@@ -568,6 +621,11 @@ class Operator:
     def rhs(self, b: Vector, kind: int = 0):
         """Operator::rhs; kind = SimulationType (0 "Constant": f = 1, g = 0; 1 "Gaussian")"""
         _chk(_lib.mgamd_level_op_rhs_kind(self._h, kind, b._h))
+
+    def rhs_boundary_flux(self, b: Vector, q):
+        """b = boundary load of one constant flux per face (DoFs.rhs_boundary_flux), completed over the ranks like rhs"""
+        q = _flux_array(q)
+        _chk(_lib.mgamd_level_op_rhs_boundary_flux(self._h, _ptr(q), b._h))
 
     def distribute(self, x: Vector, kind: int = 0):
         """constraints.distribute(solution): Dirichlet values of `kind`, hanging nodes interpolated"""
@@ -1049,7 +1107,7 @@ class Hierarchy:
 
     def __init__(self, ctx: Context, geometry="quadrant", n_ref_global=3, degree=1, mg_type="HMG-global", n_ref_local=0,
                  smoother_degree=3, smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64,
-                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0, coefficient=None, coarse_coefficient=None):
+                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0, coefficient=None, coarse_coefficient=None, dirichlet_faces=None):
         """mass_coefficient: sigma >= 0 of the operator K + sigma M (-Laplace u + sigma u) on every level, the stand-in and nested
         hierarchies included; the local-smoothing types refuse a non-zero value
         coefficient: the diffusion coefficient a of -div(a grad u) + sigma u: f(x, y, z), evaluated at the leaf centres of the
@@ -1058,7 +1116,10 @@ class Hierarchy:
         the mesh is the carrier of the coefficient, and the caller's object shows them afterwards.
         coarse_coefficient: g(tria) -> values, called for every coarse mesh of the coarsening sequence in place of the mean over each
         leaf (create_geometric_coarsening_sequence); refused for the types without coarse meshes (PMG, HPMG-local, AMG, AMGPETSc),
-        where it would have no effect.  The local-smoothing types refuse a coefficient."""
+        where it would have no effect.  The local-smoothing types refuse a coefficient.
+        dirichlet_faces: 6-bit mask of the Dirichlet faces (Triangulation.set_dirichlet_faces); None keeps what the mesh carries (63
+        for a named geometry).  Like the coefficient it is SET ON a caller's Triangulation, and every level inherits it.  The
+        local-smoothing types refuse another mask than 63; mask 0 with mass_coefficient 0 (singular) is refused by the library."""
         self.ctx = ctx
         self.mass_coefficient = mass_coefficient
         # `geometry` may also be a caller-built Triangulation (Triangulation.from_leaves)
@@ -1068,6 +1129,7 @@ class Hierarchy:
                              "matrices have no coefficient)")
         if coarse_coefficient is not None and mg_type not in ("HMG-global", "HPMG"):
             raise MgamdError(f"Type '{mg_type}' has no coarse meshes: coarse_coefficient would have no effect")
+        _apply_dirichlet_faces(fine, mg_type, dirichlet_faces)
         _apply_coefficient(fine, coefficient)
         if mg_type in ("AMG", "AMGPETSc"):
             # solve_with_amg (ref:multigrid_throughput.cc:1877-1966): no multigrid levels; CG on the assembled matrix of the one
@@ -1142,8 +1204,9 @@ class DistributedHierarchy:
                  smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64, hanging_weight=2.0, max_brick=-1,
                  min_root_dofs=MIN_ROOT_DOFS_DEFAULT, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None,
                  min_subset_dofs=MIN_SUBSET_DOFS_DEFAULT, sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT,
-                 mass_coefficient=0.0, coefficient=None, coarse_coefficient=None):
-        """coefficient, coarse_coefficient: the diffusion coefficient, as for Hierarchy (every rank passes the same; set on the
+                 mass_coefficient=0.0, coefficient=None, coarse_coefficient=None, dirichlet_faces=None):
+        """dirichlet_faces: as for Hierarchy (every rank passes the same)
+        coefficient, coarse_coefficient: the diffusion coefficient, as for Hierarchy (every rank passes the same; set on the
         caller's Triangulation if one is passed; the coarsening sequence exists for every type here, so coarse_coefficient always acts)
         sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
         smoothed-aggregation AMG cut into rows over the ranks (replicated setup, sharded cycle; levels of at most
@@ -1152,6 +1215,7 @@ class DistributedHierarchy:
         if mg_type not in ("HMG-global", "PMG", "HPMG"):
             raise MgamdError(f"Type '{mg_type}' not implemented")
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global)
+        _apply_dirichlet_faces(fine, mg_type, dirichlet_faces)
         _apply_coefficient(fine, coefficient)
         self.mesh_sequence = create_geometric_coarsening_sequence(fine, coarse_coefficient)
         # (mesh index, degree) of every multigrid level, coarse -> fine (ref:multigrid_throughput.cc:1506-1571)

@@ -74,6 +74,10 @@ namespace mgamd
     if (global.sigma != local_sigma)
       throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the mass coefficient " + std::to_string(global.sigma) +
                                   ", the local level " + std::to_string(local_sigma) + ": the assembled matrix would be another operator's");
+    // and for the faces that are Dirichlet
+    if (global.dirichlet_faces != local.dirichlet_faces)
+      throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the dirichlet_faces mask " + std::to_string(global.dirichlet_faces) +
+                                  ", the local level " + std::to_string(local.dirichlet_faces) + ": the assembled matrix would be another operator's");
     // the same holds for the diffusion coefficient of the cells this rank works on
     // (cell by cell: both tables must describe the same mesh; another mesh is refused here, before the keys are matched)
     if (global.tria->cells.size() != local.tria->cells.size())

@@ -413,6 +413,15 @@ mgamd_level_op_rhs_kind(mgamd_level_op *op, int kind, mgamd_vec *rhs)
 }
 
 int
+mgamd_level_op_rhs_boundary_flux(mgamd_level_op *op, const double q[6], mgamd_vec *rhs)
+{
+  MGAMD_TRY
+  REQUIRE(op && q && rhs);
+  op->op->rhs_boundary_flux(*rhs, q);
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_distribute(mgamd_level_op *op, int kind, mgamd_vec *x)
 {
   MGAMD_TRY

@@ -223,6 +223,7 @@ mgamd_dofs_amg_setup_info(const mgamd_dofs *d, uint32_t *n_levels, uint32_t *row
   MGAMD_TRY
   if (!d || !n_levels)
     throw std::invalid_argument("null argument");
+  d->tables->refuse_singular("AMG setup");
   const AmgHierarchyHost H = build_smoothed_aggregation(assemble_level_matrix(*d->tables));
   *n_levels                = (uint32_t)H.levels.size();
   for (uint32_t l = 0; l < H.levels.size() && l < max_levels; ++l)
@@ -518,6 +519,48 @@ mgamd_tria_has_coefficient(const mgamd_tria *t, int *has)
   if (!t || !has)
     throw std::invalid_argument("null argument");
   *has = t->tria->coefficient.empty() ? 0 : 1;
+  MGAMD_CATCH
+}
+
+int
+mgamd_tria_set_dirichlet_faces(mgamd_tria *t, unsigned mask)
+{
+  MGAMD_TRY
+  if (!t)
+    throw std::invalid_argument("null argument");
+  t->tria->set_dirichlet_faces(mask); // (refuses a mask > 63)
+  MGAMD_CATCH
+}
+
+int
+mgamd_tria_get_dirichlet_faces(const mgamd_tria *t, unsigned *mask)
+{
+  MGAMD_TRY
+  if (!t || !mask)
+    throw std::invalid_argument("null argument");
+  *mask = t->tria->dirichlet_faces;
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_dirichlet_faces(const mgamd_dofs *d, unsigned *mask)
+{
+  MGAMD_TRY
+  if (!d || !mask)
+    throw std::invalid_argument("null argument");
+  *mask = d->tables->dirichlet_faces;
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_rhs_boundary_flux(const mgamd_dofs *d, const double q[6], double *out)
+{
+  MGAMD_TRY
+  if (!d || !q || !out)
+    throw std::invalid_argument("null argument");
+  std::vector<double> b;
+  d->tables->compute_rhs_boundary_flux(q, b); // (refuses a flux on a Dirichlet face, by name)
+  std::copy(b.begin(), b.end(), out);
   MGAMD_CATCH
 }
 

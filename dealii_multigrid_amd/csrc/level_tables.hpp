@@ -10,7 +10,8 @@
 //      I  slot-interior DoFs (strictly inside a slot's node lattice; touched by that slot only),
 //         contiguous per slot in lattice-lexicographic order  -> implicit, coalesced addressing
 //      T  'tail': unconstrained DoFs on slot shells (shared between slots), in first-touch order
-//      D  Dirichlet DoFs (boundary id 0 = whole boundary, ref:multigrid_throughput.cc:1585-1591)
+//      D  Dirichlet DoFs: those on a Dirichlet face of the mesh (Tria::dirichlet_faces; the default, every face, is the reference's
+//         boundary id 0 = whole boundary, ref:multigrid_throughput.cc:1585-1591).  DoFs on natural faces only are T (or H)
 //      H  hanging-node DoFs (own DoFs of fine faces/edges next to a coarser cell); like deal.II
 //         they are part of the vector (n_dofs parity) but only ever see the identity row
 //         (ref:include/operator.h:170-172).
@@ -376,6 +377,22 @@ namespace mgamd
     // were built (a later Tria::set_coefficient does not reach them); empty: a = 1.  The slots carry it too (SlotGroup::a): a
     // brick is only formed of cells with the bit-identical value (DESIGN.md "Diffusion coefficient").
     std::vector<double> coefficient;
+    // Which faces of the cube are Dirichlet (bit f = 2 axis + side; Tria::dirichlet_faces at the time these tables were built).  A
+    // DoF on natural faces only is an ordinary unknown: tail class, or hanging if it hangs (DESIGN.md "Boundary conditions").
+    unsigned dirichlet_faces = Tria::ALL_DIRICHLET;
+    // no Dirichlet face and sigma == 0: the constants are in the operator's kernel.  Operators stay available; solvers refuse.
+    bool
+    singular() const
+    {
+      return dirichlet_faces == 0 && sigma == 0.0;
+    }
+    void
+    refuse_singular(const char *who) const
+    {
+      if (singular())
+        throw std::invalid_argument(std::string(who) + ": refused, the operator is singular: dirichlet_faces mask 0 (no Dirichlet face) with "
+                                    "mass coefficient sigma = 0 has the constants in its kernel, and no mean-value projection is built");
+    }
     double
     coefficient_of(size_t cell) const
     {
@@ -425,7 +442,11 @@ namespace mgamd
       , shared(shared)
       , my_rank(my_rank)
     {
-      coefficient = t.coefficient;
+      coefficient     = t.coefficient;
+      dirichlet_faces = t.dirichlet_faces;
+      if (ls_level && dirichlet_faces != Tria::ALL_DIRICHLET)
+        throw std::invalid_argument("local-smoothing level tables of a triangulation with the dirichlet_faces mask " +
+                                    std::to_string(dirichlet_faces) + ": not implemented, only the mask 63");
       if (ls_level && !coefficient.empty())
         throw std::invalid_argument("local-smoothing level tables of a triangulation with a diffusion coefficient: not implemented "
                                     "(the refinement-edge matrices have no coefficient)");
@@ -488,12 +509,17 @@ namespace mgamd
       const int      dm = (a[0] % p ? 1 : 0) | (a[1] % p ? 2 : 0) | (a[2] % p ? 4 : 0);
       return pack_key((c.i * p + a[0]) * S, (c.j * p + a[1]) * S, (c.k * p + a[2]) * S, dm, c.level);
     }
+    // does the DoF lie on at least one Dirichlet face of the mesh (dirichlet_faces; edges and corners shared with one count)?
     bool
-    key_on_boundary(uint64_t key) const
+    key_on_dirichlet_face(uint64_t key) const
     {
-      const DofKey   k   = unpack_key(key);
-      const int32_t  top = p << LMAX;
-      return k.px == 0 || k.py == 0 || k.pz == 0 || k.px == top || k.py == top || k.pz == top;
+      const DofKey  k    = unpack_key(key);
+      const int32_t top  = p << LMAX;
+      const int32_t x[3] = {k.px, k.py, k.pz};
+      for (int d = 0; d < 3; ++d)
+        if ((x[d] == 0 && ((dirichlet_faces >> (2 * d)) & 1)) || (x[d] == top && ((dirichlet_faces >> (2 * d + 1)) & 1)))
+          return true;
+      return false;
     }
 
     // global DoF index gathered by cell ci at local node (a0,a1,a2); INVALID_DOF for Dirichlet.
@@ -797,6 +823,64 @@ namespace mgamd
         b[i] = 0.0;
     }
 
+    // boundary load of a constant flux q[f] through every natural face f of the cube:  b_i = sum_f q_f int_{Gamma_f} phi_i.  Per
+    // boundary cell face the face nodes get q h^2 m (x) m; then C^T through the hanging-node constraints, as the volume load;
+    // constrained rows 0.  Independent of a and sigma.  A non-zero flux on a Dirichlet face is refused by name.
+    void
+    compute_rhs_boundary_flux(const double q[6], std::vector<double> &b) const
+    {
+      static const char *const face_name[6] = {"x=-1", "x=+1", "y=-1", "y=+1", "z=-1", "z=+1"};
+      for (int f = 0; f < 6; ++f)
+        {
+          if (!std::isfinite(q[f]))
+            throw std::invalid_argument("boundary flux on face " + std::to_string(f) + " (" + face_name[f] + ") is not finite");
+          if (q[f] != 0.0 && ((dirichlet_faces >> f) & 1))
+            throw std::invalid_argument("boundary flux " + std::to_string(q[f]) + " on face " + std::to_string(f) + " (" + face_name[f] +
+                                        ") refused: the face is Dirichlet (dirichlet_faces mask " + std::to_string(dirichlet_faces) +
+                                        "), a flux load needs a natural face");
+        }
+      b.assign(n_dofs, 0.0);
+      const int           n = p + 1, n3 = n * n * n;
+      std::vector<double> load(n3);
+      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
+        {
+          if (!cell_is_local(ci))
+            continue;
+          const Cell    &c      = tria->cells[ci];
+          const uint32_t last   = (1u << c.level) - 1;
+          const uint32_t ijk[3] = {c.i, c.j, c.k};
+          const double   h      = 2.0 / (double)(1u << c.level);
+          bool           any    = false;
+          std::fill(load.begin(), load.end(), 0.0);
+          for (int f = 0; f < 6; ++f)
+            {
+              const int d = f >> 1, side = f & 1;
+              if (q[f] == 0.0 || ijk[d] != (side ? last : 0u))
+                continue;
+              any          = true;
+              const int st[3] = {1, n, n * n};
+              const int e = (d + 1) % 3, g = (d + 2) % 3;
+              for (int ae = 0; ae < n; ++ae)
+                for (int ag = 0; ag < n; ++ag)
+                  load[side * p * st[d] + ae * st[e] + ag * st[g]] += q[f] * h * h * fe.m[ae] * fe.m[ag];
+            }
+          if (!any)
+            continue;
+          interpolate_hanging(fe, tria->masks[ci], load.data(), true);
+          for (int z = 0; z < n; ++z)
+            for (int y = 0; y < n; ++y)
+              for (int x = 0; x < n; ++x)
+                {
+                  const int      a[3] = {x, y, z};
+                  const uint32_t idx  = cell_node_index(ci, a);
+                  if (idx != INVALID_DOF)
+                    b[idx] += load[(z * n + y) * n + x];
+                }
+        }
+      for (uint32_t i = first_constrained(); i < n_dofs; ++i)
+        b[i] = 0.0;
+    }
+
     // constraints.distribute(x) for data `kind`: Dirichlet DoFs = g at their support point, hanging-node DoFs = the
     // interpolant of their parent face/edge (x holds the solved free DoFs)
     void
@@ -813,7 +897,7 @@ namespace mgamd
                 {
                   const int      a[3] = {xx, y, z};
                   const uint64_t key  = resolved_key(ci, a);
-                  if (!key_on_boundary(key))
+                  if (!key_on_dirichlet_face(key))
                     continue;
                   const int32_t *gi = keymap.find(key);
                   if (gi && (uint32_t)*gi >= first_dirichlet() && (uint32_t)*gi < first_dirichlet() + n_dirichlet)
@@ -1128,7 +1212,7 @@ namespace mgamd
                 }
               else
                 key = own_key(anchor, a);
-              const int32_t id = classify(key, key_on_boundary(key) ? 1 : ((ls_level && edge_keys.find(key)) ? 4 : 0));
+              const int32_t id = classify(key, key_on_dirichlet_face(key) ? 1 : ((ls_level && edge_keys.find(key)) ? 4 : 0));
               g.shell_idx[(size_t)r.slot * g.n_shell + s] = (uint32_t)id; // provisional
             }
         }

@@ -96,6 +96,20 @@ namespace mgamd
       check(mgamd_tria_has_coefficient(h.get(), &has));
       return has != 0;
     }
+    // Which faces of the cube are Dirichlet: bit f = 2 axis + side (0: x = -1, 1: x = +1, ... 5: z = +1); the others are natural
+    // (Neumann).  Default 0x3F.  coarsen() inherits it; DoFs copy it when they are built (mgamd_tria_set_dirichlet_faces).
+    void
+    set_dirichlet_faces(unsigned mask)
+    {
+      check(mgamd_tria_set_dirichlet_faces(h.get(), mask));
+    }
+    unsigned
+    dirichlet_faces() const
+    {
+      unsigned mask = 0;
+      check(mgamd_tria_get_dirichlet_faces(h.get(), &mask));
+      return mask;
+    }
     // local smoothing: all cells of refinement level `level`, active or not (the level of DoFHandler::distribute_mg_dofs)
     std::shared_ptr<Triangulation>
     level_mesh(unsigned level) const
@@ -319,6 +333,14 @@ namespace mgamd
       double lo = 1.0, hi = 1.0;
       check(mgamd_dofs_coefficient_range(h.get(), &lo, &hi));
       return {lo, hi};
+    }
+    // the dirichlet_faces mask these DoFs were built with
+    unsigned
+    dirichlet_faces() const
+    {
+      unsigned mask = 0;
+      check(mgamd_dofs_dirichlet_faces(h.get(), &mask));
+      return mask;
     }
     mgamd_dofs_info_t info;
 
@@ -673,6 +695,12 @@ namespace mgamd
     rhs(Vector &system_rhs, int simulation_kind = 0) const
     {
       check(mgamd_level_op_rhs_kind(h.get(), simulation_kind, system_rhs.get()));
+    }
+    // boundary load of one constant flux q[f] per natural face f (mgamd_level_op_rhs_boundary_flux); add it to rhs()
+    void
+    rhs_boundary_flux(Vector &load, const std::array<double, 6> &q) const
+    {
+      check(mgamd_level_op_rhs_boundary_flux(h.get(), q.data(), load.get()));
     }
     // constraints.distribute(solution)
     void

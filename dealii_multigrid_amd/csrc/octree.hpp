@@ -203,6 +203,18 @@ namespace mgamd
     {
       return coefficient.empty() ? 1.0 : coefficient[cell];
     }
+    // Boundary condition per face of the cube [-1,1]^3, face f = 2 axis + side (0: x = -1, 1: x = +1, ... 5: z = +1): bit f set
+    // means face f is Dirichlet, clear means natural (Neumann).  The default is the reference's boundary id 0 on the whole surface
+    // (ref:multigrid_throughput.cc:1585-1593).  Level tables copy it when they are built (DESIGN.md "Boundary conditions").
+    static constexpr unsigned ALL_DIRICHLET = 0x3F;
+    unsigned                  dirichlet_faces = ALL_DIRICHLET;
+    void
+    set_dirichlet_faces(unsigned mask)
+    {
+      if (mask > ALL_DIRICHLET)
+        throw std::invalid_argument("dirichlet_faces mask " + std::to_string(mask) + " refused: the cube has six faces, the mask is at most 63");
+      dirichlet_faces = mask;
+    }
 
     static Tria
     create(const std::string &geometry, unsigned n_ref_global, unsigned n_ref_local);
@@ -214,7 +226,8 @@ namespace mgamd
     static Tria
     from_leaves_checked(std::vector<Cell> leaves);
     Tria
-    coarsen_global() const; // one level of the geometric coarsening sequence; the coefficient goes down as the mean over each leaf
+    coarsen_global() const; // one level of the geometric coarsening sequence; the coefficient goes down as the mean over each leaf,
+                            // the dirichlet_faces mask unchanged
     // local smoothing: ALL cells of refinement level `level`, active or not (DoFHandler::distribute_mg_dofs levels)
     Tria
     level_mesh(int level) const
@@ -222,6 +235,9 @@ namespace mgamd
       if (!coefficient.empty())
         throw std::invalid_argument("level_mesh: the triangulation carries a diffusion coefficient: local smoothing with a "
                                     "coefficient is not implemented (the refinement-edge matrices have none)");
+      if (dirichlet_faces != ALL_DIRICHLET)
+        throw std::invalid_argument("level_mesh: the triangulation carries the dirichlet_faces mask " + std::to_string(dirichlet_faces) +
+                                    ": local smoothing with natural (Neumann) faces is not implemented, only the mask 63");
       std::vector<Cell> out;
       FlatMap           seen;
       seen.erase_all_and_reserve(cells.size());
@@ -665,7 +681,8 @@ namespace mgamd
   inline Tria
   Tria::coarsen_global() const
   {
-    Tria coarse = coarsen_cells();
+    Tria coarse            = coarsen_cells();
+    coarse.dirichlet_faces = dirichlet_faces;
     if (!coefficient.empty())
       {
         // Re-discretisation, not a Galerkin product: a coarse leaf is one of this mesh's leaves (its own value) or the parent of

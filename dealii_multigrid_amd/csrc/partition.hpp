@@ -347,7 +347,7 @@ namespace mgamd
                 bool           corner = false;
                 const bool     via_parent =
                   (mask >> MASK_FACE_SHIFT) && LevelTables::node_on_constrained_entity(mask, p, a, &corner) && !corner;
-                out.push_back({key, (uint8_t)((probe.key_on_boundary(key) ? 1 : 0) | (via_parent ? 0 : 0x80))});
+                out.push_back({key, (uint8_t)((probe.key_on_dirichlet_face(key) ? 1 : 0) | (via_parent ? 0 : 0x80))});
                 if (via_parent)
                   out.push_back({probe.own_key(c, a), (uint8_t)(2 | 0x80)});
               }

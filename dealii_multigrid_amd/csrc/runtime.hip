@@ -260,6 +260,23 @@ namespace mgamd
       throw std::invalid_argument("rhs: vector size mismatch");
     std::vector<double> h;
     tables->compute_rhs_function(kind, h);
+    upload_load(b, h);
+  }
+
+  void
+  LevelOperatorBase::rhs_boundary_flux(mgamd_vec &b, const double q[6])
+  {
+    if (b.n != n_dofs())
+      throw std::invalid_argument("rhs_boundary_flux: vector size mismatch");
+    std::vector<double> h;
+    tables->compute_rhs_boundary_flux(q, h);
+    upload_load(b, h);
+  }
+
+  // a load vector assembled over this rank's cells -> b, then the other ranks' contributions to shared DoFs
+  void
+  LevelOperatorBase::upload_load(mgamd_vec &b, const std::vector<double> &h)
+  {
     if (b.type == MGAMD_F64)
       HIP_CHECK(hipMemcpyAsync(b.data, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     else
@@ -2234,6 +2251,9 @@ namespace mgamd
   {
     if (!n_levels || !levels || !levels[0])
       throw std::invalid_argument("multigrid: no levels");
+    for (unsigned l = 0; l < n_levels; ++l)
+      if (levels[l])
+        levels[l]->refuse_singular("multigrid");
     if (levels[0]->type == MGAMD_F64)
       return new MultigridT<double>(ctx, n_levels, levels, transfers, smoothers, coarse_solver, nested, n_cycles, amg_global,
                                     amg_min_sharded_rows);
@@ -2277,6 +2297,7 @@ namespace mgamd
     const size_t n = A.n_dofs();
     if (x.n != n || b.n != n || x.type != A.type || b.type != A.type)
       throw std::invalid_argument("SolverCG::solve: bad vectors");
+    A.refuse_singular("SolverCG::solve");
     if (A.type == MGAMD_F64)
       solve_cg_T<double>(A, M, x, b, reltol, abstol, maxiter, n_iterations, residual);
     else
@@ -2362,6 +2383,7 @@ namespace mgamd
   ThetaStepperBase *
   make_theta_stepper(LevelOperatorBase &A, MultigridBase *M, double theta, double dt)
   {
+    A.refuse_singular("time stepper");
     return new ThetaStepper(A, M, theta, dt);
   }
 
@@ -2499,6 +2521,7 @@ namespace mgamd
   std::shared_ptr<AssembledMatrixBase>
   make_assembled_matrix(Ctx *ctx, const mgamd_dofs *dofs)
   {
+    dofs->tables->refuse_singular("assembled matrix (Type AMG)");
     return std::make_shared<AssembledMatrix>(ctx, dofs);
   }
   AmgPreconditionerBase *

@@ -140,7 +140,25 @@ struct RunParameters
   // this project's extension: "MassCoefficient": sigma >= 0 solves -Laplace u + sigma u = f (the operator K + sigma M); default 0,
   // the reference's Laplace problem.  The local-smoothing Types have no mass term: a non-zero value is "not implemented" there.
   double       mass_coefficient     = 0.0;
+  // this project's extension: "NeumannFaces": a string of face digits such as "1" or "024" (face f = 2 axis + side: 0 is x = -1,
+  // 1 is x = +1, ... 5 is z = +1): those faces are natural (zero flux), the others stay Dirichlet; default "", the reference's
+  // boundary id 0 on the whole surface (ref:multigrid_throughput.cc:1585-1593).  Refused for the local-smoothing Types, and for
+  // all six faces with MassCoefficient 0 (the singular pure-Neumann problem).
+  std::string  neumann_faces        = "";
   MultigridParameters mg_data;
+
+  unsigned
+  dirichlet_faces() const
+  {
+    unsigned mask = 0x3F;
+    for (const char c : neumann_faces)
+      {
+        if (c < '0' || c > '5')
+          throw std::runtime_error("NeumannFaces '" + neumann_faces + "': not implemented (a string of face digits 0 to 5)");
+        mask &= ~(1u << (c - '0'));
+      }
+    return mask;
+  }
 
   void
   parse(const std::string &file_name)
@@ -179,6 +197,7 @@ struct RunParameters
     get("ShardedAMG", sharded_amg);
     get("AMGMinShardedRows", amg_min_sharded_rows);
     get("MassCoefficient", mass_coefficient);
+    get("NeumannFaces", neumann_faces);
     get("SimulationType", simulation_type); // unknown keys are ignored (skip_undefined = true)
   }
 };
@@ -280,7 +299,20 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
   else
     throw std::runtime_error("MGNumberType '" + params.mg_number_type + "': not implemented");
 
-  auto tria = std::make_shared<const Triangulation>(params.geometry_type, params.n_ref_global, params.n_ref_local);
+  const unsigned dirichlet_faces = params.dirichlet_faces();
+  if (dirichlet_faces != 0x3F && (params.type == "HMG-local" || params.type == "HPMG-local"))
+    throw std::runtime_error("NeumannFaces '" + params.neumann_faces + "' with Type '" + params.type +
+                             "': not implemented (local smoothing takes Dirichlet conditions on the whole boundary only)");
+  if (dirichlet_faces == 0 && params.mass_coefficient == 0.0)
+    throw std::runtime_error("NeumannFaces '" + params.neumann_faces + "' with MassCoefficient 0: not implemented (no Dirichlet face and "
+                             "no mass term: the operator is singular, and no mean-value projection is built)");
+  std::shared_ptr<const Triangulation> tria;
+  {
+    auto mesh = std::make_shared<Triangulation>(params.geometry_type, params.n_ref_global, params.n_ref_local);
+    if (dirichlet_faces != 0x3F)
+      mesh->set_dirichlet_faces(dirichlet_faces); // before anything is built on the mesh: coarse meshes and DoFs inherit it
+    tria = mesh;
+  }
 
   // ---- level hierarchy (ref:multigrid_throughput.cc:2219-2260, 1506-1596): the meshes here, the levels on them from the library
   // (mgamd_level_plan), which also refuses the Types without levels
@@ -568,6 +600,8 @@ main(int argc, char **argv)
           params.parse(std::string(argv[i]));
           if (rank == 0 && params.mass_coefficient != 0.0)
             std::cout << "MassCoefficient: " << params.mass_coefficient << std::endl;
+          if (rank == 0 && !params.neumann_faces.empty())
+            std::cout << "NeumannFaces: " << params.neumann_faces << " (dirichlet_faces mask " << params.dirichlet_faces() << ")" << std::endl;
           run(ctx, params, table, sharded ? &comm : nullptr);
           if (rank == 0)
             table.write_text(std::cout);

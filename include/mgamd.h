@@ -61,7 +61,8 @@ int mgamd_tria_create(const char *geometry, unsigned n_ref_global, unsigned n_re
  * reference hands to the path: ref:multigrid_throughput.cc:2048-2062 builds it, :1540-1604 consumes it), given as octree leaves
  * (level, i, j, k), 0 <= i, j, k < 2^level, in any order.  The leaves must tile the cube exactly and be 2:1 balanced across
  * faces, edges and corners (p4est's full balance, deal.II's default); otherwise MGAMD_ERR_INVALID with the offending leaf in
- * mgamd_last_error().  Zero Dirichlet data on the whole boundary, as for the named geometries. */
+ * mgamd_last_error().  Zero Dirichlet data on the whole boundary, as for the named geometries (mgamd_tria_set_dirichlet_faces
+ * changes that for either). */
 int mgamd_tria_create_from_leaves(uint64_t n_leaves, const uint8_t *level, const uint32_t *i, const uint32_t *j, const uint32_t *k,
                                   mgamd_tria **out);
 /* one level of MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence
@@ -89,6 +90,22 @@ int mgamd_tria_get_cells(const mgamd_tria *t, uint8_t *level, uint32_t *i, uint3
 int mgamd_tria_set_coefficient(mgamd_tria *t, const double *a);
 int mgamd_tria_get_coefficient(const mgamd_tria *t, double *a);
 int mgamd_tria_has_coefficient(const mgamd_tria *t, int *has);
+
+/* Boundary conditions per face of the cube [-1,1]^3; this project's extension of the reference's homogeneous Dirichlet condition on
+ * boundary id 0, the whole surface (ref:multigrid_throughput.cc:1585-1593).  Faces are numbered f = 2 axis + side: 0 is x = -1, 1 is
+ * x = +1, 2 is y = -1, ... 5 is z = +1.  Bit f of the mask set: face f is Dirichlet; clear: natural (Neumann, zero flux unless
+ * mgamd_dofs_rhs_boundary_flux adds one).  A boundary DoF is Dirichlet iff it lies on at least one Dirichlet face (shared edges and
+ * corners included); a DoF on natural faces only is an ordinary unknown.  The Gaussian data g is imposed on Dirichlet faces only.
+ * The default of every new triangulation is 0x3F, all Dirichlet.  MGAMD_ERR_INVALID for a mask > 63.
+ * mgamd_tria_coarsen inherits the mask; mgamd_dofs_create and mgamd_dofs_create_local COPY it, as they copy the coefficient, and
+ * mgamd_dofs_dirichlet_faces reads that copy.  Local smoothing is not implemented for another mask than 0x3F: mgamd_tria_level_mesh
+ * is MGAMD_ERR_INVALID then.
+ * Mask 0 with mass coefficient sigma == 0 is the singular pure-Neumann operator (constants in its kernel).  Operators, mass
+ * products, inverse diagonals and Chebyshev smoothers are built on it; mgamd_mg_create*, mgamd_matrix_create (and with it
+ * mgamd_amg_create), mgamd_dofs_amg_setup_info, mgamd_solve_cg* and mgamd_time_stepper_create are MGAMD_ERR_INVALID with the mask
+ * and sigma in mgamd_last_error(): no mean-value projection is built. */
+int mgamd_tria_set_dirichlet_faces(mgamd_tria *t, unsigned mask);
+int mgamd_tria_get_dirichlet_faces(const mgamd_tria *t, unsigned *mask);
 
 typedef struct
 {
@@ -136,6 +153,13 @@ int mgamd_dofs_rhs_constant(const mgamd_dofs *d, double *out);
  * (ref:include/operator.h:362-447); and AffineConstraints::distribute on a host vector of n_dofs values */
 int mgamd_dofs_rhs(const mgamd_dofs *d, int kind, double *out);
 int mgamd_dofs_distribute(const mgamd_dofs *d, int kind, double *x);
+/* the dirichlet_faces mask these tables were built with (ref:multigrid_throughput.cc:1585-1593 fixes it to the whole boundary) */
+int mgamd_dofs_dirichlet_faces(const mgamd_dofs *d, unsigned *mask);
+/* boundary load of one constant flux q[f] per face f (a grad u . n = q_f on natural faces):  out_i = sum_f q_f int_{Gamma_f} phi_i,
+ * mapped through the hanging-node constraints like the volume load of mgamd_dofs_rhs, constrained rows 0; independent of the
+ * diffusion coefficient and of sigma, and additive to mgamd_dofs_rhs (ref:include/operator.h:362-447 has no boundary term).
+ * MGAMD_ERR_INVALID, naming the face, for a non-zero q[f] on a Dirichlet face. */
+int mgamd_dofs_rhs_boundary_flux(const mgamd_dofs *d, const double q[6], double *out);
 /* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
  * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
  * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
@@ -333,6 +357,9 @@ int mgamd_level_op_inverse_diagonal(mgamd_level_op *op, mgamd_vec *diagonal);
 int mgamd_level_op_rhs(mgamd_level_op *op, mgamd_vec *rhs);
 /* the same for SimulationType `kind` (see mgamd_dofs_rhs), and constraints.distribute(solution) after the solve */
 int mgamd_level_op_rhs_kind(mgamd_level_op *op, int kind, mgamd_vec *rhs);
+/* mgamd_dofs_rhs_boundary_flux into a device vector of the operator; on a distributed operator each rank integrates over its own
+ * cells and the shared entries are completed over the ranks, as for mgamd_level_op_rhs_kind */
+int mgamd_level_op_rhs_boundary_flux(mgamd_level_op *op, const double q[6], mgamd_vec *rhs);
 int mgamd_level_op_distribute(mgamd_level_op *op, int kind, mgamd_vec *x);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is
