@@ -178,6 +178,19 @@ class Triangulation:
         _chk(_lib.mgamd_tria_get_dirichlet_faces(self._h, C.byref(m)))
         return m.value
 
+    def set_robin_coefficients(self, beta):
+        """convective (Robin) faces: a grad u . n + beta[f] (u - u_ext) = 0 on face f (numbered as for set_dirichlet_faces), beta[f]
+        >= 0; 6 values or {face: value}, default 0.  The operator gains sum_f beta[f] B_f (surface mass matrices); the load of u_ext
+        is rhs_boundary_flux with q[f] = beta[f] u_ext.  coarsen() inherits the values; DoFs copy them when they are built
+        (mgamd_tria_set_robin_coefficients).  MgamdError for a negative or non-finite value and for beta[f] > 0 on a Dirichlet face."""
+        beta = _flux_array(beta, "Robin coefficients")
+        _chk(_lib.mgamd_tria_set_robin_coefficients(self._h, _ptr(beta)))
+
+    def robin_coefficients(self):
+        beta = np.zeros(6)
+        _chk(_lib.mgamd_tria_get_robin_coefficients(self._h, _ptr(beta)))
+        return beta
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mgamd_tria_destroy(self._h)
@@ -196,26 +209,32 @@ def create_geometric_coarsening_sequence(fine: Triangulation, coarse_coefficient
     return seq[::-1]
 
 
-def _flux_array(q):
-    """six face fluxes as a contiguous double array: a sequence of 6 values or {face: value}"""
+def _flux_array(q, what="boundary flux"):
+    """six face values (fluxes, Robin coefficients) as a contiguous double array: a sequence of 6 values or {face: value}"""
     if isinstance(q, dict):
         a = np.zeros(6)
         for f, v in q.items():
             if not 0 <= int(f) <= 5:
-                raise MgamdError(f"boundary flux: face {f} refused, the faces are 0 to 5")
+                raise MgamdError(f"{what}: face {f} refused, the faces are 0 to 5")
             a[int(f)] = v
         return a
     a = np.ascontiguousarray(q, np.float64)
     if a.shape != (6,):
-        raise ValueError(f"boundary flux: {a.shape} values for the 6 faces")
+        raise ValueError(f"{what}: {a.shape} values for the 6 faces")
     return a
 
 
-def _apply_dirichlet_faces(fine: Triangulation, mg_type: str, dirichlet_faces):
-    """Hierarchy(dirichlet_faces=...): set on the mesh (the carrier, as for the coefficient) before anything is built from it; the
-    local-smoothing types refuse another mask than 63 by name"""
+def _apply_dirichlet_faces(fine: Triangulation, mg_type: str, dirichlet_faces, robin=None):
+    """Hierarchy(dirichlet_faces=..., robin=...): set on the mesh (the carrier, as for the coefficient) before anything is built from
+    it, the mask first (a convective face must not be Dirichlet); the local-smoothing types refuse a positive Robin coefficient
+    and another mask than 63 by name, in that order (a convective face implies another mask)"""
     if dirichlet_faces is not None:
         fine.set_dirichlet_faces(dirichlet_faces)
+    if robin is not None:
+        fine.set_robin_coefficients(robin)
+    if mg_type in ("HMG-local", "HPMG-local") and np.any(fine.robin_coefficients() > 0):
+        raise MgamdError(f"Type '{mg_type}' with the Robin coefficients {fine.robin_coefficients().tolist()}: not implemented (local "
+                         "smoothing takes no convective faces)")
     if mg_type in ("HMG-local", "HPMG-local") and fine.dirichlet_faces() != ALL_DIRICHLET:
         raise MgamdError(f"Type '{mg_type}' with the dirichlet_faces mask {fine.dirichlet_faces()}: not implemented (local smoothing "
                          "takes the mask 63 only)")
@@ -312,6 +331,23 @@ class DoFs:
         m = C.c_uint()
         _chk(_lib.mgamd_dofs_dirichlet_faces(self._h, C.byref(m)))
         return m.value
+
+    def robin_coefficients(self):
+        """the Robin coefficients these DoFs were built with (their mesh's at that time)"""
+        beta = np.zeros(6)
+        _chk(_lib.mgamd_dofs_robin_coefficients(self._h, _ptr(beta)))
+        return beta
+
+    def robin_faces(self):
+        """the table of boundary cell faces on convective faces (this rank's cells): (idx [n, (p+1)^2] uint32 with INVALID_DOF on
+        Dirichlet DoFs, flags [n] uint8, scale [n] = beta_f h^2); see mgamd_dofs_robin_faces"""
+        n = C.c_uint64()
+        _chk(_lib.mgamd_dofs_robin_faces(self._h, C.byref(n), None, None, None))
+        n2 = (self.degree + 1) ** 2
+        idx, flags, scale = np.zeros((n.value, n2), np.uint32), np.zeros(n.value, np.uint8), np.zeros(n.value)
+        if n.value:
+            _chk(_lib.mgamd_dofs_robin_faces(self._h, C.byref(n), _ptr(idx), _ptr(flags), _ptr(scale)))
+        return idx, flags, scale
 
     def rhs_boundary_flux(self, q):
         """boundary load of one constant flux per face, host vector: sum_f q[f] int_{face f} phi_i, through the hanging-node
@@ -1107,7 +1143,8 @@ class Hierarchy:
 
     def __init__(self, ctx: Context, geometry="quadrant", n_ref_global=3, degree=1, mg_type="HMG-global", n_ref_local=0,
                  smoother_degree=3, smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64,
-                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0, coefficient=None, coarse_coefficient=None, dirichlet_faces=None):
+                 max_brick=-1, coarse_n_cycles=1, mass_coefficient=0.0, coefficient=None, coarse_coefficient=None, dirichlet_faces=None,
+                 robin=None):
         """mass_coefficient: sigma >= 0 of the operator K + sigma M (-Laplace u + sigma u) on every level, the stand-in and nested
         hierarchies included; the local-smoothing types refuse a non-zero value
         coefficient: the diffusion coefficient a of -div(a grad u) + sigma u: f(x, y, z), evaluated at the leaf centres of the
@@ -1119,7 +1156,10 @@ class Hierarchy:
         where it would have no effect.  The local-smoothing types refuse a coefficient.
         dirichlet_faces: 6-bit mask of the Dirichlet faces (Triangulation.set_dirichlet_faces); None keeps what the mesh carries (63
         for a named geometry).  Like the coefficient it is SET ON a caller's Triangulation, and every level inherits it.  The
-        local-smoothing types refuse another mask than 63; mask 0 with mass_coefficient 0 (singular) is refused by the library."""
+        local-smoothing types refuse another mask than 63; mask 0 with mass_coefficient 0 (singular) is refused by the library.
+        robin: Robin coefficients of the convective faces (Triangulation.set_robin_coefficients), set on the mesh after the mask; None
+        keeps what the mesh carries.  The local-smoothing types refuse a positive value.  One positive value makes mask 0 with
+        mass_coefficient 0 regular.  Levels with a convective face run their transfers un-fused (DESIGN.md "Convective faces")."""
         self.ctx = ctx
         self.mass_coefficient = mass_coefficient
         # `geometry` may also be a caller-built Triangulation (Triangulation.from_leaves)
@@ -1129,7 +1169,7 @@ class Hierarchy:
                              "matrices have no coefficient)")
         if coarse_coefficient is not None and mg_type not in ("HMG-global", "HPMG"):
             raise MgamdError(f"Type '{mg_type}' has no coarse meshes: coarse_coefficient would have no effect")
-        _apply_dirichlet_faces(fine, mg_type, dirichlet_faces)
+        _apply_dirichlet_faces(fine, mg_type, dirichlet_faces, robin)
         _apply_coefficient(fine, coefficient)
         if mg_type in ("AMG", "AMGPETSc"):
             # solve_with_amg (ref:multigrid_throughput.cc:1877-1966): no multigrid levels; CG on the assembled matrix of the one
@@ -1204,8 +1244,8 @@ class DistributedHierarchy:
                  smoothing_range=20.0, eig_cg_n_iterations=20, coarse_solver="amg", number_type=F64, hanging_weight=2.0, max_brick=-1,
                  min_root_dofs=MIN_ROOT_DOFS_DEFAULT, mg_type="HMG-global", coarse_n_cycles=1, subset_group=None,
                  min_subset_dofs=MIN_SUBSET_DOFS_DEFAULT, sharded_amg=False, amg_min_sharded_rows=AMG_MIN_SHARDED_ROWS_DEFAULT,
-                 mass_coefficient=0.0, coefficient=None, coarse_coefficient=None, dirichlet_faces=None):
-        """dirichlet_faces: as for Hierarchy (every rank passes the same)
+                 mass_coefficient=0.0, coefficient=None, coarse_coefficient=None, dirichlet_faces=None, robin=None):
+        """dirichlet_faces, robin: as for Hierarchy (every rank passes the same)
         coefficient, coarse_coefficient: the diffusion coefficient, as for Hierarchy (every rank passes the same; set on the
         caller's Triangulation if one is passed; the coarsening sequence exists for every type here, so coarse_coefficient always acts)
         sharded_amg: run the AMG coarse solvers ("amg", "cg_with_amg", "amg_petsc") on a large coarse level as the library's
@@ -1215,7 +1255,7 @@ class DistributedHierarchy:
         if mg_type not in ("HMG-global", "PMG", "HPMG"):
             raise MgamdError(f"Type '{mg_type}' not implemented")
         fine = geometry if isinstance(geometry, Triangulation) else Triangulation(geometry, n_ref_global)
-        _apply_dirichlet_faces(fine, mg_type, dirichlet_faces)
+        _apply_dirichlet_faces(fine, mg_type, dirichlet_faces, robin)
         _apply_coefficient(fine, coefficient)
         self.mesh_sequence = create_geometric_coarsening_sequence(fine, coarse_coefficient)
         # (mesh index, degree) of every multigrid level, coarse -> fine (ref:multigrid_throughput.cc:1506-1571)

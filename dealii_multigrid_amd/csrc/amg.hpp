@@ -203,6 +203,22 @@ namespace mgamd
                     at(idx[ci * n3 + i], idx[ci * n3 + j]) += s3 * Me[(size_t)i * n3 + j];
           }
       }
+    // convective faces (LevelTables::robin_faces): + C^T (sum_f beta_f h^2 M (x) M) C; a face's DoFs are DoFs of its cell, so the
+    // pattern holds the entries already
+    {
+      const int           n2 = n * n;
+      std::vector<double> Bf;
+      for (size_t e = 0; e < L.robin_faces.size(); ++e)
+        {
+          L.robin_face_matrix(e, Bf);
+          const uint32_t *fi = &L.robin_faces.idx[e * n2];
+          for (int i = 0; i < n2; ++i)
+            if (fi[i] != INVALID_DOF)
+              for (int j = 0; j < n2; ++j)
+                if (fi[j] != INVALID_DOF)
+                  at(fi[i], fi[j]) += Bf[(size_t)i * n2 + j];
+        }
+    }
     for (uint32_t i = L.first_constrained(); i < L.n_dofs; ++i)
       at(i, i) = 1.0;
     return A;

@@ -78,6 +78,12 @@ namespace mgamd
     if (global.dirichlet_faces != local.dirichlet_faces)
       throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the dirichlet_faces mask " + std::to_string(global.dirichlet_faces) +
                                   ", the local level " + std::to_string(local.dirichlet_faces) + ": the assembled matrix would be another operator's");
+    // and for the Robin coefficients of the convective faces
+    for (int f = 0; f < 6; ++f)
+      if (global.robin[f] != local.robin[f])
+        throw std::invalid_argument("sharded AMG: the global coarse DoFs carry the Robin coefficient " + std::to_string(global.robin[f]) +
+                                    " on face " + std::to_string(f) + ", the local level " + std::to_string(local.robin[f]) +
+                                    ": the assembled matrix would be another operator's");
     // the same holds for the diffusion coefficient of the cells this rank works on
     // (cell by cell: both tables must describe the same mesh; another mesh is refused here, before the keys are matched)
     if (global.tria->cells.size() != local.tria->cells.size())

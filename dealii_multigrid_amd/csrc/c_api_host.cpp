@@ -553,6 +553,53 @@ mgamd_dofs_dirichlet_faces(const mgamd_dofs *d, unsigned *mask)
 }
 
 int
+mgamd_tria_set_robin_coefficients(mgamd_tria *t, const double beta[6])
+{
+  MGAMD_TRY
+  if (!t || !beta)
+    throw std::invalid_argument("null argument");
+  t->tria->set_robin_coefficients(beta); // (refuses a negative or non-finite value, and a positive one on a Dirichlet face)
+  MGAMD_CATCH
+}
+
+int
+mgamd_tria_get_robin_coefficients(const mgamd_tria *t, double beta[6])
+{
+  MGAMD_TRY
+  if (!t || !beta)
+    throw std::invalid_argument("null argument");
+  std::copy(t->tria->robin, t->tria->robin + 6, beta);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_robin_coefficients(const mgamd_dofs *d, double beta[6])
+{
+  MGAMD_TRY
+  if (!d || !beta)
+    throw std::invalid_argument("null argument");
+  std::copy(d->tables->robin, d->tables->robin + 6, beta);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_robin_faces(const mgamd_dofs *d, uint64_t *n_faces, uint32_t *idx, uint8_t *flags, double *scale)
+{
+  MGAMD_TRY
+  if (!d || !n_faces)
+    throw std::invalid_argument("null argument");
+  const auto &rf = d->tables->robin_faces;
+  *n_faces       = rf.size();
+  if (idx)
+    std::copy(rf.idx.begin(), rf.idx.end(), idx);
+  if (flags)
+    std::copy(rf.flags.begin(), rf.flags.end(), flags);
+  if (scale)
+    std::copy(rf.scale.begin(), rf.scale.end(), scale);
+  MGAMD_CATCH
+}
+
+int
 mgamd_dofs_rhs_boundary_flux(const mgamd_dofs *d, const double q[6], double *out)
 {
   MGAMD_TRY

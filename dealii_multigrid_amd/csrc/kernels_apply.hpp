@@ -1458,6 +1458,175 @@ namespace mgamd
       }
   }
 
+  // Convective (Robin) faces: the face term  sum_f beta_f B_f x  of the operator, matrix-free, added into the accumulator of the
+  // tail rows before their epilogue (every boundary DoF that is neither Dirichlet nor hanging is a tail row).  One entry of the
+  // face table (level_tables.hpp, RobinFaces) is one boundary cell face with N2 = (P+1)^2 nodes: gather, interpolation C2 on the
+  // flagged hanging lines, M along u, M along v, scale beta h^2, C2^T, atomic add.
+  // Packing: a workgroup of 256 threads holds 256 / N2 faces at a time, one thread per face node (64, 28, 16, 10, 7, 5, 4 faces for
+  // P = 1..7: at most 11 of the 256 lanes have no node), two LDS buffers of one value per node that the six 1D passes ping-pong
+  // between, and walks the groups of faces with a grid stride.  The gather and the atomic adds are one 4- or 8-byte access per
+  // lane at scattered rows, as the shell entries of the slot kernels are.
+  // X_FROM_B: MODE_CHEB_FIRST, the source x = c0 D^-1 b is never stored and is formed here (D^-1 through the byte codes of the
+  // tail rows where the pass has them).  DIAG: the diagonal of the face term, one unit vector per face node through the same passes.
+  template <typename T, int P>
+  struct RobinArgs
+  {
+    const uint32_t *idx;   // [n_faces][N2], DEV_INVALID on Dirichlet DoFs
+    const uint8_t  *flags; // [n_faces]
+    const double   *scale; // [n_faces] beta h^2
+    uint32_t        n_faces;
+    T               M[(P + 1) * (P + 1)], I0[(P + 1) * (P + 1)], I1[(P + 1) * (P + 1)];
+    const T        *src;
+    T              *tail_acc;
+    uint32_t        n_interior, gather_limit, scatter_limit;
+    // X_FROM_B only
+    const T       *b, *dinv;
+    T              c0;
+    const uint8_t *dinv_code;
+    const T       *dinv_table;
+  };
+  template <int P>
+  constexpr int
+  robin_faces_per_workgroup()
+  {
+    return 256 / ((P + 1) * (P + 1));
+  }
+
+  template <typename T, int P, bool X_FROM_B, bool DIAG>
+  __global__ void
+  __launch_bounds__(256) robin_face_kernel(RobinArgs<T, P> a)
+  {
+    constexpr int N = P + 1, N2 = N * N, FPB = robin_faces_per_workgroup<P>();
+    __shared__ T  bufA[FPB * N2], bufB[FPB * N2], sM[N2], sI[2 * N2];
+    const int     tid = threadIdx.x;
+    for (int i = tid; i < N2; i += 256)
+      {
+        sM[i]      = a.M[i];
+        sI[i]      = a.I0[i];
+        sI[N2 + i] = a.I1[i];
+      }
+    const int      fl = tid / N2, node = tid - fl * N2, au = node % N, av = node / N;
+    T             *A = bufA + (fl < FPB ? fl : 0) * N2, *B = bufB + (fl < FPB ? fl : 0) * N2;
+    const uint32_t n_groups = (a.n_faces + FPB - 1) / FPB;
+    for (uint32_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) // (uniform over the workgroup: the barriers below are safe)
+      {
+        const uint32_t face = grp * FPB + fl;
+        const bool     act  = fl < FPB && face < a.n_faces;
+        uint32_t       gi = DEV_INVALID, flg = 0;
+        T              scale = T(0);
+        if (act)
+          {
+            gi    = a.idx[(size_t)face * N2 + node];
+            flg   = a.flags[face];
+            scale = (T)a.scale[face];
+          }
+        const bool on_u = (flg & 1u) && av == (int)((flg >> 3) & 1u) * P; // this node's line along u hangs
+        const bool on_v = (flg & 2u) && au == (int)((flg >> 2) & 1u) * P; // this node's line along v hangs
+        const T   *Iu = sI + ((flg >> 2) & 1u) * N2, *Iv = sI + ((flg >> 3) & 1u) * N2;
+        const bool gathered = act && gi < a.gather_limit;
+        T          x = T(0);
+        if (!DIAG && gathered)
+          {
+            if (X_FROM_B)
+              {
+                T d;
+                if (a.dinv_code != nullptr && gi >= a.n_interior) // (entry i of the codes belongs to DoF n_interior + i)
+                  {
+                    const uint32_t c = a.dinv_code[gi - a.n_interior];
+                    d                = c != 255u ? a.dinv_table[c] : a.dinv[gi];
+                  }
+                else
+                  d = a.dinv[gi];
+                x = a.c0 * d * a.b[gi];
+              }
+            else
+              x = a.src[gi];
+          }
+        T result = T(0);
+        for (int j = 0; j < (DIAG ? N2 : 1); ++j)
+          {
+            if (DIAG)
+              x = (gathered && node == j) ? T(1) : T(0);
+            if (act)
+              A[node] = x;
+            __syncthreads();
+            T v = T(0);
+            if (act) // C2 along u
+              {
+                v = A[node];
+                if (on_u)
+                  {
+                    v = T(0);
+#pragma unroll
+                    for (int b = 0; b < N; ++b)
+                      v += Iu[au * N + b] * A[av * N + b];
+                  }
+                B[node] = v;
+              }
+            __syncthreads();
+            if (act) // C2 along v
+              {
+                v = B[node];
+                if (on_v)
+                  {
+                    v = T(0);
+#pragma unroll
+                    for (int b = 0; b < N; ++b)
+                      v += Iv[av * N + b] * B[b * N + au];
+                  }
+                A[node] = v;
+              }
+            __syncthreads();
+            if (act) // M along u
+              {
+                v = T(0);
+#pragma unroll
+                for (int b = 0; b < N; ++b)
+                  v += sM[au * N + b] * A[av * N + b];
+                B[node] = v;
+              }
+            __syncthreads();
+            if (act) // M along v, beta h^2
+              {
+                v = T(0);
+#pragma unroll
+                for (int b = 0; b < N; ++b)
+                  v += sM[av * N + b] * B[b * N + au];
+                A[node] = scale * v;
+              }
+            __syncthreads();
+            if (act) // C2^T along v
+              {
+                v = A[node];
+                if (on_v)
+                  {
+                    v = T(0);
+#pragma unroll
+                    for (int b = 0; b < N; ++b)
+                      v += Iv[b * N + av] * A[b * N + au];
+                  }
+                B[node] = v;
+              }
+            __syncthreads();
+            if (act) // C2^T along u
+              {
+                v = B[node];
+                if (on_u)
+                  {
+                    v = T(0);
+#pragma unroll
+                    for (int b = 0; b < N; ++b)
+                      v += Iu[b * N + au] * B[av * N + b];
+                  }
+                if (!DIAG || node == j)
+                  result = v;
+              }
+          }
+        if (act && gi >= a.n_interior && gi < a.scatter_limit)
+          atomic_add(&a.tail_acc[gi - a.n_interior], result);
+      }
+  }
+
   // Epilogue for the tail (accumulated shell sums) and the constrained DoFs (identity rows:
   // ref:include/operator.h:170-172; MODE_MASS: zero rows); re-zeroes the accumulator for the next application.
   // tail_rows is the epilogue of the U rows row[u] (tail index; row >= n_tail: a constrained DoF) with live[u]; the two kernels

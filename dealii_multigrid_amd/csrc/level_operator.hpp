@@ -303,6 +303,17 @@ namespace mgamd
     };
     std::unique_ptr<HaloDev> halo;
 
+    // device image of the table of convective faces (LevelTables::robin_faces); null where this rank's cells have none: such a
+    // level has no face step in its launch plan and runs the launches it ran without the feature
+    struct RobinDev
+    {
+      DBuf<uint32_t> idx;
+      DBuf<uint8_t>  flags;
+      DBuf<double>   scale;
+      uint32_t       n_faces = 0;
+    };
+    std::unique_ptr<RobinDev> robin;
+
     // The kernel launches of one operator application, planned once (build_launch_plan): one step per launch, in launch order.
     enum class LaunchKind
     {
@@ -311,7 +322,8 @@ namespace mgamd
       BRICK_PAIR,          // the plain bricks g + the constrained bricks `partner` of the same size (p = 1, launch_pair)
       BRICKS_AND_CELLS,    // the 2^3 bricks g + the single cells `partner` (p >= 2, lattice_apply_small_kernel)
       BRICKS_AND_CLUSTERS, // the 8^3 bricks g + the cell clusters `partner` (p = 1, lattice_cluster_kernel)
-      CLUSTERS             // the cell clusters of g (p = 1, cell_cluster_apply_kernel)
+      CLUSTERS,            // the cell clusters of g (p = 1, cell_cluster_apply_kernel)
+      ROBIN_FACES          // the convective faces of the level (robin_face_kernel); g is null, [begin, end) the face entries
     };
     struct LaunchStep
     {
@@ -399,6 +411,14 @@ namespace mgamd
         }
       tail_acc.alloc(std::max<uint32_t>(tables->n_tail + tables->n_edge, 1));
       tail_acc.zero(ctx->stream);
+      if (tables->robin_faces.size())
+        {
+          robin = std::make_unique<RobinDev>();
+          robin->idx.upload(tables->robin_faces.idx);
+          robin->flags.upload(tables->robin_faces.flags);
+          robin->scale.upload(tables->robin_faces.scale);
+          robin->n_faces = (uint32_t)tables->robin_faces.size();
+        }
       build_launch_plan();
     }
 
@@ -454,6 +474,15 @@ namespace mgamd
             }
         }
 
+      // The convective faces add into the tail accumulator like a slot's shell sums: after the slots, before the exchange and the
+      // tail epilogue (level_operator_apply.hpp)
+      const LaunchStep faces{K::ROBIN_FACES, nullptr, nullptr, 0, robin ? robin->n_faces : 0};
+      if (robin)
+        {
+          plan.diagonal.push_back(faces);
+          plan.ordinary.push_back(faces);
+        }
+
       // The halo-overlap pass of a sharded level: no merges, every group split at the end of its halo slots (LevelTables
       // puts them at the front of every group).  Only where some slots are left to run under the exchange.
       if (!halo || !halo_overlap)
@@ -471,6 +500,9 @@ namespace mgamd
         for (auto &g : groups)
           if (halo_end(*g) > 0)
             plan.halo_slots.push_back(on_its_own(g.get(), 0, halo_end(*g)));
+      // boundary DoFs may be shared: the faces run with the halo slots, and the exchange sums their contributions over the ranks
+      if (robin && !plan.interior_slots.empty())
+        plan.halo_slots.push_back(faces);
     }
 
     // tail[t] <- sum over the sharing ranks (ascending rank order) of their partial tail[t]
@@ -701,6 +733,8 @@ namespace mgamd
     {
       constexpr int MODE = base_mode(MODE_);
       using K            = LaunchKind;
+      if (s.kind == K::ROBIN_FACES)
+        return launch_robin_faces<P, MODE>(st, a, diag);
       GroupDev<T> *g     = s.g;
       a.g                = g->view(s.begin, s.end, MODE == MODE_MASS);
       a.stamps           = nullptr;
@@ -739,6 +773,49 @@ namespace mgamd
           case K::CLUSTERS:
             launch_clusters<P, MODE == MODE_MASS>(st, *g, a, MODE == MODE_CHEB_FIRST, s.begin, s.end);
             break;
+          case K::ROBIN_FACES: // (above)
+            break;
+        }
+    }
+
+    // the face term of the convective faces into the tail accumulator (kernels.hpp robin_face_kernel); the mass pass has none
+    template <int P, int MODE>
+    void
+    launch_robin_faces(hipStream_t st, const ApplyArgs<T, P> &a, bool diag)
+    {
+      if constexpr (MODE != MODE_MASS)
+        {
+          RobinArgs<T, P> r;
+          r.idx     = robin->idx.p;
+          r.flags   = robin->flags.p;
+          r.scale   = robin->scale.p;
+          r.n_faces = robin->n_faces;
+          for (int i = 0; i < (P + 1) * (P + 1); ++i)
+            {
+              r.M[i]  = a.m.M[i];
+              r.I0[i] = a.m.I0[i];
+              r.I1[i] = a.m.I1[i];
+            }
+          r.src           = a.src;
+          r.tail_acc      = a.tail_acc;
+          r.n_interior    = a.n_interior;
+          r.gather_limit  = a.gather_limit;
+          r.scatter_limit = a.scatter_limit;
+          r.b             = a.epi.b;
+          r.dinv          = a.epi.dinv;
+          r.c0            = a.epi.c0;
+          r.dinv_code     = a.epi.dinv_code;
+          r.dinv_table    = a.epi.dinv_table;
+          // two groups of faces per workgroup where there are that many: the 1D matrices are staged in LDS once per workgroup
+          const uint32_t n_groups = (r.n_faces + robin_faces_per_workgroup<P>() - 1) / robin_faces_per_workgroup<P>();
+          const uint32_t grid     = std::min<uint32_t>(1024u, (n_groups + 1) / 2);
+          if (diag)
+            hipLaunchKernelGGL((robin_face_kernel<T, P, false, true>), grid, 256, 0, st, r);
+          else if (MODE == MODE_CHEB_FIRST)
+            hipLaunchKernelGGL((robin_face_kernel<T, P, true, false>), grid, 256, 0, st, r);
+          else
+            hipLaunchKernelGGL((robin_face_kernel<T, P, false, false>), grid, 256, 0, st, r);
+          HIP_CHECK(hipGetLastError());
         }
     }
 

@@ -73,7 +73,7 @@ namespace mgamd
     };
     for (const LaunchStep &s : diag ? plan.diagonal : plan.ordinary)
       {
-        const bool prof = prof_begin(*s.g);
+        const bool prof = s.g && prof_begin(*s.g); // (the step of the convective faces has no slot group)
         launch_step<P, MODE>(main, a, s, diag, fused, !diag);
         if (prof)
           prof_end(*s.g, s.g->n_slots);

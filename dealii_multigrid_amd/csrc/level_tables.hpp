@@ -380,18 +380,103 @@ namespace mgamd
     // Which faces of the cube are Dirichlet (bit f = 2 axis + side; Tria::dirichlet_faces at the time these tables were built).  A
     // DoF on natural faces only is an ordinary unknown: tail class, or hanging if it hangs (DESIGN.md "Boundary conditions").
     unsigned dirichlet_faces = Tria::ALL_DIRICHLET;
-    // no Dirichlet face and sigma == 0: the constants are in the operator's kernel.  Operators stay available; solvers refuse.
+    // Robin coefficient beta_f >= 0 per face of the cube (Tria::robin at the time these tables were built): the operator is
+    // K_a + sigma M + sum_f beta_f B_f, B_f the surface mass matrix of face f (DESIGN.md "Convective faces").  All 0: no face term.
+    double robin[6] = {0, 0, 0, 0, 0, 0};
+    bool
+    has_robin() const
+    {
+      for (int f = 0; f < 6; ++f)
+        if (robin[f] > 0.0)
+          return true;
+      return false;
+    }
+    // The boundary cell faces of this rank's cells that lie on a face with beta_f > 0, in the order of the cells (Morton) and of the
+    // faces within a cell.  A face has n2 = (p+1)^2 nodes, the lower of its two in-face axes (u < v) fastest.
+    //   idx    [n][n2]  the DoF the cell gathers at the face node (cell_node_index: hanging entities resolved to the parent's DoFs,
+    //                   INVALID_DOF on Dirichlet DoFs)
+    //   flags  [n]      the restriction of the cell's constraint mask to the face: bit 0 the line along u at v = cv p hangs, bit 1
+    //                   the line along v at u = cu p hangs; bits 2 and 3 are cu and cv, the cell's child position along u and v
+    //                   (which half I_0 / I_1 of the parent's line it sees).  The two other in-face edges never hang: they lie
+    //                   inside the parent.  The boundary face itself never hangs, and along its normal the interpolation is the
+    //                   identity on face nodes (the cell's child position there is the boundary side).
+    //   scale  [n]      beta_f h^2
+    // The face term of one entry is  scale C2^T (M (x) M) C2  on idx, C2 the interpolation along u, then along v, on the flagged lines.
+    struct RobinFaces
+    {
+      std::vector<uint32_t> idx;
+      std::vector<uint8_t>  flags;
+      std::vector<double>   scale;
+      size_t
+      size() const
+      {
+        return scale.size();
+      }
+    } robin_faces;
+    // the face-local interpolation C2 (or its transpose) of one entry of robin_faces on n2 values
+    void
+    robin_face_interpolate(uint8_t flags, double *v, bool transpose) const
+    {
+      const int n = p + 1, cu = (flags >> 2) & 1, cv = (flags >> 3) & 1;
+      double    tmp[MAX_DEGREE + 1];
+      for (int pass = 0; pass < 2; ++pass)
+        {
+          const bool along_u = (pass == 0) != transpose;
+          if (!((flags >> (along_u ? 0 : 1)) & 1))
+            continue;
+          const double *Ic     = fe.I[along_u ? cu : cv].data();
+          double       *line   = along_u ? v + cv * p * n : v + cu * p;
+          const int     stride = along_u ? 1 : n;
+          for (int a = 0; a < n; ++a)
+            {
+              double s = 0;
+              for (int b = 0; b < n; ++b)
+                s += (transpose ? Ic[b * n + a] : Ic[a * n + b]) * line[b * stride];
+              tmp[a] = s;
+            }
+          for (int a = 0; a < n; ++a)
+            line[a * stride] = tmp[a];
+        }
+    }
+    // the n2 x n2 matrix  scale C2^T (M (x) M) C2  of entry e (row-major), for the assembled matrix
+    void
+    robin_face_matrix(size_t e, std::vector<double> &B) const
+    {
+      const int           n = p + 1, n2 = n * n;
+      std::vector<double> v(n2), w(n2);
+      B.assign((size_t)n2 * n2, 0.0);
+      for (int j = 0; j < n2; ++j)
+        {
+          std::fill(v.begin(), v.end(), 0.0);
+          v[j] = 1.0;
+          robin_face_interpolate(robin_faces.flags[e], v.data(), false);
+          for (int bv = 0; bv < n; ++bv)
+            for (int bu = 0; bu < n; ++bu)
+              {
+                double s = 0;
+                for (int av = 0; av < n; ++av)
+                  for (int au = 0; au < n; ++au)
+                    s += fe.M[bu * n + au] * fe.M[bv * n + av] * v[av * n + au];
+                w[bv * n + bu] = robin_faces.scale[e] * s;
+              }
+          robin_face_interpolate(robin_faces.flags[e], w.data(), true);
+          for (int i = 0; i < n2; ++i)
+            B[(size_t)i * n2 + j] = w[i];
+        }
+    }
+    // no Dirichlet face, sigma == 0 and no convective face: the constants are in the operator's kernel.  Operators stay available;
+    // solvers refuse.
     bool
     singular() const
     {
-      return dirichlet_faces == 0 && sigma == 0.0;
+      return dirichlet_faces == 0 && sigma == 0.0 && !has_robin();
     }
     void
     refuse_singular(const char *who) const
     {
       if (singular())
         throw std::invalid_argument(std::string(who) + ": refused, the operator is singular: dirichlet_faces mask 0 (no Dirichlet face) with "
-                                    "mass coefficient sigma = 0 has the constants in its kernel, and no mean-value projection is built");
+                                    "mass coefficient sigma = 0 and no convective face has the constants in its kernel, and no mean-value projection is built");
     }
     double
     coefficient_of(size_t cell) const
@@ -444,6 +529,10 @@ namespace mgamd
     {
       coefficient     = t.coefficient;
       dirichlet_faces = t.dirichlet_faces;
+      std::copy(t.robin, t.robin + 6, robin);
+      if (ls_level && has_robin())
+        throw std::invalid_argument("local-smoothing level tables of a triangulation with Robin coefficients (convective faces): not "
+                                    "implemented, only all coefficients 0");
       if (ls_level && dirichlet_faces != Tria::ALL_DIRICHLET)
         throw std::invalid_argument("local-smoothing level tables of a triangulation with the dirichlet_faces mask " +
                                     std::to_string(dirichlet_faces) + ": not implemented, only the mask 63");
@@ -751,6 +840,12 @@ namespace mgamd
           compute_rhs_constant(b);
           return;
         }
+      // the lifting of non-zero Dirichlet data below goes through the cell matrices only: a convective face next to a Dirichlet face
+      // couples the two through its surface mass matrix, which it would miss
+      if (has_robin())
+        throw std::invalid_argument("right-hand side of SimulationType " + std::to_string(kind) +
+                                    " with Robin coefficients (convective faces): not implemented, the lifting of non-zero Dirichlet "
+                                    "data carries no face term; only kind 0 (f = 1, g = 0)");
       b.assign(n_dofs, 0.0);
       const int           n = p + 1, n3 = n * n * n;
       std::vector<double> fq(n3), t1(n3), t2(n3), load(n3), xg(n3), lift(n3);
@@ -1308,6 +1403,52 @@ namespace mgamd
               for (size_t ci = 0; ci < nc; ++ci)
                 if (cell_group[ci] == gi)
                   cell_slot[ci] = new_of_old[cell_slot[ci]];
+            }
+        }
+      build_robin_faces();
+    }
+
+    // robin_faces from the final numbering; nothing where every beta is 0
+    void
+    build_robin_faces()
+    {
+      if (!has_robin())
+        return;
+      const int n = p + 1;
+      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
+        {
+          if (!cell_is_local(ci))
+            continue;
+          const Cell    &c      = tria->cells[ci];
+          const uint16_t mask   = tria->masks[ci];
+          const uint32_t last   = (1u << c.level) - 1;
+          const uint32_t ijk[3] = {c.i, c.j, c.k};
+          const double   h      = 2.0 / (double)(1u << c.level);
+          for (int f = 0; f < 6; ++f)
+            {
+              const int d = f >> 1, side = f & 1;
+              if (!(robin[f] > 0.0) || ijk[d] != (side ? last : 0u))
+                continue;
+              const int u = d == 0 ? 1 : 0, v = d == 2 ? 1 : 2; // the in-face axes, u < v
+              for (int av = 0; av < n; ++av)
+                for (int au = 0; au < n; ++au)
+                  {
+                    int a[3];
+                    a[d] = side * p;
+                    a[u] = au;
+                    a[v] = av;
+                    robin_faces.idx.push_back(cell_node_index(ci, a));
+                  }
+              const bool    hanging = (mask >> MASK_FACE_SHIFT) != 0;
+              const int     cu = (mask >> u) & 1, cv = (mask >> v) & 1;
+              // interpolate_hanging, pass along u: the line at v = cv p, normal coordinate = the boundary side, is flagged by the
+              // hanging face with normal v or the hanging edge along u; likewise along v
+              const bool hang_u = hanging && (((mask >> (MASK_FACE_SHIFT + v)) & 1) || ((mask >> (MASK_EDGE_SHIFT + u)) & 1));
+              const bool hang_v = hanging && (((mask >> (MASK_FACE_SHIFT + u)) & 1) || ((mask >> (MASK_EDGE_SHIFT + v)) & 1));
+              if (hanging && (((mask >> d) & 1) != side || ((mask >> (MASK_FACE_SHIFT + d)) & 1)))
+                throw std::runtime_error("convective faces: a boundary cell face with a hanging face of its own");
+              robin_faces.flags.push_back((uint8_t)((hang_u ? 1 : 0) | (hang_v ? 2 : 0) | (cu << 2) | (cv << 3)));
+              robin_faces.scale.push_back(robin[f] * h * h);
             }
         }
     }

@@ -110,6 +110,21 @@ namespace mgamd
       check(mgamd_tria_get_dirichlet_faces(h.get(), &mask));
       return mask;
     }
+    // Convective (Robin) faces: a grad u . n + beta[f] (u - u_ext) = 0 on face f, beta[f] >= 0, default 0; refused on a Dirichlet
+    // face.  coarsen() inherits the values; DoFs copy them when they are built (mgamd_tria_set_robin_coefficients).  The load of
+    // u_ext is Operator::rhs_boundary_flux with q[f] = beta[f] u_ext.
+    void
+    set_robin_coefficients(const std::array<double, 6> &beta)
+    {
+      check(mgamd_tria_set_robin_coefficients(h.get(), beta.data()));
+    }
+    std::array<double, 6>
+    robin_coefficients() const
+    {
+      std::array<double, 6> beta{};
+      check(mgamd_tria_get_robin_coefficients(h.get(), beta.data()));
+      return beta;
+    }
     // local smoothing: all cells of refinement level `level`, active or not (the level of DoFHandler::distribute_mg_dofs)
     std::shared_ptr<Triangulation>
     level_mesh(unsigned level) const
@@ -341,6 +356,14 @@ namespace mgamd
       unsigned mask = 0;
       check(mgamd_dofs_dirichlet_faces(h.get(), &mask));
       return mask;
+    }
+    // the Robin coefficients these DoFs were built with
+    std::array<double, 6>
+    robin_coefficients() const
+    {
+      std::array<double, 6> beta{};
+      check(mgamd_dofs_robin_coefficients(h.get(), beta.data()));
+      return beta;
     }
     mgamd_dofs_info_t info;
 

@@ -213,7 +213,40 @@ namespace mgamd
     {
       if (mask > ALL_DIRICHLET)
         throw std::invalid_argument("dirichlet_faces mask " + std::to_string(mask) + " refused: the cube has six faces, the mask is at most 63");
+      for (int f = 0; f < 6; ++f)
+        if (((mask >> f) & 1) && robin[f] > 0.0)
+          throw std::invalid_argument("dirichlet_faces mask " + std::to_string(mask) + " refused: face " + std::to_string(f) +
+                                      " carries the Robin coefficient " + std::to_string(robin[f]) +
+                                      ", a convective face cannot be Dirichlet (set its coefficient to 0 first)");
       dirichlet_faces = mask;
+    }
+    // Convective (Robin) faces:  a grad u . n + beta_f (u - u_ext) = 0  on face f, beta_f >= 0 (0: the face is natural or Dirichlet as
+    // the mask says).  The operator gains  sum_f beta_f B_f,  B_f the surface mass matrix of face f; the load beta_f u_ext,f int phi_i
+    // is LevelTables::compute_rhs_boundary_flux with q_f = beta_f u_ext,f.  A face is Dirichlet or convective, never both.  Level
+    // tables copy the values when they are built (DESIGN.md "Convective faces").
+    double robin[6] = {0, 0, 0, 0, 0, 0};
+    bool
+    has_robin() const
+    {
+      for (int f = 0; f < 6; ++f)
+        if (robin[f] > 0.0)
+          return true;
+      return false;
+    }
+    void
+    set_robin_coefficients(const double beta[6])
+    {
+      for (int f = 0; f < 6; ++f)
+        {
+          if (!(beta[f] >= 0.0) || !std::isfinite(beta[f]))
+            throw std::invalid_argument("Robin coefficient " + std::to_string(beta[f]) + " on face " + std::to_string(f) +
+                                        " refused: it must be finite and >= 0");
+          if (beta[f] > 0.0 && ((dirichlet_faces >> f) & 1))
+            throw std::invalid_argument("Robin coefficient " + std::to_string(beta[f]) + " on face " + std::to_string(f) +
+                                        " refused: the face is Dirichlet (dirichlet_faces mask " + std::to_string(dirichlet_faces) +
+                                        "), a convective face needs a natural one");
+        }
+      std::copy(beta, beta + 6, robin);
     }
 
     static Tria
@@ -227,7 +260,7 @@ namespace mgamd
     from_leaves_checked(std::vector<Cell> leaves);
     Tria
     coarsen_global() const; // one level of the geometric coarsening sequence; the coefficient goes down as the mean over each leaf,
-                            // the dirichlet_faces mask unchanged
+                            // the dirichlet_faces mask and the Robin coefficients unchanged
     // local smoothing: ALL cells of refinement level `level`, active or not (DoFHandler::distribute_mg_dofs levels)
     Tria
     level_mesh(int level) const
@@ -235,6 +268,9 @@ namespace mgamd
       if (!coefficient.empty())
         throw std::invalid_argument("level_mesh: the triangulation carries a diffusion coefficient: local smoothing with a "
                                     "coefficient is not implemented (the refinement-edge matrices have none)");
+      if (has_robin()) // (before the mask: a convective face is never Dirichlet, so the mask would always answer first)
+        throw std::invalid_argument("level_mesh: the triangulation carries Robin coefficients (convective faces): local smoothing with "
+                                    "convective faces is not implemented, only all coefficients 0");
       if (dirichlet_faces != ALL_DIRICHLET)
         throw std::invalid_argument("level_mesh: the triangulation carries the dirichlet_faces mask " + std::to_string(dirichlet_faces) +
                                     ": local smoothing with natural (Neumann) faces is not implemented, only the mask 63");
@@ -683,6 +719,7 @@ namespace mgamd
   {
     Tria coarse            = coarsen_cells();
     coarse.dirichlet_faces = dirichlet_faces;
+    std::copy(robin, robin + 6, coarse.robin); // (a re-discretisation, like the coefficient: the same beta on every mesh)
     if (!coefficient.empty())
       {
         // Re-discretisation, not a Galerkin product: a coarse leaf is one of this mesh's leaves (its own value) or the parent of

@@ -688,8 +688,10 @@ namespace mgamd
       ctx    = f->ctx;
       // the fine group whose bricks carry the fused transfers: the plain 17-point lattices of an h-transfer (persistent
       // workgroups); not on local-smoothing levels (edge rows, partial coverage)
+      // nor on a fine level with a convective face: the fused bricks restrict and prolongate tail rows that never pass through the
+      // accumulator, where the face kernel adds its term (DESIGN.md "Convective faces": the known cost of such levels)
       int fuse_group = -1;
-      if (!getenv("MGAMD_NO_FUSED_TRANSFER") && f->tables->tria != c->tables->tria && f->tables->p == c->tables->p &&
+      if (!getenv("MGAMD_NO_FUSED_TRANSFER") && !f->tables->has_robin() && f->tables->tria != c->tables->tria && f->tables->p == c->tables->p &&
           !f->tables->ls_level && !c->tables->ls_level && fused_transfer_supported(f->tables->p))
         for (size_t gi = 0; gi < f->tables->groups.size(); ++gi)
           {

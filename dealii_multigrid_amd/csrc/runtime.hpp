@@ -175,14 +175,15 @@ namespace mgamd
     // mass coefficient of K + sigma M: the operator's OWN copy of tables->sigma, taken at construction (a time-stepping caller
     // changes it on the tables and builds new operators)
     double sigma = 0.0;
-    // no Dirichlet face and sigma == 0 (the operator's own): the constants are in the kernel.  The operator, its mass product,
+    // no Dirichlet face, sigma == 0 (the operator's own) and no convective face: the constants are in the kernel.  The operator, its mass product,
     // inverse diagonal and Chebyshev stay available; every solver built on it refuses through this (DESIGN.md "Boundary conditions")
     void
     refuse_singular(const char *who) const
     {
-      if (tables->dirichlet_faces == 0 && sigma == 0.0)
+      if (tables->dirichlet_faces == 0 && sigma == 0.0 && !tables->has_robin())
         throw std::invalid_argument(std::string(who) + ": refused, the operator is singular: dirichlet_faces mask 0 (no Dirichlet face) with "
-                                    "mass coefficient sigma = 0 has the constants in its kernel, and no mean-value projection is built");
+                                    "mass coefficient sigma = 0 and no convective face has the constants in its kernel, and no mean-value "
+                                    "projection is built");
     }
     virtual ~LevelOperatorBase() = default;
     // inner product counting every DoF once across ranks (copies of DoFs owned by other ranks are skipped)

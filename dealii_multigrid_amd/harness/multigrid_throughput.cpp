@@ -145,6 +145,10 @@ struct RunParameters
   // boundary id 0 on the whole surface (ref:multigrid_throughput.cc:1585-1593).  Refused for the local-smoothing Types, and for
   // all six faces with MassCoefficient 0 (the singular pure-Neumann problem).
   std::string  neumann_faces        = "";
+  // this project's extension: "RobinCoefficients": six comma-separated numbers beta_f >= 0, one per face in the numbering above (a
+  // string because this parser is flat), such as "2.5,0,0,0.75,0,0": face f is convective, a grad u . n + beta_f u = 0, where
+  // beta_f > 0; such a face must be listed in NeumannFaces.  Default "": no convective face.  Refused for the local-smoothing Types.
+  std::string  robin_coefficients   = "";
   MultigridParameters mg_data;
 
   unsigned
@@ -158,6 +162,37 @@ struct RunParameters
         mask &= ~(1u << (c - '0'));
       }
     return mask;
+  }
+
+  std::array<double, 6>
+  robin() const
+  {
+    std::array<double, 6> beta{};
+    if (robin_coefficients.empty())
+      return beta;
+    const std::string what = "RobinCoefficients '" + robin_coefficients + "': not implemented (six comma-separated numbers >= 0)";
+    std::stringstream in(robin_coefficients);
+    std::string       item;
+    int               f = 0;
+    while (std::getline(in, item, ','))
+      {
+        size_t used = 0;
+        double v    = -1.0;
+        try
+          {
+            v = std::stod(item, &used);
+          }
+        catch (const std::exception &)
+          {
+            throw std::runtime_error(what);
+          }
+        if (f >= 6 || item.find_first_not_of(" \t", used) != std::string::npos || !(v >= 0.0) || !std::isfinite(v))
+          throw std::runtime_error(what);
+        beta[f++] = v;
+      }
+    if (f != 6)
+      throw std::runtime_error(what);
+    return beta;
   }
 
   void
@@ -198,6 +233,7 @@ struct RunParameters
     get("AMGMinShardedRows", amg_min_sharded_rows);
     get("MassCoefficient", mass_coefficient);
     get("NeumannFaces", neumann_faces);
+    get("RobinCoefficients", robin_coefficients);
     get("SimulationType", simulation_type); // unknown keys are ignored (skip_undefined = true)
   }
 };
@@ -300,10 +336,20 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
     throw std::runtime_error("MGNumberType '" + params.mg_number_type + "': not implemented");
 
   const unsigned dirichlet_faces = params.dirichlet_faces();
+  // (the convective faces first: they imply another mask than 0x3F, which would answer for them below)
+  const std::array<double, 6> robin     = params.robin();
+  const bool                  convective = std::any_of(robin.begin(), robin.end(), [](double b) { return b > 0.0; });
+  if (convective && (params.type == "HMG-local" || params.type == "HPMG-local"))
+    throw std::runtime_error("RobinCoefficients '" + params.robin_coefficients + "' with Type '" + params.type +
+                             "': not implemented (local smoothing takes no convective faces)");
+  for (int f = 0; f < 6; ++f)
+    if (robin[f] > 0.0 && ((dirichlet_faces >> f) & 1))
+      throw std::runtime_error("RobinCoefficients '" + params.robin_coefficients + "': not implemented on face " + std::to_string(f) +
+                               ", which is Dirichlet (list it in NeumannFaces)");
   if (dirichlet_faces != 0x3F && (params.type == "HMG-local" || params.type == "HPMG-local"))
     throw std::runtime_error("NeumannFaces '" + params.neumann_faces + "' with Type '" + params.type +
                              "': not implemented (local smoothing takes Dirichlet conditions on the whole boundary only)");
-  if (dirichlet_faces == 0 && params.mass_coefficient == 0.0)
+  if (dirichlet_faces == 0 && params.mass_coefficient == 0.0 && !convective)
     throw std::runtime_error("NeumannFaces '" + params.neumann_faces + "' with MassCoefficient 0: not implemented (no Dirichlet face and "
                              "no mass term: the operator is singular, and no mean-value projection is built)");
   std::shared_ptr<const Triangulation> tria;
@@ -311,6 +357,8 @@ run(const Context &ctx, const RunParameters &params, ConvergenceTable &table, co
     auto mesh = std::make_shared<Triangulation>(params.geometry_type, params.n_ref_global, params.n_ref_local);
     if (dirichlet_faces != 0x3F)
       mesh->set_dirichlet_faces(dirichlet_faces); // before anything is built on the mesh: coarse meshes and DoFs inherit it
+    if (convective)
+      mesh->set_robin_coefficients(robin); // after the mask: a convective face must not be Dirichlet
     tria = mesh;
   }
 
@@ -602,6 +650,8 @@ main(int argc, char **argv)
             std::cout << "MassCoefficient: " << params.mass_coefficient << std::endl;
           if (rank == 0 && !params.neumann_faces.empty())
             std::cout << "NeumannFaces: " << params.neumann_faces << " (dirichlet_faces mask " << params.dirichlet_faces() << ")" << std::endl;
+          if (rank == 0 && !params.robin_coefficients.empty())
+            std::cout << "RobinCoefficients: " << params.robin_coefficients << std::endl;
           run(ctx, params, table, sharded ? &comm : nullptr);
           if (rank == 0)
             table.write_text(std::cout);

@@ -106,6 +106,20 @@ int mgamd_tria_has_coefficient(const mgamd_tria *t, int *has);
  * and sigma in mgamd_last_error(): no mean-value projection is built. */
 int mgamd_tria_set_dirichlet_faces(mgamd_tria *t, unsigned mask);
 int mgamd_tria_get_dirichlet_faces(const mgamd_tria *t, unsigned *mask);
+/* Convective (Robin) faces, this project's extension:  a grad u . n + beta_f (u - u_ext,f) = 0  on face f of the cube, beta_f >= 0, one
+ * value per face in the numbering above; the default is 0 on every face (natural or Dirichlet, as the mask says).  The operator
+ * becomes  A = K_a + sigma M + sum_f beta_f B_f,  B_f the surface mass matrix of face f, in every product, residual, smoother,
+ * inverse diagonal and assembled matrix (not in the mass product).  u_ext needs no entry of its own: its load
+ * beta_f u_ext,f int_{face f} phi_i  is mgamd_dofs_rhs_boundary_flux with q[f] = beta_f u_ext,f.
+ * MGAMD_ERR_INVALID, naming the face and the value: a negative, NaN or infinite beta_f; beta_f > 0 on a face whose Dirichlet bit is
+ * set (checked here against the current mask and in mgamd_tria_set_dirichlet_faces against the current beta, so the two setters
+ * work in either order).  mgamd_tria_coarsen inherits the values (a re-discretisation, like the coefficient); mgamd_dofs_create and
+ * mgamd_dofs_create_local COPY them, and mgamd_dofs_robin_coefficients reads that copy.  Local smoothing is not implemented with
+ * any beta_f > 0: mgamd_tria_level_mesh is MGAMD_ERR_INVALID then.  One beta_f > 0 makes the operator regular: mask 0 with sigma 0
+ * is then accepted by every solver.  The level transfers fused into the operator passes are not used on a level with a beta_f > 0
+ * (mgamd_transfer2_n_fused_bricks reports 0 there). */
+int mgamd_tria_set_robin_coefficients(mgamd_tria *t, const double beta[6]);
+int mgamd_tria_get_robin_coefficients(const mgamd_tria *t, double beta[6]);
 
 typedef struct
 {
@@ -160,6 +174,13 @@ int mgamd_dofs_dirichlet_faces(const mgamd_dofs *d, unsigned *mask);
  * diffusion coefficient and of sigma, and additive to mgamd_dofs_rhs (ref:include/operator.h:362-447 has no boundary term).
  * MGAMD_ERR_INVALID, naming the face, for a non-zero q[f] on a Dirichlet face. */
 int mgamd_dofs_rhs_boundary_flux(const mgamd_dofs *d, const double q[6], double *out);
+/* the Robin coefficients these tables were built with (mgamd_tria_set_robin_coefficients).  The load of a convective face's
+ * exterior temperature is mgamd_dofs_rhs_boundary_flux with q[f] = beta_f u_ext,f: that function refuses Dirichlet faces only. */
+int mgamd_dofs_robin_coefficients(const mgamd_dofs *d, double beta[6]);
+/* the table of boundary cell faces on convective faces that the face kernel walks (this rank's cells, Morton order): *n_faces
+ * entries of (degree+1)^2 DoF indices (hanging entities resolved to the parent's DoFs, 0xFFFFFFFF on Dirichlet DoFs), one byte of
+ * hanging flags (level_tables.hpp, RobinFaces) and the scale beta_f h^2.  Null arrays are skipped: call once for the count. */
+int mgamd_dofs_robin_faces(const mgamd_dofs *d, uint64_t *n_faces, uint32_t *idx, uint8_t *flags, double *scale);
 /* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
  * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
  * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
