@@ -11,7 +11,11 @@ from conftest import rel_err
 pytestmark = pytest.mark.gpu
 
 CASES = [("quadrant", 3, 1), ("quadrant", 4, 1), ("quadrant", 4, 2), ("quadrant", 3, 4), ("annulus", 5, 1), ("annulus", 5, 2), ("quadrant", 5, 1),
-         ("hypercube", 3, 2)]
+         ("hypercube", 3, 2),
+         # circle: point refinement at the origin, entirely in the interior.  The refinement levels above 3 are patches that never touch
+         # the boundary: their whole surface is refinement edge, the Dirichlet block of [I | T | E | D] is empty, and the patch repeats
+         # with identical size level after level (125 DoFs of which 98 edge at p = 1)
+         ("circle", 5, 1), ("circle", 5, 2), ("circle", 6, 1), ("circle", 6, 2)]
 
 
 @pytest.fixture(scope="module")
@@ -40,6 +44,9 @@ def test_level_operators_edge_matrices_and_transfers(mgamd, ctx, ls_hierarchies,
         first_edge = info.n_interior + info.n_tail
         assert h.dofs[l].n_dofs == Lv.n and info.n_edge == Lv.edge.sum() and info.n_hanging == 0
         assert Lv.edge[first_edge:first_edge + info.n_edge].all() and Lv.edge.sum() == info.n_edge  # [I | T | E | D]
+        if geo == "circle" and l > 3:  # an interior patch: edge DoFs and no Dirichlet DoF
+            assert info.n_edge > 0 and info.n_dirichlet == 0 and first_edge + info.n_edge == Lv.n and not Lv.dirichlet.any()
+            assert (Lv.n, info.n_edge) == {(5, 1): (125, 98), (5, 2): (729, 386), (6, 1): (425, 290), (6, 2): (2673, 1154)}[(L, p)]
         x = rng.standard_normal(Lv.n)
         src, dst = op.initialize_dof_vector().from_host(x), op.initialize_dof_vector()
         op.vmult(dst, src)  # edge DoFs: zero input, identity rows (ref:include/operator.h:152-183)
@@ -109,7 +116,7 @@ def test_float_levels_local_smoothing(mgamd, ctx):
     assert abs(it - ref.solve(1e-4)[1]) <= 1
 
 
-@pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 4), ("annulus", 5, 2), ("quadrant", 4, 2)])
+@pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 4), ("annulus", 5, 2), ("quadrant", 4, 2), ("circle", 5, 2)])
 def test_hpmg_local(mgamd, ctx, geo, L, p):
     """`HPMG-local` (ref:multigrid_throughput.cc:1685-1695,1846-1860): p-multigrid on the active mesh over ONE local-smoothing
     V-cycle at the lowest degree, against the composed oracle"""

@@ -11,7 +11,16 @@ import pytest
 from conftest import oracle_level, ROOT
 
 CASES = [("quadrant", 3, 1, 0), ("quadrant", 3, 2, 0), ("quadrant", 3, 4, 0), ("quadrant", 4, 1, 0), ("quadrant", 3, 4, 1),
-         ("quadrant", 3, 3, 0), ("hypercube", 3, 1, 0), ("hypercube", 2, 4, 0), ("annulus", 5, 2, 0), ("circle", 4, 1, 0)]
+         ("quadrant", 3, 3, 0), ("hypercube", 3, 1, 0), ("hypercube", 2, 4, 0), ("annulus", 5, 2, 0), ("circle", 4, 1, 0),
+         ("quadrant_flexible", (2, 2), 2, 0), ("quadrant_flexible", (2, 2), 4, 0), ("quadrant_flexible", (3, 1), 1, 0)]
+# quadrant_flexible (the harness's default geometry): (NRefGlobal, NRefLocal) = (2, 2) and (3, 1), refined octants that quadrant
+# cannot produce
+FLEXIBLE = [("quadrant_flexible", (2, 2)), ("quadrant_flexible", (3, 1))]
+
+
+def refs(L):
+    """(n_ref_global, n_ref_local) of a case's refinement entry: a tuple for quadrant_flexible, NRefGlobal alone elsewhere"""
+    return L if isinstance(L, tuple) else (L,)
 
 
 def test_c_abi_exports_every_declared_symbol(mgamd):
@@ -48,9 +57,9 @@ def test_device_calls_fail_loudly_without_gpu(mgamd):
 
 
 def test_mesh_generators_match_oracle(mgamd, oracle):
-    for geo, L in (("quadrant", 4), ("quadrant", 5), ("annulus", 5), ("annulus", 6), ("circle", 5), ("hypercube", 3), ("quadrant", 0)):
-        t = mgamd.Triangulation(geo, L)
-        m = oracle.create_mesh(geo, L)
+    for geo, L in [("quadrant", 4), ("quadrant", 5), ("annulus", 5), ("annulus", 6), ("circle", 5), ("hypercube", 3), ("quadrant", 0)] + FLEXIBLE:
+        t = mgamd.Triangulation(geo, *refs(L))
+        m = oracle.create_mesh(geo, *refs(L))
         lev, i, j, k, mask = t.cells()
         assert set(zip(lev.tolist(), i.tolist(), j.tolist(), k.tolist())) == m
         assert [oracle.morton_key(c) for c in zip(lev.tolist(), i.tolist(), j.tolist(), k.tolist())] == sorted(oracle.morton_key(c) for c in m)
@@ -67,6 +76,25 @@ def test_geometric_coarsening_sequence(mgamd, oracle):
         for t, m in zip(seq, ref):
             lev, i, j, k, _ = t.cells()
             assert set(zip(lev.tolist(), i.tolist(), j.tolist(), k.tolist())) == m
+
+
+@pytest.mark.parametrize("geo,L", [("circle", 5), ("circle", 6), ("circle", 7), ("quadrant_flexible", (2, 2))])
+def test_geometric_coarsening_sequence_of_centre_refined_meshes(mgamd, oracle, geo, L):
+    """circle: the background (level 3) coarsens in one step while the centre keeps its hanging-node shells, then only the centre
+    changes; quadrant_flexible: NRefLocal > 0.  Level by level as cell sets, and the sizes the oracle was run for"""
+    seq = mgamd.create_geometric_coarsening_sequence(mgamd.Triangulation(geo, *refs(L)))
+    ref = oracle.coarsening_sequence(oracle.create_mesh(geo, *refs(L)))
+    assert [t.n_cells for t in seq] == [len(m) for m in ref]
+    for t, m in zip(seq, ref):
+        lev, i, j, k, _ = t.cells()
+        assert set(zip(lev.tolist(), i.tolist(), j.tolist(), k.tolist())) == m
+        assert t.n_cells_hn == sum(oracle.is_cell_constrained(m, c) for c in m)
+    if geo == "circle":
+        assert [t.n_cells for t in seq][-3:] == {5: [120, 176, 624], 6: [176, 232, 1184], 7: [232, 960, 2976]}[L]
+    if (geo, L) == ("circle", 5):
+        assert [t.n_cells for t in seq] == [1, 8, 64, 120, 176, 624]
+        assert seq[-2].n_cells < 0.3 * seq[-1].n_cells  # one step removes most cells
+        assert [mgamd.DoFs(t, 1).n_dofs for t in seq] == [8, 27, 125, 223, 321, 925]
 
 
 def test_survey_appendix_b_counts(mgamd):
@@ -106,9 +134,9 @@ def _interp(oracle, fe, mask, v, transpose):
 
 @pytest.mark.parametrize("geo,L,p,max_brick", CASES)
 def test_tables_reproduce_assembled_operator(mgamd, oracle, geo, L, p, max_brick):
-    t = mgamd.Triangulation(geo, L)
+    t = mgamd.Triangulation(geo, *refs(L))
     d = mgamd.DoFs(t, p, max_brick)
-    lv = oracle_level(oracle, d, geo, L, p)
+    lv = oracle_level(oracle, d, geo, L, p, mesh=oracle.create_mesh(geo, *refs(L)))
     info = d.info
     assert d.n_dofs == lv.n
     first_c = info.n_interior + info.n_tail
@@ -172,12 +200,12 @@ def test_transfer_tables_reproduce_oracle_prolongation(mgamd, oracle, geo, L, p,
     assert np.abs(out - ref).max() < 1e-13 * max(np.abs(ref).max(), 1)
 
 
-@pytest.mark.parametrize("geo,L", [("quadrant", 4), ("annulus", 5), ("circle", 4), ("hypercube", 3)])
+@pytest.mark.parametrize("geo,L", [("quadrant", 4), ("annulus", 5), ("circle", 4), ("hypercube", 3), ("circle", 6)] + FLEXIBLE)
 @pytest.mark.parametrize("p", [1, 2, 3, 4])
 def test_slot_decomposition_covers_every_cell_once(mgamd, geo, L, p, monkeypatch):
     """bricks (incl. constrained 2^3 families), and single cells partition the leaves; switching the constrained families
     off only moves cells between the groups and never changes the DoF count"""
-    t = mgamd.Triangulation(geo, L)
+    t = mgamd.Triangulation(geo, *refs(L))
     d = mgamd.DoFs(t, p, 0)
     assert sum(B ** 3 * n for B, n in d.groups()) == t.n_cells
     monkeypatch.setenv("MGAMD_NO_HANGING_BRICKS", "1")
@@ -189,14 +217,15 @@ def test_slot_decomposition_covers_every_cell_once(mgamd, geo, L, p, monkeypatch
         assert d.info.n_interior >= d0.info.n_interior
 
 
-@pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 1), ("quadrant", 3, 2), ("quadrant", 3, 4), ("annulus", 5, 2), ("hypercube", 2, 3), ("circle", 4, 3)])
+@pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 1), ("quadrant", 3, 2), ("quadrant", 3, 4), ("annulus", 5, 2), ("hypercube", 2, 3), ("circle", 4, 3),
+                                      ("quadrant_flexible", (2, 2), 2), ("quadrant_flexible", (2, 2), 4), ("quadrant_flexible", (3, 1), 1)])
 def test_gaussian_right_hand_side_and_distribute(mgamd, oracle, geo, L, p):
     """SimulationType "Gaussian" (ref:multigrid_throughput.cc:60-125,2294-2298): quadrature load vector of f minus the
     Dirichlet lifting of g (ref:include/operator.h:362-447), and constraints.distribute, against the textbook oracle
     (assembled K, explicit hanging-node matrix)."""
-    t = mgamd.Triangulation(geo, L)
+    t = mgamd.Triangulation(geo, *refs(L))
     d = mgamd.DoFs(t, p, 0)
-    lv = oracle_level(oracle, d, geo, L, p)
+    lv = oracle_level(oracle, d, geo, L, p, mesh=oracle.create_mesh(geo, *refs(L)))
     ref = lv.rhs_function(oracle.gaussian_rhs, oracle.gaussian_solution)
     got = d.rhs_function(1)
     assert np.abs(got - ref).max() <= 1e-12 * max(np.abs(ref).max(), 1e-300)

@@ -4,7 +4,9 @@ right-hand side on every copy."""
 import numpy as np
 import pytest
 
-CASES = [("quadrant", 4, 4, 2), ("quadrant", 5, 2, 3), ("hypercube", 4, 2, 2), ("annulus", 6, 1, 4), ("quadrant", 5, 1, 8)]
+CASES = [("quadrant", 4, 4, 2), ("quadrant", 5, 2, 3), ("hypercube", 4, 2, 2), ("annulus", 6, 1, 4), ("quadrant", 5, 1, 8),
+         # circle: the weight of the finest level sits in a small central region that the space-filling-curve cut has to split
+         ("circle", 6, 2, 3), ("circle", 6, 2, 4), ("circle", 5, 1, 4)]
 
 
 def keyset(keys):
@@ -163,7 +165,8 @@ def test_partition_statistics_match_a_python_restatement(mgamd):
     assert one["workload_eff"] == 1.0 and one["vertical_eff"] == 1.0 and one["horizontal_eff"] == 1.0
 
 
-@pytest.mark.parametrize("geo,L,p,n_ranks", [("quadrant", 5, 2, 3), ("quadrant", 5, 4, 2), ("annulus", 6, 1, 4), ("hypercube", 5, 2, 2)])
+@pytest.mark.parametrize("geo,L,p,n_ranks", [("quadrant", 5, 2, 3), ("quadrant", 5, 4, 2), ("annulus", 6, 1, 4), ("hypercube", 5, 2, 2),
+                                             ("circle", 6, 2, 3), ("circle", 6, 2, 4), ("circle", 5, 1, 4)])
 def test_halo_slots_come_first(mgamd, geo, L, p, n_ranks):
     """sharded level: in every slot group the slots that touch DoFs shared with other ranks are at the front
     (group_halo_slots), so that the halo exchange of an operator application can run underneath the remaining slots"""
@@ -195,7 +198,8 @@ def test_halo_slots_come_first(mgamd, geo, L, p, n_ranks):
         assert 0 < n_front < len(touches)  # and there is an interior part to overlap with
 
 
-@pytest.mark.parametrize("geo,L,n_ranks,group", [("quadrant", 6, 8, 4), ("quadrant", 6, 8, 2), ("annulus", 7, 4, 2), ("hypercube", 5, 8, 4)])
+@pytest.mark.parametrize("geo,L,n_ranks,group", [("quadrant", 6, 8, 4), ("quadrant", 6, 8, 2), ("annulus", 7, 4, 2), ("hypercube", 5, 8, 4),
+                                                 ("circle", 7, 4, 2)])
 def test_two_tier_partition_is_nested_and_balanced(mgamd, geo, L, n_ranks, group):
     """Partition tiers (csrc/partition.hpp; the counterpart of the reference's agglomeration of coarse levels onto fewer processes,
     ref:multigrid_throughput.cc:379-418,1464-1501): the levels [sub_root_level, root_level) are cut into n_ranks / group parts, the
