@@ -356,6 +356,52 @@ class DoFs:
         _chk(_lib.mgamd_dofs_rhs_boundary_flux(self._h, _ptr(q), _ptr(b)))
         return b
 
+    def dirichlet_cells(self):
+        """the table the lifting of Dirichlet data walks (this rank's cells, in Morton order, that gather a Dirichlet DoF):
+        (idx [n, (p+1)^3] uint32 with the real index on Dirichlet DoFs, mask [n] uint16 the cell's hanging mask, scale [n, 2] =
+        (a h, h)); see mgamd_dofs_dirichlet_cells"""
+        n = C.c_uint64()
+        _chk(_lib.mgamd_dofs_dirichlet_cells(self._h, C.byref(n), None, None, None))
+        n3 = (self.degree + 1) ** 3
+        idx, mask, scale = np.zeros((n.value, n3), np.uint32), np.zeros(n.value, np.uint16), np.zeros((n.value, 2))
+        if n.value:
+            _chk(_lib.mgamd_dofs_dirichlet_cells(self._h, C.byref(n), _ptr(idx), _ptr(mask), _ptr(scale)))
+        return idx, mask, scale
+
+    def rhs_dirichlet(self, g, include_mass: bool = True):
+        """the lifting of the Dirichlet data g (n_dofs values, only those at Dirichlet DoFs are read), host vector:
+        -[C^T (K_a + s sigma M) C g^] on free rows, 0 on constrained rows, s = include_mass; additive to rhs_function,
+        rhs_boundary_flux and M f.  MgamdError where a convective face shares an edge with a Dirichlet face."""
+        g, b = self._data_array(g, "rhs_dirichlet"), np.zeros(self.n_dofs)
+        _chk(_lib.mgamd_dofs_rhs_dirichlet(self._h, _ptr(g), 1 if include_mass else 0, _ptr(b)))
+        return b
+
+    def distribute_values(self, x, g):
+        """a copy of the host vector x with the Dirichlet DoFs set to the values of g and the hanging DoFs interpolated from
+        their parents; free DoFs are untouched"""
+        x, g = self._data_array(x, "distribute_values").copy(), self._data_array(g, "distribute_values")
+        _chk(_lib.mgamd_dofs_distribute_values(self._h, _ptr(g), _ptr(x)))
+        return x
+
+    def dirichlet_face_values(self, v):
+        """Dirichlet data of one constant per face: v[f] on the Dirichlet DoFs of face f (6 values or {face: value}; a DoF on
+        several Dirichlet faces takes the lowest-numbered one), 0 elsewhere.  MgamdError for a non-zero value on a natural face."""
+        v, g = _flux_array(v, "Dirichlet values"), np.zeros(self.n_dofs)
+        _chk(_lib.mgamd_dofs_dirichlet_face_values(self._h, _ptr(v), _ptr(g)))
+        return g
+
+    def node_positions(self):
+        """the support point of every DoF, (n_dofs, 3): g = f(*dofs.node_positions().T) is the nodal interpolant of f"""
+        xyz = np.zeros((self.n_dofs, 3))
+        _chk(_lib.mgamd_dofs_node_positions(self._h, _ptr(xyz)))
+        return xyz
+
+    def _data_array(self, a, who):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (self.n_dofs,):
+            raise ValueError(f"{who}: {a.shape} values for {self.n_dofs} DoFs")
+        return a
+
     def keys(self):
         k = np.zeros((self.n_dofs, 5), np.int32)
         _chk(_lib.mgamd_dofs_get_keys(self._h, _ptr(k)))
@@ -667,6 +713,15 @@ class Operator:
         """constraints.distribute(solution): Dirichlet values of `kind`, hanging nodes interpolated"""
         _chk(_lib.mgamd_level_op_distribute(self._h, kind, x._h))
 
+    def rhs_dirichlet(self, b: Vector, g: Vector, include_mass: bool = True):
+        """b = the lifting of the Dirichlet data g (DoFs.rhs_dirichlet) by the device kernel over the cells that gather a
+        Dirichlet DoF; overwrites b, stream-ordered, completed over the ranks (mgamd_level_op_rhs_dirichlet)"""
+        _chk(_lib.mgamd_level_op_rhs_dirichlet(self._h, g._h, 1 if include_mass else 0, b._h))
+
+    def distribute_values(self, x: Vector, g: Vector):
+        """x: Dirichlet DoFs from g, then hanging DoFs from their parents, on the device (mgamd_level_op_distribute_values)"""
+        _chk(_lib.mgamd_level_op_distribute_values(self._h, x._h, g._h))
+
     def get_system_matrix(self) -> "SparseMatrix":
         """Operator::get_trilinos_system_matrix: the assembled matrix of this operator's DoFs on the device (FP64, one rank)"""
         if self.dofs.mass_coefficient() != self.mass_coefficient():  # the matrix is assembled from the DoFs' tables
@@ -909,12 +964,20 @@ class TimeStepper:
         """sigma = 1 / (theta dt)"""
         return 1.0 / (theta * dt)
 
-    def step(self, u: Vector, f_old: Vector = None, f_new: Vector = None, reltol=1e-4, abstol=1e-20, maxiter=10000):
-        """one step; f_old / f_new: nodal source values at t and t + dt (both None: f = 0).  Returns the CG's iterations and
-        final residual norm.  Constrained entries of u are not read and are 0 on return."""
+    def step(self, u: Vector, f_old: Vector = None, f_new: Vector = None, reltol=1e-4, abstol=1e-20, maxiter=10000, g_old: Vector = None,
+             g_new: Vector = None, load: Vector = None):
+        """one step; f_old / f_new: nodal source values at t and t + dt (both None: f = 0).  g_old / g_new: Dirichlet values at t and
+        t + dt (both None: homogeneous data), load: a boundary load theta l_new + (1 - theta) l_old (Operator.rhs_boundary_flux);
+        with one of the three the step is mgamd_time_stepper_step_data.  Returns the CG's iterations and final residual norm.
+        Constrained entries of u are not read and are 0 on return: Operator.distribute_values(u, g_new) fills them for output."""
         it, res = C.c_uint(), C.c_double()
-        _chk(_lib.mgamd_time_stepper_step(self._h, u._h, f_old._h if f_old is not None else None, f_new._h if f_new is not None else None,
-                                          C.c_double(reltol), C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
+        h = lambda v: v._h if v is not None else None
+        if g_old is None and g_new is None and load is None:
+            _chk(_lib.mgamd_time_stepper_step(self._h, u._h, h(f_old), h(f_new), C.c_double(reltol), C.c_double(abstol), maxiter,
+                                              C.byref(it), C.byref(res)))
+        else:
+            _chk(_lib.mgamd_time_stepper_step_data(self._h, u._h, h(f_old), h(f_new), h(g_old), h(g_new), h(load), C.c_double(reltol),
+                                                   C.c_double(abstol), maxiter, C.byref(it), C.byref(res)))
         return it.value, res.value
 
     def time(self) -> float:

@@ -24,4 +24,6 @@ namespace mgamd
   MGAMD_INST(MODE_CHEB_PROLONGATE)
 #endif
 #undef MGAMD_INST
+  // the lifting of non-zero Dirichlet data (kernels_boundary.hpp)
+  template void LevelOperator<MGAMD_INST_T>::lift_P<MGAMD_INST_P>(MGAMD_INST_T *, const MGAMD_INST_T *, double, double);
 } // namespace mgamd

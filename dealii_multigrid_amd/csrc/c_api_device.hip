@@ -433,6 +433,24 @@ mgamd_level_op_distribute(mgamd_level_op *op, int kind, mgamd_vec *x)
 }
 
 int
+mgamd_level_op_rhs_dirichlet(mgamd_level_op *op, const mgamd_vec *g, int include_mass, mgamd_vec *rhs)
+{
+  MGAMD_TRY
+  REQUIRE(op && g && rhs);
+  op->op->rhs_dirichlet(*rhs, *g, include_mass != 0);
+  MGAMD_CATCH
+}
+
+int
+mgamd_level_op_distribute_values(mgamd_level_op *op, mgamd_vec *x, const mgamd_vec *g)
+{
+  MGAMD_TRY
+  REQUIRE(op && x && g);
+  op->op->distribute_values(*x, *g);
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_debug_stamps(mgamd_level_op *op, unsigned long long *out, uint64_t max_count, uint64_t *count)
 {
   MGAMD_TRY
@@ -848,6 +866,23 @@ mgamd_time_stepper_step(mgamd_time_stepper *ts, mgamd_vec *u, const mgamd_vec *f
   unsigned it  = 0;
   double   res = 0;
   ts->ts->step(*u, f_old, f_new, reltol, abstol, maxiter, it, res);
+  if (n_iterations)
+    *n_iterations = it;
+  if (residual_norm)
+    *residual_norm = res;
+  MGAMD_CATCH
+}
+
+int
+mgamd_time_stepper_step_data(mgamd_time_stepper *ts, mgamd_vec *u, const mgamd_vec *f_old, const mgamd_vec *f_new, const mgamd_vec *g_old,
+                             const mgamd_vec *g_new, const mgamd_vec *load, double reltol, double abstol, unsigned maxiter,
+                             unsigned *n_iterations, double *residual_norm)
+{
+  MGAMD_TRY
+  REQUIRE(ts && u);
+  unsigned it  = 0;
+  double   res = 0;
+  ts->ts->step_data(*u, f_old, f_new, g_old, g_new, load, reltol, abstol, maxiter, it, res);
   if (n_iterations)
     *n_iterations = it;
   if (residual_norm)

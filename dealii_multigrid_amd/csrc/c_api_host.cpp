@@ -612,6 +612,71 @@ mgamd_dofs_rhs_boundary_flux(const mgamd_dofs *d, const double q[6], double *out
 }
 
 int
+mgamd_dofs_dirichlet_cells(const mgamd_dofs *d, uint64_t *n_cells, uint32_t *idx, uint16_t *mask, double *scale)
+{
+  MGAMD_TRY
+  if (!d || !n_cells)
+    throw std::invalid_argument("null argument");
+  const auto &dc = d->tables->dirichlet_cells;
+  *n_cells       = dc.size();
+  if (idx)
+    std::copy(dc.idx.begin(), dc.idx.end(), idx);
+  if (mask)
+    std::copy(dc.mask.begin(), dc.mask.end(), mask);
+  if (scale)
+    std::copy(dc.scale.begin(), dc.scale.end(), scale);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_rhs_dirichlet(const mgamd_dofs *d, const double *g, int include_mass, double *out)
+{
+  MGAMD_TRY
+  if (!d || !g || !out)
+    throw std::invalid_argument("null argument");
+  std::vector<double> b;
+  d->tables->compute_rhs_dirichlet(g, include_mass != 0, b); // (refuses a convective face next to a Dirichlet face, by name)
+  std::copy(b.begin(), b.end(), out);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_distribute_values(const mgamd_dofs *d, const double *g, double *x)
+{
+  MGAMD_TRY
+  if (!d || !g || !x)
+    throw std::invalid_argument("null argument");
+  std::vector<double> v(x, x + d->tables->n_dofs);
+  d->tables->distribute_values(g, v);
+  std::copy(v.begin(), v.end(), x);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_dirichlet_face_values(const mgamd_dofs *d, const double v[6], double *g)
+{
+  MGAMD_TRY
+  if (!d || !v || !g)
+    throw std::invalid_argument("null argument");
+  std::vector<double> h;
+  d->tables->dirichlet_face_values(v, h); // (refuses a value on a natural face, by name)
+  std::copy(h.begin(), h.end(), g);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_node_positions(const mgamd_dofs *d, double *xyz)
+{
+  MGAMD_TRY
+  if (!d || !xyz)
+    throw std::invalid_argument("null argument");
+  std::vector<double> h;
+  d->tables->export_node_positions(h);
+  std::copy(h.begin(), h.end(), xyz);
+  MGAMD_CATCH
+}
+
+int
 mgamd_dofs_coefficient_range(const mgamd_dofs *d, double *min, double *max)
 {
   MGAMD_TRY

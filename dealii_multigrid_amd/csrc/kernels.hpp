@@ -24,11 +24,15 @@
 // K7  csr_spmv_kernel        CSR products of the algebraic coarse solver, fused with the Chebyshev update; one body
 //                            (csr_spmv_rows), two entry points: all rows, and csr_spmv_range_kernel for a sharded level's rows.
 //
+// K9  dirichlet_lift_kernel  the lifting of non-zero Dirichlet data over the cells that gather a Dirichlet DoF
+//
 // The kernels live in kernels_common.hpp (1D products, sweeps, constraint passes, argument structs), kernels_apply.hpp (K1-K3),
-// kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header includes them all.
+// kernels_boundary.hpp (K9), kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header
+// includes them all.
 #pragma once
 #include "kernels_common.hpp"
 #include "kernels_apply.hpp"
+#include "kernels_boundary.hpp"
 #include "kernels_transfer.hpp"
 #include "kernels_vector.hpp"
 #include "kernels_amg.hpp"

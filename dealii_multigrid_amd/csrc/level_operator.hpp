@@ -314,6 +314,24 @@ namespace mgamd
     };
     std::unique_ptr<RobinDev> robin;
 
+    // Non-zero Dirichlet data: device images of LevelTables::dirichlet_cells (the lifting) and LevelTables::hanging_rows
+    // (distribute_values), uploaded by the first call that needs them: an operator that never sees such data allocates nothing
+    struct DirichletDev
+    {
+      DBuf<uint32_t> idx;
+      DBuf<uint16_t> mask;
+      DBuf<double>   scale;
+      uint32_t       n_cells = 0;
+    };
+    std::unique_ptr<DirichletDev> dirichlet;
+    struct HangingDev
+    {
+      DBuf<uint32_t> ptr, col;
+      DBuf<double>   val;
+      uint32_t       n_rows = 0;
+    };
+    std::unique_ptr<HangingDev> hanging;
+
     // The kernel launches of one operator application, planned once (build_launch_plan): one step per launch, in launch order.
     enum class LaunchKind
     {
@@ -1058,6 +1076,84 @@ namespace mgamd
       if (dst.data == src.data)
         throw std::invalid_argument("vmult_mass: dst and src must differ");
       vmult_mass_raw(dst.as<T>(), src.as<T>());
+    }
+
+    // defined in level_operator_apply.hpp, instantiated in apply_inst.hip with the operator passes
+    template <int P>
+    void
+    lift_P(T *dst, const T *g, double mass_sigma, double alpha);
+
+    // dst += alpha C^T (K_a + [include_mass] sigma M) C g^ on the free rows, this rank's cells (kernels_boundary.hpp); nothing is
+    // launched where no cell gathers a Dirichlet DoF
+    void
+    dirichlet_lift_add_raw(T *dst, const T *g, bool include_mass, double alpha)
+    {
+      tables->refuse_dirichlet_lift("rhs_dirichlet");
+      if (!dirichlet)
+        {
+          dirichlet = std::make_unique<DirichletDev>();
+          dirichlet->idx.upload(tables->dirichlet_cells.idx);
+          dirichlet->mask.upload(tables->dirichlet_cells.mask);
+          dirichlet->scale.upload(tables->dirichlet_cells.scale);
+          dirichlet->n_cells = (uint32_t)tables->dirichlet_cells.size();
+        }
+      if (!dirichlet->n_cells)
+        return;
+      if (!dispatch_degree(p, [&](auto P) { lift_P<P()>(dst, g, include_mass ? sigma : 0.0, alpha); }))
+        throw std::runtime_error("degree not instantiated");
+    }
+    // rhs = the lifting of g, completed over the ranks; constrained rows 0
+    void
+    rhs_dirichlet_raw(T *rhs, const T *g, bool include_mass)
+    {
+      HIP_CHECK(hipMemsetAsync(rhs, 0, (size_t)n_dofs() * sizeof(T), ctx->stream));
+      dirichlet_lift_add_raw(rhs, g, include_mass, -1.0);
+      exchange_add_raw(rhs + tables->n_interior);
+    }
+    void
+    rhs_dirichlet(mgamd_vec &rhs, const mgamd_vec &g, bool include_mass) override
+    {
+      if (rhs.n != n_dofs() || g.n != n_dofs())
+        throw std::invalid_argument("rhs_dirichlet: vector size mismatch (" + std::to_string(rhs.n) + ", " + std::to_string(g.n) + " for " +
+                                    std::to_string(n_dofs()) + " DoFs)");
+      if (rhs.data == g.data)
+        throw std::invalid_argument("rhs_dirichlet: rhs and g must differ");
+      rhs_dirichlet_raw(rhs.as<T>(), g.as<T>(), include_mass);
+    }
+    // x: the Dirichlet range from g, then the hanging DoFs from their parents (Dirichlet parents read the value just written)
+    void
+    distribute_values(mgamd_vec &x, const mgamd_vec &g) override
+    {
+      if (x.n != n_dofs() || g.n != n_dofs())
+        throw std::invalid_argument("distribute_values: vector size mismatch (" + std::to_string(x.n) + ", " + std::to_string(g.n) + " for " +
+                                    std::to_string(n_dofs()) + " DoFs)");
+      if (tables->ls_level)
+        throw std::invalid_argument("distribute_values: refused on the level of a local-smoothing hierarchy; use the active-mesh operator");
+      T       *xp = x.as<T>();
+      const T *gp = g.as<T>();
+      if (!hanging)
+        {
+          hanging = std::make_unique<HangingDev>();
+          std::vector<uint32_t> ptr, col;
+          std::vector<double>   val;
+          tables->hanging_rows(ptr, col, val);
+          hanging->n_rows = (uint32_t)ptr.size() - 1;
+          if (col.empty())
+            hanging->n_rows = 0;
+          else
+            {
+              hanging->ptr.upload(ptr);
+              hanging->col.upload(col);
+              hanging->val.upload(val);
+            }
+        }
+      const uint32_t d0 = tables->first_dirichlet(), d1 = d0 + tables->n_dirichlet;
+      if (d1 > d0 && xp != gp)
+        hipLaunchKernelGGL(dirichlet_copy_kernel<T>, grid_for(d1 - d0), 256, 0, ctx->stream, xp, gp, d0, d1);
+      if (hanging->n_rows)
+        hipLaunchKernelGGL(hanging_rows_kernel<T>, grid_for(hanging->n_rows), 256, 0, ctx->stream, xp, hanging->ptr.p, hanging->col.p,
+                           hanging->val.p, d1, hanging->n_rows);
+      HIP_CHECK(hipGetLastError());
     }
 
     size_t

@@ -90,4 +90,35 @@ namespace mgamd
     launch_tail<MODE>(main, 0, tail_end, true, epi, diag);
   }
 
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::lift_P(T *dst, const T *g, double mass_sigma, double alpha)
+  {
+    DirichletLiftArgs<T, P> a;
+    a.idx     = dirichlet->idx.p;
+    a.mask    = dirichlet->mask.p;
+    a.scale   = dirichlet->scale.p;
+    a.n_cells = dirichlet->n_cells;
+    for (int i = 0; i < (P + 1) * (P + 1); ++i)
+      {
+        a.K[i]  = tables->fe.K[i];
+        a.M[i]  = tables->fe.M[i];
+        a.I0[i] = tables->fe.I[0][i];
+        a.I1[i] = tables->fe.I[1][i];
+      }
+    a.g               = g;
+    a.dst             = dst;
+    a.dirichlet_begin = tables->first_dirichlet();
+    a.dirichlet_end   = tables->first_dirichlet() + tables->n_dirichlet;
+    a.scatter_limit   = tables->first_constrained(); // the free rows; on a sharded level the copies of shared rows too (the exchange sums them)
+    a.alpha           = (T)alpha;
+    a.sigma           = (T)mass_sigma;
+    // two groups of cells per workgroup where there are that many: the 1D matrices are staged in LDS once per workgroup
+    const uint32_t n_groups = (a.n_cells + dirichlet_cells_per_workgroup<P>() - 1) / dirichlet_cells_per_workgroup<P>();
+    const uint32_t grid     = std::min<uint32_t>(2048u, (n_groups + 1) / 2);
+    hipLaunchKernelGGL((dirichlet_lift_kernel<T, P>), grid, 256, 0, ctx->stream, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
 } // namespace mgamd

@@ -464,6 +464,204 @@ namespace mgamd
             B[(size_t)i * n2 + j] = w[i];
         }
     }
+    // Non-zero Dirichlet data (DESIGN.md "Dirichlet data"): this rank's cells, in Morton order, that gather at least one Dirichlet
+    // DoF.  The lifting  b_I -= A_ID g  only runs over them.  Built where the tables have a Dirichlet face (not on the levels of
+    // local smoothing, whose operators refuse the lifting).
+    //   idx    [n][n3]  the DoF the cell gathers at node (x fastest), hanging entities resolved to the parent's DoFs as in
+    //                   cell_node_index, but a Dirichlet DoF keeps its real index (in [first_dirichlet(), + n_dirichlet))
+    //   mask   [n]      the cell's constraint mask (Tria::masks)
+    //   scale  [n][2]   a h and h
+    struct DirichletCells
+    {
+      std::vector<uint32_t> idx;
+      std::vector<uint16_t> mask;
+      std::vector<double>   scale;
+      size_t
+      size() const
+      {
+        return mask.size();
+      }
+    } dirichlet_cells;
+    bool
+    is_dirichlet_index(uint32_t gi) const
+    {
+      return gi >= first_dirichlet() && gi < first_dirichlet() + n_dirichlet;
+    }
+    static const char *
+    face_name(int f)
+    {
+      static const char *const name[6] = {"x=-1", "x=+1", "y=-1", "y=+1", "z=-1", "z=+1"};
+      return name[f];
+    }
+    // The lifting goes through the cell matrices only.  The surface mass matrix of a convective face couples to the Dirichlet DoFs
+    // on an edge it shares with a Dirichlet face: every Dirichlet face but the opposite one.  That term is not built: refused.
+    void
+    refuse_dirichlet_lift(const char *who) const
+    {
+      if (ls_level)
+        throw std::invalid_argument(std::string(who) + ": refused on the level of a local-smoothing hierarchy (its refinement-edge DoFs "
+                                                       "are constrained like Dirichlet DoFs); use the active-mesh operator");
+      for (int f = 0; f < 6; ++f)
+        if (robin[f] > 0.0)
+          for (int f2 = 0; f2 < 6; ++f2)
+            if (((dirichlet_faces >> f2) & 1) && (f2 >> 1) != (f >> 1))
+              throw std::invalid_argument(std::string(who) + ": refused, the convective face " + std::to_string(f) + " (" + face_name(f) +
+                                          ", Robin coefficient " + std::to_string(robin[f]) + ") shares an edge with the Dirichlet face " +
+                                          std::to_string(f2) + " (" + face_name(f2) +
+                                          "): the lifting of Dirichlet data carries no face term; only the face opposite a convective "
+                                          "face may be Dirichlet");
+    }
+    // lift(g, include_mass) = -[C^T (K_a + s sigma M) C g^]  on free rows, 0 on constrained rows; g^ = g on Dirichlet DoFs, 0
+    // elsewhere (the entries of g at free and hanging DoFs are not read).  Host restatement of dirichlet_lift_kernel.
+    void
+    compute_rhs_dirichlet(const double *g, bool include_mass, std::vector<double> &b) const
+    {
+      refuse_dirichlet_lift("rhs_dirichlet");
+      b.assign(n_dofs, 0.0);
+      const int           n = p + 1, n3 = n * n * n;
+      std::vector<double> xg(n3), lift(n3);
+      for (size_t e = 0; e < dirichlet_cells.size(); ++e)
+        {
+          const uint32_t *idx = &dirichlet_cells.idx[e * n3];
+          for (int t = 0; t < n3; ++t)
+            xg[t] = is_dirichlet_index(idx[t]) ? g[idx[t]] : 0.0;
+          const uint16_t mask = dirichlet_cells.mask[e];
+          const double   ah = dirichlet_cells.scale[2 * e], h = dirichlet_cells.scale[2 * e + 1];
+          interpolate_hanging(fe, mask, xg.data(), false);
+          cell_stiffness_apply(ah, xg.data(), lift.data());
+          if (include_mass && sigma != 0.0)
+            cell_mass_add(h, sigma, xg.data(), lift.data());
+          interpolate_hanging(fe, mask, lift.data(), true);
+          for (int t = 0; t < n3; ++t)
+            if (idx[t] < first_constrained())
+              b[idx[t]] -= lift[t];
+        }
+    }
+    // g = v[f] on the Dirichlet DoFs of face f (the lowest-numbered Dirichlet face of a DoF on several), 0 elsewhere
+    void
+    dirichlet_face_values(const double v[6], std::vector<double> &g) const
+    {
+      for (int f = 0; f < 6; ++f)
+        {
+          if (!std::isfinite(v[f]))
+            throw std::invalid_argument("Dirichlet value on face " + std::to_string(f) + " (" + face_name(f) + ") is not finite");
+          if (v[f] != 0.0 && !((dirichlet_faces >> f) & 1))
+            throw std::invalid_argument("Dirichlet value " + std::to_string(v[f]) + " on face " + std::to_string(f) + " (" + face_name(f) +
+                                        ") refused: the face is natural (dirichlet_faces mask " + std::to_string(dirichlet_faces) +
+                                        "), a Dirichlet value needs a Dirichlet face");
+        }
+      g.assign(n_dofs, 0.0);
+      const int32_t top = p << LMAX;
+      keymap_for_each([&](uint64_t key, int32_t idx) {
+        if (!is_dirichlet_index((uint32_t)idx))
+          return;
+        const DofKey  k    = unpack_key(key);
+        const int32_t x[3] = {k.px, k.py, k.pz};
+        for (int f = 0; f < 6; ++f)
+          if (((dirichlet_faces >> f) & 1) && x[f >> 1] == ((f & 1) ? top : 0))
+            {
+              g[idx] = v[f];
+              return;
+            }
+      });
+    }
+    // support point of every DoF, [n_dofs][3]
+    void
+    export_node_positions(std::vector<double> &xyz) const
+    {
+      std::vector<DofKey> keys;
+      export_dof_keys(keys);
+      xyz.assign((size_t)n_dofs * 3, 0.0);
+      for (uint32_t i = 0; i < n_dofs; ++i)
+        {
+          const int32_t x[3] = {keys[i].px, keys[i].py, keys[i].pz};
+          for (int d = 0; d < 3; ++d)
+            {
+              // a coordinate strictly inside a cell (direction mask bit set) is a node of the key's level; the others are vertices
+              const int     lev = ((keys[i].dirmask >> d) & 1) ? keys[i].level : LMAX;
+              const int32_t q   = x[d] >> (LMAX - lev); // cell index * p + local node
+              xyz[(size_t)i * 3 + d] = -1.0 + 2.0 / (double)(1u << lev) * ((double)(q / p) + fe.nodes[q % p]);
+            }
+        }
+    }
+    // distribute for caller data: Dirichlet DoFs take the values of g, then the hanging DoFs are interpolated from their parents;
+    // free DoFs are untouched
+    void
+    distribute_values(const double *g, std::vector<double> &x) const
+    {
+      for (uint32_t i = first_dirichlet(); i < first_dirichlet() + n_dirichlet; ++i)
+        x[i] = g[i];
+      distribute_hanging(x);
+    }
+    // The hanging DoFs as rows of parents and weights (CSR over the hanging range, row r = DoF first_dirichlet() + n_dirichlet + r),
+    // from the same per-cell interpolation as distribute_hanging: row of node t = C^T e_t.  A DoF no local cell reaches has no entries.
+    void
+    hanging_rows(std::vector<uint32_t> &ptr, std::vector<uint32_t> &col, std::vector<double> &val) const
+    {
+      const int      n = p + 1, n3 = n * n * n;
+      const uint32_t first_hanging = first_dirichlet() + n_dirichlet, nh = n_dofs - first_hanging;
+      std::vector<std::vector<std::pair<uint32_t, double>>> rows(nh);
+      std::vector<uint8_t>                                  done(nh, 0);
+      std::vector<double>                                   w(n3);
+      std::vector<uint32_t>                                 idx(n3);
+      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
+        {
+          const uint16_t mask = tria->masks[ci];
+          if (!cell_is_local(ci) || !(mask >> MASK_FACE_SHIFT))
+            continue;
+          bool gathered = false;
+          for (int t = 0; t < n3; ++t)
+            {
+              const int a[3] = {t % n, (t / n) % n, t / (n * n)};
+              bool      corner;
+              if (!node_on_constrained_entity(mask, p, a, &corner) || corner)
+                continue;
+              const int32_t *own = keymap.find(own_key(tria->cells[ci], a));
+              if (!own || (uint32_t)*own < first_hanging || done[*own - first_hanging])
+                continue;
+              if (!gathered)
+                {
+                  for (int s = 0; s < n3; ++s)
+                    {
+                      const int b[3] = {s % n, (s / n) % n, s / (n * n)};
+                      idx[s]         = gathered_index(ci, b);
+                    }
+                  gathered = true;
+                }
+              std::fill(w.begin(), w.end(), 0.0);
+              w[t] = 1.0;
+              interpolate_hanging(fe, mask, w.data(), true);
+              auto &row = rows[*own - first_hanging];
+              for (int s = 0; s < n3; ++s)
+                if (w[s] != 0.0 && idx[s] != INVALID_DOF)
+                  row.push_back({idx[s], w[s]});
+              done[*own - first_hanging] = 1;
+            }
+        }
+      ptr.assign(nh + 1, 0);
+      col.clear();
+      val.clear();
+      for (uint32_t r = 0; r < nh; ++r)
+        {
+          for (const auto &e : rows[r])
+            {
+              col.push_back(e.first);
+              val.push_back(e.second);
+            }
+          ptr[r + 1] = (uint32_t)col.size();
+        }
+    }
+    // cell_node_index with the real index on Dirichlet DoFs (INVALID_DOF only where the DoF is not numbered on this rank)
+    uint32_t
+    gathered_index(size_t ci, const int a[3]) const
+    {
+      uint32_t id = cell_node_index(ci, a);
+      if (id == INVALID_DOF)
+        if (const int32_t *gi = keymap.find(resolved_key(ci, a)))
+          id = (uint32_t)*gi;
+      return id;
+    }
+
     // no Dirichlet face, sigma == 0 and no convective face: the constants are in the operator's kernel.  Operators stay available;
     // solvers refuse.
     bool
@@ -1002,6 +1200,14 @@ namespace mgamd
                       x[*gi] = data_g(kind, pos);
                     }
                 }
+      distribute_hanging(x);
+    }
+    // hanging-node DoFs = the interpolant of their parent face/edge, Dirichlet parents included (their values are in x)
+    void
+    distribute_hanging(std::vector<double> &x) const
+    {
+      const int           n = p + 1, n3 = n * n * n;
+      std::vector<double> v(n3);
       for (size_t ci = 0; ci < tria->cells.size(); ++ci)
         {
           const uint16_t mask = tria->masks[ci];
@@ -1406,6 +1612,50 @@ namespace mgamd
             }
         }
       build_robin_faces();
+      build_dirichlet_cells();
+    }
+
+    // dirichlet_cells from the final numbering; nothing without a Dirichlet face
+    void
+    build_dirichlet_cells()
+    {
+      if (dirichlet_faces == 0 || ls_level || n_dirichlet == 0)
+        return;
+      const int             n = p + 1, n3 = n * n * n;
+      std::vector<uint32_t> idx(n3);
+      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
+        {
+          if (!cell_is_local(ci))
+            continue;
+          const Cell    &c      = tria->cells[ci];
+          const uint16_t mask   = tria->masks[ci];
+          const uint32_t ijk[3] = {c.i, c.j, c.k};
+          // a cell gathers DoFs of its own nodes and, on hanging entities, of its parent's: only cells that touch a Dirichlet face
+          // themselves or through their parent can hold one
+          bool near = false;
+          for (int lev = c.level; lev >= (int)c.level - ((mask >> MASK_FACE_SHIFT) ? 1 : 0) && lev >= 0; --lev)
+            for (int d = 0; d < 3; ++d)
+              {
+                const uint32_t q = ijk[d] >> (c.level - lev), last = (1u << lev) - 1;
+                near |= (q == 0 && ((dirichlet_faces >> (2 * d)) & 1)) || (q == last && ((dirichlet_faces >> (2 * d + 1)) & 1));
+              }
+          if (!near)
+            continue;
+          bool any = false;
+          for (int t = 0; t < n3; ++t)
+            {
+              const int a[3] = {t % n, (t / n) % n, t / (n * n)};
+              idx[t]         = gathered_index(ci, a);
+              any |= is_dirichlet_index(idx[t]);
+            }
+          if (!any)
+            continue;
+          const double h = 2.0 / (double)(1u << c.level);
+          dirichlet_cells.idx.insert(dirichlet_cells.idx.end(), idx.begin(), idx.end());
+          dirichlet_cells.mask.push_back(mask);
+          dirichlet_cells.scale.push_back(coefficient_of(ci) * h);
+          dirichlet_cells.scale.push_back(h);
+        }
     }
 
     // robin_faces from the final numbering; nothing where every beta is 0

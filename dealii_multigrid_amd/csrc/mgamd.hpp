@@ -365,6 +365,23 @@ namespace mgamd
       check(mgamd_dofs_robin_coefficients(h.get(), beta.data()));
       return beta;
     }
+    // Dirichlet data of one constant per face: v[f] on the Dirichlet DoFs of face f (the lowest-numbered Dirichlet face of a DoF on
+    // several), 0 elsewhere; a host vector of n_dofs values for Vector::copy_from_host.  Refuses a non-zero value on a natural face.
+    std::vector<double>
+    dirichlet_face_values(const std::array<double, 6> &v) const
+    {
+      std::vector<double> g(info.n_dofs);
+      check(mgamd_dofs_dirichlet_face_values(h.get(), v.data(), g.data()));
+      return g;
+    }
+    // support points of the DoFs, xyz[3 i ..]: the nodal interpolant of a function is one loop over them
+    std::vector<double>
+    node_positions() const
+    {
+      std::vector<double> xyz(3 * (size_t)info.n_dofs);
+      check(mgamd_dofs_node_positions(h.get(), xyz.data()));
+      return xyz;
+    }
     mgamd_dofs_info_t info;
 
   private:
@@ -730,6 +747,20 @@ namespace mgamd
     distribute(Vector &solution, int simulation_kind = 0) const
     {
       check(mgamd_level_op_distribute(h.get(), simulation_kind, solution.get()));
+    }
+    // Non-zero Dirichlet data g (a vector of n_dofs values, only its entries at Dirichlet DoFs are read): load = the lifting
+    // -[C^T (K_a + sigma M) C g^] on the free rows, by the device kernel over the cells that gather a Dirichlet DoF
+    // (mgamd_level_op_rhs_dirichlet); overwrites load, which is additive to rhs(), rhs_boundary_flux() and M f
+    void
+    rhs_dirichlet(Vector &load, const Vector &g, bool include_mass = true) const
+    {
+      check(mgamd_level_op_rhs_dirichlet(h.get(), g.get(), include_mass ? 1 : 0, load.get()));
+    }
+    // solution: Dirichlet DoFs from g, then hanging DoFs from their parents, on the device (mgamd_level_op_distribute_values)
+    void
+    distribute_values(Vector &solution, const Vector &g) const
+    {
+      check(mgamd_level_op_distribute_values(h.get(), solution.get(), g.get()));
     }
     mgamd_level_op *
     get() const
@@ -1211,6 +1242,26 @@ namespace mgamd
     {
       unsigned it = 0;
       check(mgamd_time_stepper_step(h.get(), u.get(), f_old.get(), f_new.get(), reltol, abstol, maxiter, &it, &residual));
+      return it;
+    }
+    // one step with Dirichlet values g_old at t and g_new at t + dt, no source; load (may be null): a boundary load
+    // theta l_new + (1 - theta) l_old (mgamd_time_stepper_step_data).  Operator::distribute_values(u, g_new) fills u for output.
+    unsigned
+    step(Vector &u, const Vector &g_old, const Vector &g_new, const Vector *load, double reltol, double abstol = 1e-20, unsigned maxiter = 10000)
+    {
+      unsigned it = 0;
+      check(mgamd_time_stepper_step_data(h.get(), u.get(), nullptr, nullptr, g_old.get(), g_new.get(), load ? load->get() : nullptr, reltol,
+                                         abstol, maxiter, &it, &residual));
+      return it;
+    }
+    // the same with the nodal source values at t and t + dt
+    unsigned
+    step(Vector &u, const Vector &f_old, const Vector &f_new, const Vector &g_old, const Vector &g_new, const Vector *load, double reltol,
+         double abstol = 1e-20, unsigned maxiter = 10000)
+    {
+      unsigned it = 0;
+      check(mgamd_time_stepper_step_data(h.get(), u.get(), f_old.get(), f_new.get(), g_old.get(), g_new.get(), load ? load->get() : nullptr,
+                                         reltol, abstol, maxiter, &it, &residual));
       return it;
     }
     double

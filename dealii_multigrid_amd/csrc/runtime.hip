@@ -2348,14 +2348,36 @@ namespace mgamd
     step(mgamd_vec &u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol, double abstol, unsigned maxiter, unsigned &n_iterations,
          double &residual) override
     {
+      step_data(u, f_old, f_new, nullptr, nullptr, nullptr, reltol, abstol, maxiter, n_iterations, residual);
+    }
+
+    // r += the lifting of gd (dirichlet_lift_kernel, alpha = -1).  One rank: straight into r.  Sharded: through the work vector Ad
+    // (free after the residual pass) and the exchange, as r is already complete over the ranks.
+    void
+    add_lift(const double *gd, bool include_mass)
+    {
+      if (!op->halo)
+        return op->dirichlet_lift_add_raw(g->as<double>(), gd, include_mass, -1.0);
+      op->rhs_dirichlet_raw(Ad->as<double>(), gd, include_mass);
+      vec_sadd(*g, 1.0, 1.0, *Ad);
+    }
+
+    void
+    step_data(mgamd_vec &u, const mgamd_vec *f_old, const mgamd_vec *f_new, const mgamd_vec *g_old, const mgamd_vec *g_new, const mgamd_vec *load,
+              double reltol, double abstol, unsigned maxiter, unsigned &n_iterations, double &residual) override
+    {
       Ctx         *ctx = op->ctx;
       const size_t n   = op->n_dofs();
       if ((f_old == nullptr) != (f_new == nullptr))
         throw std::invalid_argument("time stepper: exactly one of f_old / f_new is given (both, or neither for f = 0)");
-      for (const mgamd_vec *v : {(const mgamd_vec *)&u, f_old, f_new})
+      if ((g_old == nullptr) != (g_new == nullptr))
+        throw std::invalid_argument("time stepper: exactly one of g_old / g_new is given (both, or neither for homogeneous Dirichlet data)");
+      for (const mgamd_vec *v : {(const mgamd_vec *)&u, f_old, f_new, g_old, g_new, load})
         if (v && (v->n != n || v->type != MGAMD_F64))
           throw std::invalid_argument("time stepper: a vector of " + std::to_string(v->n) + " entries of " + std::to_string(v->type) +
                                       " bytes where the operator has " + std::to_string(n) + " FP64 DoFs");
+      if (g_old)
+        op->tables->refuse_dirichlet_lift("time stepper");
       const size_t n_free = (size_t)op->tables->n_interior + op->tables->n_tail; // the constrained DoFs are numbered last
       const int    grid   = grid_for(n);
       double      *up     = u.as<double>();
@@ -2363,7 +2385,18 @@ namespace mgamd
                          f_new ? f_new->as<double>() : nullptr, theta, op->sigma, n);
       op->vmult_mass_raw(d->as<double>(), Ad->as<double>());
       op->residual_raw(g->as<double>(), d->as<double>(), up);
+      // the data terms (DESIGN.md "Dirichlet data"): r = M w + l - A u - K_ID g_old, then r / theta - A_ID (g_new - g_old)
+      if (load)
+        vec_sadd(*g, 1.0, 1.0, *load);
+      if (g_old)
+        add_lift(g_old->as<double>(), false);
       hipLaunchKernelGGL(theta_rhs_kernel<double>, grid, 256, 0, ctx->stream, g->as<double>(), theta, n_free, n);
+      if (g_old)
+        {
+          vec_copy(*d, *g_new);
+          vec_sadd(*d, 1.0, -1.0, *g_old);
+          add_lift(d->as<double>(), true);
+        }
       device_pcg<double>(
         ctx, op->comm.get(), ctx->d_cg, n, op->n_dot(), delta->as<double>(), g->as<double>(), h->as<double>(), d->as<double>(), Ad->as<double>(),
         [&](double *Ap, const double *p) { op->vmult_raw(Ap, p); },

@@ -231,6 +231,13 @@ namespace mgamd
     rhs_boundary_flux(mgamd_vec &b, const double q[6]);
     void
     distribute(mgamd_vec &x, int kind);
+    // Non-zero Dirichlet data (level_tables.hpp, DirichletCells): rhs = -[C^T (K_a + [include_mass] sigma M) C g^] on free rows, 0
+    // on constrained rows, g^ = g on Dirichlet DoFs and 0 elsewhere; stream-ordered, completed over the ranks
+    virtual void
+    rhs_dirichlet(mgamd_vec &rhs, const mgamd_vec &g, bool include_mass) = 0;
+    // x: Dirichlet DoFs from g, then hanging DoFs from their parents; free DoFs untouched; stream-ordered
+    virtual void
+    distribute_values(mgamd_vec &x, const mgamd_vec &g) = 0;
 
   private:
     void
@@ -376,6 +383,14 @@ namespace mgamd
     virtual void
     step(mgamd_vec &u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol, double abstol, unsigned maxiter, unsigned &n_iterations,
          double &residual) = 0;
+    // The same step with non-zero Dirichlet data and a boundary load.  g_old, g_new: Dirichlet values at t and t + dt (only their
+    // entries at Dirichlet DoFs are read), both null for homogeneous data; load: l = theta l_new + (1 - theta) l_old (a flux,
+    // beta u_ext), may be null.  On the free rows
+    //     A delta = (M w + l - A u - K_ID g_old) / theta - A_ID (g_new - g_old),   u += delta
+    // with two launches of the lifting kernel.  All three null: the launches of step, in its order.
+    virtual void
+    step_data(mgamd_vec &u, const mgamd_vec *f_old, const mgamd_vec *f_new, const mgamd_vec *g_old, const mgamd_vec *g_new, const mgamd_vec *load,
+              double reltol, double abstol, unsigned maxiter, unsigned &n_iterations, double &residual) = 0;
   };
   ThetaStepperBase *
   make_theta_stepper(LevelOperatorBase &A, MultigridBase *M, double theta, double dt);

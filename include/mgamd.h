@@ -181,6 +181,26 @@ int mgamd_dofs_robin_coefficients(const mgamd_dofs *d, double beta[6]);
  * entries of (degree+1)^2 DoF indices (hanging entities resolved to the parent's DoFs, 0xFFFFFFFF on Dirichlet DoFs), one byte of
  * hanging flags (level_tables.hpp, RobinFaces) and the scale beta_f h^2.  Null arrays are skipped: call once for the count. */
 int mgamd_dofs_robin_faces(const mgamd_dofs *d, uint64_t *n_faces, uint32_t *idx, uint8_t *flags, double *scale);
+/* Non-zero Dirichlet data, this project's extension.  The data is a vector g of n_dofs values in the level's numbering of which only
+ * the entries at Dirichlet DoFs are ever read (so the nodal interpolant of any function may be passed); a hanging node on the
+ * boundary gets its value from its parents.  With g^ = g on Dirichlet DoFs and 0 elsewhere and C the hanging-node interpolation,
+ *     out_i = -[C^T (K_a + s sigma M) C g^]_i  on free rows, 0 on constrained rows,  s = 1 if include_mass else 0:
+ * the lifting of the data, a load vector additive to mgamd_dofs_rhs, mgamd_dofs_rhs_boundary_flux and M f.  It runs over the cells
+ * of mgamd_dofs_dirichlet_cells only.  MGAMD_ERR_INVALID, naming both faces, where a face with a Robin coefficient > 0 shares an
+ * edge with a Dirichlet face (every Dirichlet face but the opposite one: the face term of the lifting is not built), and for the
+ * tables of a local-smoothing level. */
+int mgamd_dofs_rhs_dirichlet(const mgamd_dofs *d, const double *g, int include_mass, double *out);
+/* x: Dirichlet DoFs take the values of g, then hanging DoFs are interpolated from their parents; free DoFs are untouched */
+int mgamd_dofs_distribute_values(const mgamd_dofs *d, const double *g, double *x);
+/* g = v[f] on the Dirichlet DoFs of face f (a DoF on several Dirichlet faces takes the lowest-numbered one), 0 elsewhere.
+ * MGAMD_ERR_INVALID, naming the face, for a non-finite value and for a non-zero value on a natural face. */
+int mgamd_dofs_dirichlet_face_values(const mgamd_dofs *d, const double v[6], double *g);
+/* the table the lifting walks: this rank's cells, in Morton order, that gather at least one Dirichlet DoF.  *n_cells entries of
+ * (degree+1)^3 DoF indices (x fastest, hanging entities resolved to the parent's DoFs, Dirichlet DoFs with their real index), the
+ * cell's hanging mask and scale[2] = {a h, h}.  Null arrays are skipped: call once for the count. */
+int mgamd_dofs_dirichlet_cells(const mgamd_dofs *d, uint64_t *n_cells, uint32_t *idx, uint16_t *mask, double *scale);
+/* support point of every DoF: xyz[3 i ..] */
+int mgamd_dofs_node_positions(const mgamd_dofs *d, double *xyz);
 /* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
  * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
  * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
@@ -382,6 +402,18 @@ int mgamd_level_op_rhs_kind(mgamd_level_op *op, int kind, mgamd_vec *rhs);
  * cells and the shared entries are completed over the ranks, as for mgamd_level_op_rhs_kind */
 int mgamd_level_op_rhs_boundary_flux(mgamd_level_op *op, const double q[6], mgamd_vec *rhs);
 int mgamd_level_op_distribute(mgamd_level_op *op, int kind, mgamd_vec *x);
+/* mgamd_dofs_rhs_dirichlet on the device: rhs is OVERWRITTEN with the lifting of the Dirichlet data g (a device vector of n_dofs
+ * values of which only the entries at Dirichlet DoFs are read), with the operator's own mass coefficient where include_mass is set.
+ * One kernel over the cells of mgamd_dofs_dirichlet_cells, stream-ordered, no host copy of a vector; on a distributed operator each
+ * rank lifts over its own cells and the shared entries are completed over the ranks.  Constrained rows are 0; without a Dirichlet
+ * face nothing is launched and rhs is 0.  MGAMD_ERR_INVALID for vectors of the wrong size or number type, rhs == g, the operator of
+ * a local-smoothing level (the active-mesh operator of such a hierarchy is an ordinary one and works) and a convective face that
+ * shares an edge with a Dirichlet face (see mgamd_dofs_rhs_dirichlet). */
+int mgamd_level_op_rhs_dirichlet(mgamd_level_op *op, const mgamd_vec *g, int include_mass, mgamd_vec *rhs);
+/* mgamd_dofs_distribute_values on the device, stream-ordered: the Dirichlet range of x is copied from g, then every hanging DoF is
+ * interpolated from its parents (one thread per hanging DoF; a Dirichlet parent contributes the value just written).  Free entries
+ * of x are untouched.  mgamd_level_op_distribute is unchanged. */
+int mgamd_level_op_distribute_values(mgamd_level_op *op, mgamd_vec *x, const mgamd_vec *g);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is
  * computed internally (DiagonalMatrix preconditioner); eigenvalues are estimated at creation with
@@ -519,6 +551,18 @@ int mgamd_time_stepper_create(mgamd_level_op *A, mgamd_mg *preconditioner, doubl
  * CG for the increment (may be NULL) */
 int mgamd_time_stepper_step(mgamd_time_stepper *ts, mgamd_vec *u, const mgamd_vec *f_old, const mgamd_vec *f_new, double reltol,
                             double abstol, unsigned maxiter, unsigned *n_iterations, double *residual_norm);
+/* The same step with non-zero, time-dependent Dirichlet data and a boundary load.  g_old / g_new: Dirichlet values at t and t + dt
+ * (vectors of n_dofs values, only the entries at Dirichlet DoFs are read), both NULL for homogeneous data; load: a boundary load
+ * l = theta l_new + (1 - theta) l_old (mgamd_level_op_rhs_boundary_flux: a flux, beta u_ext), may be NULL.  On the free rows
+ *     A delta = (M w + l - A u - K_ID g_old) / theta - A_ID (g_new - g_old);   u += delta
+ * (two launches of the lifting kernel of mgamd_level_op_rhs_dirichlet: stiffness only for g_old, K + sigma M for the increment).
+ * Constrained entries of u are still never read and are 0 on return: for output run mgamd_level_op_distribute_values(u, g_new).
+ * The mass product ignores the values of f on Dirichlet DoFs, so a source that is non-zero on a Dirichlet face loses M_ID f_D.
+ * With g_old, g_new and load all NULL this is mgamd_time_stepper_step, launch for launch.  MGAMD_ERR_INVALID in addition: exactly
+ * one of g_old / g_new; a convective face that shares an edge with a Dirichlet face (mgamd_dofs_rhs_dirichlet). */
+int mgamd_time_stepper_step_data(mgamd_time_stepper *ts, mgamd_vec *u, const mgamd_vec *f_old, const mgamd_vec *f_new,
+                                 const mgamd_vec *g_old, const mgamd_vec *g_new, const mgamd_vec *load, double reltol, double abstol,
+                                 unsigned maxiter, unsigned *n_iterations, double *residual_norm);
 /* the time reached (n_steps dt, starting at 0) and the number of steps taken; either may be NULL */
 int  mgamd_time_stepper_time(const mgamd_time_stepper *ts, double *t, uint64_t *n_steps);
 void mgamd_time_stepper_destroy(mgamd_time_stepper *ts);
