@@ -126,13 +126,7 @@ namespace mgamd
     std::vector<uint32_t> idx((size_t)nc * n3, INVALID_DOF);
     for (size_t ci = 0; ci < nc; ++ci)
       if (L.cell_is_local(ci))
-        for (int c = 0; c < n; ++c)
-          for (int b = 0; b < n; ++b)
-            for (int a = 0; a < n; ++a)
-              {
-                const int l[3]                              = {a, b, c};
-                idx[ci * n3 + (size_t)(c * n + b) * n + a] = L.cell_node_index(ci, l);
-              }
+        L.gather_cell(ci, &idx[ci * n3], false);
     CSR A;
     A.n_rows = A.n_cols = L.n_dofs;
     // pattern: per row the columns of all touching cells, then sort + unique

@@ -1129,6 +1129,11 @@ namespace mgamd
                                     std::to_string(n_dofs()) + " DoFs)");
       if (tables->ls_level)
         throw std::invalid_argument("distribute_values: refused on the level of a local-smoothing hierarchy; use the active-mesh operator");
+      distribute_values_core(x, g);
+    }
+    void
+    distribute_values_core(mgamd_vec &x, const mgamd_vec &g) override
+    {
       T       *xp = x.as<T>();
       const T *gp = g.as<T>();
       if (!hanging)

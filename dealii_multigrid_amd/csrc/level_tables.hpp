@@ -465,8 +465,9 @@ namespace mgamd
         }
     }
     // Non-zero Dirichlet data (DESIGN.md "Dirichlet data"): this rank's cells, in Morton order, that gather at least one Dirichlet
-    // DoF.  The lifting  b_I -= A_ID g  only runs over them.  Built where the tables have a Dirichlet face (not on the levels of
-    // local smoothing, whose operators refuse the lifting).
+    // DoF.  The lifting  b_I -= A_ID g  only runs over them.  Built where the tables have a Dirichlet face; on the levels of local
+    // smoothing too, for the Gaussian right-hand side (their refinement-edge DoFs keep their index, as in cell_node_index, and
+    // their rows are constrained), though the entry points for caller data refuse those levels.
     //   idx    [n][n3]  the DoF the cell gathers at node (x fastest), hanging entities resolved to the parent's DoFs as in
     //                   cell_node_index, but a Dirichlet DoF keeps its real index (in [first_dirichlet(), + n_dirichlet))
     //   mask   [n]      the cell's constraint mask (Tria::masks)
@@ -512,30 +513,13 @@ namespace mgamd
                                           "face may be Dirichlet");
     }
     // lift(g, include_mass) = -[C^T (K_a + s sigma M) C g^]  on free rows, 0 on constrained rows; g^ = g on Dirichlet DoFs, 0
-    // elsewhere (the entries of g at free and hanging DoFs are not read).  Host restatement of dirichlet_lift_kernel.
+    // elsewhere (the entries of g at free and hanging DoFs are not read)
     void
     compute_rhs_dirichlet(const double *g, bool include_mass, std::vector<double> &b) const
     {
       refuse_dirichlet_lift("rhs_dirichlet");
       b.assign(n_dofs, 0.0);
-      const int           n = p + 1, n3 = n * n * n;
-      std::vector<double> xg(n3), lift(n3);
-      for (size_t e = 0; e < dirichlet_cells.size(); ++e)
-        {
-          const uint32_t *idx = &dirichlet_cells.idx[e * n3];
-          for (int t = 0; t < n3; ++t)
-            xg[t] = is_dirichlet_index(idx[t]) ? g[idx[t]] : 0.0;
-          const uint16_t mask = dirichlet_cells.mask[e];
-          const double   ah = dirichlet_cells.scale[2 * e], h = dirichlet_cells.scale[2 * e + 1];
-          interpolate_hanging(fe, mask, xg.data(), false);
-          cell_stiffness_apply(ah, xg.data(), lift.data());
-          if (include_mass && sigma != 0.0)
-            cell_mass_add(h, sigma, xg.data(), lift.data());
-          interpolate_hanging(fe, mask, lift.data(), true);
-          for (int t = 0; t < n3; ++t)
-            if (idx[t] < first_constrained())
-              b[idx[t]] -= lift[t];
-        }
+      dirichlet_lift_add(g, include_mass, -1.0, b);
     }
     // g = v[f] on the Dirichlet DoFs of face f (the lowest-numbered Dirichlet face of a DoF on several), 0 elsewhere
     void
@@ -565,6 +549,34 @@ namespace mgamd
             }
       });
     }
+    // g = data_g(kind, support point) on the Dirichlet DoFs, 0 elsewhere: the built-in data of SimulationType `kind` as caller data
+    void
+    dirichlet_kind_values(int kind, std::vector<double> &g) const
+    {
+      g.assign(n_dofs, 0.0);
+      if (kind == 0)
+        return;
+      keymap_for_each([&](uint64_t key, int32_t idx) {
+        if (!is_dirichlet_index((uint32_t)idx))
+          return;
+        double x[3];
+        key_position(unpack_key(key), x);
+        g[idx] = data_g(kind, x);
+      });
+    }
+    // support point of the DoF behind a key
+    void
+    key_position(const DofKey &k, double xyz[3]) const
+    {
+      const int32_t x[3] = {k.px, k.py, k.pz};
+      for (int d = 0; d < 3; ++d)
+        {
+          // a coordinate strictly inside a cell (direction mask bit set) is a node of the key's level; the others are vertices
+          const int     lev = ((k.dirmask >> d) & 1) ? k.level : LMAX;
+          const int32_t q   = x[d] >> (LMAX - lev); // cell index * p + local node
+          xyz[d]            = -1.0 + 2.0 / (double)(1u << lev) * ((double)(q / p) + fe.nodes[q % p]);
+        }
+    }
     // support point of every DoF, [n_dofs][3]
     void
     export_node_positions(std::vector<double> &xyz) const
@@ -573,16 +585,7 @@ namespace mgamd
       export_dof_keys(keys);
       xyz.assign((size_t)n_dofs * 3, 0.0);
       for (uint32_t i = 0; i < n_dofs; ++i)
-        {
-          const int32_t x[3] = {keys[i].px, keys[i].py, keys[i].pz};
-          for (int d = 0; d < 3; ++d)
-            {
-              // a coordinate strictly inside a cell (direction mask bit set) is a node of the key's level; the others are vertices
-              const int     lev = ((keys[i].dirmask >> d) & 1) ? keys[i].level : LMAX;
-              const int32_t q   = x[d] >> (LMAX - lev); // cell index * p + local node
-              xyz[(size_t)i * 3 + d] = -1.0 + 2.0 / (double)(1u << lev) * ((double)(q / p) + fe.nodes[q % p]);
-            }
-        }
+        key_position(keys[i], &xyz[(size_t)i * 3]);
     }
     // distribute for caller data: Dirichlet DoFs take the values of g, then the hanging DoFs are interpolated from their parents;
     // free DoFs are untouched
@@ -620,14 +623,8 @@ namespace mgamd
               if (!own || (uint32_t)*own < first_hanging || done[*own - first_hanging])
                 continue;
               if (!gathered)
-                {
-                  for (int s = 0; s < n3; ++s)
-                    {
-                      const int b[3] = {s % n, (s / n) % n, s / (n * n)};
-                      idx[s]         = gathered_index(ci, b);
-                    }
-                  gathered = true;
-                }
+                gather_cell(ci, idx.data(), true);
+              gathered = true;
               std::fill(w.begin(), w.end(), 0.0);
               w[t] = 1.0;
               interpolate_hanging(fe, mask, w.data(), true);
@@ -660,6 +657,17 @@ namespace mgamd
         if (const int32_t *gi = keymap.find(resolved_key(ci, a)))
           id = (uint32_t)*gi;
       return id;
+    }
+    // the (p+1)^3 indices cell ci gathers, x fastest: cell_node_index, or gathered_index where real_dirichlet_index is set
+    void
+    gather_cell(size_t ci, uint32_t *idx, bool real_dirichlet_index) const
+    {
+      const int n = p + 1;
+      for (int t = 0; t < n * n * n; ++t)
+        {
+          const int a[3] = {t % n, (t / n) % n, t / (n * n)};
+          idx[t]         = real_dirichlet_index ? gathered_index(ci, a) : cell_node_index(ci, a);
+        }
     }
 
     // no Dirichlet face, sigma == 0 and no convective face: the constants are in the operator's kernel.  Operators stay available;
@@ -848,17 +856,10 @@ namespace mgamd
     void
     export_cell_dofs(std::vector<uint32_t> &out) const
     {
-      const int n = p + 1;
-      out.resize(tria->cells.size() * n * n * n);
-      size_t t = 0;
+      const size_t n3 = (size_t)(p + 1) * (p + 1) * (p + 1);
+      out.resize(tria->cells.size() * n3);
       for (size_t ci = 0; ci < tria->cells.size(); ++ci)
-        for (int c = 0; c < n; ++c)
-          for (int b = 0; b < n; ++b)
-            for (int a = 0; a < n; ++a)
-              {
-                const int l[3] = {a, b, c};
-                out[t++]       = cell_node_index(ci, l);
-              }
+        gather_cell(ci, &out[ci * n3], false);
     }
 
     // geometric identity of every DoF (for matching against an independently numbered oracle)
@@ -961,44 +962,35 @@ namespace mgamd
     {
       return kind == 0 ? 0.0 : gaussian_solution(x);
     }
-    // position of the DoF that cell ci gathers at local node a (the parent's node on hanging entities)
+    // out = A (or A^T) along direction d of one cell's (p+1)^3 values (x fastest); A is (p+1)^2, row-major
     void
-    gathered_node_position(size_t ci, const int a[3], double x[3]) const
+    sweep_1d(const double *A, bool transposed, int d, const double *in, double *out) const
     {
-      const Cell    &c    = tria->cells[ci];
-      const uint16_t mask = tria->masks[ci];
-      const bool     par  = (mask >> MASK_FACE_SHIFT) && node_on_constrained_entity(mask, p, a);
-      const uint32_t ijk[3] = {c.i, c.j, c.k};
-      const int      lev  = par ? c.level - 1 : c.level;
-      const double   h    = 2.0 / (double)(1u << lev);
-      for (int d = 0; d < 3; ++d)
-        x[d] = -1.0 + h * ((double)(par ? ijk[d] >> 1 : ijk[d]) + fe.nodes[a[d]]);
+      const int n = p + 1, n3 = n * n * n, st = d == 0 ? 1 : (d == 1 ? n : n * n);
+      const int row = transposed ? 1 : n, col = transposed ? n : 1;
+      for (int line = 0; line < n3; line += st * n) // the lines along d start at line + i, i < st
+        for (int a = 0; a < n; ++a)
+          for (int i = 0; i < st; ++i)
+            {
+              double s = 0;
+              for (int b = 0; b < n; ++b)
+                s += A[a * row + b * col] * in[line + i + b * st];
+              out[line + i + a * st] = s;
+            }
     }
-
     // y = K_cell x on one cell's (p+1)^3 values (x fastest), h = cell size
     void
     cell_stiffness_apply(double h, const double *x, double *y) const
     {
       const int           n = p + 1, n3 = n * n * n;
       std::vector<double> t1(n3), t2(n3), t3(n3);
-      auto                sweep = [&](const std::vector<double> &A, int d, const double *in, double *out) {
-        const int st = d == 0 ? 1 : (d == 1 ? n : n * n);
-        for (int i = 0; i < n3; ++i)
-          {
-            const int id = (i / st) % n;
-            double    s  = 0;
-            for (int b = 0; b < n; ++b)
-              s += A[id * n + b] * in[i + (b - id) * st];
-            out[i] = s;
-          }
-      };
       for (int i = 0; i < n3; ++i)
         y[i] = 0;
       for (int dk = 0; dk < 3; ++dk)
         { // K in direction dk, M in the others
-          sweep(dk == 0 ? fe.K : fe.M, 0, x, t1.data());
-          sweep(dk == 1 ? fe.K : fe.M, 1, t1.data(), t2.data());
-          sweep(dk == 2 ? fe.K : fe.M, 2, t2.data(), t3.data());
+          sweep_1d((dk == 0 ? fe.K : fe.M).data(), false, 0, x, t1.data());
+          sweep_1d((dk == 1 ? fe.K : fe.M).data(), false, 1, t1.data(), t2.data());
+          sweep_1d((dk == 2 ? fe.K : fe.M).data(), false, 2, t2.data(), t3.data());
           for (int i = 0; i < n3; ++i)
             y[i] += h * t3[i];
         }
@@ -1009,26 +1001,15 @@ namespace mgamd
     {
       const int           n = p + 1, n3 = n * n * n;
       std::vector<double> t1(n3), t2(n3);
-      for (int d = 0; d < 3; ++d)
-        {
-          const int     st = d == 0 ? 1 : (d == 1 ? n : n * n);
-          const double *in = d == 0 ? x : (d == 1 ? t1.data() : t2.data());
-          double       *out = d == 1 ? t2.data() : t1.data();
-          for (int i = 0; i < n3; ++i)
-            {
-              const int id = (i / st) % n;
-              double    s  = 0;
-              for (int b = 0; b < n; ++b)
-                s += fe.M[id * n + b] * in[i + (b - id) * st];
-              out[i] = s;
-            }
-        }
+      sweep_1d(fe.M.data(), false, 0, x, t1.data());
+      sweep_1d(fe.M.data(), false, 1, t1.data(), t2.data());
+      sweep_1d(fe.M.data(), false, 2, t2.data(), t1.data());
       for (int i = 0; i < n3; ++i)
         y[i] += sigma * h * h * h * t1[i];
     }
 
-    // right-hand side for data `kind` (ref:include/operator.h:362-447): load vector by QGauss(p+1) quadrature of f,
-    // minus the operator without Dirichlet constraints applied to the boundary interpolant of g; constrained rows 0.
+    // right-hand side for data `kind` (ref:include/operator.h:362-447): load vector by QGauss(p+1) quadrature of f, constrained
+    // rows 0, minus the lifting of the boundary interpolant of g (dirichlet_kind_values through dirichlet_lift_add).
     // With a mass coefficient the manufactured load is -Laplace u_g + sigma u_g and the lifting uses K + sigma M.
     void
     compute_rhs_function(int kind, std::vector<double> &b) const
@@ -1045,16 +1026,16 @@ namespace mgamd
                                     " with Robin coefficients (convective faces): not implemented, the lifting of non-zero Dirichlet "
                                     "data carries no face term; only kind 0 (f = 1, g = 0)");
       b.assign(n_dofs, 0.0);
-      const int           n = p + 1, n3 = n * n * n;
-      std::vector<double> fq(n3), t1(n3), t2(n3), load(n3), xg(n3), lift(n3);
+      const int             n = p + 1, n3 = n * n * n;
+      std::vector<double>   fq(n3), t1(n3), t2(n3), load(n3);
+      std::vector<uint32_t> idx(n3);
       for (size_t ci = 0; ci < tria->cells.size(); ++ci)
         {
           if (!cell_is_local(ci))
             continue;
-          const Cell    &c    = tria->cells[ci];
-          const uint16_t mask = tria->masks[ci];
-          const double   h    = 2.0 / (double)(1u << c.level);
-          const double   o[3] = {-1.0 + h * c.i, -1.0 + h * c.j, -1.0 + h * c.k};
+          const Cell  &c    = tria->cells[ci];
+          const double h    = 2.0 / (double)(1u << c.level);
+          const double o[3] = {-1.0 + h * c.i, -1.0 + h * c.j, -1.0 + h * c.k};
           // f at the quadrature points, times JxW
           for (int qz = 0; qz < n; ++qz)
             for (int qy = 0; qy < n; ++qy)
@@ -1065,55 +1046,20 @@ namespace mgamd
                   fq[(qz * n + qy) * n + qx] = f * h * h * h * fe.wq[qx] * fe.wq[qy] * fe.wq[qz];
                 }
           // integrate against the shape functions: load[a] = sum_q S[q][a] ... per direction
-          auto integrate = [&](int d, const double *in, double *out) {
-            const int st = d == 0 ? 1 : (d == 1 ? n : n * n);
-            for (int i = 0; i < n3; ++i)
-              {
-                const int id = (i / st) % n;
-                double    s  = 0;
-                for (int q = 0; q < n; ++q)
-                  s += fe.S[q * n + id] * in[i + (q - id) * st];
-                out[i] = s;
-              }
-          };
-          integrate(0, fq.data(), t1.data());
-          integrate(1, t1.data(), t2.data());
-          integrate(2, t2.data(), load.data());
-          // boundary interpolant of g on this cell's gathered DoFs, operator without Dirichlet constraints
-          bool any_g = false;
-          uint32_t idx[512];
-          for (int z = 0; z < n; ++z)
-            for (int y = 0; y < n; ++y)
-              for (int x = 0; x < n; ++x)
-                {
-                  const int a[3] = {x, y, z};
-                  const int t    = (z * n + y) * n + x;
-                  idx[t]         = cell_node_index(ci, a);
-                  xg[t]          = 0.0;
-                  if (idx[t] == INVALID_DOF)
-                    {
-                      double pos[3];
-                      gathered_node_position(ci, a, pos);
-                      xg[t] = data_g(kind, pos);
-                      any_g |= xg[t] != 0.0;
-                    }
-                }
-          if (any_g)
-            {
-              interpolate_hanging(fe, mask, xg.data(), false);
-              cell_stiffness_apply(coefficient_of(ci) * h, xg.data(), lift.data()); // (a K_cell: the cell matrix is linear in its scale)
-              if (sigma != 0.0)
-                cell_mass_add(h, sigma, xg.data(), lift.data());
-              for (int t = 0; t < n3; ++t)
-                load[t] -= lift[t];
-            }
-          interpolate_hanging(fe, mask, load.data(), true);
+          sweep_1d(fe.S.data(), true, 0, fq.data(), t1.data());
+          sweep_1d(fe.S.data(), true, 1, t1.data(), t2.data());
+          sweep_1d(fe.S.data(), true, 2, t2.data(), load.data());
+          interpolate_hanging(fe, tria->masks[ci], load.data(), true);
+          gather_cell(ci, idx.data(), false);
           for (int t = 0; t < n3; ++t)
             if (idx[t] != INVALID_DOF)
               b[idx[t]] += load[t];
         }
       for (uint32_t i = first_constrained(); i < n_dofs; ++i)
         b[i] = 0.0;
+      std::vector<double> g;
+      dirichlet_kind_values(kind, g);
+      dirichlet_lift_add(g.data(), true, -1.0, b);
     }
 
     // boundary load of a constant flux q[f] through every natural face f of the cube:  b_i = sum_f q_f int_{Gamma_f} phi_i.  Per
@@ -1122,19 +1068,19 @@ namespace mgamd
     void
     compute_rhs_boundary_flux(const double q[6], std::vector<double> &b) const
     {
-      static const char *const face_name[6] = {"x=-1", "x=+1", "y=-1", "y=+1", "z=-1", "z=+1"};
       for (int f = 0; f < 6; ++f)
         {
           if (!std::isfinite(q[f]))
-            throw std::invalid_argument("boundary flux on face " + std::to_string(f) + " (" + face_name[f] + ") is not finite");
+            throw std::invalid_argument("boundary flux on face " + std::to_string(f) + " (" + face_name(f) + ") is not finite");
           if (q[f] != 0.0 && ((dirichlet_faces >> f) & 1))
-            throw std::invalid_argument("boundary flux " + std::to_string(q[f]) + " on face " + std::to_string(f) + " (" + face_name[f] +
+            throw std::invalid_argument("boundary flux " + std::to_string(q[f]) + " on face " + std::to_string(f) + " (" + face_name(f) +
                                         ") refused: the face is Dirichlet (dirichlet_faces mask " + std::to_string(dirichlet_faces) +
                                         "), a flux load needs a natural face");
         }
       b.assign(n_dofs, 0.0);
-      const int           n = p + 1, n3 = n * n * n;
-      std::vector<double> load(n3);
+      const int             n = p + 1, n3 = n * n * n;
+      std::vector<double>   load(n3);
+      std::vector<uint32_t> idx(n3);
       for (size_t ci = 0; ci < tria->cells.size(); ++ci)
         {
           if (!cell_is_local(ci))
@@ -1160,15 +1106,10 @@ namespace mgamd
           if (!any)
             continue;
           interpolate_hanging(fe, tria->masks[ci], load.data(), true);
-          for (int z = 0; z < n; ++z)
-            for (int y = 0; y < n; ++y)
-              for (int x = 0; x < n; ++x)
-                {
-                  const int      a[3] = {x, y, z};
-                  const uint32_t idx  = cell_node_index(ci, a);
-                  if (idx != INVALID_DOF)
-                    b[idx] += load[(z * n + y) * n + x];
-                }
+          gather_cell(ci, idx.data(), false);
+          for (int t = 0; t < n3; ++t)
+            if (idx[t] != INVALID_DOF)
+              b[idx[t]] += load[t];
         }
       for (uint32_t i = first_constrained(); i < n_dofs; ++i)
         b[i] = 0.0;
@@ -1179,62 +1120,34 @@ namespace mgamd
     void
     distribute(int kind, std::vector<double> &x) const
     {
-      const int           n = p + 1, n3 = n * n * n;
-      std::vector<double> v(n3);
-      // Dirichlet values first (hanging nodes may depend on them)
-      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
-        if (cell_is_local(ci))
-          for (int z = 0; z < n; ++z)
-            for (int y = 0; y < n; ++y)
-              for (int xx = 0; xx < n; ++xx)
-                {
-                  const int      a[3] = {xx, y, z};
-                  const uint64_t key  = resolved_key(ci, a);
-                  if (!key_on_dirichlet_face(key))
-                    continue;
-                  const int32_t *gi = keymap.find(key);
-                  if (gi && (uint32_t)*gi >= first_dirichlet() && (uint32_t)*gi < first_dirichlet() + n_dirichlet)
-                    {
-                      double pos[3];
-                      gathered_node_position(ci, a, pos);
-                      x[*gi] = data_g(kind, pos);
-                    }
-                }
-      distribute_hanging(x);
+      std::vector<double> g;
+      dirichlet_kind_values(kind, g);
+      distribute_values(g.data(), x);
     }
     // hanging-node DoFs = the interpolant of their parent face/edge, Dirichlet parents included (their values are in x)
     void
     distribute_hanging(std::vector<double> &x) const
     {
-      const int           n = p + 1, n3 = n * n * n;
-      std::vector<double> v(n3);
+      const int             n = p + 1, n3 = n * n * n;
+      std::vector<double>   v(n3);
+      std::vector<uint32_t> idx(n3);
       for (size_t ci = 0; ci < tria->cells.size(); ++ci)
         {
           const uint16_t mask = tria->masks[ci];
           if (!cell_is_local(ci) || !(mask >> MASK_FACE_SHIFT))
             continue;
-          for (int z = 0; z < n; ++z)
-            for (int y = 0; y < n; ++y)
-              for (int xx = 0; xx < n; ++xx)
-                {
-                  const int      a[3] = {xx, y, z};
-                  const int32_t *gi   = keymap.find(resolved_key(ci, a));
-                  uint32_t       id   = cell_node_index(ci, a);
-                  if (id == INVALID_DOF && gi)
-                    id = (uint32_t)*gi; // Dirichlet DoF: its value was set above
-                  v[(z * n + y) * n + xx] = id != INVALID_DOF ? x[id] : 0.0;
-                }
+          gather_cell(ci, idx.data(), true); // (a Dirichlet parent keeps its index: its value is in x)
+          for (int t = 0; t < n3; ++t)
+            v[t] = idx[t] != INVALID_DOF ? x[idx[t]] : 0.0;
           interpolate_hanging(fe, mask, v.data(), false);
-          for (int z = 0; z < n; ++z)
-            for (int y = 0; y < n; ++y)
-              for (int xx = 0; xx < n; ++xx)
-                {
-                  const int a[3] = {xx, y, z};
-                  bool      corner;
-                  if (node_on_constrained_entity(mask, p, a, &corner) && !corner)
-                    if (const int32_t *own = keymap.find(own_key(tria->cells[ci], a)))
-                      x[*own] = v[(z * n + y) * n + xx];
-                }
+          for (int t = 0; t < n3; ++t)
+            {
+              const int a[3] = {t % n, (t / n) % n, t / (n * n)};
+              bool      corner;
+              if (node_on_constrained_entity(mask, p, a, &corner) && !corner)
+                if (const int32_t *own = keymap.find(own_key(tria->cells[ci], a)))
+                  x[*own] = v[t];
+            }
         }
     }
 
@@ -1615,11 +1528,36 @@ namespace mgamd
       build_dirichlet_cells();
     }
 
+    // b += alpha C^T (K_a + s sigma M) C g^  on the free rows, over dirichlet_cells: the core of compute_rhs_dirichlet and of the
+    // Gaussian right-hand side.  Host restatement of dirichlet_lift_kernel.  It refuses nothing: its callers do
+    void
+    dirichlet_lift_add(const double *g, bool include_mass, double alpha, std::vector<double> &b) const
+    {
+      const int           n = p + 1, n3 = n * n * n;
+      std::vector<double> xg(n3), lift(n3);
+      for (size_t e = 0; e < dirichlet_cells.size(); ++e)
+        {
+          const uint32_t *idx = &dirichlet_cells.idx[e * n3];
+          for (int t = 0; t < n3; ++t)
+            xg[t] = is_dirichlet_index(idx[t]) ? g[idx[t]] : 0.0;
+          const uint16_t mask = dirichlet_cells.mask[e];
+          const double   ah = dirichlet_cells.scale[2 * e], h = dirichlet_cells.scale[2 * e + 1];
+          interpolate_hanging(fe, mask, xg.data(), false);
+          cell_stiffness_apply(ah, xg.data(), lift.data());
+          if (include_mass && sigma != 0.0)
+            cell_mass_add(h, sigma, xg.data(), lift.data());
+          interpolate_hanging(fe, mask, lift.data(), true);
+          for (int t = 0; t < n3; ++t)
+            if (idx[t] < first_constrained())
+              b[idx[t]] += alpha * lift[t];
+        }
+    }
+
     // dirichlet_cells from the final numbering; nothing without a Dirichlet face
     void
     build_dirichlet_cells()
     {
-      if (dirichlet_faces == 0 || ls_level || n_dirichlet == 0)
+      if (dirichlet_faces == 0 || n_dirichlet == 0)
         return;
       const int             n = p + 1, n3 = n * n * n;
       std::vector<uint32_t> idx(n3);
@@ -1641,14 +1579,8 @@ namespace mgamd
               }
           if (!near)
             continue;
-          bool any = false;
-          for (int t = 0; t < n3; ++t)
-            {
-              const int a[3] = {t % n, (t / n) % n, t / (n * n)};
-              idx[t]         = gathered_index(ci, a);
-              any |= is_dirichlet_index(idx[t]);
-            }
-          if (!any)
+          gather_cell(ci, idx.data(), true);
+          if (std::none_of(idx.begin(), idx.end(), [&](uint32_t i) { return is_dirichlet_index(i); }))
             continue;
           const double h = 2.0 / (double)(1u << c.level);
           dirichlet_cells.idx.insert(dirichlet_cells.idx.end(), idx.begin(), idx.end());

@@ -228,29 +228,31 @@ namespace mgamd
     return x.type == MGAMD_F64 ? dot_raw(x.ctx, x.as<double>(), y.as<double>(), x.n) : dot_raw(x.ctx, x.as<float>(), y.as<float>(), x.n);
   }
 
+  // host values -> a device vector of either number type, on the stream; returns when they have arrived
+  static void
+  upload(Ctx *ctx, mgamd_vec &v, const std::vector<double> &h)
+  {
+    std::vector<float> f;
+    if (v.type == MGAMD_F32)
+      f.assign(h.begin(), h.end());
+    const void *src = v.type == MGAMD_F32 ? (const void *)f.data() : (const void *)h.data();
+    HIP_CHECK(hipMemcpyAsync(v.data, src, h.size() * (size_t)v.type, hipMemcpyHostToDevice, ctx->stream));
+    ctx->sync();
+  }
+
+  // the built-in Dirichlet values of `kind` as caller data: computed on the host, uploaded once, distributed by the kernels of
+  // distribute_values behind whatever the stream holds for x
   void
   LevelOperatorBase::distribute(mgamd_vec &x, int kind)
   {
     if (x.n != n_dofs())
       throw std::invalid_argument("distribute: vector size mismatch");
-    std::vector<double> h(x.n);
-    ctx->sync();
-    if (x.type == MGAMD_F64)
-      HIP_CHECK(hipMemcpy(h.data(), x.data, h.size() * 8, hipMemcpyDeviceToHost));
-    else
-      {
-        std::vector<float> f(x.n);
-        HIP_CHECK(hipMemcpy(f.data(), x.data, f.size() * 4, hipMemcpyDeviceToHost));
-        std::copy(f.begin(), f.end(), h.begin());
-      }
-    tables->distribute(kind, h);
-    if (x.type == MGAMD_F64)
-      HIP_CHECK(hipMemcpy(x.data, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    else
-      {
-        std::vector<float> f(h.begin(), h.end());
-        HIP_CHECK(hipMemcpy(x.data, f.data(), f.size() * 4, hipMemcpyHostToDevice));
-      }
+    std::vector<double> g;
+    tables->dirichlet_kind_values(kind, g);
+    std::unique_ptr<mgamd_vec> gd(vec_create(ctx, x.n, x.type));
+    upload(ctx, *gd, g);
+    distribute_values_core(x, *gd);
+    ctx->sync(); // gd is freed on return
   }
 
   void
@@ -277,15 +279,7 @@ namespace mgamd
   void
   LevelOperatorBase::upload_load(mgamd_vec &b, const std::vector<double> &h)
   {
-    if (b.type == MGAMD_F64)
-      HIP_CHECK(hipMemcpyAsync(b.data, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    else
-      {
-        std::vector<float> f(h.begin(), h.end());
-        HIP_CHECK(hipMemcpyAsync(b.data, f.data(), f.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        ctx->sync();
-      }
-    ctx->sync();
+    upload(ctx, b, h);
     exchange_add_tail(b); // contributions of the other ranks' cells to shared DoFs
     ctx->sync();
   }

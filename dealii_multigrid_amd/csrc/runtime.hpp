@@ -240,6 +240,9 @@ namespace mgamd
     distribute_values(mgamd_vec &x, const mgamd_vec &g) = 0;
 
   private:
+    // distribute_values without its refusals (sizes, local-smoothing levels): distribute(x, kind) runs on every level
+    virtual void
+    distribute_values_core(mgamd_vec &x, const mgamd_vec &g) = 0;
     void
     upload_load(mgamd_vec &b, const std::vector<double> &h);
   };

@@ -164,8 +164,11 @@ int mgamd_dofs_get_cell_dofs(const mgamd_dofs *d, uint32_t *out);
 int mgamd_dofs_rhs_constant(const mgamd_dofs *d, double *out);
 /* Operator::rhs for SimulationType `kind` (0 "Constant": f = 1, g = 0; 1 "Gaussian": source and boundary values of
  * ref:multigrid_throughput.cc:60-125,2294-2298): QGauss(p+1) load vector minus the Dirichlet lifting, constrained rows 0
- * (ref:include/operator.h:362-447); and AffineConstraints::distribute on a host vector of n_dofs values */
+ * (ref:include/operator.h:362-447).  The lifting is that of mgamd_dofs_rhs_dirichlet, mass part included, for the Gaussian at the
+ * support points of the Dirichlet DoFs. */
 int mgamd_dofs_rhs(const mgamd_dofs *d, int kind, double *out);
+/* AffineConstraints::distribute on a host vector of n_dofs values: mgamd_dofs_distribute_values with the boundary values of `kind`
+ * at the support points of the Dirichlet DoFs (kind 0: exact zeros) */
 int mgamd_dofs_distribute(const mgamd_dofs *d, int kind, double *x);
 /* the dirichlet_faces mask these tables were built with (ref:multigrid_throughput.cc:1585-1593 fixes it to the whole boundary) */
 int mgamd_dofs_dirichlet_faces(const mgamd_dofs *d, unsigned *mask);
@@ -396,11 +399,16 @@ int mgamd_level_op_vmult_mass(mgamd_level_op *op, mgamd_vec *dst, const mgamd_ve
 int mgamd_level_op_inverse_diagonal(mgamd_level_op *op, mgamd_vec *diagonal);
 /* Operator::rhs with f == 1, g == 0 (ref:include/operator.h:362-447) */
 int mgamd_level_op_rhs(mgamd_level_op *op, mgamd_vec *rhs);
-/* the same for SimulationType `kind` (see mgamd_dofs_rhs), and constraints.distribute(solution) after the solve */
+/* the same for SimulationType `kind` (see mgamd_dofs_rhs) */
 int mgamd_level_op_rhs_kind(mgamd_level_op *op, int kind, mgamd_vec *rhs);
 /* mgamd_dofs_rhs_boundary_flux into a device vector of the operator; on a distributed operator each rank integrates over its own
  * cells and the shared entries are completed over the ranks, as for mgamd_level_op_rhs_kind */
 int mgamd_level_op_rhs_boundary_flux(mgamd_level_op *op, const double q[6], mgamd_vec *rhs);
+/* constraints.distribute(solution) after the solve, for SimulationType `kind`: the boundary values of `kind` are computed on the host
+ * (mgamd_dofs_distribute) and copied to the device once, in the operator's number type; the kernels of
+ * mgamd_level_op_distribute_values then fill x, stream-ordered behind whatever the stream holds for x.  Nothing is copied from the
+ * device to the host; the call returns when x is filled.  Works on the operator of a local-smoothing level too (its
+ * refinement-edge entries are left alone). */
 int mgamd_level_op_distribute(mgamd_level_op *op, int kind, mgamd_vec *x);
 /* mgamd_dofs_rhs_dirichlet on the device: rhs is OVERWRITTEN with the lifting of the Dirichlet data g (a device vector of n_dofs
  * values of which only the entries at Dirichlet DoFs are read), with the operator's own mass coefficient where include_mass is set.
@@ -412,7 +420,8 @@ int mgamd_level_op_distribute(mgamd_level_op *op, int kind, mgamd_vec *x);
 int mgamd_level_op_rhs_dirichlet(mgamd_level_op *op, const mgamd_vec *g, int include_mass, mgamd_vec *rhs);
 /* mgamd_dofs_distribute_values on the device, stream-ordered: the Dirichlet range of x is copied from g, then every hanging DoF is
  * interpolated from its parents (one thread per hanging DoF; a Dirichlet parent contributes the value just written).  Free entries
- * of x are untouched.  mgamd_level_op_distribute is unchanged. */
+ * of x are untouched.  mgamd_level_op_distribute runs the same two kernels on the built-in values.  MGAMD_ERR_INVALID for vectors of
+ * the wrong size or number type and for the operator of a local-smoothing level. */
 int mgamd_level_op_distribute_values(mgamd_level_op *op, mgamd_vec *x, const mgamd_vec *g);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is

@@ -1,6 +1,8 @@
 """Non-zero Dirichlet data on the host (no GPU): the table of cells that gather a Dirichlet DoF, the lifting b_I -= A_ID g, the
 distribute for caller data, the per-face constants, a two-rank partition and what is refused, by name.
 Oracle: tests/dirichlet_data_oracle.py on the levels of boundary_oracle / coefficient_oracle / helmholtz_oracle."""
+import os
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -12,7 +14,7 @@ import dirichlet_data_oracle as do
 import helmholtz_oracle as ho
 import robin_oracle as ro
 import time_stepping_oracle as tso
-from conftest import rel_err
+from conftest import ROOT, rel_err
 
 TOL_LOAD = 1e-13  # test_boundary_host.py's bound for loads
 MASKS = [bo.ALL, bo.M1, bo.M2]
@@ -133,6 +135,25 @@ def test_gaussian_values_give_the_gaussian_distribute(mgamd, oracle):
             assert np.linalg.norm(d.rhs_dirichlet(g) + load - full) <= TOL_LOAD * np.linalg.norm(full)
 
 
+def test_gaussian_data_on_a_local_smoothing_level_is_the_recorded_one(mgamd):
+    """The Gaussian right-hand side and distribute on the tables of a local-smoothing level (quadrant 3, p = 2, the finest refinement
+    level: 64 cells with refinement-edge DoFs, gathered as ordinary indices, their rows constrained), which no oracle test covers.
+    tests/golden/ls_level_quadrant3_p2_gaussian.npz holds x and both results as computed before the Gaussian data went through the
+    Dirichlet-data path (load and lifting summed per cell); 1e-13 of the largest entry allows the reordered sum and nothing more."""
+    fix = np.load(os.path.join(ROOT, "tests", "golden", "ls_level_quadrant3_p2_gaussian.npz"))
+    t = mgamd.Triangulation("quadrant", 3)
+    d = mgamd.DoFs(t.level_mesh(t.n_levels - 1), 2, 0, local_smoothing_level=True)
+    i = d.info
+    assert i.n_cells == 64 and i.n_edge > 0 and i.n_dirichlet > 0 and d.n_dofs == len(fix["x"])
+    b = d.rhs_function(1)
+    for name, got in (("rhs_function_1", b), ("distribute_1", d.distribute(fix["x"], 1))):
+        want = fix[name]
+        e = np.abs(got - want).max() / np.abs(want).max()
+        print(f"local-smoothing level, {name}: {e:.2e} of the largest entry {np.abs(want).max():.3e}")
+        assert e <= 1e-13
+    assert np.all(b[i.n_interior + i.n_tail:] == 0.0)  # (refinement-edge rows too)
+
+
 def test_dirichlet_face_values_on_shared_edges_and_corners(mgamd, oracle):
     p = 2
     v = np.array([300.0, 400.0, 5.0, 0.0, 0.0, -7.0])
@@ -223,7 +244,7 @@ def test_refusals_by_message(mgamd):
     assert np.all(d.dirichlet_face_values({0: 1.0, 3: 0.0})[d.info.n_interior + d.info.n_tail:][:d.info.n_dirichlet] == 1.0)
     t = mgamd.Triangulation("quadrant", 3)
     lvl = mgamd.DoFs(t.level_mesh(2), 2, 0, local_smoothing_level=True)
-    assert len(lvl.dirichlet_cells()[0]) == 0
+    assert len(lvl.dirichlet_cells()[0]) > 0  # (the level's own Gaussian right-hand side walks it; caller data stays refused)
     with pytest.raises(mgamd.MgamdError, match="rhs_dirichlet: refused on the level of a local-smoothing hierarchy"):
         lvl.rhs_dirichlet(np.zeros(lvl.n_dofs))
     # mask 0: no Dirichlet DoF, an empty table and a zero lifting

@@ -179,6 +179,37 @@ def test_distribute_values(mgamd, oracle, ctx, L, p):
                 assert np.abs(got - d.distribute_values(x, g)).max() <= 1e-15 * np.abs(ref).max()
 
 
+@pytest.mark.parametrize("p", [1, 2, 4])
+def test_distribute_of_the_gaussian_is_distribute_values(mgamd, oracle, ctx, p):
+    """Operator.distribute(x, 1) uploads the Gaussian at the Dirichlet support points and runs the kernels of distribute_values: the
+    same bits as distribute_values with those values (read off the host distribute of a zero vector, whose Dirichlet entries are
+    exactly them), in both number types.  Quadrant 3 is the smallest mesh with hanging nodes whose parents are Dirichlet DoFs, under
+    both masks.  Constrained entries hold NaN beforehand: a row that is not written shows.  Bounds: test_distribute_values'."""
+    rng = np.random.default_rng(13)
+    for mask in (ALL, M1):
+        d = product(mgamd, 3, p, mask, 0.0)
+        lv = oracle_level(oracle, 3, p, mask, 0.0, d)
+        bd = do.dirichlet_dofs(lv)
+        assert d.info.n_hanging > 0 and lv.Ch.tocsr()[np.flatnonzero(lv.hanging)][:, np.flatnonzero(bd)].nnz > 0
+        g = d.distribute(np.zeros(lv.n), 1)
+        assert np.abs(g[bd]).max() > 0
+        x = rng.standard_normal(lv.n).astype(np.float32).astype(np.float64)
+        ref = lv.distribute(x, oracle.gaussian_solution)
+        x[lv.constrained] = np.nan
+        for number_type, tol in ((mgamd.F64, 1e-15), (mgamd.F32, TOL_F32)):
+            op = mgamd.Operator(ctx, d, number_type)
+            va, vb, v0 = vec(op, x), vec(op, x), vec(op, x)
+            op.distribute(va, 1)
+            op.distribute_values(vb, vec(op, g))
+            op.distribute(v0, 0)
+            a, b, zero = va.to_host(), vb.to_host(), v0.to_host()
+            e = rel_err(a, ref)
+            print(f"distribute(x, 1) quadrant 3 p={p} mask={mask:#04x} {'FP64' if number_type == mgamd.F64 else 'FP32'}: {e:.2e}")
+            assert np.isfinite(a).all() and np.array_equal(a, b) and e <= tol
+            assert np.array_equal(a[~lv.constrained], x[~lv.constrained])
+            assert np.isfinite(zero).all() and np.all(zero[bd] == 0.0)  # kind 0: exact zeros, nothing evaluated
+
+
 # ------------------------------------------------------------------ known answers
 @pytest.mark.parametrize("p", [1, 2])
 def test_linear_function_is_reproduced(mgamd, oracle, ctx, p):
