@@ -1,21 +1,13 @@
-"""Test-side oracle of non-zero Dirichlet data: pure numpy/scipy on the levels of tests/boundary_oracle.py, coefficient_oracle.py,
-helmholtz_oracle.py and robin_oracle.py (which carry Ch, C, K0raw, Mraw, Kraw, dirichlet, hanging, constrained), none of which is
-edited, and a theta stepper on top of tests/time_stepping_oracle.py.  Not a test module.
+"""Test-side oracle of the theta stepper with non-zero Dirichlet data, on the levels of oracle/physics_oracle.py (which carry Ch, C, K0raw,
+Braw, Mraw, dirichlet, hanging, constrained) and the solvers of tests/time_stepping_oracle.py.  Not a test module.
 
-Dirichlet data is a vector g of n values of which only the entries at Dirichlet DoFs count:  g^ = g there and 0 elsewhere.  With
-Ch the hanging-node interpolation that keeps the Dirichlet columns (nodal values = Ch @ DoF values):
+Dirichlet data is a vector g of n values of which only the entries at Dirichlet DoFs count:  g^ = physics_oracle.data(lv, g).  The
+lifting, distribute_values and face_values of a level are physics_oracle's.
 
-    lift(lv, g, include_mass)  =  -[Ch^T (K + s sigma Mraw) Ch g^]  on free rows, 0 on constrained rows
-
-K the raw stiffness matrix of the level (with its coefficient, and with the surface mass matrices of a level of robin_oracle.robin:
-where the only Dirichlet face is opposite the convective one they have no entry in a Dirichlet column, so the term vanishes by
-itself).  This is mgoracle.Level.rhs_function's lifting with g a vector.
-
-distribute_values(lv, x, g): Dirichlet DoFs from g, hanging DoFs from their parents, free DoFs kept.
-
-The stepper works on FULL nodal vectors N(u, g) = Ch (u + g^), u the free DoFs.  The semi-discrete equation on the free rows i is
-[Ch^T (Mraw N' + K N)]_i = [C^T Mraw C f]_i + l_i (the source sees the free entries of f only, as the product's mass pass).  One
-theta step with sigma = 1 / (theta dt), for the increment delta of the free DoFs:
+The stepper works on FULL nodal vectors N(u, g) = Ch (u + g^), u the free DoFs, K the raw stiffness matrix of the level with its
+coefficient and the surface term of its convective faces (physics_oracle.stiffness_raw).  The semi-discrete equation on the free
+rows i is [Ch^T (Mraw N' + K N)]_i = [C^T Mraw C f]_i + l_i (the source sees the free entries of f only, as the product's mass
+pass).  One theta step with sigma = 1 / (theta dt), for the increment delta of the free DoFs:
 
     A delta = (M^ f_theta + l - [Ch^T K N(u, g_old)]) / theta - [Ch^T (K + sigma Mraw) Ch (g_new^ - g_old^)]     on free rows
 
@@ -27,58 +19,7 @@ import numpy as np
 import scipy.sparse.linalg as spla
 
 import time_stepping_oracle as tso
-
-
-def dirichlet_dofs(lv):
-    return lv.dirichlet & ~lv.hanging
-
-
-def stiffness_raw(lv):
-    """the raw stiffness matrix of the level: with its coefficient and, on a level with convective faces, their surface term"""
-    K = lv.K0raw
-    return (K + lv.Braw).tocsr() if hasattr(lv, "Braw") else K
-
-
-def data(lv, g):
-    """g^: g on the Dirichlet DoFs, 0 elsewhere"""
-    return np.where(dirichlet_dofs(lv), g, 0.0)
-
-
-def lift(lv, g, include_mass=True):
-    K = stiffness_raw(lv)
-    if include_mass:
-        K = K + lv.mass_coefficient * lv.Mraw
-    b = -(lv.Ch.T @ (K @ (lv.Ch @ data(lv, g))))
-    b[lv.constrained] = 0.0
-    return b
-
-
-def distribute_values(lv, x, g):
-    x = np.array(x, dtype=float)
-    bd = dirichlet_dofs(lv)
-    x[bd] = g[bd]
-    x[lv.hanging] = 0.0
-    return lv.Ch @ x
-
-
-def n_cells_with_dirichlet_dof(lv):
-    """number of cells that gather at least one Dirichlet DoF, hanging nodes resolved to their parents through Ch"""
-    bd = dirichlet_dofs(lv)
-    touches = (abs(lv.Ch) @ bd.astype(float)) > 0  # per node: a Dirichlet DoF has weight in its value
-    # a hanging node whose parents include a Dirichlet DoF: the cell gathers that parent; its own nodes count directly
-    return int(np.sum(np.any(touches[lv.cell_dofs], axis=1)))
-
-
-def face_values(oracle, lv, v):
-    """v[f] on the Dirichlet DoFs of face f, the lowest-numbered Dirichlet face of a DoF on several; 0 elsewhere"""
-    top, mask, g = lv.p << oracle.LMAX, getattr(lv, "dirichlet_faces", 0x3F), np.zeros(lv.n)
-    for d in np.flatnonzero(dirichlet_dofs(lv)):
-        key = lv.keys[d]
-        for f in range(6):
-            if (mask >> f) & 1 and key[f >> 1] == (top if f & 1 else 0):
-                g[d] = v[f]
-                break
-    return g
+from physics_oracle import data, stiffness_raw
 
 
 def _nodal(lv, u, g):

@@ -11,7 +11,7 @@ import scipy.sparse as sp
 from scipy.sparse.csgraph import connected_components
 
 import amg_oracle as ao
-from test_gpu_random_meshes import random_mesh
+from support import random_mesh
 
 TOL_MAT = 1e-13
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-from test_gpu_random_meshes import random_mesh
+from support import random_mesh
 
 INVALID = 0xFFFFFFFF
 TOL = 1e-15

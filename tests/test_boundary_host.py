@@ -1,31 +1,22 @@
 """Per-face boundary conditions on the host (no GPU): the triangulation carries a 6-bit mask of its Dirichlet faces, coarsening
 inherits it, level tables copy it and classify boundary DoFs by it, the assembled matrix, the right-hand sides, distribute and the
-boundary flux load follow, and what is out of scope is refused by name.  Oracle: tests/boundary_oracle.py."""
+boundary flux load follow, and what is out of scope is refused by name.  Oracle: oracle/physics_oracle.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-import boundary_oracle as bo
-import coefficient_oracle as co
-import helmholtz_oracle as ho
+import physics_oracle as po
 import random_mesh_physics as rp
+import support as su
+from physics_oracle import Problem
 
 # (mask, sigma): M0 has no Dirichlet DoF and needs the mass term
-MASKS = [(bo.M1, 0.0), (bo.M2, 0.0), (bo.M0, 7.5)]
-_base = {}
-
+MASKS = [(po.M1, 0.0), (po.M2, 0.0), (po.M0, 7.5)]
 
 def _csr(d):
     ptr, col, val = d.matrix()
     return sp.csr_matrix((val, col.astype(np.int64), ptr.astype(np.int64)), shape=(d.n_dofs, d.n_dofs))
-
-
-def _base_level(oracle, geo, L, p):
-    """one constraint search per (mesh, degree), in the oracle's own numbering, sigma = 0, all Dirichlet"""
-    if (geo, L, p) not in _base:
-        _base[(geo, L, p)] = ho.level_class(oracle, 0.0)(oracle.create_mesh(geo, L), p)
-    return _base[(geo, L, p)]
 
 
 def _info_tuple(d):
@@ -44,14 +35,14 @@ def _check_level(oracle, d, lv, tag):
     diff = (A - lv.A).tocsr()
     e_A = (abs(diff).max() if diff.nnz else 0.0) / abs(lv.A).max()
     e_c = np.abs(d.rhs_function(0) - lv.rhs_constant).max() / np.abs(lv.rhs_constant).max()
-    ref = lv.rhs_function(ho.gaussian_load(oracle, lv.mass_coefficient), oracle.gaussian_solution)
+    ref = lv.rhs_function(po.gaussian_load(lv.mass_coefficient), oracle.gaussian_solution)
     e_g = np.abs(d.rhs_function(1) - ref).max() / np.abs(ref).max()
     x = np.random.default_rng(3).standard_normal(lv.n)
     x[lv.constrained] = 0.0
     ref = lv.distribute(x, oracle.gaussian_solution)
     e_d = np.abs(d.distribute(x, 1) - ref).max() / np.abs(ref).max()
     q = np.array([0.0 if (lv.dirichlet_faces >> f) & 1 else 1.0 + 0.5 * f for f in range(6)])
-    ref = bo.flux_load(lv, q)
+    ref = po.flux_load(lv, q)
     got = d.rhs_boundary_flux(q)
     e_q = np.abs(got - ref).max() / np.abs(ref).max()
     print(f"{tag}: n_dirichlet {i.n_dirichlet} n_hanging {i.n_hanging} matrix {e_A:.2e} rhs Constant {e_c:.2e} Gaussian {e_g:.2e} "
@@ -65,17 +56,17 @@ def _check_level(oracle, d, lv, tag):
 def test_mask_round_trip_defaults_and_coarsening(mgamd):
     t = mgamd.Triangulation("quadrant", 3)
     assert t.dirichlet_faces() == 63 == mgamd.ALL_DIRICHLET
-    t.set_dirichlet_faces(bo.M2)
-    assert t.dirichlet_faces() == bo.M2
+    t.set_dirichlet_faces(po.M2)
+    assert t.dirichlet_faces() == po.M2
     seq = mgamd.create_geometric_coarsening_sequence(t)
-    assert len(seq) > 2 and all(s.dirichlet_faces() == bo.M2 for s in seq)
-    assert t.coarsen().coarsen().dirichlet_faces() == bo.M2
+    assert len(seq) > 2 and all(s.dirichlet_faces() == po.M2 for s in seq)
+    assert t.coarsen().coarsen().dirichlet_faces() == po.M2
     lev, i, j, k, _ = t.cells()
     assert mgamd.Triangulation.from_leaves(lev, i, j, k).dirichlet_faces() == 63
     d = mgamd.DoFs(t, 2, 0)
-    assert d.dirichlet_faces() == bo.M2
-    t.set_dirichlet_faces(bo.M1)  # tables that exist keep their copy
-    assert d.dirichlet_faces() == bo.M2 and mgamd.DoFs(t, 2, 0).dirichlet_faces() == bo.M1
+    assert d.dirichlet_faces() == po.M2
+    t.set_dirichlet_faces(po.M1)  # tables that exist keep their copy
+    assert d.dirichlet_faces() == po.M2 and mgamd.DoFs(t, 2, 0).dirichlet_faces() == po.M1
 
 
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 1), ("quadrant", 3, 2), ("quadrant", 3, 4), ("hypercube", 3, 2)])
@@ -97,36 +88,40 @@ def test_quadrant_against_the_oracle(mgamd, oracle, p, mask, sigma):
     t.set_dirichlet_faces(mask)
     d = mgamd.DoFs(t, p, 0)
     d.set_mass_coefficient(sigma)
-    lv = bo.remask(oracle, ho.renumber(_base_level(oracle, "quadrant", 3, p), d.keys()), mask, sigma)
-    if mask == bo.M1:  # the refined corner touches x = -1: hanging nodes on both kinds of face
+    lv = su.oracle_level(d, "quadrant", 3, p, Problem(sigma, dirichlet_faces=mask))
+    if mask == po.M1:  # the refined corner touches x = -1: hanging nodes on both kinds of face
         top, k = p << oracle.LMAX, np.array(lv.keys)[lv.hanging]
         assert np.any(k[:, 0] == 0) and np.any((k[:, 1] == 0) | (k[:, 2] == 0))
-    if mask == bo.M0:
+    if mask == po.M0:
         assert d.info.n_dirichlet == 0
     _check_level(oracle, d, lv, f"quadrant 3 p={p} mask={mask:#04x} sigma={sigma}")
 
 
-def test_remask_is_what_the_level_class_builds(oracle):
-    """the shortcut of this file (one constraint search, re-masked) against a level built directly with the mask"""
+def test_remask_is_what_the_level_class_builds(mgamd, oracle):
+    """the shortcut of this file (one constraint search in the oracle's own numbering, cached, renumbered to the product's tables,
+    then the level formed with the mask) against a level formed on a space built directly in that numbering, and against the
+    vectors recorded from the levels the mask was first written for"""
     mesh = oracle.create_mesh("quadrant", 3)
-    for mask, sigma in MASKS:
-        direct = bo.level_class(oracle, sigma, mask)(mesh, 2)
-        short = bo.remask(oracle, _base_level(oracle, "quadrant", 3, 2), mask, sigma)
+    for (mask, sigma), name in zip(MASKS, ("M1", "M2", "M0_sigma")):
+        keys = mgamd.DoFs(su.tria(mgamd, "quadrant", 3, Problem(dirichlet_faces=mask)), 2, 0).keys()
+        direct = po.Level(po.Space(mesh, 2, numbering_keys=keys), Problem(sigma, dirichlet_faces=mask))
+        short = su.oracle_level(keys, "quadrant", 3, 2, Problem(sigma, dirichlet_faces=mask))
         assert np.array_equal(direct.dirichlet, short.dirichlet) and np.array_equal(direct.constrained, short.constrained)
         assert abs(direct.A - short.A).max() <= 1e-15 * abs(direct.A).max()
         assert np.abs(direct.rhs_constant - short.rhs_constant).max() <= 1e-15
+        su.assert_recorded(su.oracle_level(None, "quadrant", 2, 1, Problem(sigma, dirichlet_faces=mask)), name)
 
 
 @pytest.mark.parametrize("mg_type,p", [("HMG-global", 2), ("PMG", 2)])
 def test_mask_transfers_is_what_build_transfer_gives(oracle, mg_type, p):
-    """the transfers of a mask derived from those of mask 0 (boundary_oracle.mask_transfers) against build_transfer on the re-masked
-    levels"""
-    meshes, degs = ho.level_plan(oracle, "quadrant", 3, p, mg_type)
-    base = [ho.level_class(oracle, 0.0)(m, q) for m, q in zip(meshes, degs)]
-    P0 = bo.natural_transfers(oracle, base)
+    """the transfers of a mask derived from those of mask 0 (physics_oracle.mask_transfers) against build_transfer on the levels
+    of the mask"""
+    meshes, degs = po.level_plan("quadrant", 3, p, mg_type)
+    base = [su.space(m, q) for m, q in zip(meshes, degs)]
+    P0 = po.natural_transfers(base)
     for mask, sigma in MASKS:
-        levels = [bo.remask(oracle, lv, mask, sigma) for lv in base]
-        P, ref = bo.mask_transfers(P0, levels), bo.transfers(oracle, levels)
+        levels = [po.Level(s, Problem(sigma, dirichlet_faces=mask)) for s in base]
+        P, ref = po.mask_transfers(P0, levels), [None] + [oracle.build_transfer(levels[l], levels[l - 1]) for l in range(1, len(levels))]
         for l in range(1, len(levels)):
             assert P[l].shape == ref[l].shape and abs(P[l] - ref[l]).max() == 0.0 and ref[l].nnz > 0
 
@@ -134,12 +129,12 @@ def test_mask_transfers_is_what_build_transfer_gives(oracle, mg_type, p):
 @pytest.mark.parametrize("mask,sigma", MASKS)
 def test_random_octree_against_the_oracle(mgamd, oracle, mask, sigma):
     name, p = "M", 2
-    t = rp.tria_of(mgamd, rp.leaves_of(oracle, name), "per_family")
+    t = su.tria_of(mgamd, rp.leaves_of(oracle, name), Problem(coefficient="per_family"))
     t.set_dirichlet_faces(mask)
     d = mgamd.DoFs(t, p, 0)
     d.set_mass_coefficient(sigma)
     assert d.info.n_hanging > 0
-    lv = bo.remask(oracle, rp.oracle_level(oracle, name, p, "per_family", sigma, d.keys()), mask)
+    lv = su.oracle_level_on(d, rp.leaves_of(oracle, name), p, Problem(sigma, "per_family", mask))
     _check_level(oracle, d, lv, f"random octree {name} p={p} per_family mask={mask:#04x} sigma={sigma}")
 
 
@@ -150,7 +145,7 @@ def _classes(d):
     return set(k[:i.n_interior + i.n_tail]), set(k[first_d:first_d + i.n_dirichlet]), set(k[first_d + i.n_dirichlet:])
 
 
-@pytest.mark.parametrize("mask", [bo.M1, bo.M2, bo.M0])
+@pytest.mark.parametrize("mask", [po.M1, po.M2, po.M0])
 def test_two_rank_partition_classifies_like_the_global_level(mgamd, mask):
     fine = mgamd.Triangulation("quadrant", 3)
     fine.set_dirichlet_faces(mask)
@@ -186,7 +181,7 @@ def test_refusals_by_message(mgamd):
     with pytest.raises(mgamd.MgamdError, match="refused"):
         t.set_dirichlet_faces(-1)
     assert t.dirichlet_faces() == 63
-    t.set_dirichlet_faces(bo.M1)
+    t.set_dirichlet_faces(po.M1)
     d = mgamd.DoFs(t, 2, 0)
     with pytest.raises(mgamd.MgamdError, match=r"face 0 \(x=-1\) refused: the face is Dirichlet"):
         d.rhs_boundary_flux([1.0, 0, 0, 0, 0, 0])
@@ -215,10 +210,6 @@ def test_amg_setup_refuses_the_singular_operator(mgamd):
 
 
 # ------------------------------------------------------------------ known answer
-def _layers(x, planes, values):
-    return np.asarray(values)[np.sum(np.asarray(x)[..., None] > np.asarray(planes), axis=-1)]
-
-
 def _exact(x, planes, values, q, dirichlet_face):
     """u(x) with a u' = q from u(-1) = 0 (dirichlet_face 0), or -a u' = q from u(+1) = 0 (dirichlet_face 1): q times the thermal
     resistance between the Dirichlet face and x"""
@@ -240,11 +231,11 @@ def test_layered_wall_known_answer(mgamd, oracle, geo, L, p, planes, values, dir
     q = 3.0
     t = mgamd.Triangulation(geo, L)
     t.set_dirichlet_faces(1 << dirichlet_face)
-    t.set_coefficient_function(lambda x, y, z: _layers(x, planes, values))
+    t.set_coefficient_function(lambda x, y, z: su.layers(x, planes, values))
     d = mgamd.DoFs(t, p, 0)
     b = d.rhs_boundary_flux({1 - dirichlet_face: q})
     u = d.distribute(spla.spsolve(_csr(d).tocsc(), b), 0)
-    x = ho.renumber(_base_level(oracle, geo, L, p), d.keys()).node_positions()[:, 0]
+    x = su.oracle_level(d, geo, L, p).node_positions()[:, 0]
     ref = _exact(x, planes, values, q, dirichlet_face)
     err = np.abs(u - ref).max() / np.abs(ref).max()
     print(f"{geo} {L} p={p} layers {values}, Dirichlet face {dirichlet_face}: n_hanging {d.info.n_hanging}, face temperature "

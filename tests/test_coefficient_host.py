@@ -1,12 +1,13 @@
 """The diffusion coefficient on the host (no GPU): the triangulation carries one value per leaf, coarsening takes the mean over
 each coarse leaf, level tables copy it and only form bricks of cells with the bit-identical value, the assembled matrix and the
-Gaussian right-hand side follow it, and what is out of scope is refused by name.  Oracle: tests/coefficient_oracle.py."""
+Gaussian right-hand side follow it, and what is out of scope is refused by name.  Oracle: oracle/physics_oracle.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import coefficient_oracle as co
-import helmholtz_oracle as ho
+import physics_oracle as po
+import support as su
+from physics_oracle import Problem
 
 SIGMAS = [0.0, 7.5]
 
@@ -18,7 +19,7 @@ def _csr(d):
 
 def _tria(mgamd, geo, L, field):
     t = mgamd.Triangulation(geo, L)
-    t.set_coefficient(co.product_values(t, co.field_on(co.product_cells(t), field)))
+    t.set_coefficient(po.product_values(t, po.field_on(po.product_cells(t), field)))
     return t
 
 
@@ -49,14 +50,14 @@ def test_round_trip_and_reset(mgamd):
 @pytest.mark.parametrize("name", ["uniform", "octants", "inclusion", "per_cell"])
 def test_coarsen_takes_the_mean_over_each_coarse_leaf(mgamd, geo, L, name):
     """every mesh of the coarsening sequence against the oracle's volume-weighted mean of the FINEST field"""
-    fine = _tria(mgamd, geo, L, co.FIELDS[name])
-    finest = co.field_on(co.product_cells(fine), co.FIELDS[name])
+    fine = _tria(mgamd, geo, L, po.FIELDS[name])
+    finest = po.field_on(po.product_cells(fine), po.FIELDS[name])
     seq = mgamd.create_geometric_coarsening_sequence(fine)
     assert len(seq) > 2
     worst = 0.0
     for t in seq[:-1]:
         assert t.has_coefficient()
-        ref = co.product_values(t, co.restrict_field(finest, co.product_cells(t)))
+        ref = po.product_values(t, po.restrict_field(finest, po.product_cells(t)))
         worst = max(worst, np.abs(t.coefficient() / ref - 1.0).max())
     print(f"{geo} L={L} {name}: {len(seq)} meshes, worst relative difference of a coarse coefficient {worst:.2e}")
     assert worst <= 1e-15
@@ -73,7 +74,7 @@ def test_coarsen_without_a_coefficient_carries_none(mgamd):
                                                ("hypercube", 3, 2, 0), ("hypercube", 3, 4, 0), ("quadrant", 3, 4, 1)])
 @pytest.mark.parametrize("name", ["uniform", "octants", "inclusion", "per_cell"])
 def test_every_slot_has_one_bit_identical_value(mgamd, geo, L, p, max_brick, name):
-    t = _tria(mgamd, geo, L, co.FIELDS[name])
+    t = _tria(mgamd, geo, L, po.FIELDS[name])
     d = mgamd.DoFs(t, p, max_brick)
     slots, B = _slots(d, t)
     for (g, s), vals in slots.items():
@@ -88,7 +89,7 @@ def test_every_slot_has_one_bit_identical_value(mgamd, geo, L, p, max_brick, nam
 
 
 def test_octants_keep_the_eight_bricks_of_p4_and_split_the_brick_of_p2(mgamd):
-    t = _tria(mgamd, "hypercube", 3, co.octants)
+    t = _tria(mgamd, "hypercube", 3, po.octants)
     slots, B = _slots(mgamd.DoFs(t, 4, 0), t)
     bricks = [vals[0] for (g, s), vals in slots.items() if B[g] == 4]
     assert len(bricks) == 8 and len(slots) == 8
@@ -105,14 +106,14 @@ def test_octants_keep_the_eight_bricks_of_p4_and_split_the_brick_of_p2(mgamd):
 @pytest.mark.parametrize("name", ["uniform", "octants", "inclusion", "per_cell"])
 @pytest.mark.parametrize("sigma", SIGMAS)
 def test_assembled_matrix_and_gaussian_right_hand_side(mgamd, oracle, geo, L, p, name, sigma):
-    t = _tria(mgamd, geo, L, co.FIELDS[name])
+    t = _tria(mgamd, geo, L, po.FIELDS[name])
     d = mgamd.DoFs(t, p, 0)
     d.set_mass_coefficient(sigma)
-    lv = co.level(oracle, sigma, co.FIELDS[name], d, geo, L, p)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma, name))
     A = _csr(d)
     diff = (A - lv.A).tocsr()
     err = (abs(diff).max() if diff.nnz else 0.0) / abs(lv.A).max()
-    ref = lv.rhs_function(ho.gaussian_load(oracle, sigma), oracle.gaussian_solution)
+    ref = lv.rhs_function(po.gaussian_load(sigma), oracle.gaussian_solution)
     got = d.rhs_function(1)
     eb = np.abs(got - ref).max() / np.abs(ref).max()
     print(f"{geo} L={L} p={p} {name} sigma={sigma}: matrix {err:.2e}, rhs_function(1) {eb:.2e}")
@@ -165,7 +166,7 @@ def test_local_smoothing_refuses_a_coefficient(mgamd):
 
 
 def test_sharded_amg_plans_refuse_a_global_space_with_another_coefficient(mgamd):
-    fine = _tria(mgamd, "quadrant", 4, co.octants)
+    fine = _tria(mgamd, "quadrant", 4, po.octants)
     trias = mgamd.create_geometric_coarsening_sequence(fine)
     part = mgamd.Partition(trias, 2, 2.0, 0)
     loc = mgamd.DoFs(fine, 1, -1, part, len(trias) - 1, 1)

@@ -1,6 +1,6 @@
 """Non-zero Dirichlet data on the host (no GPU): the table of cells that gather a Dirichlet DoF, the lifting b_I -= A_ID g, the
 distribute for caller data, the per-face constants, a two-rank partition and what is refused, by name.
-Oracle: tests/dirichlet_data_oracle.py on the levels of boundary_oracle / coefficient_oracle / helmholtz_oracle."""
+Oracle: oracle/physics_oracle.py, and tests/dirichlet_data_oracle.py for the theta steppers."""
 import os
 
 import numpy as np
@@ -8,31 +8,22 @@ import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-import boundary_oracle as bo
-import coefficient_oracle as co
 import dirichlet_data_oracle as do
-import helmholtz_oracle as ho
-import robin_oracle as ro
+import physics_oracle as po
+import support as su
 import time_stepping_oracle as tso
 from conftest import ROOT, rel_err
+from physics_oracle import Problem
 
 TOL_LOAD = 1e-13  # test_boundary_host.py's bound for loads
-MASKS = [bo.ALL, bo.M1, bo.M2]
-_base = {}
-
-
-def _base_level(oracle, geo, L, p):
-    """one constraint search per (mesh, degree), in the oracle's own numbering, sigma = 0, all Dirichlet"""
-    if (geo, L, p) not in _base:
-        _base[(geo, L, p)] = ho.level_class(oracle, 0.0)(oracle.create_mesh(geo, L), p)
-    return _base[(geo, L, p)]
+MASKS = [po.ALL, po.M1, po.M2]
 
 
 def _product(mgamd, geo, L, p, mask, sigma, field=None, robin=None):
     t = mgamd.Triangulation(geo, L)
     t.set_dirichlet_faces(mask)
     if field is not None:
-        t.set_coefficient_function(co.XYZ[field])
+        t.set_coefficient_function(po.XYZ[field])
     if robin is not None:
         t.set_robin_coefficients(robin)
     d = mgamd.DoFs(t, p, 0)
@@ -41,10 +32,7 @@ def _product(mgamd, geo, L, p, mask, sigma, field=None, robin=None):
 
 
 def _oracle_level(oracle, geo, L, p, mask, sigma, d, field=None):
-    lv = ho.renumber(_base_level(oracle, geo, L, p), d.keys())
-    if field is not None:
-        lv = co.with_coefficient(lv, co.field_on(lv.cells, co.FIELDS[field]))
-    return bo.remask(oracle, lv, mask, sigma)
+    return su.oracle_level(d, geo, L, p, Problem(sigma, field, mask))
 
 
 def _csr(d):
@@ -67,7 +55,7 @@ def test_table_lift_and_distribute_against_the_oracle(mgamd, oracle, L, p):
                 first_d = i.n_interior + i.n_tail + i.n_edge
                 # the table: as many cells as gather a Dirichlet DoF, their Dirichlet entries in the Dirichlet range
                 idx, hmask, scale = d.dirichlet_cells()
-                assert len(idx) == do.n_cells_with_dirichlet_dof(lv) and 0 < len(idx) <= n_cells
+                assert len(idx) == po.n_cells_with_dirichlet_dof(lv) and 0 < len(idx) <= n_cells
                 in_range = (idx >= first_d) & (idx < first_d + i.n_dirichlet)
                 assert in_range.any(axis=1).all() and (idx < d.n_dofs).all()
                 cd = d.cell_dofs()  # INVALID_DOF exactly where the table holds a Dirichlet index
@@ -83,27 +71,27 @@ def test_table_lift_and_distribute_against_the_oracle(mgamd, oracle, L, p):
                 # g is random on EVERY DoF: the entries at free and hanging DoFs are not read
                 g = rng.standard_normal(lv.n)
                 for include_mass in (True, False):
-                    ref, got = do.lift(lv, g, include_mass), d.rhs_dirichlet(g, include_mass)
+                    ref, got = po.lift(lv, g, include_mass), d.rhs_dirichlet(g, include_mass)
                     e = rel_err(got, ref)
                     print(f"quadrant {L} p={p} mask={mask:#04x} {field} sigma={sigma} mass={include_mass}: table {len(idx)} of {n_cells} cells, "
                           f"lift {e:.2e}")
                     assert np.abs(ref).max() > 0
                     assert e <= TOL_LOAD and np.all(got[lv.constrained] == 0.0)
                 g2 = g.copy()
-                g2[~do.dirichlet_dofs(lv)] = 0.0
+                g2[~po.dirichlet_dofs(lv)] = 0.0
                 assert np.array_equal(d.rhs_dirichlet(g2), d.rhs_dirichlet(g))
                 x = rng.standard_normal(lv.n)
-                ref, got = do.distribute_values(lv, x, g), d.distribute_values(x, g)
+                ref, got = po.distribute_values(lv, x, g), d.distribute_values(x, g)
                 free = ~lv.constrained
                 assert rel_err(got, ref) <= TOL_LOAD and np.array_equal(got[free], x[free])
-                assert np.array_equal(got[do.dirichlet_dofs(lv)], g[do.dirichlet_dofs(lv)])
+                assert np.array_equal(got[po.dirichlet_dofs(lv)], g[po.dirichlet_dofs(lv)])
 
 
 def test_lift_is_the_matrix_block(mgamd, oracle):
     """on a mesh without a coefficient the lifting is -A_ID g with A_ID from the assembled matrix of the all-natural mesh, in which
     the Dirichlet DoFs of the masked mesh are ordinary unknowns: the product against itself"""
     p, sigma = 2, 7.5
-    d = _product(mgamd, "quadrant", 3, p, bo.M1, sigma)
+    d = _product(mgamd, "quadrant", 3, p, po.M1, sigma)
     n = _product(mgamd, "quadrant", 3, p, 0, sigma)
     key_n = {tuple(k): i for i, k in enumerate(n.keys().tolist())}
     perm = np.array([key_n[tuple(k)] for k in d.keys().tolist()])
@@ -129,7 +117,7 @@ def test_gaussian_values_give_the_gaussian_distribute(mgamd, oracle):
             a, b = d.distribute_values(x, g), d.distribute(x, 1)
             assert np.abs(a - b).max() <= 1e-15 * np.abs(b).max()
             # and the lifting of these values is what the Gaussian right-hand side carries on top of its load
-            zero_g = bo.remask(oracle, lv, mask, 0.0)
+            zero_g = po.changed(lv, sigma=0.0)
             load = zero_g.rhs_function(oracle.gaussian_rhs, lambda x, y, z: 0.0 * x)
             full = d.rhs_function(1)  # (the Gaussian is tiny on the boundary: the bound is the rounding of the load it is added to)
             assert np.linalg.norm(d.rhs_dirichlet(g) + load - full) <= TOL_LOAD * np.linalg.norm(full)
@@ -161,7 +149,7 @@ def test_dirichlet_face_values_on_shared_edges_and_corners(mgamd, oracle):
     d = _product(mgamd, "quadrant", 3, p, mask, 0.0)
     lv = _oracle_level(oracle, "quadrant", 3, p, mask, 0.0, d)
     g = d.dirichlet_face_values(v)
-    assert np.array_equal(g, do.face_values(oracle, lv, v))
+    assert np.array_equal(g, po.face_values(lv, v))
     assert np.array_equal(g, d.dirichlet_face_values({0: 300.0, 1: 400.0, 2: 5.0, 5: -7.0}))
     keys, top = np.array(lv.keys), p << oracle.LMAX
     edge = np.flatnonzero((keys[:, 0] == 0) & (keys[:, 1] == 0) & (keys[:, 2] > 0) & (keys[:, 2] < top) & ~lv.hanging)
@@ -169,7 +157,7 @@ def test_dirichlet_face_values_on_shared_edges_and_corners(mgamd, oracle):
     edge_yz = np.flatnonzero((keys[:, 0] > 0) & (keys[:, 0] < top) & (keys[:, 1] == 0) & (keys[:, 2] == top) & ~lv.hanging)
     assert len(edge) and len(corner) == 1 and len(edge_yz)
     assert np.all(g[edge] == 300.0) and g[corner[0]] == 400.0 and np.all(g[edge_yz] == 5.0)
-    assert np.all(g[~do.dirichlet_dofs(lv)] == 0.0)
+    assert np.all(g[~po.dirichlet_dofs(lv)] == 0.0)
     natural = np.flatnonzero((keys[:, 1] == top) & (keys[:, 0] > 0) & (keys[:, 0] < top) & (keys[:, 2] > 0) & (keys[:, 2] < top))
     assert len(natural) and np.all(g[natural] == 0.0)
 
@@ -179,7 +167,7 @@ def test_dirichlet_face_values_on_shared_edges_and_corners(mgamd, oracle):
 def test_linear_function_is_reproduced(mgamd, oracle, p):
     """g = nodal values of 1 + 2x - 3y + 0.5z on all six faces, f = 0, sigma = 0: the solution is that function, at hanging nodes
     too.  The product's matrix and lifting, solved with scipy and distributed (test_boundary_host's known-answer bound, 1e-12)"""
-    d = _product(mgamd, "quadrant", 3, p, bo.ALL, 0.0)
+    d = _product(mgamd, "quadrant", 3, p, po.ALL, 0.0)
     pos = d.node_positions()
     exact = 1.0 + 2.0 * pos[:, 0] - 3.0 * pos[:, 1] + 0.5 * pos[:, 2]
     u = d.distribute_values(spla.spsolve(_csr(d).tocsc(), d.rhs_dirichlet(exact)), exact)
@@ -216,23 +204,23 @@ def test_two_rank_partition_sums_to_the_global_lift(mgamd, mask):
 def test_convective_wall_with_a_hot_wall_is_accepted(mgamd, oracle):
     """beta > 0 on x = +1, the only Dirichlet face x = -1 opposite: no DoF is shared and the face term of the lifting vanishes (the
     oracle's lifting carries the surface matrix and shows it)"""
-    p, mask, beta = 2, bo.M1, (0.0, 2.5, 0.0, 0.0, 0.0, 0.0)
+    p, mask, beta = 2, po.M1, (0.0, 2.5, 0.0, 0.0, 0.0, 0.0)
     d = _product(mgamd, "quadrant", 3, p, mask, 0.0, robin=beta)
-    lv = ro.robin(_oracle_level(oracle, "quadrant", 3, p, mask, 0.0, d), beta)
+    lv = su.oracle_level(d, "quadrant", 3, p, Problem(0.0, None, mask, beta))
     g = d.dirichlet_face_values({0: 350.0})
-    ref = do.lift(lv, g)
+    ref = po.lift(lv, g)
     assert np.abs(ref).max() > 0 and rel_err(d.rhs_dirichlet(g), ref) <= TOL_LOAD
     with pytest.raises(mgamd.MgamdError, match="SimulationType 1 with Robin coefficients"):
         d.rhs_function(1)  # (the Gaussian lifting keeps its refusal)
 
 
 def test_refusals_by_message(mgamd):
-    d = _product(mgamd, "quadrant", 3, 2, bo.M1, 0.0, robin=(0.0, 0.0, 0.0, 0.75, 0.0, 0.0))
+    d = _product(mgamd, "quadrant", 3, 2, po.M1, 0.0, robin=(0.0, 0.0, 0.0, 0.75, 0.0, 0.0))
     g = np.zeros(d.n_dofs)
     with pytest.raises(mgamd.MgamdError, match=r"convective face 3 \(y=\+1, Robin coefficient 0.75\d*\) shares an edge with the Dirichlet "
                                                r"face 0 \(x=-1\)"):
         d.rhs_dirichlet(g)
-    d = _product(mgamd, "quadrant", 3, 2, bo.M1, 0.0)
+    d = _product(mgamd, "quadrant", 3, 2, po.M1, 0.0)
     with pytest.raises(mgamd.MgamdError, match=r"Dirichlet value 2.0\d* on face 3 \(y=\+1\) refused: the face is natural"):
         d.dirichlet_face_values({0: 1.0, 3: 2.0})
     with pytest.raises(mgamd.MgamdError, match=r"face 0 \(x=-1\) is not finite"):
@@ -256,13 +244,13 @@ def test_refusals_by_message(mgamd):
 def test_increment_form_of_the_oracle_stepper_is_the_direct_step(oracle):
     """dirichlet_data_oracle.theta_step_data (the increment, as the product solves it) against theta_step_direct (u_new itself, every
     term on full vectors), with a source, time-dependent values and a flux load"""
-    p, theta, dt, mask = 2, 0.5, 0.05, bo.M1
-    lv = bo.remask(oracle, _base_level(oracle, "quadrant", 2, p), mask, tso.mass_coefficient(theta, dt))
+    p, theta, dt, mask = 2, 0.5, 0.05, po.M1
+    lv = su.oracle_level(None, "quadrant", 2, p, Problem(tso.mass_coefficient(theta, dt), dirichlet_faces=mask))
     rng = np.random.default_rng(9)
     u = rng.standard_normal(lv.n)
     u[lv.constrained] = 0.0
     f0, f1, g0, g1 = (rng.standard_normal(lv.n) for _ in range(4))
-    load = bo.flux_load(lv, [0.0, 1.5, 0.0, 0.0, 0.0, 0.0])
+    load = po.flux_load(lv, [0.0, 1.5, 0.0, 0.0, 0.0, 0.0])
     a, _ = do.theta_step_data(lv, u, f0, f1, g0, g1, load, theta, dt, tso.exact_solver(lv))
     b = do.theta_step_direct(lv, u, f0, f1, g0, g1, load, theta, dt)
     assert rel_err(a, b) <= 1e-12

@@ -1,18 +1,18 @@
 """Per-face boundary conditions on the GPU: the kernels are the ones that ran before, the tables are new.  With natural (Neumann)
 faces the boundary shell gathers and atomic scatters of every kernel family, the coarse boundary DoFs of the fused transfers, the
 D^-1 byte codes of many more tail rows and levels without any constrained DoF carry live rows for the first time.  Everything is
-held against the test-side numpy oracle tests/boundary_oracle.py (mgoracle levels re-masked by face; oracle/ is not edited).
+held against the numpy oracle oracle/physics_oracle.py (Dirichlet DoFs chosen by face).
 
-Masks (boundary_oracle): M1 only x = -1 is Dirichlet (on quadrant the refined corner touches it: hanging nodes on both kinds of
+Masks (physics_oracle): M1 only x = -1 is Dirichlet (on quadrant the refined corner touches it: hanging nodes on both kinds of
 face), M2 the three "+" faces (hanging nodes on Neumann faces, a Neumann-Neumann edge and corner in the refined region), M0 none,
 with sigma = 7.5.  Bounds are the project's own: operator <= 1e-13, Chebyshev <= 1e-12, V-cycle <= 1e-11, CG iterates <= 1e-10 with
 equal iteration counts, FP32 single kernels <= 2e-6, FP32 V-cycle <= 16 e_ref with e_ref from oracle/f32_emulation.py run on the
-re-masked levels.  Shapes are test_gpu_helmholtz.OP_CASES.
+levels of the mask.  Shapes are support.OP_CASES.
 
-The numpy hierarchies are built once per (mesh, degree, type): one constraint search per level at sigma = 0 in the oracle's own
-numbering, the transfers once under mask 0; a case permutes them into the numbering of the product's tables (which changes with
-the mask: tail and Dirichlet DoFs are numbered apart), re-masks and shifts (boundary_oracle.remask, mask_transfers, held against
-levels built directly by test_boundary_host.py)."""
+The numpy hierarchies come from support.py: one constraint search per (mesh, degree) in the oracle's own numbering, the transfers
+once under mask 0; a case permutes them into the numbering of the product's tables (which changes with the mask: tail and
+Dirichlet DoFs are numbered apart) and forms the levels of its problem (physics_oracle.Level, mask_transfers, held against
+spaces built directly by test_boundary_host.py)."""
 import json
 import os
 import re
@@ -22,98 +22,33 @@ import threading
 import numpy as np
 import pytest
 
-import boundary_oracle as bo
-import coefficient_oracle as co
-import helmholtz_oracle as ho
+import physics_oracle as po
 import random_mesh_physics as rp
-import test_gpu_helmholtz as th
+import support as su
 import time_stepping_oracle as ts
 from conftest import ROOT, rel_err
+from physics_oracle import M0, M1, M2, Problem
+from support import GOLDEN, OP_CASES, TOL_CHEB, TOL_CYCLE, TOL_F32, TOL_OP, TOL_SOL, check_transfers, emu, final_table, run_harness, vcycle_and_solve  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-M1, M2, M0 = bo.M1, bo.M2, bo.M0
 MASKS = [(M1, 0.0), (M2, 0.0), (M0, 7.5)]
-TOL_OP, TOL_CHEB, TOL_CYCLE, TOL_SOL, TOL_F32 = 1e-13, 1e-12, 1e-11, 1e-10, 2e-6
-
-_lv = {}    # (geo, L, number of cells, p) -> level at sigma = 0, all Dirichlet, own numbering
-_hier = {}  # (geo, L, p, mg_type) -> (levels, transfers under mask 0)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
-
-
-def base_level(oracle, geo, L, p, mesh=None):
-    mesh = oracle.create_mesh(geo, L) if mesh is None else mesh
-    tag = (geo, L, len(mesh), p)
-    if tag not in _lv:
-        _lv[tag] = ho.level_class(oracle, 0.0)(mesh, p)
-    return _lv[tag]
-
-
-def oracle_level(oracle, geo, L, p, mask, sigma, d):
-    return bo.remask(oracle, ho.renumber(base_level(oracle, geo, L, p), d.keys()), mask, sigma)
-
-
-def oracle_hierarchy(oracle, case, mask, sigma, dofs):
-    """(levels, P) under the mask in the numbering of the product's level DoFs"""
-    if case not in _hier:
-        geo, L, p, mg_type = case
-        meshes, degs = ho.level_plan(oracle, geo, L, p, mg_type)
-        levels = [base_level(oracle, geo, L, q, m) for m, q in zip(meshes, degs)]
-        _hier[case] = (levels, bo.natural_transfers(oracle, levels))
-    levels, P0 = ho.renumber_hierarchy(*_hier[case], [d.keys() for d in dofs])
-    levels = [bo.remask(oracle, lv, mask, sigma) for lv in levels]
-    return levels, bo.mask_transfers(P0, levels)
-
-
-def hierarchy(mgamd, ctx, case, mask, sigma=0.0, coarse_solver="amg", **kw):
-    geo, L, p, mg_type = case
-    h = mgamd.Hierarchy(ctx, geo, L, p, mg_type, coarse_solver=coarse_solver, max_brick=0, mass_coefficient=sigma, dirichlet_faces=mask, **kw)
-    assert all(d.dirichlet_faces() == mask for d in h.dofs) and all(t.dirichlet_faces() == mask for t in h.trias)
-    return h
-
-
-def tria(mgamd, geo, L, mask):
-    t = mgamd.Triangulation(geo, L)
-    t.set_dirichlet_faces(mask)
-    return t
-
-
-def check_transfers(h, levels, P, tag):
-    rng = np.random.default_rng(6)
-    for l in range(1, len(levels)):
-        xc, xf0 = rng.standard_normal(levels[l - 1].n), rng.standard_normal(levels[l].n)
-        vc, vf = h.operators[l - 1].initialize_dof_vector().from_host(xc), h.operators[l].initialize_dof_vector().from_host(xf0)
-        h.transfers[l].prolongate_and_add(vf, vc)
-        e1 = rel_err(vf.to_host(), xf0 + P[l] @ xc)
-        rf, dc0 = rng.standard_normal(levels[l].n), rng.standard_normal(levels[l - 1].n)
-        vr, vd = h.operators[l].initialize_dof_vector().from_host(rf), h.operators[l - 1].initialize_dof_vector().from_host(dc0)
-        h.transfers[l].restrict_and_add(vd, vr)
-        e2 = rel_err(vd.to_host(), dc0 + P[l].T @ rf)
-        print(f"{tag} transfer {l - 1} <-> {l}: prolongate {e1:.2e} restrict {e2:.2e}")
-        assert e1 < TOL_OP and e2 < TOL_OP
-
 
 # ------------------------------------------------------------------ operator, mass operator, inverse diagonal
-@pytest.mark.parametrize("geo,L,p,max_brick", th.OP_CASES)
+@pytest.mark.parametrize("geo,L,p,max_brick", OP_CASES)
 def test_vmult_mass_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_brick):
     rng = np.random.default_rng(3)
     for mask, sigma in MASKS:
-        d = mgamd.DoFs(tria(mgamd, geo, L, mask), p, max_brick)
+        d = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(dirichlet_faces=mask)), p, max_brick)
         d.set_mass_coefficient(sigma)
         op = mgamd.Operator(ctx, d)
-        lv = oracle_level(oracle, geo, L, p, mask, sigma, d)
+        lv = su.oracle_level(d, geo, L, p, Problem(sigma, dirichlet_faces=mask))
         assert d.info.n_dirichlet == int((lv.dirichlet & ~lv.hanging).sum())
         Mh, c = ts.mass_matrix(lv), lv.constrained
         for trial in range(2):  # twice: a dirty tail accumulator shows in the second pass
             x = rng.standard_normal(lv.n)
-            ev = rel_err(th.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
-            y = th.apply_nan(mgamd, ctx, op.vmult_mass, x)
+            ev = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
+            y = su.apply_nan(mgamd, ctx, op.vmult_mass, x)
             em = rel_err(y, Mh @ x)
             diag = op.initialize_dof_vector().from_host(np.full(lv.n, np.nan))
             op.compute_inverse_diagonal(diag)
@@ -131,50 +66,29 @@ def test_vmult_mass_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_bric
 
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 4), ("hypercube", 3, 2), ("quadrant", 4, 1)])
 def test_default_mask_set_explicitly_is_bitwise_the_unset_mesh(mgamd, ctx, geo, L, p):
-    d0, d1 = mgamd.DoFs(mgamd.Triangulation(geo, L), p, 0), mgamd.DoFs(tria(mgamd, geo, L, 0x3F), p, 0)
+    d0, d1 = mgamd.DoFs(mgamd.Triangulation(geo, L), p, 0), mgamd.DoFs(su.tria(mgamd, geo, L, Problem(dirichlet_faces=0x3F)), p, 0)
     assert np.array_equal(d0.keys(), d1.keys()) and np.array_equal(d0.cell_dofs(), d1.cell_dofs())
     x = np.random.default_rng(13).standard_normal(d0.n_dofs)
-    a, b = (th.apply_nan(mgamd, ctx, mgamd.Operator(ctx, d).vmult, x) for d in (d0, d1))
-    det = th.atomic_contributions(d0) <= 2  # (sums of three or more atomic adds do not repeat their bits: test_gpu_helmholtz)
+    a, b = (su.apply_nan(mgamd, ctx, mgamd.Operator(ctx, d).vmult, x) for d in (d0, d1))
+    det = su.atomic_contributions(d0) <= 2  # (sums of three or more atomic adds do not repeat their bits: test_gpu_helmholtz)
     assert det.sum() > 0.8 * d0.n_dofs and np.array_equal(a[det], b[det]) and rel_err(a, b) < 1e-14
 
 
 # ------------------------------------------------------------------ V-cycle and CG
-def vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, tag, coarse="direct"):
-    mg = oracle.Multigrid(levels, P, 3, coarse=coarse)
-    evs = [s.eigenvalue_estimates()[1] for s in h.smoothers]
-    for l, ev in enumerate(evs):
-        assert ev == pytest.approx(mg.sm[l].max_ev, rel=1e-9)
-    mg = emu.with_max_evs(mg, evs)
-    Lf = levels[-1]
-    r = np.random.default_rng(7).standard_normal(Lf.n)
-    ez = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
-    xref, itref, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
-    b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
-    h.fine_operator.rhs(b)
-    eb = np.abs(b.to_host() - Lf.rhs_constant).max() / np.abs(Lf.rhs_constant).max()
-    it, _ = mgamd.solve_cg(h.fine_operator, h.mg, x, b, 1e-4)
-    ex = rel_err(x.to_host(), xref)
-    print(f"{tag}: V-cycle {ez:.2e}, rhs {eb:.2e}, CG iterations {it} (oracle {itref}), iterate {ex:.2e}")
-    assert ez < TOL_CYCLE and eb < 1e-12
-    assert it == itref and ex < TOL_SOL
-    return mg
-
-
 @pytest.mark.parametrize("case", [("hypercube", 3, 2, "HMG-global"), ("hypercube", 4, 1, "HMG-global")], ids=lambda c: "-".join(map(str, c)))
 def test_levels_without_a_constrained_row(mgamd, oracle, emu, ctx, case):
     """hypercube under M0: no Dirichlet and no hanging DoF on any level, level 0 is one cell whose DoFs are all free"""
-    h = hierarchy(mgamd, ctx, case, M0, 7.5)
+    h = su.hierarchy(mgamd, ctx, case, Problem(7.5, dirichlet_faces=M0), max_brick=0)
     assert all(d.info.n_dirichlet == 0 and d.info.n_hanging == 0 for d in h.dofs)
     assert h.dofs[0].info.n_cells == 1 and h.dofs[0].n_dofs == (case[2] + 1) ** 3
-    levels, P = oracle_hierarchy(oracle, case, M0, 7.5, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(7.5, dirichlet_faces=M0))
     rng = np.random.default_rng(5)
     for l, (op, lv) in enumerate(zip(h.operators, levels)):
         x = rng.standard_normal(lv.n)
-        assert rel_err(th.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x) < TOL_OP
+        assert rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x) < TOL_OP
         ch, ref = mgamd.PreconditionChebyshev(op, 3, 20.0, 20), oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
         assert ch.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev, rel=1e-10)
-        assert rel_err(th.apply_nan(mgamd, ctx, ch.vmult, x), ref.vmult(x)) < TOL_CHEB
+        assert rel_err(su.apply_nan(mgamd, ctx, ch.vmult, x), ref.vmult(x)) < TOL_CHEB
     check_transfers(h, levels, P, f"{case} M0")
     vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} M0 sigma=7.5")
 
@@ -183,14 +97,14 @@ def test_dinv_byte_codes_of_natural_boundary_rows(mgamd, oracle, emu, ctx, monke
     """hypercube L=5 p=1 under M2: 5768 tail rows (all-Dirichlet: 2791), above the 4096 from which tail_kernel reads D^-1 through
     one-byte codes; against the oracle and against the vector read (MGAMD_NO_DINV_CODES)"""
     case = ("hypercube", 5, 1, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, M2)
+    h = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0)
     i = h.dofs[-1].info
     assert i.n_tail > 4096 and i.n_dofs - i.n_interior >= 4096
     assert i.n_tail > mgamd.DoFs(mgamd.Triangulation("hypercube", 5), 1, 0).info.n_tail
     monkeypatch.setenv("MGAMD_NO_DINV_CODES", "1")
-    h0 = hierarchy(mgamd, ctx, case, M2)
+    h0 = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0)
     monkeypatch.delenv("MGAMD_NO_DINV_CODES")
-    levels, P = oracle_hierarchy(oracle, case, M2, 0.0, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, dirichlet_faces=M2))
     lv, rng = levels[-1], np.random.default_rng(9)
     b, x0 = rng.standard_normal(lv.n), rng.standard_normal(lv.n)
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
@@ -198,10 +112,10 @@ def test_dinv_byte_codes_of_natural_boundary_rows(mgamd, oracle, emu, ctx, monke
     for hh in (h, h0):
         op = hh.operators[-1]
         ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
-        v = th.apply_nan(mgamd, ctx, ch.vmult, b)
+        v = su.apply_nan(mgamd, ctx, ch.vmult, b)
         vx, vb = op.initialize_dof_vector().from_host(x0), op.initialize_dof_vector().from_host(b)
         ch.step(vx, vb)
-        z = th.apply_nan(mgamd, ctx, hh.mg.vmult, b)
+        z = su.apply_nan(mgamd, ctx, hh.mg.vmult, b)
         assert rel_err(v, ref.vmult(b)) < TOL_CHEB and rel_err(vx.to_host(), ref.step(x0, b)) < TOL_CHEB
         outs.append((v, vx.to_host(), z))
     for a, c in zip(*outs):
@@ -212,15 +126,15 @@ def test_dinv_byte_codes_of_natural_boundary_rows(mgamd, oracle, emu, ctx, monke
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 4), ("hypercube", 3, 2), ("quadrant", 3, 1)])
 @pytest.mark.parametrize("mask", [M1, M2])
 def test_chebyshev(mgamd, oracle, ctx, geo, L, p, mask):
-    d = mgamd.DoFs(tria(mgamd, geo, L, mask), p, 0)
+    d = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(dirichlet_faces=mask)), p, 0)
     op = mgamd.Operator(ctx, d)
-    lv = oracle_level(oracle, geo, L, p, mask, 0.0, d)
+    lv = su.oracle_level(d, geo, L, p, Problem(0.0, dirichlet_faces=mask))
     ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
     assert ch.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev, rel=1e-10)
     rng = np.random.default_rng(5)
     b, x0 = rng.standard_normal(lv.n), rng.standard_normal(lv.n)
-    ev = rel_err(th.apply_nan(mgamd, ctx, ch.vmult, b), ref.vmult(b))
+    ev = rel_err(su.apply_nan(mgamd, ctx, ch.vmult, b), ref.vmult(b))
     vb, vx = op.initialize_dof_vector().from_host(b), op.initialize_dof_vector().from_host(x0)
     ch.step(vx, vb)
     es = rel_err(vx.to_host(), ref.step(x0, b))
@@ -238,13 +152,13 @@ TRANSFER_CASES = [(("quadrant", 3, 4, "HMG-global"), M1, 0.0), (("quadrant", 3, 
 def test_transfers_vcycle_and_cg(mgamd, oracle, emu, ctx, case, mask, sigma, monkeypatch):
     """restriction and prolongation against the oracle's P^T and P, then the V-cycle and CG; with the default path (fused into the
     operator passes where the level has 17-point bricks: the coarse boundary DoFs are live there) and with separate transfer kernels"""
-    h = hierarchy(mgamd, ctx, case, mask, sigma)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, dirichlet_faces=mask), max_brick=0)
     monkeypatch.setenv("MGAMD_NO_FUSED_TRANSFER", "1")
-    h0 = hierarchy(mgamd, ctx, case, mask, sigma)
+    h0 = su.hierarchy(mgamd, ctx, case, Problem(sigma, dirichlet_faces=mask), max_brick=0)
     monkeypatch.delenv("MGAMD_NO_FUSED_TRANSFER")
     n_fused = sum(t.n_fused_bricks() for t in h.transfers[1:])
     assert (n_fused > 0) == (case in FUSED) and sum(t.n_fused_bricks() for t in h0.transfers[1:]) == 0
-    levels, P = oracle_hierarchy(oracle, case, mask, sigma, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, dirichlet_faces=mask))
     for hh, tag in ((h, f"{n_fused} fused bricks"), (h0, "separate transfers")):
         check_transfers(hh, levels, P, f"{case} mask={mask:#04x} {tag}")
         vcycle_and_solve(mgamd, oracle, emu, ctx, hh, levels, P, f"{case} mask={mask:#04x} sigma={sigma} {tag}")
@@ -253,13 +167,13 @@ def test_transfers_vcycle_and_cg(mgamd, oracle, emu, ctx, case, mask, sigma, mon
 def test_graph_replay_and_kernel_by_kernel(mgamd, oracle, emu, ctx, monkeypatch):
     """hypercube L=4 p=2 under M2: the captured cycle replayed, and the coarse levels kernel by kernel instead of collapsed"""
     case = ("hypercube", 4, 2, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, M2)
+    h = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0)
     monkeypatch.setenv("MGAMD_COLLAPSE_MAX_DOFS", "0")
-    hb = hierarchy(mgamd, ctx, case, M2)
+    hb = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0)
     monkeypatch.delenv("MGAMD_COLLAPSE_MAX_DOFS")
     assert h.mg.set_collapse(True) > 0 and hb.mg.set_collapse(True) == 0
-    levels, P = oracle_hierarchy(oracle, case, M2, 0.0, h.dofs)
-    mg = vcycle_and_solve(mgamd, oracle, emu, ctx, hb, levels, P, f"{case} M2 kernel by kernel")
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, dirichlet_faces=M2))
+    mg, _, _ = vcycle_and_solve(mgamd, oracle, emu, ctx, hb, levels, P, f"{case} M2 kernel by kernel")
     r = np.random.default_rng(12).standard_normal(levels[-1].n)
     vr, vz = h.fine_operator.initialize_dof_vector().from_host(r), h.fine_operator.initialize_dof_vector().from_host(np.full(len(r), np.nan))
     h.mg.time_vcycles(vz, vr, 2, True)
@@ -273,16 +187,16 @@ def test_graph_replay_and_kernel_by_kernel(mgamd, oracle, emu, ctx, monkeypatch)
 def test_coarse_solvers(mgamd, oracle, emu, ctx, coarse):
     """PMG on quadrant L=3: the p = 1 level is the coarse problem, with hanging nodes and natural faces"""
     case = ("quadrant", 3, 4, "PMG")
-    h = hierarchy(mgamd, ctx, case, M2, coarse_solver=coarse)
+    h = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0, coarse_solver=coarse)
     assert h.mg.coarse_solver_used() == coarse
-    levels, P = oracle_hierarchy(oracle, case, M2, 0.0, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, dirichlet_faces=M2))
     if coarse == "direct":
         vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} M2 {coarse}")
         return
     mg = emu.with_max_evs(oracle.Multigrid(levels, P, 3, coarse=coarse), [s.eigenvalue_estimates()[1] for s in h.smoothers])
     Lf = levels[-1]
     r = np.random.default_rng(7).standard_normal(Lf.n)
-    ez = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
+    ez = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
     xref, itref, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
@@ -298,14 +212,14 @@ def test_pmg_with_amg_coarse_solver(mgamd, oracle, ctx):
     import amg_oracle as ao
 
     case = ("annulus", 6, 2, "PMG")
-    h = hierarchy(mgamd, ctx, case, M2, coarse_n_cycles=2)
+    h = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0, coarse_n_cycles=2)
     assert h.mg.coarse_solver_used() == "amg"
-    levels, P = oracle_hierarchy(oracle, case, M2, 0.0, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, dirichlet_faces=M2))
     A0 = ao.csr(*h.dofs[0].matrix())
     assert abs(A0 - levels[0].A).max() <= 1e-13 * abs(levels[0].A).max()
     mg = oracle.Multigrid(levels, P, 3, coarse=ao.SmoothedAggregation(h.dofs[0].matrix()).precondition(2))
     r = np.random.default_rng(2).standard_normal(h.n_dofs)
-    err = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
+    err = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
     Lf = levels[-1]
     xref, itref, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
@@ -323,9 +237,9 @@ def test_solve_with_amg_follows_the_mesh(mgamd, oracle, ctx):
     h = mgamd.Hierarchy(ctx, geo, L, p, "AMG", dirichlet_faces=M1)
     d = h.dofs[0]
     assert d.dirichlet_faces() == M1
-    lv = oracle_level(oracle, geo, L, p, M1, 0.0, d)
+    lv = su.oracle_level(d, geo, L, p, Problem(0.0, dirichlet_faces=M1))
     x = np.random.default_rng(4).standard_normal(lv.n)
-    assert rel_err(th.apply_nan(mgamd, ctx, h.system_matrix.vmult, x), lv.A @ x) < TOL_OP
+    assert rel_err(su.apply_nan(mgamd, ctx, h.system_matrix.vmult, x), lv.A @ x) < TOL_OP
     xref, itref, _ = oracle.pcg(lv.A, lv.rhs_constant, ao.SmoothedAggregation(d.matrix()).precondition(1), 1e-4)
     b, xv = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
@@ -337,8 +251,8 @@ def test_solve_with_amg_follows_the_mesh(mgamd, oracle, ctx):
 # ------------------------------------------------------------------ FP32 levels
 def test_float_levels(mgamd, oracle, emu, ctx):
     case = ("quadrant", 3, 4, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, M2, number_type=mgamd.F32)
-    levels, P = oracle_hierarchy(oracle, case, M2, 0.0, h.dofs)
+    h = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=M2), max_brick=0, number_type=mgamd.F32)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, dirichlet_faces=M2))
     rng = np.random.default_rng(21)
     for l, op in enumerate(h.operators):
         lv = levels[l]
@@ -356,7 +270,7 @@ def test_float_levels(mgamd, oracle, emu, ctx):
     r = rng.standard_normal(Lf.n)
     ref = mgp.vcycle(r)
     e_ref = rel_err(emu.vcycle(mgp, r, np.float32).astype(np.float64), ref)
-    err = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), ref)
+    err = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), ref)
     print(f"FP32 V-cycle M2: rel.err {err:.2e}, e_ref {e_ref:.2e}, ratio {err / e_ref:.2f}")
     assert err <= 16 * e_ref
     xref, it64, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
@@ -376,12 +290,7 @@ def test_two_simulated_ranks(mgamd, oracle, case, monkeypatch):
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # the sharded path's start vector hashes the DoF key; the oracle takes the same
     n_ranks, mg_type = 2, case[3]
     ocase = case[:3] + ("HPMG" if mg_type == "PMG" else mg_type,)
-    if ocase not in _hier:
-        meshes, degs = ho.level_plan(oracle, *ocase)
-        base = [base_level(oracle, case[0], case[1], q, m) for m, q in zip(meshes, degs)]
-        _hier[ocase] = (base, bo.natural_transfers(oracle, base))
-    levels = [bo.remask(oracle, lv, M1) for lv in _hier[ocase][0]]
-    P = bo.mask_transfers(_hier[ocase][1], levels)
+    levels, P = su.oracle_hierarchy(None, ocase, Problem(dirichlet_faces=M1))
     omg = oracle.Multigrid(levels, P, 3, coarse="direct", start_vectors=[oracle.key_hash_start_vector(lv) for lv in levels])
     Lf = levels[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(Lf.keys)}
@@ -390,7 +299,7 @@ def test_two_simulated_ranks(mgamd, oracle, case, monkeypatch):
     zref = omg.vcycle(r)
     xref, itref, _ = oracle.pcg(Lf.A, Lf.rhs_constant, omg.vcycle, 1e-4)
     q = np.array([0.0, 1.5, -2.0, 0.5, 3.0, 1.0])
-    qref = bo.flux_load(Lf, q)
+    qref = po.flux_load(Lf, q)
     group = mgamd.SimGroup(n_ranks)
     out, errs = [None] * n_ranks, [None] * n_ranks
 
@@ -438,20 +347,15 @@ def test_random_octree(mgamd, oracle, emu, ctx):
     """mesh M of random_mesh_physics at p = 2 with M2, sigma = 7.5 and the per_family coefficient: operator, mass operator, inverse
     diagonal, V-cycle and CG"""
     name, p, mg_type, field, sigma = "M", 2, "HMG-global", "per_family", 7.5
-    t = rp.tria_of(mgamd, rp.leaves_of(oracle, name), field)
+    t = su.tria_of(mgamd, rp.leaves_of(oracle, name), Problem(coefficient=field))
     h = mgamd.Hierarchy(ctx, t, 0, p, mg_type, coarse_solver="amg", max_brick=0, mass_coefficient=sigma, dirichlet_faces=M2)
     assert t.dirichlet_faces() == M2 and h.dofs[-1].info.n_hanging > 0
-    base, P, meshes = rp.base_hierarchy(oracle, name, p, mg_type)
-    P0 = _hier.setdefault(("random", name, p, mg_type), (base, bo.natural_transfers(oracle, base)))[1]
-    levels, P0 = ho.renumber_hierarchy(base, P0, [d.keys() for d in h.dofs])
-    coeffs = rp.level_coefficients(oracle, name, field, meshes)
-    levels = [bo.remask(oracle, co.with_coefficient(lv, c, sigma), M2) for lv, c in zip(levels, coeffs)]
-    P = bo.mask_transfers(P0, levels)
+    levels, P = su.oracle_hierarchy_on(h.dofs, *rp.level_plan(oracle, name, p, mg_type), Problem(sigma, field, M2))
     lv, op = levels[-1], h.fine_operator
     x = np.random.default_rng(3).standard_normal(lv.n)
     diag = op.initialize_dof_vector().from_host(np.full(lv.n, np.nan))
     op.compute_inverse_diagonal(diag)
-    ev, em = rel_err(th.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x), rel_err(th.apply_nan(mgamd, ctx, op.vmult_mass, x), ts.mass_matrix(lv) @ x)
+    ev, em = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x), rel_err(su.apply_nan(mgamd, ctx, op.vmult_mass, x), ts.mass_matrix(lv) @ x)
     ed = rel_err(diag.to_host(), lv.inv_diag)
     print(f"random octree {name} p={p} {field} M2 sigma={sigma}: vmult {ev:.2e} vmult_mass {em:.2e} inverse diagonal {ed:.2e}")
     assert ev < TOL_OP and em < TOL_OP and ed < TOL_OP
@@ -459,10 +363,6 @@ def test_random_octree(mgamd, oracle, emu, ctx):
 
 
 # ------------------------------------------------------------------ known answer
-def _layers(x, planes, values):
-    return np.asarray(values)[np.sum(np.asarray(x)[..., None] > np.asarray(planes), axis=-1)]
-
-
 def _exact(x, planes, values, q, dirichlet_face):
     edges = np.concatenate(([-1.0], planes, [1.0]))
     out = np.zeros_like(x)
@@ -482,14 +382,14 @@ def test_layered_wall_known_answer(mgamd, oracle, ctx, geo, L, p, planes, values
     q = 3.0
     t = mgamd.Triangulation(geo, L)
     h = mgamd.Hierarchy(ctx, t, 0, p, "HMG-global", coarse_solver="amg", max_brick=0, dirichlet_faces=1 << dirichlet_face,
-                        coefficient=lambda x, y, z: _layers(x, planes, values))
+                        coefficient=lambda x, y, z: su.layers(x, planes, values))
     op = h.fine_operator
     b, u = op.initialize_dof_vector(), op.initialize_dof_vector()
     op.rhs_boundary_flux(b, {1 - dirichlet_face: q})
     assert np.abs(b.to_host() - h.dofs[-1].rhs_boundary_flux({1 - dirichlet_face: q})).max() == 0.0
     it, _ = mgamd.solve_cg(op, h.mg, u, b, 1e-12)
     op.distribute(u)
-    x = ho.renumber(base_level(oracle, geo, L, p), h.dofs[-1].keys()).node_positions()[:, 0]
+    x = su.oracle_level(h.dofs[-1], geo, L, p).node_positions()[:, 0]
     ref = _exact(x, planes, values, q, dirichlet_face)
     err = np.abs(u.to_host() - ref).max() / np.abs(ref).max()
     print(f"{geo} {L} p={p} layers {values}, Dirichlet face {dirichlet_face}: CG iterations {it}, relative nodal error {err:.2e}")
@@ -517,8 +417,8 @@ def test_insulated_box_conserves_heat(mgamd, oracle, emu, ctx):
     drifts by no more than ten times the oracle stepper's own drift at the same tolerances"""
     case, theta, dt, n_steps, reltol = ("quadrant", 3, 2, "HMG-global"), 0.5, 0.02, 5, 1e-6
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
-    h = hierarchy(mgamd, ctx, case, M0, sigma)
-    levels, P = oracle_hierarchy(oracle, case, M0, sigma, h.dofs)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, dirichlet_faces=M0), max_brick=0)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, dirichlet_faces=M0))
     lv, op = levels[-1], h.fine_operator
     Mh = ts.mass_matrix(lv)
     u0 = np.random.default_rng(17).standard_normal(lv.n)
@@ -547,18 +447,18 @@ def test_insulated_box_conserves_heat(mgamd, oracle, emu, ctx):
 def test_the_singular_operator_is_refused_by_every_solver(mgamd, ctx):
     """mask 0 with sigma = 0: operators, mass products, inverse diagonals and Chebyshev stay available; what solves refuses"""
     singular = "singular: dirichlet_faces mask 0.*sigma = 0"
-    t = tria(mgamd, "quadrant", 3, M0)
+    t = su.tria(mgamd, "quadrant", 3, Problem(dirichlet_faces=M0))
     d = mgamd.DoFs(t, 2, 0)
     op = mgamd.Operator(ctx, d)
     x = np.random.default_rng(1).standard_normal(d.n_dofs)
     free = np.arange(d.n_dofs) < d.info.n_interior + d.info.n_tail
-    y = th.apply_nan(mgamd, ctx, op.vmult, np.where(free, 1.0, 0.0))
+    y = su.apply_nan(mgamd, ctx, op.vmult, np.where(free, 1.0, 0.0))
     assert np.abs(y[free]).max() <= 1e-12  # the constants are in the kernel
-    assert np.isfinite(th.apply_nan(mgamd, ctx, op.vmult_mass, x)).all()
+    assert np.isfinite(su.apply_nan(mgamd, ctx, op.vmult_mass, x)).all()
     diag = op.initialize_dof_vector()
     op.compute_inverse_diagonal(diag)
     ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
-    assert np.isfinite(th.apply_nan(mgamd, ctx, ch.vmult, x)).all()
+    assert np.isfinite(su.apply_nan(mgamd, ctx, ch.vmult, x)).all()
     for mg_type in ("HMG-global", "PMG", "HPMG", "AMG"):
         with pytest.raises(mgamd.MgamdError, match=singular):
             mgamd.Hierarchy(ctx, "quadrant", 3, 2, mg_type, dirichlet_faces=M0)
@@ -584,9 +484,9 @@ def test_local_smoothing_and_flux_refusals(mgamd, ctx):
         with pytest.raises(mgamd.MgamdError, match=f"Type '{mg_type}' with the dirichlet_faces mask 1.*local smoothing"):
             mgamd.Hierarchy(ctx, "quadrant", 3, 2, mg_type, dirichlet_faces=M1)
         with pytest.raises(mgamd.MgamdError, match="local smoothing"):
-            mgamd.Hierarchy(ctx, tria(mgamd, "quadrant", 3, M1), 3, 2, mg_type)
+            mgamd.Hierarchy(ctx, su.tria(mgamd, "quadrant", 3, Problem(dirichlet_faces=M1)), 3, 2, mg_type)
         assert mgamd.Hierarchy(ctx, "quadrant", 3, 2, mg_type, dirichlet_faces=0x3F).n_dofs > 0
-    op = mgamd.Operator(ctx, mgamd.DoFs(tria(mgamd, "quadrant", 3, M2), 2, 0))
+    op = mgamd.Operator(ctx, mgamd.DoFs(su.tria(mgamd, "quadrant", 3, Problem(dirichlet_faces=M2)), 2, 0))
     b = op.initialize_dof_vector()
     with pytest.raises(mgamd.MgamdError, match=r"face 3 \(y=\+1\) refused: the face is Dirichlet"):
         op.rhs_boundary_flux(b, {0: 1.0, 3: 2.0})
@@ -599,8 +499,6 @@ def test_harness_neumann_faces(mgamd, oracle, ctx, tmp_path):
     """input_0003.json (quadrant, NRefGlobal 3, p = 4, HMG-global) with "NeumannFaces": "135" (mask 0b010101) and MassCoefficient 0:
     the CG count of the Python solve and of the oracle, the value echoed; a local-smoothing Type and the singular combination:
     "not implemented", exit code 1"""
-    from test_harness_gpu import GOLDEN, final_table, run_harness
-
     base = json.load(open(os.path.join(GOLDEN, "input_0003.json")))
     case = (base["GeometryType"], int(base["NRefGlobal"]), int(base["Degree"]), base["Type"])
     assert case == ("quadrant", 3, 4, "HMG-global")
@@ -612,11 +510,11 @@ def test_harness_neumann_faces(mgamd, oracle, ctx, tmp_path):
     assert f"NeumannFaces: 135 (dirichlet_faces mask {mask})" in out and "MassCoefficient" not in out
     _, rows = final_table(out)
     number_type = mgamd.F32 if base.get("MGNumberType", "float") == "float" else mgamd.F64
-    h = hierarchy(mgamd, ctx, case, mask, number_type=number_type)
+    h = su.hierarchy(mgamd, ctx, case, Problem(dirichlet_faces=mask), max_brick=0, number_type=number_type)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
     it, _ = mgamd.solve_cg(h.fine_operator, h.mg, x, b, float(base.get("RelativeTolerance", 1e-4)))
-    levels, P = oracle_hierarchy(oracle, case, mask, 0.0, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, dirichlet_faces=mask))
     itref = oracle.pcg(levels[-1].A, levels[-1].rhs_constant, oracle.Multigrid(levels, P, 3, coarse="direct").vcycle, 1e-4)[1]
     print(f"harness NeumannFaces 135: n_iterations {rows[0]['n_iterations']}, Python solve {it}, oracle {itref}")
     assert int(rows[0]["n_iterations"]) == it == itref

@@ -1,88 +1,31 @@
 """The piecewise-constant diffusion coefficient on the GPU: operators, smoothers, multigrid, CG, AMG and the time stepper for
-A = K_a + sigma M (-div(a grad u) + sigma u, a constant on every leaf) against the test-side numpy oracle
-tests/coefficient_oracle.py (helmholtz_oracle's level with sum a_c h_c Kc in place of the stiffness matrix; oracle/ is not edited).
+A = K_a + sigma M (-div(a grad u) + sigma u, a constant on every leaf) against the numpy oracle oracle/physics_oracle.py (sum
+a_c h_c Kc in place of the stiffness matrix).
 
-Fields (coefficient_oracle.FIELDS): uniform 3.5 (the slot structure of the mesh without a coefficient: every kernel family with
+Fields (physics_oracle.FIELDS): uniform 3.5 (the slot structure of the mesh without a coefficient: every kernel family with
 a != 1), octants (1 + 0.75 octant index: jumps on the planes through 0, bricks survive inside the octants), inclusion (1000 in
 [-0.5, 0]^3: high contrast), per_cell (no two neighbours agree: single-cell slots only, hundreds of distinct diagonals).
 sigma in {0, 7.5}: the Laplace kernels, which only see the scale a h, and the kernels of the mass term, which also need h^2 / a.
 
 Bounds are those of test_gpu_helmholtz.py: operator <= 1e-13, Chebyshev <= 1e-12, V-cycle <= 1e-11, CG iterates <= 1e-10 with equal
 iteration counts, FP32 single kernels <= 2e-6, FP32 V-cycle <= 16 e_ref with e_ref from oracle/f32_emulation.py on the test's own
-levels plus the 5e-5 cap.  Every numpy hierarchy is built once per session at sigma = 0 and re-shifted for 7.5.  The coarse
+levels plus the 5e-5 cap.  Every constraint search is made once per session (support.py).  The coarse
 coefficients of every hierarchy are checked against the oracle's own restatement before they are used."""
 import threading
 
 import numpy as np
 import pytest
 
-import coefficient_oracle as co
-import helmholtz_oracle as ho
-import test_gpu_helmholtz as th
+import physics_oracle as po
+import support as su
 import time_stepping_oracle as ts
 from conftest import rel_err
+from physics_oracle import Problem
+from support import OP_CASES, TOL_CHEB, TOL_CYCLE, TOL_F32, TOL_OP, TOL_SOL, apply_nan, assert_level_coefficients, emu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SIGMAS = [0.0, 7.5]
-TOL_OP, TOL_CHEB, TOL_CYCLE, TOL_SOL, TOL_F32 = th.TOL_OP, th.TOL_CHEB, th.TOL_CYCLE, th.TOL_SOL, th.TOL_F32
-apply_nan = th.apply_nan
-
-_hier = {}  # (case, field, restrict name) -> (keys per level, levels at sigma = 0, P)
-_lvl = {}   # (geo, L, p, field) -> (keys, level at sigma = 0)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
-
-
-def tria_with(mgamd, geo, L, name):
-    t = mgamd.Triangulation(geo, L)
-    t.set_coefficient(co.product_values(t, co.field_on(co.product_cells(t), co.FIELDS[name])))
-    return t
-
-
-def oracle_level(oracle, sigma, geo, L, p, name, dofs):
-    keys = dofs.keys()
-    hit = _lvl.get((geo, L, p, name))
-    if hit is None or not np.array_equal(hit[0], keys):
-        lv = co.level(oracle, 0.0, co.FIELDS[name], dofs, geo, L, p)
-        if hit is None:
-            _lvl[(geo, L, p, name)] = (keys, lv)
-    else:
-        lv = hit[1]
-    return lv if sigma == 0.0 else co.reshift(lv, sigma)
-
-
-def oracle_hierarchy(oracle, sigma, case, name, dofs, restrict=co.restrict_field):
-    keys = [d.keys() for d in dofs]
-    tag = (case, name, restrict.__name__)
-    hit = _hier.get(tag)
-    if hit is None or not th._same_keys(hit[0], keys):
-        levels, P = co.build_hierarchy(oracle, 0.0, co.FIELDS[name], *case, numbering_keys=keys, restrict=restrict)
-        if hit is None:
-            _hier[tag] = (keys, levels, P)
-    else:
-        _, levels, P = hit
-    return (levels if sigma == 0.0 else co.reshift_hierarchy(levels, sigma)), P
-
-
-def assert_level_coefficients(h, levels):
-    """what the product's meshes carry is what the oracle restated from the finest field"""
-    for t, lv in zip(h.trias, levels):
-        ref = co.product_values(t, lv.coefficient)
-        assert np.abs(t.coefficient() / ref - 1.0).max() <= 1e-15
-    for d, t in zip(h.dofs, h.trias):
-        assert d.coefficient_range() == (t.coefficient().min(), t.coefficient().max())
-
-
-def hierarchy(mgamd, ctx, case, name, sigma, **kw):
-    geo, L, p, mg_type = case
-    kw.setdefault("coarse_solver", "amg")
-    return mgamd.Hierarchy(ctx, geo, L, p, mg_type, mass_coefficient=sigma, coefficient=co.XYZ[name], **kw)
 
 
 def bricks_with_a_coefficient(d, t):
@@ -108,9 +51,9 @@ def plain_bricks_where_a_is_not_one(plain, t):
 
 
 @pytest.mark.parametrize("name", ["uniform", "octants"])
-@pytest.mark.parametrize("geo,L,p,max_brick", th.OP_CASES)
+@pytest.mark.parametrize("geo,L,p,max_brick", OP_CASES)
 def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_brick, name):
-    t = tria_with(mgamd, geo, L, name)
+    t = su.tria(mgamd, geo, L, Problem(coefficient=name))
     d = mgamd.DoFs(t, p, max_brick)
     plain = mgamd.DoFs(mgamd.Triangulation(geo, L), p, max_brick)
     if plain_bricks_where_a_is_not_one(plain, t):
@@ -119,7 +62,7 @@ def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_brick, na
     for sigma in SIGMAS:
         d.set_mass_coefficient(sigma)
         op = mgamd.Operator(ctx, d)
-        lv = oracle_level(oracle, sigma, geo, L, p, name, d)
+        lv = su.oracle_level(d, geo, L, p, Problem(sigma, name))
         for trial in range(2):  # twice: a dirty tail accumulator shows in the second pass
             x = rng.standard_normal(lv.n)
             err = rel_err(apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
@@ -140,7 +83,7 @@ def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_brick, na
 def test_per_cell_field(mgamd, oracle, ctx, geo, L, p):
     """every brick is split: single-cell slots only.  p = 4: thousands of tail DoFs with hundreds of distinct diagonals, so the
     one-byte D^-1 codes of the tail and their overflow code 255 run"""
-    t = tria_with(mgamd, geo, L, "per_cell")
+    t = su.tria(mgamd, geo, L, Problem(coefficient="per_cell"))
     d = mgamd.DoFs(t, p, 0)
     assert all(list(d.info.group_B)[int(g)] == 1 for g in set(d.cell_slots()[0].tolist()))
     if p == 4:
@@ -149,7 +92,7 @@ def test_per_cell_field(mgamd, oracle, ctx, geo, L, p):
     for sigma in SIGMAS:
         d.set_mass_coefficient(sigma)
         op = mgamd.Operator(ctx, d)
-        lv = oracle_level(oracle, sigma, geo, L, p, "per_cell", d)
+        lv = su.oracle_level(d, geo, L, p, Problem(sigma, "per_cell"))
         x = rng.standard_normal(lv.n)
         ev = rel_err(apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
         diag = op.initialize_dof_vector().from_host(np.full(lv.n, np.nan))
@@ -172,7 +115,7 @@ def test_per_cell_field(mgamd, oracle, ctx, geo, L, p):
 def compare_by_the_bitwise_rule(d, pairs):
     """test_sigma_zero_is_bitwise_the_laplace_path's rule: bit for bit on the DoFs whose value does not depend on the order of
     floating-point atomics (slot-interior, constrained, shell DoFs of at most two slots), 1e-14 on the rest and on a V-cycle"""
-    cnt = th.atomic_contributions(d)
+    cnt = su.atomic_contributions(d)
     det = cnt <= 2
     assert det.sum() > 0.5 * d.n_dofs
     for name, a, b in pairs:
@@ -188,7 +131,7 @@ def test_mass_operator_does_not_see_the_coefficient(mgamd, ctx, geo, L, p, name)
     """vmult_mass under a coefficient is vmult_mass without one (M does not depend on a).  Where the coefficient leaves the slots
     as they are the two run the same kernels on the same tables: the bitwise rule.  Where it splits bricks (octants on a mesh whose
     bricks straddle the planes through 0) the numbering differs: matched by the DoF keys, 1e-14."""
-    t = tria_with(mgamd, geo, L, name)
+    t = su.tria(mgamd, geo, L, Problem(coefficient=name))
     d, d0 = mgamd.DoFs(t, p, 0), mgamd.DoFs(mgamd.Triangulation(geo, L), p, 0)
     d.set_mass_coefficient(7.5)
     d0.set_mass_coefficient(7.5)
@@ -236,10 +179,10 @@ def test_ones_are_no_coefficient(mgamd, ctx, geo, L, p, sigma):
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 1), ("quadrant", 3, 2), ("quadrant", 3, 4), ("quadrant", 2, 5)])
 @pytest.mark.parametrize("sigma", SIGMAS)
 def test_chebyshev(mgamd, oracle, ctx, geo, L, p, sigma):
-    d = mgamd.DoFs(tria_with(mgamd, geo, L, "octants"), p, 0)
+    d = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(coefficient="octants")), p, 0)
     d.set_mass_coefficient(sigma)
     op = mgamd.Operator(ctx, d)
-    lv = oracle_level(oracle, sigma, geo, L, p, "octants", d)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma, "octants"))
     ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
     assert ch.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev, rel=1e-10)
@@ -259,10 +202,10 @@ def test_chebyshev(mgamd, oracle, ctx, geo, L, p, sigma):
 @pytest.mark.parametrize("name", ["octants", "inclusion"])
 @pytest.mark.parametrize("sigma", SIGMAS)
 def test_vcycle_and_cg(mgamd, oracle, emu, ctx, case, name, sigma):
-    h = hierarchy(mgamd, ctx, case, name, sigma, max_brick=0)
-    levels, P = oracle_hierarchy(oracle, sigma, case, name, h.dofs)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, name), max_brick=0)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, name))
     assert_level_coefficients(h, levels)
-    th.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} {name} sigma={sigma}")
+    su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} {name} sigma={sigma}")
 
 
 # ------------------------------------------------------------------ 7. fused transfers
@@ -271,16 +214,16 @@ def test_fused_transfers(mgamd, oracle, emu, ctx, sigma, monkeypatch):
     """hypercube L=3 p=4, octants: eight 17^3 bricks with eight coefficient values restrict and prolongate inside the operator
     passes (MODE_RESIDUAL_RESTRICT, MODE_CHEB_PROLONGATE); equal to the separate transfer kernels and to the oracle"""
     case = ("hypercube", 3, 4, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, "octants", sigma, max_brick=0)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"), max_brick=0)
     assert sum(t.n_fused_bricks() for t in h.transfers[1:]) > 0
     assert len(bricks_with_a_coefficient(h.dofs[-1], h.trias[-1])) >= 4
     monkeypatch.setenv("MGAMD_NO_FUSED_TRANSFER", "1")
-    h0 = hierarchy(mgamd, ctx, case, "octants", sigma, max_brick=0)
+    h0 = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"), max_brick=0)
     monkeypatch.delenv("MGAMD_NO_FUSED_TRANSFER")
     assert sum(t.n_fused_bricks() for t in h0.transfers[1:]) == 0
-    levels, P = oracle_hierarchy(oracle, sigma, case, "octants", h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "octants"))
     assert_level_coefficients(h, levels)
-    th.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} octants sigma={sigma} fused")
+    su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} octants sigma={sigma} fused")
     r = np.random.default_rng(11).standard_normal(levels[-1].n)
     z, z0 = apply_nan(mgamd, ctx, h.mg.vmult, r), apply_nan(mgamd, ctx, h0.mg.vmult, r)
     assert rel_err(z, z0) < 1e-13
@@ -293,14 +236,14 @@ def test_fused_transfers(mgamd, oracle, emu, ctx, sigma, monkeypatch):
 def test_collapsed_coarse_levels(mgamd, oracle, emu, ctx, sigma, monkeypatch):
     """quadrant L=4 p=1: the levels up to 2048 DoFs as one tabulated matrix, formed through the operators with their coefficient"""
     case = ("quadrant", 4, 1, "HMG-global")
-    ha = hierarchy(mgamd, ctx, case, "octants", sigma)
+    ha = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"))
     monkeypatch.setenv("MGAMD_COLLAPSE_MAX_DOFS", "0")
-    hb = hierarchy(mgamd, ctx, case, "octants", sigma)
+    hb = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"))
     monkeypatch.delenv("MGAMD_COLLAPSE_MAX_DOFS")
     assert ha.mg.set_collapse(True) > 0 and hb.mg.set_collapse(True) == 0
     for h, tag in ((ha, "collapsed"), (hb, "kernel by kernel")):
-        levels, P = oracle_hierarchy(oracle, sigma, case, "octants", h.dofs)
-        th.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} octants sigma={sigma} {tag}")
+        levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "octants"))
+        su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} octants sigma={sigma} {tag}")
 
 
 # ------------------------------------------------------------------ 9., 10. AMG
@@ -310,10 +253,10 @@ def test_assembled_matrix_amg_and_cg(mgamd, oracle, ctx, sigma):
     import amg_oracle as ao
 
     geo, L, p = "quadrant", 3, 2
-    h = mgamd.Hierarchy(ctx, geo, L, p, "AMG", mass_coefficient=sigma, coefficient=co.octants_xyz)
+    h = mgamd.Hierarchy(ctx, geo, L, p, "AMG", mass_coefficient=sigma, coefficient=po.octants_xyz)
     d = h.dofs[0]
     assert d.coefficient_range() == (1.0, 6.25)
-    lv = co.level(oracle, sigma, co.octants, d, geo, L, p)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma, "octants"))
     x = np.random.default_rng(4).standard_normal(lv.n)
     assert rel_err(apply_nan(mgamd, ctx, h.system_matrix.vmult, x), lv.A @ x) < TOL_OP
     o = ao.SmoothedAggregation(d.matrix())
@@ -331,9 +274,9 @@ def test_pmg_with_amg_coarse_solver(mgamd, oracle, ctx):
     import amg_oracle as ao
 
     sigma, case = 7.5, ("annulus", 6, 2, "PMG")
-    h = hierarchy(mgamd, ctx, case, "octants", sigma, coarse_n_cycles=2)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"), coarse_n_cycles=2)
     assert h.mg.coarse_solver_used() == "amg"
-    levels, P = co.build_hierarchy(oracle, sigma, co.octants, *case, numbering_keys=[d.keys() for d in h.dofs])
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "octants"))
     A0 = ao.csr(*h.dofs[0].matrix())
     assert abs(A0 - levels[0].A).max() <= 1e-13 * abs(levels[0].A).max()
     mg = oracle.Multigrid(levels, P, 3, coarse=ao.SmoothedAggregation(h.dofs[0].matrix()).precondition(2))
@@ -354,9 +297,9 @@ def test_pmg_with_amg_coarse_solver(mgamd, oracle, ctx):
 def test_gaussian_simulation_type(mgamd, oracle, emu, ctx, sigma):
     """Dirichlet lifting with the unconstrained K_a + sigma M, solve, constraints.distribute"""
     case = ("quadrant", 3, 4, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, "octants", sigma, max_brick=0)
-    levels, P = oracle_hierarchy(oracle, sigma, case, "octants", h.dofs)
-    x, xref = th.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"Gaussian {case} octants sigma={sigma}", rhs_kind=1)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"), max_brick=0)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "octants"))
+    _, x, xref = su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"Gaussian {case} octants sigma={sigma}", rhs_kind=1)
     h.fine_operator.distribute(x, 1)
     assert rel_err(x.to_host(), levels[-1].distribute(xref, oracle.gaussian_solution)) < 10 * TOL_SOL
 
@@ -365,8 +308,8 @@ def test_gaussian_simulation_type(mgamd, oracle, emu, ctx, sigma):
 @pytest.mark.parametrize("sigma", SIGMAS)
 def test_float_levels(mgamd, oracle, emu, ctx, sigma):
     case = ("quadrant", 3, 4, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, "octants", sigma, number_type=mgamd.F32, max_brick=0)
-    levels, P = oracle_hierarchy(oracle, sigma, case, "octants", h.dofs)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, "octants"), number_type=mgamd.F32, max_brick=0)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "octants"))
     rng = np.random.default_rng(21)
     for l, op in enumerate(h.operators):
         lv = levels[l]
@@ -401,7 +344,7 @@ def test_two_simulated_ranks(mgamd, oracle, monkeypatch):
     """quadrant L=4 p=2 HMG-global cut over two ranks: the local tables take the coefficient from the partition's meshes"""
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # the sharded path's start vector hashes the DoF key; the oracle takes the same
     sigma, case, n_ranks = 7.5, ("quadrant", 4, 2, "HMG-global"), 2
-    levels, P = co.build_hierarchy(oracle, sigma, co.octants, *case)
+    levels, P = su.oracle_hierarchy(None, case, Problem(sigma, "octants"))
     omg = oracle.Multigrid(levels, P, 3, coarse="direct", start_vectors=[oracle.key_hash_start_vector(lv) for lv in levels])
     Lf = levels[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(Lf.keys)}
@@ -416,7 +359,7 @@ def test_two_simulated_ranks(mgamd, oracle, monkeypatch):
         try:
             c = mgamd.Context(0)
             h = mgamd.DistributedHierarchy(c, group.comm(rk), *case[:3], coarse_solver="amg", max_brick=0, min_root_dofs=0,
-                                           mg_type=case[3], mass_coefficient=sigma, coefficient=co.octants_xyz)
+                                           mg_type=case[3], mass_coefficient=sigma, coefficient=po.octants_xyz)
             idx = np.array([kf[tuple(int(v) for v in k)] for k in h.dofs[-1].keys()])
             op = h.fine_operator
             vr, vz = op.initialize_dof_vector().from_host(r[idx]), op.initialize_dof_vector()
@@ -454,8 +397,8 @@ def test_time_stepper_two_materials(mgamd, oracle, emu, ctx):
     works on the hierarchy; equal CG counts in every step"""
     case, theta, dt, n_steps, reltol = ("quadrant", 3, 2, "HMG-global"), 0.5, 0.02, 3, 1e-6
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
-    h = hierarchy(mgamd, ctx, case, "inclusion", sigma, max_brick=0)
-    levels, P = oracle_hierarchy(oracle, sigma, case, "inclusion", h.dofs)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, "inclusion"), max_brick=0)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "inclusion"))
     assert_level_coefficients(h, levels)
     assert h.dofs[-1].coefficient_range() == (1.0, 1000.0)
     lv = levels[-1]
@@ -469,7 +412,7 @@ def test_time_stepper_two_materials(mgamd, oracle, emu, ctx):
     u, its = vec(u0), []
     for n in range(n_steps):
         its.append(stepper.step(u, vec(f(n)), vec(f(n + 1)), reltol=reltol)[0])
-    Mh, solve = ts.mass_matrix(lv), ts.pcg_solver(oracle, lv, th.injected(emu, oracle, levels, P, h).vcycle, reltol)
+    Mh, solve = ts.mass_matrix(lv), ts.pcg_solver(oracle, lv, su.injected(emu, oracle, levels, P, h).vcycle, reltol)
     uref, itref = u0.copy(), []
     for n in range(n_steps):
         uref, it = ts.theta_step(lv, uref, f(n), f(n + 1), theta, dt, solve, Mh)
@@ -498,7 +441,7 @@ def test_example_program_with_two_materials(oracle):
     norms = [float(m) for m in re.findall(r"\|u\| = (\S+)", run.stdout)]
     assert len(norms) == 5, run.stdout
     theta, dt = 0.5, 0.01
-    levels, P = co.build_hierarchy(oracle, ts.mass_coefficient(theta, dt), co.inclusion, "hypercube", 3, 2)
+    levels, P = su.oracle_hierarchy(None, ("hypercube", 3, 2, "HMG-global"), Problem(ts.mass_coefficient(theta, dt), "inclusion"))
     lv = levels[-1]
     u = np.ones(lv.n)
     u[lv.constrained] = 0.0
@@ -517,39 +460,39 @@ def test_harmonic_mean_on_the_coarse_meshes(mgamd, oracle, emu, ctx, sigma):
     """the caller overwrites every coarse mesh with the harmonic mean of the finest field; the level operators use what the meshes
     hold when their DoFs are built, and the V-cycle follows an oracle hierarchy built with the same values"""
     case = ("quadrant", 3, 2, "HMG-global")
-    fine = tria_with(mgamd, *case[:2], "inclusion")
-    finest = co.field_on(co.product_cells(fine), co.inclusion)
+    fine = su.tria(mgamd, *case[:2], Problem(coefficient="inclusion"))
+    finest = po.field_on(po.product_cells(fine), po.inclusion)
 
     def harmonic(t):
-        return co.product_values(t, co.harmonic_restrict_field(finest, co.product_cells(t)))
+        return po.product_values(t, po.harmonic_restrict_field(finest, po.product_cells(t)))
 
     h = mgamd.Hierarchy(ctx, fine, case[1], case[2], case[3], coarse_solver="amg", max_brick=0, mass_coefficient=sigma,
                         coarse_coefficient=harmonic)
-    levels, P = oracle_hierarchy(oracle, sigma, case, "inclusion", h.dofs, restrict=co.harmonic_restrict_field)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, "inclusion"), restrict=po.harmonic_restrict_field)
     assert_level_coefficients(h, levels)
     # it is not the arithmetic mean: the one-cell mesh holds 64 / (63 + 1 / 1000), not 1 + 999 / 64
-    mean = co.restrict_field(finest, co.product_cells(h.trias[0]))
-    assert h.trias[0].n_cells == 1 and co.product_values(h.trias[0], mean)[0] - h.trias[0].coefficient()[0] > 10.0
-    th.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} inclusion, harmonic coarse means, sigma={sigma}")
+    mean = po.restrict_field(finest, po.product_cells(h.trias[0]))
+    assert h.trias[0].n_cells == 1 and po.product_values(h.trias[0], mean)[0] - h.trias[0].coefficient()[0] > 10.0
+    su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} inclusion, harmonic coarse means, sigma={sigma}")
 
 
 # ------------------------------------------------------------------ 16. refusals
 def test_refusals(mgamd, ctx):
     for mg_type in ("HMG-local", "HPMG-local"):
         with pytest.raises(mgamd.MgamdError, match="not implemented"):
-            mgamd.Hierarchy(ctx, "quadrant", 3, 2, mg_type, coefficient=co.octants_xyz)
+            mgamd.Hierarchy(ctx, "quadrant", 3, 2, mg_type, coefficient=po.octants_xyz)
         with pytest.raises(mgamd.MgamdError, match="not implemented"):
-            mgamd.Hierarchy(ctx, tria_with(mgamd, "quadrant", 3, "octants"), 3, 2, mg_type)
+            mgamd.Hierarchy(ctx, su.tria(mgamd, "quadrant", 3, Problem(coefficient="octants")), 3, 2, mg_type)
     with pytest.raises(mgamd.MgamdError, match="cell 0 is -1"):
         mgamd.Hierarchy(ctx, "quadrant", 3, 2, "HMG-global", coefficient=lambda x, y, z: np.full(x.shape, -1.0))
     with pytest.raises(mgamd.MgamdError, match="nan"):
         mgamd.Hierarchy(ctx, "quadrant", 3, 2, "HMG-global", coefficient=lambda x, y, z: np.where(x > 0, np.nan, 1.0))
     with pytest.raises(mgamd.MgamdError, match="no coarse meshes"):
-        mgamd.Hierarchy(ctx, "quadrant", 3, 2, "PMG", coefficient=co.octants_xyz, coarse_coefficient=lambda m: np.ones(m.n_cells))
+        mgamd.Hierarchy(ctx, "quadrant", 3, 2, "PMG", coefficient=po.octants_xyz, coarse_coefficient=lambda m: np.ones(m.n_cells))
     mine = mgamd.Triangulation("quadrant", 3)
-    mgamd.Hierarchy(ctx, mine, 3, 2, "HMG-global", coefficient=co.octants_xyz)
+    mgamd.Hierarchy(ctx, mine, 3, 2, "HMG-global", coefficient=po.octants_xyz)
     assert mine.has_coefficient() and mine.coefficient().max() == 6.25  # the caller's mesh carries the values afterwards
-    t = tria_with(mgamd, "quadrant", 3, "uniform")
+    t = su.tria(mgamd, "quadrant", 3, Problem(coefficient="uniform"))
     with pytest.raises(mgamd.MgamdError, match="local smoothing"):
         t.level_mesh(1)
     # local smoothing without a coefficient stays what it was

@@ -1,7 +1,7 @@
 """Non-zero Dirichlet data on the GPU: the lifting kernel (dirichlet_lift_kernel, every degree and both number types), the device
 distribute_values, the known answer, the example program, the convective wall with a hot wall, the time stepper with time-dependent
-Dirichlet values and a boundary load, two simulated ranks and the refusals.  Oracle: tests/dirichlet_data_oracle.py on the levels of
-boundary_oracle / coefficient_oracle / robin_oracle, shared with test_gpu_boundary.py and test_gpu_robin.py through their caches.
+Dirichlet values and a boundary load, two simulated ranks and the refusals.  Oracle: oracle/physics_oracle.py, and
+tests/dirichlet_data_oracle.py for the theta steppers; the numpy spaces are shared with every other file through support.py.
 
 Shapes are the smallest that reach every branch of the kernel: quadrant 3 (120 cells) at p = 1, 2, 4 and quadrant 2 (15 cells) at
 p = 3, 5, 6, 7, where a cell has more nodes than the workgroup has threads, and the one-cell coarsest level.  Bounds are the
@@ -16,47 +16,31 @@ import numpy as np
 import pytest
 import scipy.sparse.linalg as spla
 
-import boundary_oracle as bo
-import coefficient_oracle as co
 import dirichlet_data_oracle as do
-import helmholtz_oracle as ho
-import test_gpu_boundary as tb
-import test_gpu_robin as tr
+import physics_oracle as po
+import support as su
 import time_stepping_oracle as ts
 from conftest import ROOT, rel_err
+from physics_oracle import ALL, M1, Problem
+from support import emu, vec  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ALL, M1 = bo.ALL, bo.M1
 TOL_OP, TOL_ORDER, TOL_SOL, TOL_F32 = 1e-13, 1e-14, 1e-10, 2e-6
 SIGMA = 7.5
 
 
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
-
-
-def vec(op, a):
-    return op.initialize_dof_vector().from_host(np.ascontiguousarray(a, dtype=np.float64))
-
-
 def product(mgamd, L, p, mask, sigma, field=None):
-    t = tb.tria(mgamd, "quadrant", L, mask)
+    t = su.tria(mgamd, "quadrant", L, Problem(dirichlet_faces=mask))
     if field is not None:
-        t.set_coefficient_function(co.XYZ[field])
+        t.set_coefficient_function(po.XYZ[field])
     d = mgamd.DoFs(t, p, 0)
     d.set_mass_coefficient(sigma)
     return d
 
 
 def oracle_level(oracle, L, p, mask, sigma, d, field=None):
-    lv = ho.renumber(tb.base_level(oracle, "quadrant", L, p), d.keys())
-    if field is not None:
-        lv = co.with_coefficient(lv, co.field_on(lv.cells, co.FIELDS[field]))
-    return bo.remask(oracle, lv, mask, sigma)
+    return su.oracle_level(d, "quadrant", L, p, Problem(sigma, field, mask))
 
 
 def lift(op, g, include_mass=True):
@@ -101,19 +85,19 @@ def test_lift_against_the_oracle(mgamd, oracle, ctx, L, p):
             d = product(mgamd, L, p, mask, SIGMA, field)
             lv = oracle_level(oracle, L, p, mask, SIGMA, d, field)
             n, n_hanging, n_two = table_facts(oracle, d, lv, mask)
-            assert n == do.n_cells_with_dirichlet_dof(lv) and n_hanging >= 1 and (n_two >= 1 or mask == M1)
+            assert n == po.n_cells_with_dirichlet_dof(lv) and n_hanging >= 1 and (n_two >= 1 or mask == M1)
             partial.append(n % cpw != 0)
             g = rng.standard_normal(lv.n).astype(np.float32).astype(np.float64)
             for number_type, tol in ((mgamd.F64, TOL_OP), (mgamd.F32, TOL_F32)):
                 op = mgamd.Operator(ctx, d, number_type)
                 for include_mass in (True, False):
-                    got, ref = lift(op, g, include_mass), do.lift(lv, g, include_mass)
+                    got, ref = lift(op, g, include_mass), po.lift(lv, g, include_mass)
                     e = rel_err(got, ref)
                     print(f"quadrant {L} p={p} mask={mask:#04x} {field} {'FP64' if number_type == mgamd.F64 else 'FP32'} mass={include_mass}: "
                           f"{n} entries ({n_hanging} hanging with a Dirichlet node, {n_two} on two faces), {cpw} per workgroup, lift {e:.2e}")
                     assert np.isfinite(got).all() and e < tol and np.all(got[lv.constrained] == 0.0)
             # the mass part is what include_mass switches: far above both tolerances, so a kernel that ignored the flag would fail
-            assert rel_err(do.lift(lv, g, True), do.lift(lv, g, False)) > 100 * TOL_F32
+            assert rel_err(po.lift(lv, g, True), po.lift(lv, g, False)) > 100 * TOL_F32
     assert cpw == 1 or any(partial)
 
 
@@ -126,7 +110,7 @@ def test_lift_on_the_one_cell_coarsest_level(mgamd, oracle, ctx, p):
         lv = oracle_level(oracle, 0, p, mask, SIGMA, d)
         assert d.info.n_cells == 1 and len(d.dirichlet_cells()[0]) == 1
         g = np.random.default_rng(1).standard_normal(lv.n)
-        got, ref = lift(mgamd.Operator(ctx, d), g), do.lift(lv, g)
+        got, ref = lift(mgamd.Operator(ctx, d), g), po.lift(lv, g)
         if mask == ALL and p == 1:
             assert d.info.n_dirichlet == d.n_dofs == 8 and np.all(ref == 0.0) and np.all(got == 0.0)
         else:
@@ -167,7 +151,7 @@ def test_distribute_values(mgamd, oracle, ctx, L, p):
             op = mgamd.Operator(ctx, d, number_type)
             g = rng.standard_normal(lv.n).astype(np.float32).astype(np.float64)
             x = rng.standard_normal(lv.n).astype(np.float32).astype(np.float64)
-            ref = do.distribute_values(lv, x, g)
+            ref = po.distribute_values(lv, x, g)
             x[lv.constrained] = 1e30  # hanging and Dirichlet entries hold garbage beforehand
             vx, vg = vec(op, x), vec(op, g)
             op.distribute_values(vx, vg)
@@ -189,7 +173,7 @@ def test_distribute_of_the_gaussian_is_distribute_values(mgamd, oracle, ctx, p):
     for mask in (ALL, M1):
         d = product(mgamd, 3, p, mask, 0.0)
         lv = oracle_level(oracle, 3, p, mask, 0.0, d)
-        bd = do.dirichlet_dofs(lv)
+        bd = po.dirichlet_dofs(lv)
         assert d.info.n_hanging > 0 and lv.Ch.tocsr()[np.flatnonzero(lv.hanging)][:, np.flatnonzero(bd)].nnz > 0
         g = d.distribute(np.zeros(lv.n), 1)
         assert np.abs(g[bd]).max() > 0
@@ -216,7 +200,7 @@ def test_linear_function_is_reproduced(mgamd, oracle, ctx, p):
     """g = the nodal values of 1 + 2x - 3y + 0.5z on all six faces, f = 0, sigma = 0: solve_cg with the multigrid at reltol 1e-12, then
     distribute_values; the result is the function at every node, hanging ones included, within test_gpu_boundary's
     test_layered_wall_known_answer bound (1e-8 after a solve at 1e-12; the host test's direct solve holds 1e-12)"""
-    h = tb.hierarchy(mgamd, ctx, ("quadrant", 3, p, "HMG-global"), ALL)
+    h = su.hierarchy(mgamd, ctx, ("quadrant", 3, p, "HMG-global"), Problem(), max_brick=0)
     op, d = h.fine_operator, h.dofs[-1]
     pos = d.node_positions()
     exact = 1.0 + 2.0 * pos[:, 0] - 3.0 * pos[:, 1] + 0.5 * pos[:, 2]
@@ -249,28 +233,28 @@ def test_heated_wall_example_program():
 # ------------------------------------------------------------------ convective faces
 def test_convective_wall_with_a_hot_wall(mgamd, oracle, ctx):
     """beta > 0 on x = +1 with the value T on x = -1 (the face opposite: no DoF is shared) is accepted: the lift is the oracle's, whose
-    levels carry the surface matrix (robin_oracle), and the solve with the load of u_ext is the oracle's direct solve.  beta > 0 on
+    levels carry the surface matrix (physics_oracle.Level.Braw), and the solve with the load of u_ext is the oracle's direct solve.  beta > 0 on
     y = +1 with x = -1 Dirichlet shares an edge and is refused by name."""
     case, T, u_ext = ("quadrant", 3, 2, "HMG-global"), 350.0, 290.0
     setup = (M1, (0.0, 2.5, 0.0, 0.0, 0.0, 0.0))
-    h = tr.hierarchy(mgamd, ctx, case, setup)
+    h = su.hierarchy(mgamd, ctx, case, Problem(0.0, None, *setup), max_brick=0)
     op, d = h.fine_operator, h.dofs[-1]
-    lv = tr.oracle_level(oracle, "quadrant", 3, 2, setup, d)
+    lv = su.oracle_level(d, "quadrant", 3, 2, Problem(0.0, None, *setup))
     g = d.dirichlet_face_values({0: T})
-    ref = do.lift(lv, g)
+    ref = po.lift(lv, g)
     e = rel_err(lift(op, g), ref)
-    flux = bo.flux_load(lv, [0.0, 2.5 * u_ext, 0.0, 0.0, 0.0, 0.0])
+    flux = po.flux_load(lv, [0.0, 2.5 * u_ext, 0.0, 0.0, 0.0, 0.0])
     b, q, u = (op.initialize_dof_vector() for _ in range(3))
     op.rhs_dirichlet(b, vec(op, g))
     op.rhs_boundary_flux(q, {1: 2.5 * u_ext})
     b.from_host(b.to_host() + q.to_host())
     it, _ = mgamd.solve_cg(op, h.mg, u, b, 1e-12)
     op.distribute_values(u, vec(op, g))
-    uref = do.distribute_values(lv, spla.spsolve(lv.A.tocsc(), ref + flux), g)
+    uref = po.distribute_values(lv, spla.spsolve(lv.A.tocsc(), ref + flux), g)
     eu = np.abs(u.to_host() - uref).max() / np.abs(uref).max()
     print(f"convective wall with a hot wall: lift {e:.2e}, CG iterations {it}, solution {eu:.2e}, range {uref.min():.3f} .. {uref.max():.3f}")
     assert np.abs(ref).max() > 0 and e < TOL_OP and eu <= 1e-8
-    t = tr.tria(mgamd, "quadrant", 3, (M1, (0.0, 0.0, 0.0, 0.75, 0.0, 0.0)))
+    t = su.tria(mgamd, "quadrant", 3, Problem(0.0, None, M1, (0.0, 0.0, 0.0, 0.75, 0.0, 0.0)))
     bad = mgamd.Operator(ctx, mgamd.DoFs(t, 2, 0))
     v, w = bad.initialize_dof_vector(), bad.initialize_dof_vector()
     with pytest.raises(mgamd.MgamdError, match=r"convective face 3 \(y=\+1.*shares an edge with the Dirichlet face 0 \(x=-1\)"):
@@ -286,8 +270,8 @@ def stepping(mgamd, oracle, emu, ctx, mask):
     """(hierarchy, oracle level, its mass matrix, the oracle's PCG with the multigrid at the product's eigenvalue estimates)"""
     if mask not in _stepping:
         sigma = mgamd.TimeStepper.mass_coefficient(THETA, DT)
-        h = tb.hierarchy(mgamd, ctx, CASE, mask, sigma)
-        levels, P = tb.oracle_hierarchy(oracle, CASE, mask, sigma, h.dofs)
+        h = su.hierarchy(mgamd, ctx, CASE, Problem(sigma, dirichlet_faces=mask), max_brick=0)
+        levels, P = su.oracle_hierarchy(h.dofs, CASE, Problem(sigma, dirichlet_faces=mask))
         mg = emu.with_max_evs(oracle.Multigrid(levels, P, 3, coarse="direct"), [s.eigenvalue_estimates()[1] for s in h.smoothers])
         _stepping[mask] = (h, levels[-1], ts.mass_matrix(levels[-1]), ts.pcg_solver(oracle, levels[-1], mg.vcycle, RELTOL))
     return _stepping[mask]
@@ -341,7 +325,7 @@ def test_stepper_with_a_boundary_load_and_a_source(mgamd, oracle, emu, ctx):
     f = lambda n: (1.0 + n * DT) * (np.sin(0.37 * np.arange(lv.n)) + 0.25)
     load = op.initialize_dof_vector()
     op.rhs_boundary_flux(load, {1: 1.5})
-    lref = bo.flux_load(lv, [0.0, 1.5, 0.0, 0.0, 0.0, 0.0])
+    lref = po.flux_load(lv, [0.0, 1.5, 0.0, 0.0, 0.0, 0.0])
     assert rel_err(load.to_host(), lref) < TOL_OP
     u0 = np.random.default_rng(17).standard_normal(lv.n)
     u0[lv.constrained] = 0.0
@@ -387,7 +371,7 @@ def test_two_simulated_ranks(mgamd, oracle, ctx, monkeypatch):
     against the one-rank result"""
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # a start vector of the smoothers' eigenvalue estimate that does not depend on the numbering
     n_ranks, sigma = 2, mgamd.TimeStepper.mass_coefficient(THETA, DT)
-    h1 = tb.hierarchy(mgamd, ctx, CASE, M1, sigma)
+    h1 = su.hierarchy(mgamd, ctx, CASE, Problem(sigma, dirichlet_faces=M1), max_brick=0)
     op1, d1 = h1.fine_operator, h1.dofs[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(d1.keys())}
     rng = np.random.default_rng(23)
@@ -433,7 +417,7 @@ def test_two_simulated_ranks(mgamd, oracle, ctx, monkeypatch):
 # ------------------------------------------------------------------ refusals
 def test_refusals(mgamd, ctx):
     sigma = mgamd.TimeStepper.mass_coefficient(THETA, DT)
-    h = tb.hierarchy(mgamd, ctx, CASE, ALL, sigma)
+    h = su.hierarchy(mgamd, ctx, CASE, Problem(sigma, dirichlet_faces=ALL), max_brick=0)
     op, n = h.fine_operator, h.n_dofs
     g, b = vec(op, np.ones(n)), op.initialize_dof_vector()
     with pytest.raises(mgamd.MgamdError, match="rhs_dirichlet: vector size mismatch"):

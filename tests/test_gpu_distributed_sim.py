@@ -9,32 +9,9 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from support import key_vector, keyset, run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def run_ranks(n_ranks, fn):
-    out, err = [None] * n_ranks, [None] * n_ranks
-
-    def work(r):
-        try:
-            out[r] = fn(r)
-        except BaseException as e:  # noqa
-            err[r] = e
-
-    th = [threading.Thread(target=work, args=(r,)) for r in range(n_ranks)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(timeout=600)
-    for e in err:
-        if e is not None:
-            raise e
-    return out
-
-
-def keyset(keys):
-    return [tuple(int(v) for v in k) for k in keys]
 
 
 @pytest.fixture(autouse=True)
@@ -44,13 +21,6 @@ def key_based_chebyshev_start_vector():
     os.environ["MGAMD_CHEB_KEY_INIT"] = "1"
     yield
     del os.environ["MGAMD_CHEB_KEY_INIT"]
-
-
-def key_vector(keys, seed):
-    """deterministic pseudo-random value per geometric DoF key: the same GLOBAL vector on every rank and in the oracle"""
-    k = np.asarray(keys, dtype=np.int64)
-    h = (k[:, 0] * 73856093) ^ (k[:, 1] * 19349663) ^ (k[:, 2] * 83492791) ^ (k[:, 3] * 2654435761) ^ (k[:, 4] * 97) ^ seed
-    return np.sin(h.astype(np.float64) * 1e-3) + 0.25 * np.cos(h.astype(np.float64) * 7e-5)
 
 
 # (geometry, NRefGlobal, degree, Type, coarse solver, ranks): vs the INDEPENDENT numpy oracle through the DoF keys

@@ -48,16 +48,12 @@ import os
 import numpy as np
 import pytest
 
-import boundary_oracle as bo
-import coefficient_oracle as co
-import helmholtz_oracle as ho
-import robin_oracle as ro
-import test_gpu_boundary as tb
-import test_gpu_helmholtz as th
+import physics_oracle as po
+import support as su
 from _degree_cases import float_cycle_reference, round32
 from conftest import rel_err
-from test_gpu_distributed_sim import key_vector, keyset, run_ranks
-from test_harness_gpu import GOLDEN, final_table, run_harness
+from physics_oracle import Problem
+from support import GOLDEN, emu, final_table, key_vector, keyset, run_harness, run_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -106,13 +102,6 @@ def renumber(levels, P, dofs):
         perms.append(perm)
     new = [Renumbered(lv, perm, keyset(d.keys())) for lv, perm, d in zip(levels, perms, dofs)]
     return new, [None] + [P[l][perms[l]][:, perms[l - 1]].tocsr() for l in range(1, len(levels))]
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
 
 
 @pytest.fixture(scope="module")
@@ -454,28 +443,25 @@ def test_coefficient_mass_term_and_robin_face(mgamd, oracle, emu, ctx):
     h = mgamd.Hierarchy(ctx, geo, L, p, mg_type, coarse_solver="amg", max_brick=0, mass_coefficient=sigma, dirichlet_faces=setup[0],
                         robin=setup[1], coefficient=lambda x, y, z: np.where(inside(x, y, z), 50.0, 1.0))
     assert all(np.array_equal(t.robin_coefficients(), setup[1]) and t.dirichlet_faces() == setup[0] for t in h.trias)
-    meshes, degs = ho.level_plan(oracle, geo, L, p, mg_type)
-    finest = co.field_on(meshes[-1], lambda c: 50.0 if inside(*co._centre(c)) else 1.0)
+    meshes, degs = po.level_plan(geo, L, p, mg_type)
+    finest = po.field_on(meshes[-1], lambda c: 50.0 if inside(*po._centre(c)) else 1.0)
     refined = {c for c in meshes[-1] if c[0] > 3}
     assert {c for c, a in finest.items() if a == 50.0} < refined and (sum(a == 50.0 for a in finest.values()), len(refined)) == (112, 120)
-    coeffs = [finest if len(m) == len(finest) else co.restrict_field(finest, m) for m in meshes]
+    coeffs = [finest if len(m) == len(finest) else po.restrict_field(finest, m) for m in meshes]
     for t, c in zip(h.trias, coeffs):
-        want = co.product_values(t, c)
+        want = po.product_values(t, c)
         assert np.abs(t.coefficient() - want).max() <= 1e-14 * 50.0
     assert any(1.0 < a < 50.0 for c in coeffs[:-1] for a in c.values())  # coarse cells across the inclusion's rim
-    base = [tb.base_level(oracle, geo, L, q, m) for m, q in zip(meshes, degs)]
-    P0 = tb._hier.setdefault(case, (base, bo.natural_transfers(oracle, base)))[1]
-    levels, P0 = ho.renumber_hierarchy(base, P0, [d.keys() for d in h.dofs])
-    levels = ro.robin_hierarchy([bo.remask(oracle, co.with_coefficient(lv, c, sigma), setup[0]) for lv, c in zip(levels, coeffs)], setup[1])
-    P = bo.mask_transfers(P0, levels)
+    levels, P = su.oracle_hierarchy_on(h.dofs, meshes, degs, Problem(sigma, finest, *setup))
+    assert all(lv.coefficient == c for lv, c in zip(levels, coeffs))
     for l, (op, lv) in enumerate(zip(h.operators, levels)):
         x = np.random.default_rng(3).standard_normal(lv.n)
         diag = op.initialize_dof_vector().from_host(np.full(lv.n, np.nan))
         op.compute_inverse_diagonal(diag)
-        ev, ed = rel_err(th.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x), rel_err(diag.to_host(), lv.inv_diag)
+        ev, ed = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x), rel_err(diag.to_host(), lv.inv_diag)
         print(f"circle 5 p=2 a=50|1 sigma={sigma} mask={setup[0]:#04x} beta={setup[1]} level {l}: vmult {ev:.2e} inverse diagonal {ed:.2e}")
         assert ev < TOL_OP and ed < TOL_OP
-    tb.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"circle 5 p=2 a=50|1 sigma={sigma} mask={setup[0]:#04x} beta={setup[1]}")
+    su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"circle 5 p=2 a=50|1 sigma={sigma} mask={setup[0]:#04x} beta={setup[1]}")
 
 
 # ------------------------------------------------------------------ harness

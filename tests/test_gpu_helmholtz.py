@@ -1,12 +1,12 @@
 """The mass term on the GPU: operators, smoothers, multigrid and CG for A = K + sigma M (-Laplace u + sigma u) against the
-test-side numpy oracle tests/helmholtz_oracle.py (mgoracle.Level with sigma h^3 M (x) M (x) M added; oracle/ is not edited).
+numpy oracle oracle/physics_oracle.py (sigma h^3 M (x) M (x) M added to mgoracle.Level's stiffness matrix).
 
 sigma in {7.5, 3000}: no powers of two, so a wrong power of h cannot hide; the smaller is stiffness-dominated, the larger
 mass-dominated at these mesh sizes, so a kernel family without the term cannot hide either.  Bounds are the project's own:
 operator <= 1e-13, Chebyshev <= 1e-12 (test_chebyshev), V-cycle <= 1e-11, CG iterates <= 1e-10 with equal iteration counts, FP32
 single kernels <= 2e-6, FP32 V-cycle <= 16 e_ref with e_ref from oracle/f32_emulation.py run on the helper's levels (its functions
-take them unchanged).  Shapes are the smallest that reach each kernel (test_gpu_parity.OP_CASES).  Each numpy hierarchy is built
-once per session for sigma = 7.5 and re-shifted for 3000.
+take them unchanged).  Shapes are the smallest that reach each kernel (support.OP_CASES).  Each constraint search is made once
+per session (support.py).
 
 One case is added to the issue's list: PMG with coarse_solver="amg" runs on annulus L=6 as well as L=5 -- the p = 1 level of annulus
 L=5 has 1965 DoFs, which the library solves exactly ("direct", up to 4096 DoFs), so the AMG only runs at L=6.  The sigma = 0
@@ -18,66 +18,16 @@ import threading
 import numpy as np
 import pytest
 
-import helmholtz_oracle as ho
-from conftest import ROOT, rel_err
+import support as su
+from conftest import rel_err
+from physics_oracle import Problem
+from support import (BIN, GOLDEN, OP_CASES, REFERENCE_COLUMNS, TOL_CHEB, TOL_CYCLE, TOL_F32, TOL_OP, TOL_SOL, apply_nan, atomic_contributions,
+                     emu, final_table, run_harness, vcycle_and_solve)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SIGMAS = [7.5, 3000.0]
-TOL_OP, TOL_CHEB, TOL_CYCLE, TOL_SOL, TOL_F32 = 1e-13, 1e-12, 1e-11, 1e-10, 2e-6
-
-_hier = {}  # (geo, L, p, mg_type) -> (keys per level, levels at SIGMAS[0], P)
-_lvl = {}   # (geo, L, p) -> (keys, level at SIGMAS[0])        (numbering of max_brick = 0)
-
-
-def _same_keys(a, b):
-    return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def oracle_hierarchy(oracle, sigma, case, dofs):
-    """(levels, P) of K + sigma M in the numbering of the product's level DoFs `dofs`"""
-    keys = [d.keys() for d in dofs]
-    if case not in _hier:
-        levels, P = ho.build_hierarchy(oracle, SIGMAS[0], *case, numbering_keys=keys)
-        _hier[case] = (keys, levels, P)
-        geo, L, p, _ = case
-        _lvl.setdefault((geo, L, p), (keys[-1], levels[-1]))
-    k0, levels, P = _hier[case]
-    if not _same_keys(k0, keys):  # another slot policy: another numbering of the same spaces
-        levels, P = ho.build_hierarchy(oracle, SIGMAS[0], *case, numbering_keys=keys)
-    return (levels if sigma == SIGMAS[0] else ho.reshift_hierarchy(levels, sigma)), P
-
-
-def oracle_level(oracle, sigma, geo, L, p, dofs):
-    keys = dofs.keys()
-    hit = _lvl.get((geo, L, p))
-    if hit is not None and np.array_equal(hit[0], keys):
-        lv = hit[1]
-    else:
-        lv = ho.level(oracle, SIGMAS[0], dofs, geo, L, p)
-        if hit is None:
-            _lvl[(geo, L, p)] = (keys, lv)
-    return lv if sigma == SIGMAS[0] else ho.reshift(lv, sigma)
-
-
-def apply_nan(mgamd, ctx, fn, x):
-    """fn(dst, src) into a NaN-prefilled destination; the source must come back untouched"""
-    src, dst = mgamd.Vector(ctx, len(x)).from_host(x), mgamd.Vector(ctx, len(x)).from_host(np.full(len(x), np.nan))
-    fn(dst, src)
-    assert np.array_equal(src.to_host(), x)
-    out = dst.to_host()
-    assert np.isfinite(out).all()
-    return out
-
-
 # ------------------------------------------------------------------ operator and inverse diagonal
-# families, single cells with hanging faces and edges, p = 1 clusters; wave-scoped cells only; constrained rim bricks; one
-# 17-point brick (persistent kernel, closed-form D^-1) at p = 4, 2, 1; eight 17^3 bricks sharing faces, edges and a vertex; the
-# 11- and 15-point lattices
-OP_CASES = ([("quadrant", 3, p, 0) for p in (1, 2, 3, 4)] + [("quadrant", 3, 4, 1), ("quadrant", 4, 1, 0), ("hypercube", 2, 4, 0),
-            ("hypercube", 3, 2, 0), ("hypercube", 4, 1, 0), ("hypercube", 3, 4, 0), ("quadrant", 2, 5, 0), ("quadrant", 2, 7, 0)])
-
-
 @pytest.mark.parametrize("geo,L,p,max_brick", OP_CASES)
 def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_brick):
     d = mgamd.DoFs(mgamd.Triangulation(geo, L), p, max_brick)
@@ -86,7 +36,7 @@ def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, geo, L, p, max_brick):
         d.set_mass_coefficient(sigma)
         op = mgamd.Operator(ctx, d)
         assert op.mass_coefficient() == sigma
-        lv = oracle_level(oracle, sigma, geo, L, p, d)
+        lv = su.oracle_level(d, geo, L, p, Problem(sigma))
         for trial in range(2):  # twice: a dirty tail accumulator shows in the second pass
             x = rng.standard_normal(lv.n)
             err = rel_err(apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
@@ -109,7 +59,7 @@ def test_chebyshev(mgamd, oracle, ctx, geo, L, p, sigma):
     d = mgamd.DoFs(mgamd.Triangulation(geo, L), p, 0)
     d.set_mass_coefficient(sigma)
     op = mgamd.Operator(ctx, d)
-    lv = oracle_level(oracle, sigma, geo, L, p, d)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma))
     ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
     assert ch.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev, rel=1e-10)
@@ -124,43 +74,6 @@ def test_chebyshev(mgamd, oracle, ctx, geo, L, p, sigma):
 
 
 # ------------------------------------------------------------------ V-cycle and CG
-def injected(emu, oracle, levels, P, h):
-    """oracle.Multigrid with the product's eigenvalue estimates injected (asserted first), so that the comparison is about the
-    kernels alone"""
-    mg = oracle.Multigrid(levels, P, 3, coarse="direct")
-    evs = [s.eigenvalue_estimates()[1] for s in h.smoothers]
-    for l, ev in enumerate(evs):
-        assert ev == pytest.approx(mg.sm[l].max_ev, rel=1e-9)
-    return emu.with_max_evs(mg, evs)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
-
-
-def vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, tag, rhs_kind=0):
-    mg = injected(emu, oracle, levels, P, h)
-    Lf = levels[-1]
-    r = np.random.default_rng(7).standard_normal(Lf.n)
-    ez = rel_err(apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
-    bref = Lf.rhs_constant if rhs_kind == 0 else Lf.rhs_function(ho.gaussian_load(oracle, Lf.mass_coefficient), oracle.gaussian_solution)
-    xref, itref, hist = oracle.pcg(Lf.A, bref, mg.vcycle, 1e-4)
-    b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
-    h.fine_operator.rhs(b, rhs_kind)
-    eb = np.abs(b.to_host() - bref).max() / np.abs(bref).max()
-    it, res = mgamd.solve_cg(h.fine_operator, h.mg, x, b, 1e-4)
-    ex = rel_err(x.to_host(), xref)
-    print(f"{tag}: V-cycle {ez:.2e}, rhs {eb:.2e}, CG iterations {it} (oracle {itref}), iterate {ex:.2e}")
-    assert ez < TOL_CYCLE
-    assert eb < 1e-12
-    assert it == itref
-    assert ex < TOL_SOL
-    return x, xref
-
-
 @pytest.mark.parametrize("case", [("quadrant", 3, 4, "HMG-global"), ("quadrant", 3, 4, "PMG"), ("quadrant", 3, 4, "HPMG"),
                                   ("hypercube", 5, 1, "HMG-global")], ids=lambda c: "-".join(map(str, c)))
 @pytest.mark.parametrize("sigma", SIGMAS)
@@ -168,7 +81,7 @@ def test_vcycle_and_cg(mgamd, oracle, emu, ctx, case, sigma):
     geo, L, p, mg_type = case
     h = mgamd.Hierarchy(ctx, geo, L, p, mg_type, coarse_solver="amg", max_brick=0, mass_coefficient=sigma)
     assert all(op.mass_coefficient() == sigma for op in h.operators)
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} sigma={sigma}")
 
 
@@ -183,7 +96,7 @@ def test_fused_transfers_under_the_mass_term(mgamd, oracle, emu, ctx, sigma, mon
     h0 = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", max_brick=0, mass_coefficient=sigma)
     monkeypatch.delenv("MGAMD_NO_FUSED_TRANSFER")
     assert sum(t.n_fused_bricks() for t in h0.transfers[1:]) == 0
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} sigma={sigma} fused")
     r = np.random.default_rng(11).standard_normal(levels[-1].n)
     z, z0 = apply_nan(mgamd, ctx, h.mg.vmult, r), apply_nan(mgamd, ctx, h0.mg.vmult, r)
@@ -202,7 +115,7 @@ def test_collapsed_coarse_levels(mgamd, oracle, emu, ctx, sigma, monkeypatch):
     monkeypatch.delenv("MGAMD_COLLAPSE_MAX_DOFS")
     assert ha.mg.set_collapse(True) > 0 and hb.mg.set_collapse(True) == 0
     for h, tag in ((ha, "collapsed"), (hb, "kernel by kernel")):
-        levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+        levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
         vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} sigma={sigma} {tag}")
 
 
@@ -211,8 +124,8 @@ def test_gaussian_simulation_type(mgamd, oracle, emu, ctx, sigma):
     """load -Laplace u_g + sigma u_g, Dirichlet lifting with K + sigma M, solve, constraints.distribute"""
     case = ("quadrant", 3, 4, "HMG-global")
     h = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", max_brick=0, mass_coefficient=sigma)
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
-    x, xref = vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"Gaussian {case} sigma={sigma}", rhs_kind=1)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
+    _, x, xref = vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"Gaussian {case} sigma={sigma}", rhs_kind=1)
     h.fine_operator.distribute(x, 1)
     assert rel_err(x.to_host(), levels[-1].distribute(xref, oracle.gaussian_solution)) < 10 * TOL_SOL
 
@@ -229,7 +142,7 @@ def test_pmg_with_amg_coarse_solver(mgamd, oracle, ctx, L):
     sigma, case = 7.5, ("annulus", L, 2, "PMG")
     h = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", coarse_n_cycles=2, mass_coefficient=sigma)
     assert h.mg.coarse_solver_used() == ("amg" if L == 6 else "direct")
-    levels, P = ho.build_hierarchy(oracle, sigma, *case, numbering_keys=[d.keys() for d in h.dofs])
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     A0 = ao.csr(*h.dofs[0].matrix())
     assert abs(A0 - levels[0].A).max() <= 1e-13 * abs(levels[0].A).max()
     mg = oracle.Multigrid(levels, P, 3, coarse=ao.SmoothedAggregation(h.dofs[0].matrix()).precondition(2) if L == 6 else "direct")
@@ -255,7 +168,7 @@ def test_assembled_matrix_amg_and_cg(mgamd, oracle, ctx, sigma):
     h = mgamd.Hierarchy(ctx, geo, L, p, "AMG", mass_coefficient=sigma)
     d = h.dofs[0]
     assert d.mass_coefficient() == sigma and h.fine_operator.mass_coefficient() == sigma
-    lv = ho.level(oracle, sigma, d, geo, L, p)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma))
     x = np.random.default_rng(4).standard_normal(lv.n)
     assert rel_err(apply_nan(mgamd, ctx, h.system_matrix.vmult, x), lv.A @ x) < TOL_OP
     o = ao.SmoothedAggregation(d.matrix())
@@ -275,7 +188,7 @@ def test_float_levels(mgamd, oracle, emu, ctx, sigma):
     outer cap); the outer CG needs the FP64 count"""
     case = ("quadrant", 3, 4, "HMG-global")
     h = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", number_type=mgamd.F32, max_brick=0, mass_coefficient=sigma)
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     rng = np.random.default_rng(21)
     for l, op in enumerate(h.operators):
         lv = levels[l]
@@ -310,7 +223,7 @@ def test_two_simulated_ranks(mgamd, oracle, monkeypatch):
     """quadrant L=4 p=2 HMG-global cut over two ranks (host threads over the in-process communicator)"""
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # the sharded path's start vector hashes the DoF key; the oracle takes the same
     sigma, case, n_ranks = 7.5, ("quadrant", 4, 2, "HMG-global"), 2
-    levels, P = ho.build_hierarchy(oracle, sigma, *case)
+    levels, P = su.oracle_hierarchy(None, case, Problem(sigma))
     omg = oracle.Multigrid(levels, P, 3, coarse="direct", start_vectors=[oracle.key_hash_start_vector(lv) for lv in levels])
     Lf = levels[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(Lf.keys)}
@@ -357,25 +270,6 @@ def test_two_simulated_ranks(mgamd, oracle, monkeypatch):
 
 
 # ------------------------------------------------------------------ sigma = 0 is today's code path
-def atomic_contributions(d):
-    """per DoF, how many partial sums the operator kernels add into it with floating-point atomics: one per slot (brick, family
-    or single cell) that has the DoF on its shell, counted from the cell -> slot and cell -> DoF tables; 0 for slot-interior DoFs,
-    which one thread completes, and for constrained DoFs (identity rows)"""
-    grp, slot = d.cell_slots()
-    cd = d.cell_dofs()
-    pairs = set()
-    for c in range(len(grp)):
-        for g in cd[c]:
-            if g != 0xFFFFFFFF:
-                pairs.add((int(g), int(grp[c]), int(slot[c])))
-    cnt = np.zeros(d.n_dofs, np.int64)
-    for g, _, _ in pairs:
-        cnt[g] += 1
-    cnt[:d.info.n_interior] = 0
-    cnt[d.info.n_interior + d.info.n_tail:] = 0
-    return cnt
-
-
 @pytest.mark.parametrize("geo", ["quadrant", "hypercube"])
 def test_sigma_zero_is_bitwise_the_laplace_path(mgamd, ctx, geo):
     """mass_coefficient=0.0 passed explicitly and the argument left out, L=3 p=4.  vmult and the stored inverse diagonal are
@@ -452,8 +346,6 @@ def test_operator_reports_what_it_was_built_with(mgamd, ctx):
 def test_harness_mass_coefficient(oracle, tmp_path):
     """input_0003.json (octant, NRefGlobal 3, p = 4, HMG-global) with "MassCoefficient": 7.5: the helper's iteration count, the
     table unchanged in columns and order, the value echoed; a local-smoothing Type: "not implemented", exit code 1"""
-    from test_harness_gpu import BIN, GOLDEN, REFERENCE_COLUMNS, final_table, run_harness
-
     base = json.load(open(os.path.join(GOLDEN, "input_0003.json")))
     f = str(tmp_path / "mass.json")
     json.dump(dict(base, MassCoefficient=7.5), open(f, "w"))
@@ -466,10 +358,7 @@ def test_harness_mass_coefficient(oracle, tmp_path):
                                                "dofs_per_s_per_vcycle", "coarse_solver"]
     case = (base["GeometryType"], int(base["NRefGlobal"]), int(base["Degree"]), base["Type"])
     assert case == ("quadrant", 3, 4, "HMG-global")
-    if case in _hier:
-        levels, P = _hier[case][1], _hier[case][2]  # (iteration counts do not depend on the numbering)
-    else:
-        levels, P = ho.build_hierarchy(oracle, 7.5, *case)
+    levels, P = su.oracle_hierarchy(None, case, Problem(7.5))  # (iteration counts do not depend on the numbering)
     itref = oracle.pcg(levels[-1].A, levels[-1].rhs_constant, oracle.Multigrid(levels, P, 3, coarse="direct").vcycle, 1e-4)[1]
     print(f"harness MassCoefficient 7.5: n_iterations {rows[0]['n_iterations']}, helper {itref}")
     assert int(rows[0]["n_iterations"]) == itref

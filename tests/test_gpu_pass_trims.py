@@ -19,8 +19,8 @@ import sys
 import numpy as np
 import pytest
 
-import coefficient_oracle as co
-import test_gpu_helmholtz as th
+import physics_oracle as po
+import support as su
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -77,14 +77,14 @@ def test_accumulator_left_clean(mgamd, ctx, hierarchies, case):
     h, ref = hierarchies(case)
     n = h.n_dofs
     r = np.random.default_rng(7).standard_normal(n)
-    z1 = th.apply_nan(mgamd, ctx, h.mg.vmult, r)
+    z1 = su.apply_nan(mgamd, ctx, h.mg.vmult, r)
     rng = np.random.default_rng(3)
     for l, op in enumerate(h.operators):  # an accumulator entry the residual pass left behind is added to A x here
         x = rng.standard_normal(h.dofs[l].n_dofs)
-        err = rel_err(th.apply_nan(mgamd, ctx, op.vmult, x), ref.A[l] @ x)
+        err = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), ref.A[l] @ x)
         print(f"{case} level {l}: vmult after a V-cycle rel.err {err:.2e}")
         assert err <= TOL_OP
-    z2 = th.apply_nan(mgamd, ctx, h.mg.vmult, r)
+    z2 = su.apply_nan(mgamd, ctx, h.mg.vmult, r)
     err = rel_err(z2, z1)
     print(f"{case}: second V-cycle against the first {err:.2e}")
     assert err <= 1e-14
@@ -97,7 +97,7 @@ def test_cycle_unchanged(mgamd, oracle, ctx, hierarchies, case):
         assert s.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev[l], rel=1e-9)
     n = h.n_dofs
     r = np.random.default_rng(7).standard_normal(n)
-    err = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), ref.mg.vcycle(r))
+    err = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), ref.mg.vcycle(r))
     print(f"{case}: V-cycle rel.err {err:.2e}")
     assert err <= TOL_CYCLE
     # zero-start vmult (MODE_CHEB_FIRST, MODE_CHEB_SECOND, MODE_CHEB) and step, on the finest level (code table) and on the
@@ -110,7 +110,7 @@ def test_cycle_unchanged(mgamd, oracle, ctx, hierarchies, case):
             cref = oracle.Chebyshev(ref.A[l], ref.inv_diag[l], degree, 20.0, 20)
             assert ch.eigenvalue_estimates()[1] == pytest.approx(cref.max_ev, rel=1e-10)
             b, x0 = rng.standard_normal(nl), rng.standard_normal(nl)
-            ev = rel_err(th.apply_nan(mgamd, ctx, ch.vmult, b), cref.vmult(b))
+            ev = rel_err(su.apply_nan(mgamd, ctx, ch.vmult, b), cref.vmult(b))
             vx, vb = op.initialize_dof_vector().from_host(x0), op.initialize_dof_vector().from_host(b)
             ch.step(vx, vb)
             es = rel_err(vx.to_host(), cref.step(x0, b))
@@ -142,9 +142,9 @@ def test_several_bricks_per_persistent_workgroup(tmp_path):
 
 def test_code_255_on_the_shell_of_a_brick(mgamd, oracle, ctx):
     """quadrant L=4 p=4 with a coefficient that is 2 on the cells of the one 17-point brick and differs from cell to cell around it
-    (coefficient_oracle.per_cell): the shell entries of the brick carry more than 255 distinct D^-1 values (278 measured), so
+    (physics_oracle.per_cell): the shell entries of the brick carry more than 255 distinct D^-1 values (278 measured), so
     whatever the 255 table entries of the level are, some of the brick's shell DoFs have code 255 and whoever reads D^-1 through
-    the codes -- tail_kernel today -- reads the vector for them.  V-cycle against tests/coefficient_oracle.py."""
+    the codes -- tail_kernel today -- reads the vector for them.  V-cycle against oracle/physics_oracle.py."""
     import f32_emulation as emu
 
     case = ("quadrant", 4, 4, "HMG-global")
@@ -152,14 +152,14 @@ def test_code_255_on_the_shell_of_a_brick(mgamd, oracle, ctx):
     grp, _ = plain.cell_slots()
     B = list(plain.info.group_B)
     t = mgamd.Triangulation("quadrant", 4)
-    cells = co.product_cells(t)
+    cells = po.product_cells(t)
     in_brick = {c for c, g in zip(cells, grp) if B[int(g)] == 4}
     assert len(in_brick) == 64
 
     def field(cell):
-        return 2.0 if tuple(cell) in in_brick else co.per_cell(cell)
+        return 2.0 if tuple(cell) in in_brick else po.per_cell(cell)
 
-    t.set_coefficient(co.product_values(t, co.field_on(cells, field)))
+    t.set_coefficient(po.product_values(t, po.field_on(cells, field)))
     h = mgamd.Hierarchy(ctx, t, 4, 4, "HMG-global", coarse_solver="amg", max_brick=0)
     d = h.dofs[-1]
     assert (4, 1) in [tuple(g) for g in d.groups()]  # the brick survived the field
@@ -176,9 +176,9 @@ def test_code_255_on_the_shell_of_a_brick(mgamd, oracle, ctx):
     n_distinct = len(np.unique(np.round(np.log(dv[shell]) * 1e9)))
     print(f"{len(shell)} tail DoFs on the brick's shell with {n_distinct} distinct D^-1 values")
     assert n_distinct > 255
-    levels, P = co.build_hierarchy(oracle, 0.0, field, *case, numbering_keys=[dd.keys() for dd in h.dofs])
-    mg = th.injected(emu, oracle, levels, P, h)
+    levels, P = su.oracle_hierarchy(h.dofs, case, po.Problem(0.0, field))
+    mg = su.injected(emu, oracle, levels, P, h)
     r = np.random.default_rng(7).standard_normal(levels[-1].n)
-    err = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
+    err = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
     print(f"V-cycle rel.err {err:.2e}")
     assert err <= TOL_CYCLE

@@ -7,22 +7,9 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from support import key_vector, keyset, random_mesh, run_ranks
 
 pytestmark = pytest.mark.gpu
-
-
-def random_mesh(oracle, seed, n_global, rounds, fraction):
-    rng = np.random.default_rng(seed)
-    leaves = oracle.refine_global({(0, 0, 0, 0)}, n_global)
-    for _ in range(rounds):
-        cells = sorted(leaves)
-        # a random blob (cells near a random point) plus a sprinkle of single cells
-        c = rng.random(3)
-        centre = lambda cell: (np.array(cell[1:]) + 0.5) / (1 << cell[0])
-        near = [cell for cell in cells if np.linalg.norm(centre(cell) - c) < 0.3 and rng.random() < 0.7]
-        single = [cells[t] for t in rng.choice(len(cells), max(1, int(fraction * len(cells))), replace=False)]
-        leaves = oracle.refine(leaves, list(set(near) | set(single)))
-    return leaves
 
 
 # (seed, global refinements, random rounds, sprinkle fraction, degree)
@@ -81,8 +68,6 @@ def test_random_octree_through_the_whole_path(mgamd, oracle, ctx, seed, n_global
 def test_random_octree_sharded(mgamd, oracle, seed, n_global, rounds, fraction, p, n_ranks, monkeypatch):
     """the same caller-built meshes through the SHARDED path (partition of the caller's octree, halo plans, rank-local transfers,
     all-reduce onto the replicated levels) on simulated ranks, against the numpy oracle through the DoF keys"""
-    from test_gpu_distributed_sim import key_vector, keyset, run_ranks
-
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # numbering-independent Chebyshev start vector (the sharded path has no global index)
     leaves = random_mesh(oracle, seed, n_global, rounds, fraction)
     arr = np.array(sorted(leaves), dtype=np.int64)

@@ -1,6 +1,6 @@
 """Mass term, diffusion coefficient and mass operator on caller-built RANDOM octrees with coefficient fields that differ from brick
 to brick: A = K_a + sigma M through the operators of every level, Chebyshev, V-cycle and CG (HMG-global, PMG, HPMG), FP32 levels,
-the theta time stepper and simulated ranks, against the numpy oracle on the same leaves (tests/random_mesh_physics.py).
+the theta time stepper and simulated ranks, against the numpy oracle on the same leaves (oracle/physics_oracle.py).
 
 Why these fields.  The kernels that hold several slots in one workgroup (three 2^3 families, four wave-scoped cells, the p = 1
 pair and cluster launches, the per-slot D^-1 table of the persistent kernels) read the scale a h and the ratio h^2 / a by the slot
@@ -10,51 +10,33 @@ every brick.  per_family keeps the 2^3 bricks and gives every family its own val
 on a random octree consecutive slots also differ in the cell level.  assert_slots_differ computes that from the tables of every
 case and asserts it.
 
-Meshes S, M, B, R: random_mesh_physics.  sigma in {0, 7.5, 3000}.  Bounds are the project's (test_gpu_helmholtz.py): operator
+Meshes S, M, B, R: random_mesh_physics.  sigma in {0, 7.5, 3000}.  Bounds are the project's (support.py): operator
 <= 1e-13, Chebyshev <= 1e-12, V-cycle <= 1e-11, CG iterates <= 1e-10 with equal iteration counts, FP32 single kernels <= 2e-6, FP32
-V-cycle <= 16 e_ref (oracle/f32_emulation.py on the test's own levels) and <= 5e-5.  Every numpy level is built once per module
-at sigma = 0 and re-shifted."""
+V-cycle <= 16 e_ref (oracle/f32_emulation.py on the test's own levels) and <= 5e-5.  Every constraint search is made once per
+session (support.py)."""
 import numpy as np
 import pytest
 
-import coefficient_oracle as co
+import physics_oracle as po
 import random_mesh_physics as rm
-import test_gpu_helmholtz as th
+import support as su
 import time_stepping_oracle as ts
 from conftest import rel_err
-from test_gpu_coefficient import assert_level_coefficients
+from physics_oracle import Problem
+from support import (TOL_CHEB, TOL_CYCLE, TOL_F32, TOL_OP, TOL_SOL, apply_nan, assert_level_coefficients, emu, key_vector, keyset,  # noqa: F401
+                     linear_source, oracle_steps, run_ranks, run_steps)
 
 pytestmark = pytest.mark.gpu
 
 SIGMAS = [0.0, 7.5, 3000.0]
-TOL_OP, TOL_CHEB, TOL_CYCLE, TOL_SOL, TOL_F32 = th.TOL_OP, th.TOL_CHEB, th.TOL_CYCLE, th.TOL_SOL, th.TOL_F32
-apply_nan = th.apply_nan
-
-_hier = {}  # (mesh, degree, type, field) -> (keys per level, levels at sigma = 0, P)
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
 
 
 def oracle_hierarchy(oracle, name, p, mg_type, field, sigma, dofs):
-    keys = [d.keys() for d in dofs]
-    tag = (name, p, mg_type, field)
-    hit = _hier.get(tag)
-    if hit is None or not th._same_keys(hit[0], keys):
-        levels, P = rm.oracle_hierarchy(oracle, name, p, mg_type, field, 0.0, keys)
-        if hit is None:
-            _hier[tag] = (keys, levels, P)
-    else:
-        _, levels, P = hit
-    return (levels if sigma == 0.0 else co.reshift_hierarchy(levels, sigma)), P
+    return su.oracle_hierarchy_on(dofs, *rm.level_plan(oracle, name, p, mg_type), Problem(sigma, field))
 
 
 def hierarchy(mgamd, ctx, oracle, name, p, mg_type, field, sigma, **kw):
-    t = rm.tria_of(mgamd, rm.leaves_of(oracle, name), field)
+    t = su.tria_of(mgamd, rm.leaves_of(oracle, name), Problem(coefficient=field))
     h = mgamd.Hierarchy(ctx, t, None, p, mg_type, coarse_solver="amg", max_brick=0, mass_coefficient=sigma, **kw)
     assert h.mg.coarse_solver_used() == "direct"
     return h
@@ -76,7 +58,7 @@ OP_CASES = ([("S", 5, f, 0) for f in (None, "per_family", "per_cell", "octants")
 def test_operator_trio_on_every_level(mgamd, oracle, ctx, name, p, field, max_brick):
     """vmult, compute_inverse_diagonal and vmult_mass on EVERY level of the HMG-global hierarchy (the coarse levels carry restricted,
     mixed coefficients), each twice into a NaN-prefilled destination; vmult_mass against C^T Mraw C"""
-    fine = rm.tria_of(mgamd, rm.leaves_of(oracle, name), field)
+    fine = su.tria_of(mgamd, rm.leaves_of(oracle, name), Problem(coefficient=field))
     seq = mgamd.create_geometric_coarsening_sequence(fine)
     dofs = [mgamd.DoFs(t, p, max_brick) for t in seq]
     if max_brick == 0:
@@ -86,7 +68,7 @@ def test_operator_trio_on_every_level(mgamd, oracle, ctx, name, p, field, max_br
     levels0, _ = oracle_hierarchy(oracle, name, p, "HMG-global", field, 0.0, dofs)
     if field is not None:
         for t, d, lv in zip(seq, dofs, levels0):
-            assert np.abs(t.coefficient() / co.product_values(t, lv.coefficient) - 1.0).max() <= 1e-15
+            assert np.abs(t.coefficient() / po.product_values(t, lv.coefficient) - 1.0).max() <= 1e-15
             assert d.coefficient_range() == (t.coefficient().min(), t.coefficient().max())
     rng = np.random.default_rng(3)
     worst = dict(vmult=0.0, diag=0.0, mass=0.0)
@@ -95,7 +77,7 @@ def test_operator_trio_on_every_level(mgamd, oracle, ctx, name, p, field, max_br
         for sigma in SIGMAS:
             d.set_mass_coefficient(sigma)
             op = mgamd.Operator(ctx, d)
-            lv = lv0 if sigma == 0.0 else co.reshift(lv0, sigma)
+            lv = lv0 if sigma == 0.0 else po.changed(lv0, sigma=sigma)
             for trial in range(2):  # twice: a dirty tail accumulator shows in the second pass
                 x = rng.standard_normal(lv.n)
                 ev = rel_err(apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
@@ -119,12 +101,12 @@ def test_operator_trio_on_every_level(mgamd, oracle, ctx, name, p, field, max_br
                                           ("R", 1, "octants")])
 @pytest.mark.parametrize("sigma", [0.0, 7.5])
 def test_chebyshev(mgamd, oracle, ctx, name, p, field, sigma):
-    t = rm.tria_of(mgamd, rm.leaves_of(oracle, name), field)
+    t = su.tria_of(mgamd, rm.leaves_of(oracle, name), Problem(coefficient=field))
     d = mgamd.DoFs(t, p, 0)
     rm.assert_slots_differ(mgamd, name, p, field, d, t)
     d.set_mass_coefficient(sigma)
     op = mgamd.Operator(ctx, d)
-    lv = rm.oracle_level(oracle, name, p, field, sigma, d.keys())
+    lv = su.oracle_level_on(d, rm.leaves_of(oracle, name), p, Problem(sigma, field))
     ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
     assert ch.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev, rel=1e-10)
@@ -154,7 +136,7 @@ def test_vcycle_and_cg(mgamd, oracle, emu, ctx, name, p, mg_type, field, sigma):
         rm.assert_slots_differ(mgamd, name, p, field, h.dofs[-1], h.trias[-1])
     levels, P = oracle_hierarchy(oracle, name, p, mg_type, field, sigma, h.dofs)
     assert_level_coefficients(h, levels)
-    th.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{name} p={p} {mg_type} {field} sigma={sigma}")
+    su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{name} p={p} {mg_type} {field} sigma={sigma}")
 
 
 # ------------------------------------------------------------------ (d) FP32 levels
@@ -201,8 +183,6 @@ def test_float_levels(mgamd, oracle, emu, ctx, name, p):
 @pytest.mark.parametrize("theta,n_steps", [(0.5, 2), (1.0, 1)])
 def test_time_stepper(mgamd, oracle, emu, ctx, theta, n_steps):
     """Crank-Nicolson and implicit Euler steps with a source term on M p = 2 under per_family; test_gpu_time_stepping.test_source_term"""
-    from test_gpu_time_stepping import linear_source, oracle_steps, run_steps
-
     name, p, field, dt, reltol = "M", 2, "per_family", 0.02, 1e-6
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
     h = hierarchy(mgamd, ctx, oracle, name, p, "HMG-global", field, sigma)
@@ -214,7 +194,7 @@ def test_time_stepper(mgamd, oracle, emu, ctx, theta, n_steps):
     u0[lv.constrained] = 0.0
     f = linear_source(lv.n, dt)
     u, its = run_steps(mgamd, h, mgamd.TimeStepper(h.fine_operator, h.mg, theta, dt), u0, n_steps, reltol, f)
-    uref, itref = oracle_steps(oracle, lv, th.injected(emu, oracle, levels, P, h).vcycle, u0, theta, dt, n_steps, reltol, f)
+    uref, itref = oracle_steps(oracle, lv, su.injected(emu, oracle, levels, P, h).vcycle, u0, theta, dt, n_steps, reltol, f)
     err = rel_err(u, uref)
     print(f"time stepper {name} p={p} {field} theta={theta}: CG iterations {its} (oracle {itref}), iterate {err:.2e}")
     assert its == itref
@@ -226,13 +206,10 @@ def test_time_stepper(mgamd, oracle, emu, ctx, theta, n_steps):
 def test_simulated_ranks(mgamd, oracle, name, p, n_ranks, monkeypatch):
     """the sharded path (test_gpu_random_meshes.test_random_octree_sharded) under per_family and sigma = 7.5: the halo-first slot
     permutation of the local tables carries a and h^2 / a with the slot"""
-    from test_gpu_distributed_sim import key_vector, keyset, run_ranks
-
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # numbering-independent Chebyshev start vector (the sharded path has no global index)
     field, sigma = "per_family", 7.5
     leaves = rm.leaves_of(oracle, name)
-    base, P, meshes = rm.base_hierarchy(oracle, name, p, "HMG-global")
-    levels = [co.with_coefficient(lv, c, sigma) for lv, c in zip(base, rm.level_coefficients(oracle, name, field, meshes))]
+    levels, P = oracle_hierarchy(oracle, name, p, "HMG-global", field, sigma, None)
     omg = oracle.Multigrid(levels, P, 3, coarse="direct", start_vectors=[oracle.key_hash_start_vector(lv) for lv in levels])
     Lf = levels[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(Lf.keys)}
@@ -244,7 +221,7 @@ def test_simulated_ranks(mgamd, oracle, name, p, n_ranks, monkeypatch):
 
     def rank_main(rk):
         c = mgamd.Context(0)
-        h = mgamd.DistributedHierarchy(c, sim.comm(rk), rm.tria_of(mgamd, leaves, field), None, p, coarse_solver="amg", max_brick=0,
+        h = mgamd.DistributedHierarchy(c, sim.comm(rk), su.tria_of(mgamd, leaves, Problem(coefficient=field)), None, p, coarse_solver="amg", max_brick=0,
                                        min_root_dofs=0, min_subset_dofs=0, mass_coefficient=sigma)
         idx = np.array([kf[k] for k in keyset(h.dofs[-1].keys())])
         op = h.fine_operator

@@ -1,9 +1,9 @@
 """Convective (Robin) faces on the GPU: robin_face_kernel adds the face term  sum_f beta_f B_f x  into the accumulator of the tail
 rows in every operator pass (product, residual, the three Chebyshev passes, the diagonal) of both number types; the mass pass has
-none.  Everything is held against the test-side numpy oracle tests/robin_oracle.py (the re-masked levels of boundary_oracle.py plus
-the surface mass matrices; oracle/ is not edited), with the helpers and the cached numpy hierarchies of test_gpu_boundary.py.
+none.  Everything is held against the numpy oracle oracle/physics_oracle.py (the surface mass matrices of the convective faces
+in Kraw), with the helpers and the cached spaces of support.py.
 
-Setups (robin_oracle): R1 only x = +1 Dirichlet, beta = 2.5 on x = -1 (hanging nodes on quadrant) and 0.75 on y = +1; R2 no
+Setups (physics_oracle): R1 only x = +1 Dirichlet, beta = 2.5 on x = -1 (hanging nodes on quadrant) and 0.75 on y = +1; R2 no
 Dirichlet face, sigma = 0, beta = 1.5 on y = -1 and 4 on z = +1, regular only through the faces.  Bounds are the project's own:
 operator <= 1e-13, Chebyshev <= 1e-12, V-cycle <= 1e-11, CG iterates <= 1e-10 with equal iteration counts, FP32 single kernels
 <= 2e-6, FP32 V-cycle <= 16 e_ref (oracle/f32_emulation.py on the Robin levels) and <= 5e-5."""
@@ -16,56 +16,18 @@ import threading
 import numpy as np
 import pytest
 
-import boundary_oracle as bo
-import coefficient_oracle as co
-import helmholtz_oracle as ho
 import random_mesh_physics as rp
-import robin_oracle as ro
-import test_gpu_boundary as tb
-import test_gpu_helmholtz as th
+import support as su
 import time_stepping_oracle as ts
 from conftest import ROOT, rel_err
+from physics_oracle import R1, R2, Problem
+from support import GOLDEN, TOL_CHEB, TOL_CYCLE, TOL_F32, TOL_OP, TOL_SOL, emu, final_table, run_harness  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-R1, R2 = ro.R1, ro.R2
-TOL_OP, TOL_CHEB, TOL_CYCLE, TOL_SOL, TOL_F32 = 1e-13, 1e-12, 1e-11, 1e-10, 2e-6
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
-
-
-def tria(mgamd, geo, L, setup):
-    t = mgamd.Triangulation(geo, L)
-    t.set_dirichlet_faces(setup[0])
-    t.set_robin_coefficients(setup[1])
-    return t
-
-
-def oracle_level(oracle, geo, L, p, setup, d, sigma=0.0):
-    return ro.robin(tb.oracle_level(oracle, geo, L, p, setup[0], sigma, d), setup[1])
-
-
-def oracle_hierarchy(oracle, case, setup, dofs, sigma=0.0):
-    levels, P = tb.oracle_hierarchy(oracle, case, setup[0], sigma, dofs)
-    return ro.robin_hierarchy(levels, setup[1]), P
-
-
-def hierarchy(mgamd, ctx, case, setup, sigma=0.0, coarse_solver="amg", **kw):
-    geo, L, p, mg_type = case
-    h = mgamd.Hierarchy(ctx, geo, L, p, mg_type, coarse_solver=coarse_solver, max_brick=0, mass_coefficient=sigma, dirichlet_faces=setup[0],
-                        robin=setup[1], **kw)
-    assert all(np.array_equal(d.robin_coefficients(), setup[1]) for d in h.dofs)
-    assert all(np.array_equal(t.robin_coefficients(), setup[1]) for t in h.trias)
-    return h
-
 
 # ------------------------------------------------------------------ operator and inverse diagonal, both number types
-OP_CASES = [(c, s) for c in th.OP_CASES for s in ("R1", "R2")] + [(("hypercube", 5, 1, 0), "R2")]
+OP_CASES = [(c, s) for c in su.OP_CASES for s in ("R1", "R2")] + [(("hypercube", 5, 1, 0), "R2")]
 
 
 @pytest.mark.parametrize("case,setup", OP_CASES, ids=lambda c: "-".join(map(str, c)) if isinstance(c, tuple) else c)
@@ -73,8 +35,8 @@ def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, case, setup):
     """hypercube L=5 p=1 under R2 has 2 x 1024 face cells: 32 groups of 64 faces, 16 workgroups with a grid stride of 2"""
     geo, L, p, max_brick = case
     setup = {"R1": R1, "R2": R2}[setup]
-    d = mgamd.DoFs(tria(mgamd, geo, L, setup), p, max_brick)
-    lv = oracle_level(oracle, geo, L, p, setup, d)
+    d = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(0.0, None, *setup)), p, max_brick)
+    lv = su.oracle_level(d, geo, L, p, Problem(0.0, None, *setup))
     n_faces = len(d.robin_faces()[2])
     assert n_faces > 0
     rng = np.random.default_rng(3)
@@ -98,13 +60,13 @@ def test_vmult_and_inverse_diagonal(mgamd, oracle, ctx, case, setup):
 
 def test_the_mass_product_has_no_face_term(mgamd, oracle, ctx):
     geo, L, p = "quadrant", 3, 2
-    d1, d0 = mgamd.DoFs(tria(mgamd, geo, L, R1), p, 0), mgamd.DoFs(tria(mgamd, geo, L, (R1[0], np.zeros(6))), p, 0)
+    d1, d0 = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(0.0, None, *R1)), p, 0), mgamd.DoFs(su.tria(mgamd, geo, L, Problem(dirichlet_faces=R1[0])), p, 0)
     assert np.array_equal(d0.keys(), d1.keys())
     x = np.random.default_rng(13).standard_normal(d0.n_dofs)
-    a, b = (th.apply_nan(mgamd, ctx, mgamd.Operator(ctx, d).vmult_mass, x) for d in (d0, d1))
-    det = th.atomic_contributions(d0) <= 2  # (sums of three or more atomic adds do not repeat their bits: test_gpu_helmholtz)
+    a, b = (su.apply_nan(mgamd, ctx, mgamd.Operator(ctx, d).vmult_mass, x) for d in (d0, d1))
+    det = su.atomic_contributions(d0) <= 2  # (sums of three or more atomic adds do not repeat their bits: test_gpu_helmholtz)
     assert det.sum() > 0.5 * d0.n_dofs and np.array_equal(a[det], b[det]) and rel_err(a, b) < 1e-14
-    lv = oracle_level(oracle, geo, L, p, R1, d1)
+    lv = su.oracle_level(d1, geo, L, p, Problem(0.0, None, *R1))
     assert rel_err(b, ts.mass_matrix(lv) @ x) < TOL_OP
 
 
@@ -112,15 +74,15 @@ def test_the_mass_product_has_no_face_term(mgamd, oracle, ctx):
 @pytest.mark.parametrize("p", [2, 5])
 def test_chebyshev(mgamd, oracle, ctx, p):
     geo, L = "quadrant", 3
-    d = mgamd.DoFs(tria(mgamd, geo, L, R1), p, 0)
+    d = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(0.0, None, *R1)), p, 0)
     op = mgamd.Operator(ctx, d)
-    lv = oracle_level(oracle, geo, L, p, R1, d)
+    lv = su.oracle_level(d, geo, L, p, Problem(0.0, None, *R1))
     ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
     assert ch.eigenvalue_estimates()[1] == pytest.approx(ref.max_ev, rel=1e-10)
     rng = np.random.default_rng(5)
     b, x0 = rng.standard_normal(lv.n), rng.standard_normal(lv.n)
-    ev = rel_err(th.apply_nan(mgamd, ctx, ch.vmult, b), ref.vmult(b))
+    ev = rel_err(su.apply_nan(mgamd, ctx, ch.vmult, b), ref.vmult(b))
     vb, vx = op.initialize_dof_vector().from_host(b), op.initialize_dof_vector().from_host(x0)
     ch.step(vx, vb)
     es = rel_err(vx.to_host(), ref.step(x0, b))
@@ -132,9 +94,9 @@ def test_chebyshev_through_the_byte_codes(mgamd, oracle, ctx, monkeypatch):
     """hypercube L=5 p=1 under R2: 6000 and more tail rows, above the 4096 from which the tail rows, and with them the face kernel's
     x = c0 D^-1 b, read D^-1 through one-byte codes; against the oracle and against the vector read (MGAMD_NO_DINV_CODES)"""
     geo, L, p = "hypercube", 5, 1
-    d = mgamd.DoFs(tria(mgamd, geo, L, R2), p, 0)
+    d = mgamd.DoFs(su.tria(mgamd, geo, L, Problem(0.0, None, *R2)), p, 0)
     assert d.n_dofs - d.info.n_interior >= 4096
-    lv = oracle_level(oracle, geo, L, p, R2, d)
+    lv = su.oracle_level(d, geo, L, p, Problem(0.0, None, *R2))
     ref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
     b = np.random.default_rng(9).standard_normal(lv.n)
     outs = []
@@ -143,7 +105,7 @@ def test_chebyshev_through_the_byte_codes(mgamd, oracle, ctx, monkeypatch):
             monkeypatch.setenv("MGAMD_NO_DINV_CODES", "1")
         op = mgamd.Operator(ctx, d)
         ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
-        outs.append(th.apply_nan(mgamd, ctx, ch.vmult, b))
+        outs.append(su.apply_nan(mgamd, ctx, ch.vmult, b))
         assert rel_err(outs[-1], ref.vmult(b)) < TOL_CHEB
     monkeypatch.delenv("MGAMD_NO_DINV_CODES")
     assert rel_err(outs[0], outs[1]) < 1e-12
@@ -156,16 +118,16 @@ CYCLE_CASES = [(("quadrant", 3, 2, "HMG-global"), "R1"), (("quadrant", 3, 4, "HP
 @pytest.mark.parametrize("case,setup", CYCLE_CASES, ids=lambda c: "-".join(map(str, c)) if isinstance(c, tuple) else c)
 def test_vcycle_and_cg(mgamd, oracle, emu, ctx, case, setup):
     setup = {"R1": R1, "R2": R2}[setup]
-    h = hierarchy(mgamd, ctx, case, setup, coarse_solver="direct")
+    h = su.hierarchy(mgamd, ctx, case, Problem(0.0, None, *setup), max_brick=0, coarse_solver="direct")
     assert h.mg.coarse_solver_used() == "direct"
     n_fused = sum(t.n_fused_bricks() for t in h.transfers[1:])
     assert n_fused == 0  # levels with a convective face run their transfers un-fused
     if case[0] == "hypercube":  # the same meshes and mask without a convective face (sigma = 1 keeps it regular) do fuse
         h1 = mgamd.Hierarchy(ctx, *case, coarse_solver="direct", max_brick=0, mass_coefficient=1.0, dirichlet_faces=setup[0])
         assert sum(t.n_fused_bricks() for t in h1.transfers[1:]) > 0
-    levels, P = oracle_hierarchy(oracle, case, setup, h.dofs)
-    tb.check_transfers(h, levels, P, f"{case} beta={setup[1]}")
-    mg = tb.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} mask={setup[0]:#04x} beta={setup[1]} eager")
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, None, *setup))
+    su.check_transfers(h, levels, P, f"{case} beta={setup[1]}")
+    mg, _, _ = su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"{case} mask={setup[0]:#04x} beta={setup[1]} eager")
     r = np.random.default_rng(12).standard_normal(levels[-1].n)
     vr, vz = h.fine_operator.initialize_dof_vector().from_host(r), h.fine_operator.initialize_dof_vector().from_host(np.full(len(r), np.nan))
     h.mg.time_vcycles(vz, vr, 2, True)
@@ -175,7 +137,7 @@ def test_vcycle_and_cg(mgamd, oracle, emu, ctx, case, setup):
     # the stage callbacks (HIP-event stage timing): the same cycle, stages recorded (on these small hierarchies the levels are
     # collapsed into the coarse solve of the collapse level: test_gpu_parity.test_event_stage_timing)
     h.mg.stage_timing(True)
-    zs = th.apply_nan(mgamd, ctx, h.mg.vmult, r)
+    zs = su.apply_nan(mgamd, ctx, h.mg.vmult, r)
     ms = h.mg.stage_times()
     h.mg.stage_timing(False)
     assert rel_err(zs, mg.vcycle(r)) < TOL_CYCLE and (ms >= 0).all() and ms.sum() > 0
@@ -184,13 +146,13 @@ def test_vcycle_and_cg(mgamd, oracle, emu, ctx, case, setup):
 def test_coarse_solver_cg_with_chebyshev(mgamd, oracle, emu, ctx):
     """PMG on quadrant L=3 p=2 under R1: the p = 1 level with hanging nodes and convective faces is the coarse problem"""
     case, coarse = ("quadrant", 3, 2, "PMG"), "cg_with_chebyshev"
-    h = hierarchy(mgamd, ctx, case, R1, coarse_solver=coarse)
+    h = su.hierarchy(mgamd, ctx, case, Problem(0.0, None, *R1), max_brick=0, coarse_solver=coarse)
     assert h.mg.coarse_solver_used() == coarse
-    levels, P = oracle_hierarchy(oracle, case, R1, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, None, *R1))
     mg = emu.with_max_evs(oracle.Multigrid(levels, P, 3, coarse=coarse), [s.eigenvalue_estimates()[1] for s in h.smoothers])
     Lf = levels[-1]
     r = np.random.default_rng(7).standard_normal(Lf.n)
-    ez = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
+    ez = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
     xref, itref, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
@@ -208,9 +170,9 @@ def test_solve_with_amg(mgamd, oracle, ctx):
     geo, L, p = "quadrant", 3, 2
     h = mgamd.Hierarchy(ctx, geo, L, p, "AMG", dirichlet_faces=R1[0], robin=R1[1])
     d = h.dofs[0]
-    lv = oracle_level(oracle, geo, L, p, R1, d)
+    lv = su.oracle_level(d, geo, L, p, Problem(0.0, None, *R1))
     x = np.random.default_rng(4).standard_normal(lv.n)
-    assert rel_err(th.apply_nan(mgamd, ctx, h.system_matrix.vmult, x), lv.A @ x) < TOL_OP
+    assert rel_err(su.apply_nan(mgamd, ctx, h.system_matrix.vmult, x), lv.A @ x) < TOL_OP
     xref, itref, _ = oracle.pcg(lv.A, lv.rhs_constant, ao.SmoothedAggregation(d.matrix()).precondition(1), 1e-4)
     b, xv = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
@@ -225,14 +187,14 @@ def test_pmg_with_amg_coarse_solver(mgamd, oracle, ctx):
     import amg_oracle as ao
 
     case = ("annulus", 6, 2, "PMG")
-    h = hierarchy(mgamd, ctx, case, R1, coarse_n_cycles=2)
+    h = su.hierarchy(mgamd, ctx, case, Problem(0.0, None, *R1), max_brick=0, coarse_n_cycles=2)
     assert h.mg.coarse_solver_used() == "amg"
-    levels, P = oracle_hierarchy(oracle, case, R1, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, None, *R1))
     A0 = ao.csr(*h.dofs[0].matrix())
     assert abs(A0 - levels[0].A).max() <= 1e-13 * abs(levels[0].A).max()
     mg = oracle.Multigrid(levels, P, 3, coarse=ao.SmoothedAggregation(h.dofs[0].matrix()).precondition(2))
     r = np.random.default_rng(2).standard_normal(h.n_dofs)
-    err = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
+    err = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), mg.vcycle(r))
     Lf = levels[-1]
     xref, itref, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
@@ -245,15 +207,15 @@ def test_pmg_with_amg_coarse_solver(mgamd, oracle, ctx):
 # ------------------------------------------------------------------ FP32 levels
 def test_float_levels(mgamd, oracle, emu, ctx):
     case = ("quadrant", 3, 4, "HMG-global")
-    h = hierarchy(mgamd, ctx, case, R1, number_type=mgamd.F32)
-    levels, P = oracle_hierarchy(oracle, case, R1, h.dofs)
+    h = su.hierarchy(mgamd, ctx, case, Problem(0.0, None, *R1), max_brick=0, number_type=mgamd.F32)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, None, *R1))
     mg = oracle.Multigrid(levels, P, 3, coarse="direct")
     mgp = emu.with_max_evs(mg, [s.eigenvalue_estimates()[1] for s in h.smoothers])
     Lf = levels[-1]
     r = np.random.default_rng(21).standard_normal(Lf.n)
     ref = mgp.vcycle(r)
     e_ref = rel_err(emu.vcycle(mgp, r, np.float32).astype(np.float64), ref)
-    err = rel_err(th.apply_nan(mgamd, ctx, h.mg.vmult, r), ref)
+    err = rel_err(su.apply_nan(mgamd, ctx, h.mg.vmult, r), ref)
     print(f"FP32 V-cycle R1: rel.err {err:.2e}, e_ref {e_ref:.2e}, ratio {err / e_ref:.2f}")
     assert err <= 16 * e_ref and err <= 5e-5
     xref, it64, _ = oracle.pcg(Lf.A, Lf.rhs_constant, mg.vcycle, 1e-4)
@@ -270,12 +232,7 @@ def test_two_simulated_ranks(mgamd, oracle, monkeypatch):
     V-cycle and CG against the one-rank numpy oracle through the DoF keys"""
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # the sharded path's start vector hashes the DoF key; the oracle takes the same
     case, n_ranks = ("quadrant", 3, 2, "HMG-global"), 2
-    if case not in tb._hier:
-        meshes, degs = ho.level_plan(oracle, *case)
-        base = [tb.base_level(oracle, case[0], case[1], q, m) for m, q in zip(meshes, degs)]
-        tb._hier[case] = (base, bo.natural_transfers(oracle, base))
-    levels = ro.robin_hierarchy([bo.remask(oracle, lv, R1[0]) for lv in tb._hier[case][0]], R1[1])
-    P = bo.mask_transfers(tb._hier[case][1], levels)
+    levels, P = su.oracle_hierarchy(None, case, Problem(0.0, None, *R1))
     omg = oracle.Multigrid(levels, P, 3, coarse="direct", start_vectors=[oracle.key_hash_start_vector(lv) for lv in levels])
     Lf = levels[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(Lf.keys)}
@@ -327,30 +284,21 @@ def test_random_octree(mgamd, oracle, emu, ctx):
     """mesh M of random_mesh_physics at p = 2 with R1, sigma = 7.5 and the per_family coefficient: operator, inverse diagonal,
     V-cycle and CG"""
     name, p, mg_type, field, sigma = "M", 2, "HMG-global", "per_family", 7.5
-    t = rp.tria_of(mgamd, rp.leaves_of(oracle, name), field)
+    t = su.tria_of(mgamd, rp.leaves_of(oracle, name), Problem(coefficient=field))
     h = mgamd.Hierarchy(ctx, t, 0, p, mg_type, coarse_solver="amg", max_brick=0, mass_coefficient=sigma, dirichlet_faces=R1[0], robin=R1[1])
     assert np.array_equal(t.robin_coefficients(), R1[1]) and h.dofs[-1].info.n_hanging > 0
-    base, P, meshes = rp.base_hierarchy(oracle, name, p, mg_type)
-    P0 = tb._hier.setdefault(("random", name, p, mg_type), (base, bo.natural_transfers(oracle, base)))[1]
-    levels, P0 = ho.renumber_hierarchy(base, P0, [d.keys() for d in h.dofs])
-    coeffs = rp.level_coefficients(oracle, name, field, meshes)
-    levels = ro.robin_hierarchy([bo.remask(oracle, co.with_coefficient(lv, c, sigma), R1[0]) for lv, c in zip(levels, coeffs)], R1[1])
-    P = bo.mask_transfers(P0, levels)
+    levels, P = su.oracle_hierarchy_on(h.dofs, *rp.level_plan(oracle, name, p, mg_type), Problem(sigma, field, *R1))
     lv, op = levels[-1], h.fine_operator
     x = np.random.default_rng(3).standard_normal(lv.n)
     diag = op.initialize_dof_vector().from_host(np.full(lv.n, np.nan))
     op.compute_inverse_diagonal(diag)
-    ev, ed = rel_err(th.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x), rel_err(diag.to_host(), lv.inv_diag)
+    ev, ed = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x), rel_err(diag.to_host(), lv.inv_diag)
     print(f"random octree {name} p={p} {field} R1 sigma={sigma}: vmult {ev:.2e} inverse diagonal {ed:.2e}")
     assert ev < TOL_OP and ed < TOL_OP
-    tb.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"random octree {name} p={p} {field} R1 sigma={sigma}")
+    su.vcycle_and_solve(mgamd, oracle, emu, ctx, h, levels, P, f"random octree {name} p={p} {field} R1 sigma={sigma}")
 
 
 # ------------------------------------------------------------------ known answer
-def _layers(x, planes, values):
-    return np.asarray(values)[np.sum(np.asarray(x)[..., None] > np.asarray(planes), axis=-1)]
-
-
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 2), ("hypercube", 2, 3)])
 def test_convective_wall_known_answer(mgamd, oracle, ctx, geo, L, p):
     """three layers 1 | 5 | 0.2, f = 0, u = 0 on x = -1, a convective face at x = +1 with beta = 2 and u_ext = 7: the solution is q
@@ -358,13 +306,13 @@ def test_convective_wall_known_answer(mgamd, oracle, ctx, geo, L, p):
     at reltol 1e-12, then distribute: only the solver tolerance times the conditioning of these small meshes remains"""
     planes, values, beta, u_ext = [-0.5, 0.0], [1.0, 5.0, 0.2], 2.0, 7.0
     h = mgamd.Hierarchy(ctx, mgamd.Triangulation(geo, L), 0, p, "HMG-global", coarse_solver="amg", max_brick=0, dirichlet_faces=0b000001,
-                        robin={1: beta}, coefficient=lambda x, y, z: _layers(x, planes, values))
+                        robin={1: beta}, coefficient=lambda x, y, z: su.layers(x, planes, values))
     op = h.fine_operator
     b, u = op.initialize_dof_vector(), op.initialize_dof_vector()
     op.rhs_boundary_flux(b, {1: beta * u_ext})
     it, _ = mgamd.solve_cg(op, h.mg, u, b, 1e-12)
     op.distribute(u)
-    x = ho.renumber(tb.base_level(oracle, geo, L, p), h.dofs[-1].keys()).node_positions()[:, 0]
+    x = su.oracle_level(h.dofs[-1], geo, L, p).node_positions()[:, 0]
     edges = np.concatenate(([-1.0], planes, [1.0]))
     R = sum((hi - lo) / a for lo, hi, a in zip(edges[:-1], edges[1:], values))
     q = beta * u_ext / (1.0 + beta * R)
@@ -397,8 +345,8 @@ def test_a_box_with_two_convective_faces_cools(mgamd, oracle, emu, ctx):
     case, theta, dt, n_steps, reltol = ("quadrant", 3, 2, "HMG-global"), 0.5, 0.02, 5, 1e-6
     setup = (0, (0.0, 3.0, 0.0, 0.0, 1.0, 0.0))
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
-    h = hierarchy(mgamd, ctx, case, setup, sigma)
-    levels, P = oracle_hierarchy(oracle, case, setup, h.dofs, sigma)
+    h = su.hierarchy(mgamd, ctx, case, Problem(sigma, None, *setup), max_brick=0)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma, None, *setup))
     lv, op = levels[-1], h.fine_operator
     Mh = ts.mass_matrix(lv)
     u0 = 1.0 + np.random.default_rng(17).random(lv.n)
@@ -429,7 +377,7 @@ def test_device_side_refusals(mgamd, ctx):
     with pytest.raises(mgamd.MgamdError, match="singular: dirichlet_faces mask 0.*sigma = 0"):
         mgamd.Hierarchy(ctx, "quadrant", 3, 2, "HMG-global", dirichlet_faces=0)
     # one convective face makes mask 0 with sigma 0 regular: every solver entry accepts it
-    h = hierarchy(mgamd, ctx, ("quadrant", 3, 2, "HMG-global"), R2)
+    h = su.hierarchy(mgamd, ctx, ("quadrant", 3, 2, "HMG-global"), Problem(0.0, None, *R2), max_brick=0)
     op = h.fine_operator
     b, v = op.initialize_dof_vector(), op.initialize_dof_vector()
     op.rhs(b)
@@ -444,8 +392,6 @@ def test_harness_robin_coefficients(mgamd, oracle, ctx, tmp_path):
     """input_0003.json (quadrant, NRefGlobal 3, p = 4, HMG-global) with "NeumannFaces": "023" and "RobinCoefficients" on faces 0
     and 3: the CG count of the Python solve and of the oracle, the value echoed; a local-smoothing Type and a coefficient on a
     Dirichlet face: "not implemented", exit code 1"""
-    from test_harness_gpu import GOLDEN, final_table, run_harness
-
     base = json.load(open(os.path.join(GOLDEN, "input_0003.json")))
     case = (base["GeometryType"], int(base["NRefGlobal"]), int(base["Degree"]), base["Type"])
     assert case == ("quadrant", 3, 4, "HMG-global")
@@ -457,11 +403,11 @@ def test_harness_robin_coefficients(mgamd, oracle, ctx, tmp_path):
     assert "RobinCoefficients: 2.5,0,0,0.75,0,0" in out
     _, rows = final_table(out)
     number_type = mgamd.F32 if base.get("MGNumberType", "float") == "float" else mgamd.F64
-    h = hierarchy(mgamd, ctx, case, setup, number_type=number_type)
+    h = su.hierarchy(mgamd, ctx, case, Problem(0.0, None, *setup), max_brick=0, number_type=number_type)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
     it, _ = mgamd.solve_cg(h.fine_operator, h.mg, x, b, float(base.get("RelativeTolerance", 1e-4)))
-    levels, P = oracle_hierarchy(oracle, case, setup, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(0.0, None, *setup))
     itref = oracle.pcg(levels[-1].A, levels[-1].rhs_constant, oracle.Multigrid(levels, P, 3, coarse="direct").vcycle, 1e-4)[1]
     print(f"harness RobinCoefficients: n_iterations {rows[0]['n_iterations']}, Python solve {it}, oracle {itref}")
     assert int(rows[0]["n_iterations"]) == it == itref

@@ -6,8 +6,8 @@ Bounds are the project's own: operator <= 1e-13, FP32 single kernels <= 2e-6, su
 for theta >= 1/2.  The eigenmode runs stop at reltol 1e-10, where no test of the project pins counts: there the counts are held to
 +-1 of the oracle's and the result to 1e-9 = reltol x 5 steps x 2 (residual against iterate), as in the host test.
 
-Shapes: test_gpu_helmholtz.OP_CASES reach every kernel family the launch plan can choose; its numpy levels and hierarchies are
-shared through its caches (built for sigma = 7.5 and re-shifted, the mass matrix does not depend on sigma)."""
+Shapes: support.OP_CASES reach every kernel family the launch plan can choose; the numpy levels come from support.py (the mass
+matrix does not depend on sigma)."""
 import os
 import re
 import subprocess
@@ -16,35 +16,23 @@ import threading
 import numpy as np
 import pytest
 
-import helmholtz_oracle as ho
+import physics_oracle as po
+import support as su
 import time_stepping_oracle as ts
 from conftest import ROOT, rel_err
-from test_gpu_helmholtz import OP_CASES, apply_nan, injected, oracle_hierarchy, oracle_level
+from physics_oracle import Problem
+from support import OP_CASES, apply_nan, emu, injected, linear_source, oracle_steps, run_steps, vec  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TOL_OP, TOL_ORDER, TOL_SOL, TOL_F32 = 1e-13, 1e-14, 1e-10, 2e-6
-_mass, _eig = {}, {}
-
-
-@pytest.fixture(scope="module")
-def emu():
-    import f32_emulation
-
-    return f32_emulation
+_eig = {}
 
 
 def level_and_mass(oracle, geo, L, p, d):
-    """the oracle level numbered like d (any sigma) and its mass matrix, once per numbering"""
-    lv = oracle_level(oracle, 7.5, geo, L, p, d)
-    hit = _mass.get((geo, L, p))
-    if hit is None or hit[0] is not lv:
-        _mass[(geo, L, p)] = hit = (lv, ts.mass_matrix(lv))
-    return hit
-
-
-def vec(op, a):
-    return op.initialize_dof_vector().from_host(np.ascontiguousarray(a, dtype=np.float64))
+    """the oracle level numbered like d (any sigma) and its mass matrix"""
+    lv = su.oracle_level(d, geo, L, p, Problem(7.5))
+    return lv, ts.mass_matrix(lv)
 
 
 # ------------------------------------------------------------------ the mass operator
@@ -58,7 +46,7 @@ def test_vmult_mass(mgamd, oracle, ctx, geo, L, p, max_brick):
     for sigma in (0.0, 7.5):
         d.set_mass_coefficient(sigma)
         op = mgamd.Operator(ctx, d)
-        A = ho.reshift(lv, sigma).A
+        A = po.changed(lv, sigma=sigma).A
         x = np.random.default_rng(3).standard_normal(lv.n)
         for trial in range(2):  # twice in a row: the accumulator is left clean
             y = apply_nan(mgamd, ctx, op.vmult_mass, x)
@@ -108,29 +96,6 @@ def test_vmult_mass_float(mgamd, oracle, ctx, geo, L, p):
 
 
 # ------------------------------------------------------------------ the stepper
-def run_steps(mgamd, h, stepper, u0, n_steps, reltol, source=None):
-    """n steps on the GPU; source(n) -> nodal values of f at t_n.  Returns the iterate and the CG iterations per step"""
-    op = h.fine_operator
-    u, its = vec(op, u0), []
-    for n in range(n_steps):
-        if source is None:
-            it, _ = stepper.step(u, reltol=reltol)
-        else:
-            it, _ = stepper.step(u, vec(op, source(n)), vec(op, source(n + 1)), reltol=reltol)
-        its.append(it)
-    assert stepper.n_steps() == n_steps
-    return u.to_host(), its
-
-
-def oracle_steps(oracle, lv, precond, u0, theta, dt, n_steps, reltol, source=None):
-    Mh, solve = ts.mass_matrix(lv), ts.pcg_solver(oracle, lv, precond, reltol)
-    u, its = u0.copy(), []
-    for n in range(n_steps):
-        u, it = ts.theta_step(lv, u, None if source is None else source(n), None if source is None else source(n + 1), theta, dt, solve, Mh)
-        its.append(it)
-    return u, its
-
-
 @pytest.mark.parametrize("theta", [1.0, 0.5])
 @pytest.mark.parametrize("case", [("hypercube", 2, 2, "HMG-global"), ("quadrant", 3, 2, "HMG-global"), ("quadrant", 3, 4, "HMG-global"),
                                   ("quadrant", 3, 4, "PMG")], ids=lambda c: "-".join(map(str, c)))
@@ -140,7 +105,7 @@ def test_eigenmode_decay(mgamd, oracle, emu, ctx, case, theta):
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
     assert sigma == ts.mass_coefficient(theta, dt)
     h = mgamd.Hierarchy(ctx, geo, L, p, mg_type, coarse_solver="amg", max_brick=0, mass_coefficient=sigma)
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     lv = levels[-1]
     hit = _eig.get((geo, L, p))
     if hit is None or not np.array_equal(hit[0], lv.keys):
@@ -160,18 +125,13 @@ def test_eigenmode_decay(mgamd, oracle, emu, ctx, case, theta):
     assert (u[lv.constrained] == 0.0).all()
 
 
-def linear_source(n_dofs, dt):
-    f0 = np.sin(0.37 * np.arange(n_dofs)) + 0.25
-    return lambda n: (1.0 + n * dt) * f0
-
-
 @pytest.mark.parametrize("theta", [1.0, 0.5])
 @pytest.mark.parametrize("case", [("quadrant", 3, 4, "HMG-global"), ("hypercube", 5, 1, "HMG-global")], ids=lambda c: "-".join(map(str, c)))
 def test_source_term(mgamd, oracle, emu, ctx, case, theta):
     dt, n_steps, reltol = 0.02, 3, 1e-6
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
     h = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", max_brick=0, mass_coefficient=sigma)
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     lv = levels[-1]
     u0 = np.random.default_rng(17).standard_normal(lv.n)
     u0[lv.constrained] = 0.0
@@ -189,7 +149,7 @@ def test_distributed_input(mgamd, oracle, emu, ctx):
     case, theta, dt = ("quadrant", 3, 4, "HMG-global"), 0.5, 0.02
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
     h = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", max_brick=0, mass_coefficient=sigma)
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     lv, op = levels[-1], h.fine_operator
     u0 = np.random.default_rng(19).standard_normal(lv.n)
     u0[lv.constrained] = 0.0
@@ -216,7 +176,7 @@ def test_float_levels(mgamd, oracle, emu, ctx):
     sigma = mgamd.TimeStepper.mass_coefficient(theta, dt)
     h = mgamd.Hierarchy(ctx, *case, coarse_solver="amg", number_type=mgamd.F32, max_brick=0, mass_coefficient=sigma)
     assert h.fine_operator is not h.operators[-1]
-    levels, P = oracle_hierarchy(oracle, sigma, case, h.dofs)
+    levels, P = su.oracle_hierarchy(h.dofs, case, Problem(sigma))
     lv = levels[-1]
     u0 = np.random.default_rng(17).standard_normal(lv.n)
     u0[lv.constrained] = 0.0
@@ -235,7 +195,7 @@ def test_two_simulated_ranks(mgamd, oracle, monkeypatch):
     monkeypatch.setenv("MGAMD_CHEB_KEY_INIT", "1")  # the sharded path's start vector hashes the DoF key; the oracle takes the same
     case, n_ranks, theta, dt, n_steps, reltol = ("quadrant", 4, 2, "HMG-global"), 2, 1.0, 0.02, 2, 1e-6
     sigma = ts.mass_coefficient(theta, dt)
-    levels, P = ho.build_hierarchy(oracle, sigma, *case)
+    levels, P = su.oracle_hierarchy(None, case, Problem(sigma))
     omg = oracle.Multigrid(levels, P, 3, coarse="direct", start_vectors=[oracle.key_hash_start_vector(lv) for lv in levels])
     Lf = levels[-1]
     kf = {tuple(int(v) for v in k): i for i, k in enumerate(Lf.keys)}
@@ -346,7 +306,7 @@ def test_example_program(oracle):
     norms = [float(m) for m in re.findall(r"\|u\| = (\S+)", run.stdout)]
     assert len(norms) == 5, run.stdout
     theta, dt = 0.5, 0.01
-    levels, P = ho.build_hierarchy(oracle, ts.mass_coefficient(theta, dt), "hypercube", 3, 2)
+    levels, P = su.oracle_hierarchy(None, ("hypercube", 3, 2, "HMG-global"), Problem(ts.mass_coefficient(theta, dt)))
     lv = levels[-1]
     u = np.ones(lv.n)
     u[lv.constrained] = 0.0

@@ -9,30 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from support import BIN, GOLDEN, REFERENCE_COLUMNS, final_table, run_harness
 
 pytestmark = pytest.mark.gpu
-
-BIN = os.path.join(ROOT, "dealii_multigrid_amd", "bin", "multigrid_throughput")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-# ref:multigrid_throughput.cc:2328-2335 (dim..n_dofs), :1488 (sub_comm_size), :1278-1283 (n_levels..throughput),
-# :1381-1394 (stage times), :1396-1401 (transfer times); this project's additions come after them
-REFERENCE_COLUMNS = ["dim", "n_cells", "n_cells_hn", "n_cells_n", "degree", "n_ref_global", "n_ref_local", "n_dofs", "sub_comm_size",
-                     "n_levels", "n_iterations", "time", "time_cg", "throughput", "time_pre", "time_residuum", "time_res", "time_cs",
-                     "time_pro", "time_edge_pro", "time_post", "time_to_mg", "time_to_global"]
-
-
-def run_harness(*files):
-    r = subprocess.run([BIN, *files], capture_output=True, text=True, timeout=600)
-    return r.returncode, r.stdout, r.stderr
-
-
-def final_table(stdout):
-    lines = stdout.rstrip().split("\n")
-    start = max(i for i, l in enumerate(lines) if l.startswith("dim "))
-    header = lines[start].split()
-    return header, [dict(zip(header, l.split())) for l in lines[start + 1:] if l.strip()]
-
 
 def oracle_iterations(oracle, geo, L, p, mg_type="HMG-global"):
     levels, P = oracle.build_hierarchy(geo, L, p, mg_type)

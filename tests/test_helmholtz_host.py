@@ -1,11 +1,12 @@
 """The mass term on the host (no GPU): level tables carry sigma of A = K + sigma M; the assembled matrix, the Gaussian right-hand
-side and the AMG set-up follow it; what is out of scope is refused by name.  Oracle: tests/helmholtz_oracle.py."""
+side and the AMG set-up follow it; what is out of scope is refused by name.  Oracle: oracle/physics_oracle.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import helmholtz_oracle as ho
-from conftest import oracle_level
+import physics_oracle as po
+import support as su
+from physics_oracle import Problem
 
 SIGMAS = [7.5, 3000.0]  # no powers of two: a wrong power of h cannot hide; stiffness- and mass-dominated at these mesh sizes
 
@@ -20,7 +21,7 @@ def _csr(d):
 def test_assembled_matrix_is_helper_matrix(mgamd, oracle, geo, L, p, sigma):
     d = mgamd.DoFs(mgamd.Triangulation(geo, L), p, 0)
     d.set_mass_coefficient(sigma)
-    lv = ho.level(oracle, sigma, d, geo, L, p)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma))
     A = _csr(d)
     diff = (A - lv.A).tocsr()
     err = (abs(diff).max() if diff.nnz else 0.0) / abs(lv.A).max()
@@ -41,7 +42,7 @@ def test_mass_matrix_integrates_one_to_the_volume(mgamd, oracle, geo, L, p):
     A0 = _csr(d)
     d.set_mass_coefficient(sigma)
     M = (_csr(d) - A0) / sigma
-    hel = ho.level(oracle, 1.0, d, geo, L, p)
+    hel = su.oracle_level(d, geo, L, p, Problem(1.0))
     free = ~hel.constrained
     Mref = (hel.C.T @ hel.Mraw @ hel.C).tocsr()
     assert abs((M - Mref)[free][:, free]).max() <= 1e-13 * abs(Mref).max()
@@ -60,8 +61,8 @@ def test_gaussian_right_hand_side(mgamd, oracle, geo, L, p, sigma):
     d = mgamd.DoFs(mgamd.Triangulation(geo, L), p, 0)
     b0 = d.rhs_function(1)
     d.set_mass_coefficient(sigma)
-    lv = ho.level(oracle, sigma, d, geo, L, p)
-    ref = lv.rhs_function(ho.gaussian_load(oracle, sigma), oracle.gaussian_solution)
+    lv = su.oracle_level(d, geo, L, p, Problem(sigma))
+    ref = lv.rhs_function(po.gaussian_load(sigma), oracle.gaussian_solution)
     got = d.rhs_function(1)
     assert np.abs(got - ref).max() <= 1e-12 * max(np.abs(ref).max(), 1e-300)  # the bound of test_gaussian_right_hand_side_and_distribute
     assert np.abs(got - b0).max() > 1e-3 * np.abs(b0).max()  # the mass term is in it

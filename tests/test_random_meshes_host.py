@@ -1,18 +1,19 @@
 """Mass term and diffusion coefficient on caller-built random octrees, on the host (no GPU): the assembled matrix of
 A = K_a + sigma M, the constant and the Gaussian right-hand side, and the coarse coefficients of the coarsening sequence on the
-meshes M (344 cells, levels 2-4) and S (50 cells, levels 1-3) of tests/random_mesh_physics.py, against tests/coefficient_oracle.py
+meshes M (344 cells, levels 2-4) and S (50 cells, levels 1-3) of tests/random_mesh_physics.py, against oracle/physics_oracle.py
 on the same leaves through the DoF keys.  Fields: none, per_family (2^3 bricks survive, neighbouring families differ) and per_cell.
 On these meshes a coarse cell covers leaves of two or three levels, so the 8^-k weights of the mean are exercised.
 
-The numpy levels come from random_mesh_physics.oracle_hierarchy (one constraint search per mesh and degree, then permuted into the
-product's numbering); test_the_renumbered_level_is_the_level_built_directly holds that against coefficient_oracle.level_on."""
+The numpy levels come from support.oracle_level_on (one constraint search per mesh and degree, then permuted into the product's
+numbering); test_the_renumbered_level_is_the_level_built_directly holds that against a space built directly in that numbering."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
-import coefficient_oracle as co
-import helmholtz_oracle as ho
+import physics_oracle as po
 import random_mesh_physics as rm
+import support as su
+from physics_oracle import Problem
 
 SIGMAS = [0.0, 7.5, 3000.0]
 CASES = [("M", 1), ("M", 2), ("M", 3), ("M", 4), ("S", 5)]
@@ -25,16 +26,18 @@ def _csr(d):
 
 
 def _finest(oracle, name, p, field, sigma, d):
-    return rm.oracle_level(oracle, name, p, field, sigma, d.keys())
+    return su.oracle_level_on(d, rm.leaves_of(oracle, name), p, Problem(sigma, field))
 
 
 def test_the_renumbered_level_is_the_level_built_directly(mgamd, oracle):
-    """helmholtz_oracle.renumber + coefficient_oracle.with_coefficient against level_on with numbering_keys, M p = 2 per_family:
-    the same tables, the same matrices up to the order of the sums over the cells"""
+    """the level formed on the cached space renumbered to the product's tables against the level formed on a space built directly
+    with numbering_keys, M p = 2 per_family: the same tables, the same matrices up to the order of the sums over the cells; and the
+    same path on the recorded mesh against the vectors recorded from a level that was built directly"""
     name, p, field, sigma = "M", 2, "per_family", 7.5
     leaves = rm.leaves_of(oracle, name)
-    d = mgamd.DoFs(rm.tria_of(mgamd, leaves, field), p, 0)
-    a, b = _finest(oracle, name, p, field, sigma, d), co.level_on(oracle, sigma, co.FIELDS[field], d, leaves, p)
+    d = mgamd.DoFs(su.tria_of(mgamd, leaves, Problem(coefficient=field)), p, 0)
+    a = _finest(oracle, name, p, field, sigma, d)
+    b = po.Level(po.Space(leaves, p, numbering_keys=d.keys()), Problem(sigma, po.field_on(leaves, po.FIELDS[field])))
     assert a.keys == b.keys and a.key_to_dof == b.key_to_dof and np.array_equal(a.cell_dofs, b.cell_dofs)
     for attr in ("dirichlet", "hanging", "constrained"):
         assert np.array_equal(getattr(a, attr), getattr(b, attr)), attr
@@ -42,13 +45,14 @@ def test_the_renumbered_level_is_the_level_built_directly(mgamd, oracle):
         assert abs(getattr(a, attr) - getattr(b, attr)).max() <= 1e-15 * abs(getattr(b, attr)).max(), attr
     assert np.abs(a.inv_diag / b.inv_diag - 1.0).max() <= 1e-15 and np.abs(a.rhs_constant - b.rhs_constant).max() <= 1e-17
     assert a.mass_coefficient == b.mass_coefficient == sigma and a.coefficient == b.coefficient
+    su.assert_recorded(su.oracle_level(None, "quadrant", 2, 1, Problem(7.5, "octants")), "octants_sigma")
 
 
 @pytest.mark.parametrize("name,p", CASES)
 @pytest.mark.parametrize("field", FIELDS)
 def test_assembled_matrix_and_right_hand_sides(mgamd, oracle, name, p, field):
     leaves = rm.leaves_of(oracle, name)
-    t = rm.tria_of(mgamd, leaves, field)
+    t = su.tria_of(mgamd, leaves, Problem(coefficient=field))
     d = mgamd.DoFs(t, p, 0)
     if field is not None:
         rm.assert_slots_differ(mgamd, name, p, field, d, t)
@@ -58,7 +62,7 @@ def test_assembled_matrix_and_right_hand_sides(mgamd, oracle, name, p, field):
         A = _csr(d)
         diff = (A - lv.A).tocsr()
         err = (abs(diff).max() if diff.nnz else 0.0) / abs(lv.A).max()
-        ref = lv.rhs_function(ho.gaussian_load(oracle, sigma), oracle.gaussian_solution)
+        ref = lv.rhs_function(po.gaussian_load(sigma), oracle.gaussian_solution)
         eg = np.abs(d.rhs_function(1) - ref).max() / np.abs(ref).max()
         ec = np.abs(d.rhs_constant() - lv.rhs_constant).max()
         print(f"{name} p={p} {field} sigma={sigma}: matrix {err:.2e}, rhs_function(1) {eg:.2e}, rhs_constant {ec:.2e}")
@@ -75,15 +79,15 @@ def test_coarse_coefficients(mgamd, oracle, name, p, field):
     """every mesh of the product's coarsening sequence against restrict_field of the FINEST field, and coefficient_range of the
     tables built on it"""
     leaves = rm.leaves_of(oracle, name)
-    fine = rm.tria_of(mgamd, leaves, field)
-    finest = co.field_on(leaves, co.FIELDS[field])
+    fine = su.tria_of(mgamd, leaves, Problem(coefficient=field))
+    finest = po.field_on(leaves, po.FIELDS[field])
     seq = mgamd.create_geometric_coarsening_sequence(fine)
     assert [t.n_cells for t in seq] == [len(m) for m in oracle.coarsening_sequence(leaves)]
     worst, mixed = 0.0, 0
     for t in seq:
-        cells = co.product_cells(t)
+        cells = po.product_cells(t)
         cell_set = set(cells)
-        ref = co.product_values(t, co.restrict_field(finest, cells))
+        ref = po.product_values(t, po.restrict_field(finest, cells))
         worst = max(worst, np.abs(t.coefficient() / ref - 1.0).max())
         # coarse cells that cover finest leaves of more than one level: the weights 8^-k differ inside one mean
         depth = {}

@@ -1,29 +1,21 @@
 """Convective (Robin) faces on the host (no GPU): the triangulation carries six Robin coefficients, coarsening inherits them, level
 tables copy them and build the table of convective cell faces, the assembled matrix carries the face term, a convective face makes
-the pure-Neumann box regular, and what is out of scope is refused by name.  Oracle: tests/robin_oracle.py."""
+the pure-Neumann box regular, and what is out of scope is refused by name.  Oracle: oracle/physics_oracle.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
-import boundary_oracle as bo
-import helmholtz_oracle as ho
+import physics_oracle as po
 import random_mesh_physics as rp
-import robin_oracle as ro
+import support as su
+from physics_oracle import Problem
 
-SETUPS = [ro.R1, ro.R2]
-_base = {}
-
+SETUPS = [po.R1, po.R2]
 
 def _csr(d):
     ptr, col, val = d.matrix()
     return sp.csr_matrix((val, col.astype(np.int64), ptr.astype(np.int64)), shape=(d.n_dofs, d.n_dofs))
-
-
-def _base_level(oracle, geo, L, p):
-    if (geo, L, p) not in _base:
-        _base[(geo, L, p)] = ho.level_class(oracle, 0.0)(oracle.create_mesh(geo, L), p)
-    return _base[(geo, L, p)]
 
 
 def _tria(mgamd, geo, L, mask, beta):
@@ -57,7 +49,7 @@ def _check_level(d, lv, tag):
 def test_round_trip_defaults_coarsening_and_copies(mgamd):
     t = mgamd.Triangulation("quadrant", 3)
     assert np.array_equal(t.robin_coefficients(), np.zeros(6))
-    mask, beta = ro.R1
+    mask, beta = po.R1
     t.set_dirichlet_faces(mask)
     t.set_robin_coefficients(beta)
     assert np.array_equal(t.robin_coefficients(), beta)
@@ -77,7 +69,7 @@ def test_round_trip_defaults_coarsening_and_copies(mgamd):
 def test_zero_coefficients_set_explicitly_are_bit_identical(mgamd, geo, L, p):
     t0, t1 = mgamd.Triangulation(geo, L), mgamd.Triangulation(geo, L)
     for t in (t0, t1):
-        t.set_dirichlet_faces(bo.M1)
+        t.set_dirichlet_faces(po.M1)
     t1.set_robin_coefficients(np.zeros(6))
     d0, d1 = mgamd.DoFs(t0, p, 0), mgamd.DoFs(t1, p, 0)
     assert np.array_equal(d0.keys(), d1.keys()) and np.array_equal(d0.cell_dofs(), d1.cell_dofs())
@@ -93,10 +85,10 @@ def test_zero_coefficients_set_explicitly_are_bit_identical(mgamd, geo, L, p):
 def test_quadrant_against_the_oracle(mgamd, oracle, p, setup):
     mask, beta = setup
     d = mgamd.DoFs(_tria(mgamd, "quadrant", 3, mask, beta), p, 0)
-    lv = ro.robin(bo.remask(oracle, ho.renumber(_base_level(oracle, "quadrant", 3, p), d.keys()), mask, 0.0), beta)
+    lv = su.oracle_level(d, "quadrant", 3, p, Problem(0.0, None, mask, beta))
     idx, flags, scale = d.robin_faces()
     assert len(scale) > 0 and (scale > 0).all() and idx.shape == (len(scale), (p + 1) ** 2)
-    if setup is ro.R1:  # the refined corner touches x = -1: the convective face 0 carries hanging nodes, face 3 none
+    if setup is po.R1:  # the refined corner touches x = -1: the convective face 0 carries hanging nodes, face 3 none
         assert np.any(flags & 3) and np.any((flags & 3) == 0)
         k = np.array(lv.keys)[lv.hanging]
         assert np.any(k[:, 0] == 0)
@@ -104,7 +96,7 @@ def test_quadrant_against_the_oracle(mgamd, oracle, p, setup):
     else:
         assert d.info.n_dirichlet == 0 and not np.any(idx == mgamd.INVALID_DOF)
     A = _check_level(d, lv, f"quadrant 3 p={p} mask={mask:#04x} beta={beta}")
-    if setup is ro.R2:  # regular only through the faces: without them the constants are in the kernel
+    if setup is po.R2:  # regular only through the faces: without them the constants are in the kernel
         one = np.where(lv.constrained, 0.0, 1.0)
         K = _csr(mgamd.DoFs(_tria(mgamd, "quadrant", 3, mask, np.zeros(6)), p, 0))
         assert np.abs(K @ one).max() <= 1e-12 * abs(K).max() and np.abs(A @ one).max() > 1e-3 * abs(A).max()
@@ -113,7 +105,7 @@ def test_quadrant_against_the_oracle(mgamd, oracle, p, setup):
 
 def test_face_table_areas(mgamd):
     """the scales of the table are beta_f h^2: per convective face of the cube they add up to beta_f times its area 4"""
-    mask, beta = ro.R1
+    mask, beta = po.R1
     d = mgamd.DoFs(_tria(mgamd, "quadrant", 3, mask, beta), 2, 0)
     _, _, scale = d.robin_faces()
     assert scale.sum() == pytest.approx(4.0 * sum(beta), rel=1e-14)
@@ -121,20 +113,20 @@ def test_face_table_areas(mgamd):
 
 def test_random_octree_against_the_oracle(mgamd, oracle):
     name, p, sigma = "M", 2, 7.5
-    mask, beta = ro.R1
-    t = rp.tria_of(mgamd, rp.leaves_of(oracle, name), "per_family")
+    mask, beta = po.R1
+    t = su.tria_of(mgamd, rp.leaves_of(oracle, name), Problem(coefficient="per_family"))
     t.set_dirichlet_faces(mask)
     t.set_robin_coefficients(beta)
     d = mgamd.DoFs(t, p, 0)
     d.set_mass_coefficient(sigma)
     assert d.info.n_hanging > 0
-    lv = ro.robin(bo.remask(oracle, rp.oracle_level(oracle, name, p, "per_family", sigma, d.keys()), mask), beta)
+    lv = su.oracle_level_on(d, rp.leaves_of(oracle, name), p, Problem(sigma, "per_family", mask, beta))
     _check_level(d, lv, f"random octree {name} p={p} per_family sigma={sigma} R1")
 
 
 # ------------------------------------------------------------------ partitions
 def test_two_rank_partition_covers_every_boundary_face_once(mgamd):
-    mask, beta = ro.R1
+    mask, beta = po.R1
     fine = _tria(mgamd, "quadrant", 3, mask, beta)
     trias = mgamd.create_geometric_coarsening_sequence(fine)
     part = mgamd.Partition(trias, 2, 2.0, 0)
@@ -164,15 +156,15 @@ def test_refusals_by_message(mgamd):
         with pytest.raises(mgamd.MgamdError, match=r"Robin coefficient \S+ on face 2 refused: it must be finite and >= 0"):
             t.set_robin_coefficients([0, 0, bad, 0, 0, 0])
     with pytest.raises(mgamd.MgamdError, match="Robin coefficient 2.5\\d* on face 0 refused: the face is Dirichlet"):
-        t.set_robin_coefficients(ro.R1[1])  # the default mask: every face is Dirichlet
+        t.set_robin_coefficients(po.R1[1])  # the default mask: every face is Dirichlet
     with pytest.raises(mgamd.MgamdError, match="faces are 0 to 5"):
         t.set_robin_coefficients({6: 1.0})
     assert np.array_equal(t.robin_coefficients(), np.zeros(6))
-    t.set_dirichlet_faces(ro.R1[0])
-    t.set_robin_coefficients(ro.R1[1])
+    t.set_dirichlet_faces(po.R1[0])
+    t.set_robin_coefficients(po.R1[1])
     with pytest.raises(mgamd.MgamdError, match="mask 63 refused: face 0 carries the Robin coefficient 2.5"):
         t.set_dirichlet_faces(63)  # the other order
-    assert t.dirichlet_faces() == ro.R1[0]
+    assert t.dirichlet_faces() == po.R1[0]
     with pytest.raises(mgamd.MgamdError, match="level_mesh: the triangulation carries Robin coefficients"):
         t.level_mesh(1)
     with pytest.raises(mgamd.MgamdError, match="local-smoothing level tables of a triangulation with Robin coefficients"):
@@ -191,7 +183,7 @@ def test_refusals_by_message(mgamd):
 
 
 def test_sharded_amg_plans_refuse_a_global_space_with_other_robin_coefficients(mgamd):
-    mask, beta = ro.R1
+    mask, beta = po.R1
     fine = _tria(mgamd, "quadrant", 4, mask, beta)
     trias = mgamd.create_geometric_coarsening_sequence(fine)
     part = mgamd.Partition(trias, 2, 2.0, 0)
@@ -211,7 +203,7 @@ def test_a_convective_face_makes_the_neumann_box_regular(mgamd):
     d = mgamd.DoFs(t, 1, 0)
     with pytest.raises(mgamd.MgamdError, match="singular: dirichlet_faces mask 0.*sigma = 0"):
         d.amg_setup_info()
-    t.set_robin_coefficients(ro.R2[1])
+    t.set_robin_coefficients(po.R2[1])
     with pytest.raises(mgamd.MgamdError, match="singular"):
         d.amg_setup_info()  # the tables keep their copy
     d = mgamd.DoFs(t, 1, 0)
@@ -221,10 +213,6 @@ def test_a_convective_face_makes_the_neumann_box_regular(mgamd):
 
 
 # ------------------------------------------------------------------ known answer
-def _layers(x, planes, values):
-    return np.asarray(values)[np.sum(np.asarray(x)[..., None] > np.asarray(planes), axis=-1)]
-
-
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 2), ("hypercube", 2, 3)])
 def test_convective_wall_known_answer(mgamd, oracle, geo, L, p):
     """three layers 1 | 5 | 0.2 between planes that are faces of every leaf, f = 0, u = 0 on x = -1, a convective face at x = +1 with
@@ -235,11 +223,11 @@ def test_convective_wall_known_answer(mgamd, oracle, geo, L, p):
     t = mgamd.Triangulation(geo, L)
     t.set_dirichlet_faces(0b000001)
     t.set_robin_coefficients({1: beta})
-    t.set_coefficient_function(lambda x, y, z: _layers(x, planes, values))
+    t.set_coefficient_function(lambda x, y, z: su.layers(x, planes, values))
     d = mgamd.DoFs(t, p, 0)
     b = d.rhs_boundary_flux({1: beta * u_ext})
     u = d.distribute(spla.spsolve(_csr(d).tocsc(), b), 0)
-    x = ho.renumber(_base_level(oracle, geo, L, p), d.keys()).node_positions()[:, 0]
+    x = su.oracle_level(d, geo, L, p).node_positions()[:, 0]
     edges = np.concatenate(([-1.0], planes, [1.0]))
     R = sum((hi - lo) / a for lo, hi, a in zip(edges[:-1], edges[1:], values))
     q = beta * u_ext / (1.0 + beta * R)

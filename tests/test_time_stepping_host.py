@@ -9,24 +9,23 @@ lambda = 7.406, 7.406, 7.402 on the three meshes (3 pi^2 / 4 = 7.402 on the cube
 import numpy as np
 import pytest
 
-import helmholtz_oracle as ho
+import physics_oracle as po
+import support as su
 import time_stepping_oracle as ts
+from physics_oracle import Problem
 
 CASES = [("hypercube", 2, 2), ("quadrant", 3, 2), ("quadrant", 3, 4)]
 THETAS = [1.0, 0.5]
 DT, N_STEPS, RELTOL, TOL = 0.01, 5, 1e-10, 1e-9
 
-_built = {}  # case -> (levels at the sigma of THETAS[0], P, lambda, phi): one numpy hierarchy per case and module
+_eig = {}  # case -> (lambda, phi), which do not depend on sigma
 
 
 def hierarchy(oracle, case, theta):
-    if case not in _built:
-        levels, P = ho.build_hierarchy(oracle, ts.mass_coefficient(THETAS[0], DT), *case, "HMG-global")
-        _built[case] = (levels, P) + ts.lowest_eigenpair(levels[-1])
-    levels, P, lam, phi = _built[case]
-    if theta != THETAS[0]:
-        levels = ho.reshift_hierarchy(levels, ts.mass_coefficient(theta, DT))
-    return levels, P, lam, phi
+    levels, P = su.oracle_hierarchy(None, case + ("HMG-global",), Problem(ts.mass_coefficient(theta, DT)))
+    if case not in _eig:
+        _eig[case] = ts.lowest_eigenpair(levels[-1])
+    return (levels, P) + _eig[case]
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "-".join(map(str, c)))
@@ -47,7 +46,7 @@ def test_mass_matrix(oracle, case):
     if case[0] == "hypercube":
         assert one @ (lv.Mraw @ one) == pytest.approx(8.0, rel=1e-13)  # the domain has side 2
     # sigma does not enter
-    assert abs(ts.mass_matrix(ho.reshift(lv, 7.5)) - M).max() == 0.0
+    assert abs(ts.mass_matrix(po.changed(lv, sigma=7.5)) - M).max() == 0.0
 
 
 @pytest.mark.parametrize("theta", THETAS)

@@ -1,4 +1,4 @@
-"""Test-side oracle of the mass matrix and the theta time stepper: pure numpy/scipy on the levels of tests/helmholtz_oracle.py,
+"""Test-side oracle of the mass matrix and the theta time stepper: pure numpy/scipy on the levels of oracle/physics_oracle.py,
 which carry Mraw, K0raw, C, A and constrained.  Not a test module.
 
 Semi-discrete heat equation with homogeneous Dirichlet data and constraints eliminated:  M^ u' + K^ u = M^ f(t),
