@@ -19,8 +19,13 @@ namespace mgamd
   if (args.stamps && tid == 0)                 \
     args.stamps[(size_t)block * 8 + (k)] = wall_clock64();
 #define MGAMD_ABLATED(bit) (args.ablate & (bit))
+// stamp 7 of a brick of the persistent kernel: 1 + the workgroup that ran it (tools/stamps.py groups the bricks by workgroup)
+#define MGAMD_STAMP_OWNER(w)                   \
+  if (args.stamps && tid == 0)                 \
+    args.stamps[(size_t)block * 8 + 7] = (w) + 1;
 #else
 #define MGAMD_STAMP(k)
+#define MGAMD_STAMP_OWNER(w)
 #define MGAMD_ABLATED(bit) false
 #endif
 
@@ -360,10 +365,12 @@ namespace mgamd
   // 16.2 us per brick, 7.8 us of them in the gather (two DEPENDENT global round trips: slot tables -> values, at the
   // loaded-memory latency), 4.4 us in the sweeps, 3.7 us in epilogue + atomics; with 2 workgroups per CU (LDS) nothing hides
   // the gather, and removing 17 % of the kernel's HBM bytes (closed-form D^-1) changed nothing: the pass is bound by that
-  // latency chain, not by bytes.  Here workgroup w walks the slots v = w, w + stride, ... (stride = number of resident
-  // workgroups, a multiple of 8: xcd_contiguous keeps every workgroup inside the Morton range of its XCD) and runs a
-  // software pipeline over them:
-  //     top      values of slot v (requested one iteration earlier) -> LDS;  slot tables of v' = v + stride requested
+  // latency chain, not by bytes.  Here workgroup w of the `stride` resident ones (a multiple of 8) takes slot
+  // xcd_contiguous(w, n) and then whatever the ticket counter of its XCD hands it inside that XCD's Morton range (TicketSchedule,
+  // kernels_common.hpp: with the fixed walk v = w, w + stride, ... the median workgroup of a level-8 pass had finished 130 us
+  // before the last one, 14 % of the pass idle), and runs a software pipeline over its slots:
+  //     top      values of slot v (requested one iteration earlier) -> LDS;  slot tables of the next slot v' requested, the ticket
+  //              of the one after it drawn (and handed to the workgroup before the sweeps begin)
   //     sweeps   (epilogue operands of v in flight, as before)
   //     after    the VALUES of v' are requested (the registers of the sweeps are free again), then epilogue + atomics of v
   // so both round trips of the next gather overlap with work of the current slot.  D^-1 of interior DoFs always in closed
@@ -411,6 +418,13 @@ namespace mgamd
     const uint32_t n   = args.g.n_slots;
     if (w >= n)
       return;
+    // the slots after the first: by ticket (TicketSchedule).  Lane 0 draws; the ticket reaches the others through one LDS word (the
+    // 1/h entry of apply_lds_bytes, which this body does not use) behind barriers that the pipeline has anyway
+    const TicketSchedule sched(args.tickets, w, stride, n);
+    uint32_t *const      ticket_word = reinterpret_cast<uint32_t *>(dtab + 2 * P * P * P);
+    uint32_t             drawn       = 0;
+    if (sched.active && tid == 0)
+      drawn = sched.draw();
 
     if (is_cheb(MODE))
       {
@@ -468,6 +482,8 @@ namespace mgamd
         const int idx = tid + it * BLOCK;
         spos[it]      = idx < G::N_SHELL ? (int)args.g.shell_pos[idx] : -1;
       }
+    if (sched.active && tid == 0)
+      sched.publish(drawn, ticket_word);
     __syncthreads();
 
     constexpr bool x_from_b = MODE == MODE_CHEB_FIRST; // x = c0 dinv b, never stored
@@ -475,10 +491,10 @@ namespace mgamd
     // they are live across the sweeps, which is why the sweeps are streamed cell by cell (line_stream: ~35 instead of ~70
     // doubles per thread).  Requested after the sweeps, or between the y and the x sweep, they fit whole-line sweeps but expose
     // their latency (measured: no gain over the one-workgroup-per-brick kernel).
-    // slot tables of virtual block v
-    auto load_tables = [&](uint32_t v, uint32_t &slot, uint32_t &base, uint32_t(&sg)[ITERS], double &h, uint32_t &fm, uint32_t &fl,
+    // slot tables of slot s
+    auto load_tables = [&](uint32_t s, uint32_t &slot, uint32_t &base, uint32_t(&sg)[ITERS], double &h, uint32_t &fm, uint32_t &fl,
                            uint32_t(&cg)[ITC]) {
-      slot = xcd_contiguous(v, n);
+      slot = s;
       base = args.g.interior_base[slot];
       h    = args.g.h[slot];
       fm   = 0;
@@ -538,16 +554,24 @@ namespace mgamd
     uint32_t slot, base, sgi[ITERS], fmcur, flcur, cgi[ITC];
     double   hcur;
     T        xg[ITER], sval[ITERS], sb[ITERS], cval[ITC];
-    load_tables(w, slot, base, sgi, hcur, fmcur, flcur, cgi);
+    load_tables(xcd_contiguous(w, n), slot, base, sgi, hcur, fmcur, flcur, cgi);
     load_values(base, sgi, flcur, cgi, xg, sval, sb, cval);
 
-    for (uint32_t v = w;;)
+    for (;;)
       {
-        const uint32_t block    = v;
+        const uint32_t block = slot;
         (void)block;
-        const uint32_t vn       = v + stride;
-        const bool     has_next = vn < n;
+        // the next slot: the ticket published one iteration ago (or before the loop).  A workgroup draws no more after its first
+        // ticket out of range.
+        // The ticket of the slot after the next is drawn now and handed on behind the barrier under stamp 1, which every thread
+        // passes after it has taken this one: the draw rides under the gather phase, and its register is free again before the
+        // sweeps (held across the sweeps or across the epilogue it costs the 5-word modes 3 to 6 spilled VGPRs).
+        uint32_t   vn       = slot;
+        const bool has_next = sched.active && sched.take(ticket_word, vn);
+        if (has_next && tid == 0)
+          drawn = sched.draw();
         MGAMD_STAMP(0)
+        MGAMD_STAMP_OWNER(w)
         const T rh = T(1) / T(hcur);
         // Mass term: d = h (s_K + c s_M) with c = sigma h^2 of THIS slot, so the table is formed anew for every slot by its first
         // P^3 threads.  The barrier at the end of the slot loop (or the one before the loop) has every reader of the previous
@@ -682,6 +706,8 @@ namespace mgamd
               bufA[wk.pos()] = x_from_b ? args.epi.c0 * interior_dinv(wk.type()) * bv[it] : xg[it];
         }
         __syncthreads();
+        if (has_next && tid == 0)
+          sched.publish(drawn, ticket_word); // (the barrier that ends the iteration publishes it)
         MGAMD_STAMP(1)
 
         bool any_hanging = false;
@@ -808,7 +834,6 @@ namespace mgamd
         MGAMD_STAMP(4)
         if (!has_next)
           break;
-        v    = vn;
         slot  = slotn;
         base  = basen;
         hcur  = hn;
@@ -834,6 +859,7 @@ namespace mgamd
       }
   }
 #undef MGAMD_STAMP
+#undef MGAMD_STAMP_OWNER
 #undef MGAMD_ABLATED
 
   // single cells, WAVE-SCOPED: a 256-thread workgroup = four wavefronts with their own cells (64 / (p+1)^2 cells each) and their
@@ -1003,6 +1029,7 @@ namespace mgamd
         ApplyArgs<T, P> a = args.a;
         a.g               = args.g_constrained;
         a.stamps          = nullptr;
+        a.tickets += 8; // (the constrained half has a walk of its own: the second set of counters)
         lattice_apply_persistent_body<T, P, B, base_mode(MODE), true, MASS>(a, blockIdx.x, gridDim.x, smem_raw);
         __syncthreads(); // the lattice of the last constrained brick has been read by every thread
         lattice_apply_persistent_body<T, P, B, MODE, false, MASS>(args.a, blockIdx.x, gridDim.x, smem_raw);
@@ -1014,6 +1041,7 @@ namespace mgamd
         ApplyArgs<T, P> a = args.a;
         a.g               = args.g_constrained;
         a.stamps          = nullptr;
+        a.tickets += 8;
         lattice_apply_persistent_body<T, P, B, base_mode(MODE), true, MASS>(a, blockIdx.x - args.n_wg_plain, gridDim.x - args.n_wg_plain, smem_raw);
       }
   }

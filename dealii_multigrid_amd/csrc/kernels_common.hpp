@@ -37,6 +37,60 @@ namespace mgamd
     return k * q + (k < r ? k : r) + (b >> 3);
   }
 
+  // Ticket schedule of the persistent workgroups (lattice_apply_persistent_body).  Workgroup w of a grid of `stride` takes item
+  // xcd_contiguous(w, n) first, statically; every further item is handed out by a ticket counter of its XCD k = w & 7: ticket t is
+  // position W_k + t of the XCD's contiguous range of q_k items, W_k = the workgroups of the grid with w & 7 == k.  So the
+  // workgroups of an XCD work on neighbouring items whatever their speeds, and one that started late or runs slowly simply takes
+  // fewer.  A workgroup stops after its first ticket that is out of range, so a launch draws exactly (q_k - W_k) + W_k = q_k
+  // tickets from counter k (q_k >= W_k because n > stride).  The draw is a wrapping increment (atomicInc with the bound q_k - 1):
+  // the last draw of the launch, and only it, finds q_k - 1 and leaves 0.  Nobody touches the counter after it in this launch, and
+  // the end of the kernel publishes the value to the next launch: no memset, no host code between launches (graph replay).
+  // n <= stride: every item is somebody's first one, and no counter is touched.
+  // (A fetch-add with a store of 0 by the last drawer does the same, but the compiler rewrites a fetch-add on a uniform address
+  // into a one-lane add whose result it broadcasts at once, behind `s_waitcnt vmcnt(0)`: the round trip of the draw and every load
+  // in flight were waited for at the top of each iteration, +0.8 us per brick in the stamps.  It leaves the increment alone.)
+  // The counter is only ever accessed with device-scope atomics: w & 7 being the XCD is a matter of locality, not correctness.
+  // Use (one lane draws, the others learn the ticket through a 4-byte LDS word behind barriers the caller has anyway):
+  //     lane 0:  t = draw();  ...  publish(t, word);   barrier;   all:  take(word, item)   barrier before the next publish
+  struct TicketSchedule
+  {
+    uint32_t *ctr;     // counter of this workgroup's XCD
+    uint32_t  first;   // item of ticket 0
+    uint32_t  n_valid; // tickets below this are items
+    uint32_t  n_draws; // draws of one launch from this counter
+    bool      active;  // n > stride
+    __device__ __forceinline__
+    TicketSchedule(uint32_t *counters, uint32_t w, uint32_t stride, uint32_t n)
+    {
+      const uint32_t k = w & 7u, q = n >> 3, r = n & 7u;
+      const uint32_t q_k = q + (k < r ? 1u : 0u), W_k = (stride - k + 7u) >> 3;
+      active  = n > stride;
+      ctr     = counters + k;
+      first   = k * q + (k < r ? k : r) + W_k;
+      n_valid = q_k - W_k; // (only read where active)
+      n_draws = q_k;
+    }
+    __device__ __forceinline__ uint32_t
+    draw() const
+    {
+      return atomicInc(ctr, n_draws - 1u); // (device scope, relaxed)
+    }
+    // the lane that drew t hands it to the workgroup
+    __device__ __forceinline__ void
+    publish(uint32_t t, uint32_t *word) const
+    {
+      *word = t;
+    }
+    // every lane, behind a barrier after publish(): the published ticket as a scalar; false = out of range (stop)
+    __device__ __forceinline__ bool
+    take(const uint32_t *word, uint32_t &item) const
+    {
+      const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)*word);
+      item             = first + t;
+      return t < n_valid;
+    }
+  };
+
   // S: the number type of the kernel that takes them as arguments (round 3: float kernels converted the double constants at every
   // use, which cost them the registers of the double kernels)
   template <int P, typename S = double>
@@ -1269,6 +1323,9 @@ namespace mgamd
     uint32_t gather_limit, scatter_limit;
     FusedTransferDev<T, P> fused; // MODE_RESIDUAL_RESTRICT / MODE_CHEB_PROLONGATE only
     double sigma = 0.0; // mass coefficient of K + sigma M (lattice_sweeps); 0: the Laplace operator
+    // persistent kernels: the 8 ticket counters of this launch (TicketSchedule; the pair kernel's constrained half uses the 8 after
+    // them), zero before and after every launch.  Owned by the LevelOperator, one set per step of its launch plan.
+    uint32_t *tickets = nullptr;
   };
   static_assert(sizeof(ApplyArgs<double, MAX_KERNEL_DEGREE>) <= KERNARG_LIMIT, "ApplyArgs exceeds the kernel-argument segment");
 

@@ -77,11 +77,18 @@ namespace mgamd
   }
 
   // a launch of PERSISTENT workgroups: at most the resident ones (per_cu on every CU), which walk the n_work items
+  // grid_cap > 0: at most that many (LevelOperator::persistent_grid_cap, a development switch)
+  inline int
+  persistent_grid(const Ctx *ctx, int n_work, int per_cu, int grid_cap)
+  {
+    const int resident = resident_workgroups(ctx, per_cu);
+    return std::min(n_work, grid_cap > 0 ? std::min(resident, grid_cap) : resident);
+  }
   template <typename A>
   inline void
-  launch_persistent(Ctx *ctx, hipStream_t st, void (*kern)(A), int n_work, int per_cu, int block, size_t lds, const A &args)
+  launch_persistent(Ctx *ctx, hipStream_t st, void (*kern)(A), int n_work, int per_cu, int block, size_t lds, const A &args, int grid_cap = 0)
   {
-    launch_lds(ctx, st, kern, std::min(n_work, resident_workgroups(ctx, per_cu)), block, lds, args);
+    launch_lds(ctx, st, kern, persistent_grid(ctx, n_work, per_cu, grid_cap), block, lds, args);
   }
 
   // f(std::integral_constant<int, V>) for the V among Vs... that equals v; false if there is none
@@ -112,7 +119,7 @@ namespace mgamd
   // one slot group: its diagonal, or one operator application with the kernel of its lattice
   template <typename T, int P, int B, int MODE, bool CONSTR = false>
   inline void
-  launch_lattice(Ctx *ctx, hipStream_t st, const ApplyArgs<T, P> &a, bool diag)
+  launch_lattice(Ctx *ctx, hipStream_t st, const ApplyArgs<T, P> &a, bool diag, int grid_cap = 0)
   {
     using G = Geo<P, B>;
     if (a.g.n_slots == 0)
@@ -140,7 +147,7 @@ namespace mgamd
         if constexpr (MODE != MODE_MASS)
           if (a.sigma != 0.0)
             kern = lattice_apply_persistent_kernel<T, P, B, MODE, CONSTR, true>;
-        launch_persistent(ctx, st, kern, grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
+        launch_persistent(ctx, st, kern, grid, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a, grid_cap);
       }
     else
       launch_lds(ctx, st, lattice_apply_kernel<T, P, B, MODE, CONSTR>, grid, G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
@@ -293,6 +300,12 @@ namespace mgamd
     DBuf<unsigned long long>                  stamps;     // debug: MGAMD_STAMPS=<mode>, 8 stamps per workgroup of the largest group
     int                                       stamp_mode = -1;
     bool                                      halo_overlap = true; // MGAMD_NO_HALO_OVERLAP=1: exchange after all slots, on the main queue
+    // Ticket counters of the persistent kernels (kernels.hpp TicketSchedule): TICKETS_PER_STEP per step of the ordinary and of the
+    // halo-overlap plan (8 for the step's bricks, 8 for the constrained partner of a pair launch), so no two launches that may be
+    // in flight together share a set.  Zeroed here once; every launch leaves its counters at zero.
+    static constexpr size_t                   TICKETS_PER_STEP = 16;
+    DBuf<uint32_t>                            ticket_counters;
+    int                                       persistent_grid_cap = 0; // development: MGAMD_PERSISTENT_GRID=<n> (at least 8), 0 = none
 
     // sharded runs: device image of the halo plan
     struct HaloDev
@@ -348,6 +361,7 @@ namespace mgamd
       LaunchKind   kind;
       GroupDev<T> *g, *partner;
       size_t       begin, end; // slots of g (the whole group except in the halo-overlap pass)
+      uint32_t    *tickets = nullptr; // this step's ticket counters in ticket_counters (persistent kernels, TicketSchedule)
     };
     struct LaunchPlan
     {
@@ -437,7 +451,20 @@ namespace mgamd
           robin->scale.upload(tables->robin_faces.scale);
           robin->n_faces = (uint32_t)tables->robin_faces.size();
         }
+      // development: fewer persistent workgroups than the resident ones, so that small meshes draw many tickets per workgroup.
+      // At least 8: the ticket schedule needs a workgroup for every one of the 8 item ranges.
+      if (const char *e = getenv("MGAMD_PERSISTENT_GRID"))
+        persistent_grid_cap = std::max(8, atoi(e));
       build_launch_plan();
+      ticket_counters.alloc(TICKETS_PER_STEP * (plan.ordinary.size() + plan.halo_slots.size() + plan.interior_slots.size()));
+      ticket_counters.zero(ctx->stream);
+      uint32_t *next_set = ticket_counters.p;
+      for (std::vector<LaunchStep> *steps : {&plan.ordinary, &plan.halo_slots, &plan.interior_slots})
+        for (LaunchStep &s : *steps)
+          {
+            s.tickets = next_set;
+            next_set += TICKETS_PER_STEP;
+          }
     }
 
     // Which kernel runs which slot group, and with whom: every merging rule of the operator's launches is here.
@@ -650,13 +677,13 @@ namespace mgamd
       const int n_wg   = (int)(pa.n_wg_plain + (uint32_t)((g_constrained->n_slots + G::SPW - 1) / G::SPW));
       if constexpr (persistent_lattice(G::N))
         {
-          if (n_wg > resident_workgroups(ctx))
+          if (n_wg > persistent_grid(ctx, n_wg, 2, persistent_grid_cap))
             pa.n_wg_plain = 0; // every workgroup walks both kinds (kernels.hpp)
           void (*kern)(BrickPairArgs<T, P>) = lattice_apply_persistent_pair_kernel<T, P, B, MODE, false>;
           if constexpr (MODE != MODE_MASS) // (launch_lattice)
             if (a.sigma != 0.0)
               kern = lattice_apply_persistent_pair_kernel<T, P, B, MODE, true>;
-          launch_persistent(ctx, st, kern, n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa);
+          launch_persistent(ctx, st, kern, n_wg, 2, G::ABLOCK, apply_lds_bytes<T, P, B>(), pa, persistent_grid_cap);
         }
       else if constexpr (MODE != base_mode(MODE))
         throw std::runtime_error("fused transfers need the persistent brick kernel");
@@ -697,7 +724,7 @@ namespace mgamd
           launch_persistent(ctx, st,
                             a.sigma != 0.0 ? lattice_apply_persistent_kernel<T, P, B, MODE, false, true> :
                                              lattice_apply_persistent_kernel<T, P, B, MODE, false, false>,
-                            (int)a.g.n_slots, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a);
+                            (int)a.g.n_slots, persistent_wgs_per_cu<T, P>(), G::ABLOCK, apply_lds_bytes<T, P, B>(), a, persistent_grid_cap);
           HIP_CHECK(hipGetLastError());
         }
       else
@@ -756,6 +783,7 @@ namespace mgamd
       GroupDev<T> *g     = s.g;
       a.g                = g->view(s.begin, s.end, MODE == MODE_MASS);
       a.stamps           = nullptr;
+      a.tickets          = s.tickets;
       if constexpr (MODE_ != MODE)
         if (fused && fused->group >= 0 && g == groups[fused->group].get())
           return launch_fused<P, MODE_>(st, a, s.begin, s.partner, *fused);
@@ -765,12 +793,12 @@ namespace mgamd
       switch (s.kind)
         {
           case K::LATTICE:
-            if (!dispatch_brick_size<P, 1, 2, 4, 8, 16>(g->B, [&](auto B) { launch_lattice<T, P, B(), MODE>(ctx, st, a, diag); }))
+            if (!dispatch_brick_size<P, 1, 2, 4, 8, 16>(g->B, [&](auto B) { launch_lattice<T, P, B(), MODE>(ctx, st, a, diag, persistent_grid_cap); }))
               throw std::runtime_error("unsupported brick size");
             break;
           case K::LATTICE_CONSTRAINED:
             if constexpr (P == 1)
-              done = dispatch_brick_size<P, 4, 8, 16>(g->B, [&](auto B) { launch_lattice<T, P, B(), MODE, true>(ctx, st, a, diag); });
+              done = dispatch_brick_size<P, 4, 8, 16>(g->B, [&](auto B) { launch_lattice<T, P, B(), MODE, true>(ctx, st, a, diag, persistent_grid_cap); });
             if (!done)
               throw std::runtime_error("constrained bricks of this size/degree are not instantiated");
             break;

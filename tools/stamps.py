@@ -24,6 +24,7 @@ ctx.synchronize()
 buf = np.zeros(8 * 70000, np.uint64); cnt = C.c_uint64()
 m._chk(m._lib.mgamd_level_op_debug_stamps(op._h, buf.ctypes.data_as(C.c_void_p), C.c_uint64(buf.size), C.byref(cnt)))
 st = buf[: cnt.value].reshape(-1, 8).astype(np.int64)
+vpos = np.nonzero(st[:, 0] > 0)[0]  # row = position v of the brick in the walk of the persistent kernel
 st = st[st[:, 0] > 0]
 t0 = st[:, 0].min()
 tick = 0.01  # us per tick (100 MHz)
@@ -43,3 +44,33 @@ print("  WG start times (us) quantiles:", [round(float(np.percentile(starts, q))
 ends = (st[:, 4] - t0) * tick
 span = ends.max()
 print(f"  avg concurrent WGs: {dur.sum()/span:.1f}  (256 CUs)")
+
+# ---- the schedule of the persistent kernel, workgroup by workgroup (bricks grouped by the workgroup that ran them) ----
+# Stamp 7 of a brick, where the build writes it, is 1 + the id of the workgroup that ran it (ticket schedule); without it the
+# bricks of workgroup w are v = w, w + grid, ... (static walk).  MGAMD_STAMPS_GRID: the grid of the launch (default: two
+# workgroups on each of 256 CUs, or the cap MGAMD_PERSISTENT_GRID).
+grid = int(os.environ.get("MGAMD_STAMPS_GRID", os.environ.get("MGAMD_PERSISTENT_GRID", "512")))
+n_bricks = int(vpos.max()) + 1
+if (st[:, 5] == 0).all() and n_bricks > grid:
+    owner = st[:, 7] - 1 if (st[:, 7] > 0).all() else vpos % grid
+    order = np.lexsort((st[:, 0], owner))
+    o, s0, s4 = owner[order], st[order, 0], st[order, 4]
+    first = np.r_[True, o[1:] != o[:-1]]
+    last = np.r_[first[1:], True]
+    wg_start, wg_end = s0[first], s4[last]
+    n_per_wg = np.diff(np.r_[np.nonzero(first)[0], len(o)])
+    gaps = np.where(first[1:], 0, s0[1:] - s4[:-1])  # stamp 4 of one brick -> stamp 0 of the workgroup's next
+    gap_sum = np.add.reduceat(np.r_[0, gaps], np.nonzero(first)[0]) * tick
+    k_start, k_end = wg_start.min(), wg_end.max()
+    q = lambda a: "min %7.2f  median %7.2f  p95 %7.2f  max %7.2f" % (a.min(), np.median(a), np.percentile(a, 95), a.max())
+    late, early = (wg_start - k_start) * tick, (k_end - wg_end) * tick
+    n_wg = len(wg_start)
+    print(f"  schedule: {n_wg} workgroups ({'stamped owner' if (st[:, 7] > 0).all() else 'v mod %d' % grid}), "
+          f"bricks per workgroup min {n_per_wg.min()} median {int(np.median(n_per_wg))} max {n_per_wg.max()}")
+    print(f"  first stamp 0 after the earliest (us): {q(late)}")
+    print(f"  last stamp 4 before the latest (us)  : {q(early)}")
+    print(f"  gaps stamp 4 -> next stamp 0, summed per workgroup (us): {q(gap_sum)}")
+    span_s = (k_end - k_start) * tick
+    print(f"  idle share: start {late.sum() / (n_wg * span_s) * 100:5.2f} %  end {early.sum() / (n_wg * span_s) * 100:5.2f} %  "
+          f"total {(late.sum() + early.sum()) / (n_wg * span_s) * 100:5.2f} % of {n_wg} x {span_s:.1f} us;  "
+          f"gaps {gap_sum.sum() / (n_wg * span_s) * 100:5.2f} %;  mean brick lifetime {dur.mean():.2f} us")
