@@ -6,6 +6,8 @@ Tolerances are FP64 rounding-level (north_star: solution within a stated FP64 to
 import numpy as np
 import pytest
 
+import polynomial_exactness as pe
+import support as su
 from conftest import oracle_level, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -249,6 +251,16 @@ def test_size_independent_properties_at_scale(mgamd, ctx):
         assert rel_err(Aw.to_host(), 2.0 * Au.to_host() - 3.0 * Av.to_host()) < 1e-13  # linearity
         first_c = d.info.n_interior + d.info.n_tail
         assert np.array_equal(Au.to_host()[first_c:], u[first_c:])  # identity rows (ref:include/operator.h:170-172)
+        # and a known answer at this size: a harmonic polynomial of Q_p has zero rows (tests/polynomial_exactness.py, identity 1)
+        free = np.arange(n) < first_c
+        h = pe.harmonic(p)(*d.node_positions().T)
+        y = su.apply_nan(mgamd, ctx, op.vmult, np.where(free, h, 1e30))
+        lift, dinv = op.initialize_dof_vector(), op.initialize_dof_vector()
+        op.rhs_dirichlet(lift, op.initialize_dof_vector().from_host(h))
+        op.compute_inverse_diagonal(dinv)
+        e = pe.row_figure(pe.row_residual(y, lift.to_host(), free), 1.0 / dinv.to_host()[free], h)
+        print(f"{geo} {L} p={p}: {n} DoFs, row figure of the harmonic polynomial {e:.2e}")
+        assert e <= pe.RHO * su.TOL_OP
 
 
 @pytest.mark.parametrize("geo,L,p,mg_type", [("quadrant", 3, 1, "HMG-global"), ("quadrant", 3, 4, "HMG-global"), ("annulus", 5, 2, "HMG-global"),
