@@ -123,6 +123,31 @@ class Triangulation:
         _chk(_lib.mgamd_tria_coarsen(self._h, C.byref(h)))
         return Triangulation(_handle=h)
 
+    def refine(self, flags, return_parent: bool = False):
+        """flagged refinement (mgamd_tria_refine): every leaf with a non-zero flag (one per leaf, order of cells()) is replaced by its
+        eight children, then the minimal ripple to the full 2:1 balance runs.  Children inherit the coefficient value of their
+        parent; the dirichlet_faces mask and the Robin coefficients are copied.  With return_parent also the index, per new leaf,
+        of the old leaf that is it or contains it.  MgamdError for flags None and for a flagged leaf at the deepest level."""
+        h, par = C.c_void_p(), np.zeros(0, np.uint64)
+        if flags is None:
+            _chk(_lib.mgamd_tria_refine(self._h, None, C.byref(h), None))  # (refused by name)
+            raise MgamdError("refine: flags is None")
+        fl = np.ascontiguousarray(np.asarray(flags) != 0, np.uint8)
+        if fl.shape != (self.n_cells,):
+            raise ValueError(f"refine: {fl.shape} flags for {self.n_cells} cells")
+        if return_parent:
+            # (mgamd_tria_refine: at most 8 n_cells new cells, every leaf split once)
+            par = np.zeros(8 * self.n_cells, np.uint64)
+        _chk(_lib.mgamd_tria_refine(self._h, _ptr(fl), C.byref(h), _ptr(par) if return_parent else None))
+        fine = Triangulation(_handle=h)
+        return (fine, par[:fine.n_cells].copy()) if return_parent else fine
+
+    def _face_neighbours(self):
+        """the face-neighbour table of the error indicator (mgamd_debug_tria_face_neighbours): code (n_cells, 6), nbr (n_cells, 6, 4)"""
+        code, nbr = np.zeros((self.n_cells, 6), np.uint8), np.zeros((self.n_cells, 6, 4), np.uint32)
+        _chk(_lib.mgamd_debug_tria_face_neighbours(self._h, _ptr(code), _ptr(nbr)))
+        return code, nbr
+
     def cells(self):
         n = self.n_cells
         lev = np.zeros(n, np.uint8)
@@ -195,6 +220,16 @@ class Triangulation:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.mgamd_tria_destroy(self._h)
             self._h = None
+
+
+def mark_maximum(eta, theta: float):
+    """the maximum strategy: flag every leaf with eta_K >= theta max eta (uint8, one per leaf).  A threshold keeps the exact ties of
+    a symmetric mesh together, which a fixed-number rule would cut by rounding.  An all-zero eta flags nothing."""
+    eta = np.asarray(eta, np.float64)
+    top = eta.max() if eta.size else 0.0
+    if not top > 0.0:
+        return np.zeros(eta.shape, np.uint8)
+    return (eta >= theta * top).astype(np.uint8)
 
 
 def create_geometric_coarsening_sequence(fine: Triangulation, coarse_coefficient=None):
@@ -721,6 +756,23 @@ class Operator:
     def distribute_values(self, x: Vector, g: Vector):
         """x: Dirichlet DoFs from g, then hanging DoFs from their parents, on the device (mgamd_level_op_distribute_values)"""
         _chk(_lib.mgamd_level_op_distribute_values(self._h, x._h, g._h))
+
+    def estimate_error(self, u: Vector, q=None):
+        """the jump error indicator eta_K of u per leaf, in the order of Triangulation.cells() (mgamd_level_op_estimate_error):
+        eta_K^2 = h_K / 24 sum over the faces of the integral of the squared jump of the normal flux a d_n u; q: the six boundary
+        fluxes of rhs_boundary_flux (6 values or {face: value}) for the residual q - beta u - a d_n u on the natural and convective
+        faces, None for no boundary term.  Only entries of u at free and Dirichlet DoFs are read.  Returns a host array."""
+        eta = np.zeros(self.dofs.info.n_cells, np.float64)
+        qa = None if q is None else _flux_array(q)
+        _chk(_lib.mgamd_level_op_estimate_error(self._h, u._h, None if qa is None else _ptr(qa), _ptr(eta)))
+        return eta
+
+    def _estimator_info(self):
+        """(bytes of the indicator's device tables and scratch, host milliseconds of their build, device milliseconds of the two
+        kernels of the last call); zeros before the first estimate_error (mgamd_debug_level_op_estimator_info)"""
+        b, t0, t1 = C.c_uint64(), C.c_double(), C.c_double()
+        _chk(_lib.mgamd_debug_level_op_estimator_info(self._h, C.byref(b), C.byref(t0), C.byref(t1)))
+        return b.value, t0.value, t1.value
 
     def get_system_matrix(self) -> "SparseMatrix":
         """Operator::get_trilinos_system_matrix: the assembled matrix of this operator's DoFs on the device (FP64, one rank)"""

@@ -26,4 +26,6 @@ namespace mgamd
 #undef MGAMD_INST
   // the lifting of non-zero Dirichlet data (kernels_boundary.hpp)
   template void LevelOperator<MGAMD_INST_T>::lift_P<MGAMD_INST_P>(MGAMD_INST_T *, const MGAMD_INST_T *, double, double);
+  // the jump error indicator (kernels_estimator.hpp)
+  template void LevelOperator<MGAMD_INST_T>::estimate_P<MGAMD_INST_P>(const MGAMD_INST_T *, const double *);
 } // namespace mgamd

@@ -451,6 +451,32 @@ mgamd_level_op_distribute_values(mgamd_level_op *op, mgamd_vec *x, const mgamd_v
 }
 
 int
+mgamd_level_op_estimate_error(mgamd_level_op *op, const mgamd_vec *u, const double q[6], double *eta)
+{
+  MGAMD_TRY
+  REQUIRE(op && u);
+  op->op->estimate_error(*u, q, eta); // (refuses a null eta by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_level_op_estimator_info(const mgamd_level_op *op, uint64_t *bytes, double *build_ms, double *kernel_ms)
+{
+  MGAMD_TRY
+  REQUIRE(op);
+  uint64_t b  = 0;
+  double   t0 = 0.0, t1 = 0.0;
+  op->op->estimator_info(b, t0, t1);
+  if (bytes)
+    *bytes = b;
+  if (build_ms)
+    *build_ms = t0;
+  if (kernel_ms)
+    *kernel_ms = t1;
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_debug_stamps(mgamd_level_op *op, unsigned long long *out, uint64_t max_count, uint64_t *count)
 {
   MGAMD_TRY

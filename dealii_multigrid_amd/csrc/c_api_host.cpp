@@ -447,6 +447,38 @@ mgamd_tria_coarsen(const mgamd_tria *fine, mgamd_tria **out)
 }
 
 int
+mgamd_tria_refine(const mgamd_tria *t, const uint8_t *flags, mgamd_tria **out, uint64_t *parent)
+{
+  MGAMD_TRY
+  if (!t || !out)
+    throw std::invalid_argument("null argument");
+  std::vector<uint64_t> par;
+  auto                  fine = std::make_shared<Tria>(t->tria->refine(flags, parent ? &par : nullptr)); // (refuses null flags, by name)
+  if (parent)
+    std::copy(par.begin(), par.end(), parent);
+  auto *r = new mgamd_tria;
+  r->tria = std::move(fine);
+  *out    = r;
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_tria_face_neighbours(const mgamd_tria *t, uint8_t *code, uint32_t *nbr)
+{
+  MGAMD_TRY
+  if (!t)
+    throw std::invalid_argument("null argument");
+  std::vector<uint8_t>  c;
+  std::vector<uint32_t> n;
+  t->tria->face_neighbours(c, n);
+  if (code)
+    std::copy(c.begin(), c.end(), code);
+  if (nbr)
+    std::copy(n.begin(), n.end(), nbr);
+  MGAMD_CATCH
+}
+
+int
 mgamd_tria_destroy(mgamd_tria *t)
 {
   delete t;

@@ -25,6 +25,7 @@ namespace mgamd
     std::vector<double> M, K;   // [(p+1)^2] mass / stiffness (quadrature-evaluated, exact)
     std::vector<double> m;      // [p+1] int phi_a
     std::vector<double> I[2];   // [(p+1)^2] hanging-node interpolation: I[c][a*(p+1)+b] = phi_b((x_a+c)/2)
+    std::vector<double> D[2];   // [p+1] end-point derivatives: D[c][b] = phi_b'(c), c = 0, 1 (the normal flux on a cell face)
 
     static long double
     legendre(int n, long double x, long double *dp = nullptr)
@@ -166,6 +167,12 @@ namespace mgamd
                 for (int b = 0; b < n; ++b)
                   I[c][a * n + b] = (b == a) ? 1.0 : 0.0;
             }
+        }
+      std::vector<double> val(n);
+      for (int c = 0; c < 2; ++c)
+        {
+          D[c].assign(n, 0.0);
+          lagrange(nodes, (double)c, val.data(), D[c].data());
         }
     }
 

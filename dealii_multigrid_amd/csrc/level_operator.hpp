@@ -6,6 +6,7 @@
 #include "runtime.hpp"
 #include "kernels.hpp"
 
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -344,6 +345,28 @@ namespace mgamd
       uint32_t       n_rows = 0;
     };
     std::unique_ptr<HangingDev> hanging;
+    // The jump error indicator: device images of LevelTables::EstimatorCells, the face-flux scratch [cell][6][(p+1)^2] and the
+    // result, built by the first estimate_error and freed with the operator.  An operator that is never asked for an estimate
+    // allocates nothing and launches nothing.  Per cell 4 (p+1)^3 + 48 (p+1)^2 + 128 bytes.
+    struct EstimatorDev
+    {
+      DBuf<uint32_t> idx, nbr;
+      DBuf<uint16_t> mask;
+      DBuf<double>   scale, flux, eta;
+      DBuf<uint8_t>  code;
+      uint32_t       n_cells = 0;
+      uint64_t       bytes   = 0;
+      double         build_ms = 0.0, kernel_ms = 0.0;
+      hipEvent_t     e0 = nullptr, e1 = nullptr;
+      ~EstimatorDev()
+      {
+        if (e0)
+          (void)hipEventDestroy(e0);
+        if (e1)
+          (void)hipEventDestroy(e1);
+      }
+    };
+    std::unique_ptr<EstimatorDev> estimator;
 
     // The kernel launches of one operator application, planned once (build_launch_plan): one step per launch, in launch order.
     enum class LaunchKind
@@ -1187,6 +1210,65 @@ namespace mgamd
         hipLaunchKernelGGL(hanging_rows_kernel<T>, grid_for(hanging->n_rows), 256, 0, ctx->stream, xp, hanging->ptr.p, hanging->col.p,
                            hanging->val.p, d1, hanging->n_rows);
       HIP_CHECK(hipGetLastError());
+    }
+
+    // defined in level_operator_apply.hpp, instantiated in apply_inst.hip with the operator passes: the two launches of the
+    // indicator on the device tables
+    template <int P>
+    void
+    estimate_P(const T *u, const double *q);
+
+    void
+    estimate_error(const mgamd_vec &u, const double *q, double *eta) override
+    {
+      if (comm || halo_plan)
+        throw std::invalid_argument("estimate_error: not implemented: sharded (the operator is distributed; the jumps across the cut "
+                                    "need the neighbour rank's fluxes)");
+      tables->refuse_estimate();
+      if (!eta)
+        throw std::invalid_argument("estimate_error: eta is null (a host array of n_cells values)");
+      if (u.n != n_dofs())
+        throw std::invalid_argument("estimate_error: vector size mismatch (" + std::to_string(u.n) + " for " + std::to_string(n_dofs()) + " DoFs)");
+      const T *up = u.as<T>(); // (refuses the other number type)
+      if (q)
+        tables->check_boundary_flux(q);
+      if (!estimator)
+        {
+          const auto                   t0 = std::chrono::steady_clock::now();
+          LevelTables::EstimatorCells  ec;
+          tables->build_estimator_cells(ec);
+          auto         dev = std::make_unique<EstimatorDev>();
+          const size_t n2  = (size_t)(p + 1) * (p + 1);
+          dev->idx.upload(ec.idx);
+          dev->nbr.upload(ec.nbr);
+          dev->mask.upload(ec.mask);
+          dev->scale.upload(ec.scale);
+          dev->code.upload(ec.code);
+          dev->n_cells = (uint32_t)ec.size();
+          dev->flux.alloc(ec.size() * 6 * n2);
+          dev->eta.alloc(ec.size());
+          dev->bytes = ec.bytes() + (ec.size() * 6 * n2 + ec.size()) * sizeof(double);
+          HIP_CHECK(hipEventCreate(&dev->e0));
+          HIP_CHECK(hipEventCreate(&dev->e1));
+          dev->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+          estimator     = std::move(dev);
+        }
+      HIP_CHECK(hipEventRecord(estimator->e0, ctx->stream));
+      if (!dispatch_degree(p, [&](auto P) { estimate_P<P()>(up, q); }))
+        throw std::runtime_error("degree not instantiated");
+      HIP_CHECK(hipEventRecord(estimator->e1, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(eta, estimator->eta.p, (size_t)estimator->n_cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      ctx->sync();
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, estimator->e0, estimator->e1));
+      estimator->kernel_ms = ms;
+    }
+    void
+    estimator_info(uint64_t &bytes, double &build_ms, double &kernel_ms) const override
+    {
+      bytes     = estimator ? estimator->bytes : 0;
+      build_ms  = estimator ? estimator->build_ms : 0.0;
+      kernel_ms = estimator ? estimator->kernel_ms : 0.0;
     }
 
     size_t

@@ -121,4 +121,56 @@ namespace mgamd
     HIP_CHECK(hipGetLastError());
   }
 
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::estimate_P(const T *u, const double *q)
+  {
+    constexpr int N = P + 1, N2 = N * N;
+    EstimatorDev &e = *estimator;
+    if (!e.n_cells)
+      return;
+    FaceFluxArgs<T, P> a;
+    a.idx     = e.idx.p;
+    a.mask    = e.mask.p;
+    a.scale   = e.scale.p;
+    a.code    = e.code.p;
+    a.n_cells = e.n_cells;
+    a.n_dofs  = n_dofs();
+    a.u       = u;
+    a.flux    = e.flux.p;
+    FluxJumpArgs<T, P> b;
+    b.flux    = e.flux.p;
+    b.code    = e.code.p;
+    b.nbr     = e.nbr.p;
+    b.scale   = e.scale.p;
+    b.n_cells = e.n_cells;
+    b.eta     = e.eta.p;
+    for (int i = 0; i < N; ++i)
+      {
+        a.D[i]     = tables->fe.D[0][i];
+        a.D[N + i] = tables->fe.D[1][i];
+      }
+    for (int i = 0; i < N2; ++i)
+      {
+        a.I0[i] = b.I0[i] = tables->fe.I[0][i];
+        a.I1[i] = b.I1[i] = tables->fe.I[1][i];
+        b.M[i]  = tables->fe.M[i];
+      }
+    a.natural = 0;
+    for (int f = 0; f < 6; ++f)
+      {
+        a.q[f]    = q ? q[f] : 0.0;
+        a.beta[f] = tables->robin[f];
+        if (q && !((tables->dirichlet_faces >> f) & 1))
+          a.natural |= 1u << f;
+      }
+    // two groups of cells per workgroup where there are that many: the 1D matrices are staged in LDS once per workgroup
+    const uint32_t groups_a = (e.n_cells + dirichlet_cells_per_workgroup<P>() - 1) / dirichlet_cells_per_workgroup<P>();
+    const uint32_t groups_b = (e.n_cells + jump_cells_per_workgroup<P>() - 1) / jump_cells_per_workgroup<P>();
+    hipLaunchKernelGGL((face_flux_kernel<T, P>), std::min<uint32_t>(4096u, (groups_a + 1) / 2), 256, 0, ctx->stream, a);
+    hipLaunchKernelGGL((flux_jump_kernel<T, P>), std::min<uint32_t>(4096u, (groups_b + 1) / 2), 256, 0, ctx->stream, b);
+    HIP_CHECK(hipGetLastError());
+  }
+
 } // namespace mgamd

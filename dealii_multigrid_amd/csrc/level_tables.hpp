@@ -483,6 +483,63 @@ namespace mgamd
         return mask.size();
       }
     } dirichlet_cells;
+    // Error indicator (DESIGN.md "Error indicator and refinement"): the tables of the two jump kernels, over ALL leaves in Morton
+    // order.  Not a member: the first estimate of an operator builds them (LevelOperator), nothing else pays for them.
+    //   idx    [n][n3]    as DirichletCells::idx: hanging entities resolved to the parent's DoFs, Dirichlet DoFs with their real
+    //                     index, so that only free and Dirichlet entries of the vector are read
+    //   mask   [n]        the cell's constraint mask
+    //   scale  [n][2]     a / h (the factor of the nodal normal flux) and h
+    //   code   [n][6], nbr [n][6][4]   Tria::face_neighbours
+    struct EstimatorCells
+    {
+      std::vector<uint32_t> idx, nbr;
+      std::vector<uint16_t> mask;
+      std::vector<double>   scale;
+      std::vector<uint8_t>  code;
+      size_t
+      size() const
+      {
+        return mask.size();
+      }
+      size_t
+      bytes() const
+      {
+        return idx.size() * 4 + nbr.size() * 4 + mask.size() * 2 + scale.size() * 8 + code.size();
+      }
+    };
+    bool
+    is_sharded() const
+    {
+      return owned != nullptr;
+    }
+    void
+    refuse_estimate() const
+    {
+      if (is_sharded())
+        throw std::invalid_argument("estimate_error: not implemented: sharded (the tables hold one rank's cells of a distributed level; the "
+                                    "jumps across the cut need the neighbour rank's fluxes)");
+      if (ls_level)
+        throw std::invalid_argument("estimate_error: refused on the level of a local-smoothing hierarchy (its cells cover part of the domain "
+                                    "and its refinement-edge DoFs are constrained); use the active-mesh operator");
+    }
+    void
+    build_estimator_cells(EstimatorCells &ec) const
+    {
+      refuse_estimate();
+      const int    n = p + 1, n3 = n * n * n;
+      const size_t nc = tria->cells.size();
+      ec.idx.resize(nc * n3);
+      ec.mask.assign(tria->masks.begin(), tria->masks.end());
+      ec.scale.resize(nc * 2);
+      for (size_t ci = 0; ci < nc; ++ci)
+        {
+          gather_cell(ci, &ec.idx[ci * n3], true);
+          const double h       = 2.0 / (double)(1u << tria->cells[ci].level);
+          ec.scale[2 * ci]     = coefficient_of(ci) / h;
+          ec.scale[2 * ci + 1] = h;
+        }
+      tria->face_neighbours(ec.code, ec.nbr);
+    }
     bool
     is_dirichlet_index(uint32_t gi) const
     {
@@ -1062,11 +1119,9 @@ namespace mgamd
       dirichlet_lift_add(g.data(), true, -1.0, b);
     }
 
-    // boundary load of a constant flux q[f] through every natural face f of the cube:  b_i = sum_f q_f int_{Gamma_f} phi_i.  Per
-    // boundary cell face the face nodes get q h^2 m (x) m; then C^T through the hanging-node constraints, as the volume load;
-    // constrained rows 0.  Independent of a and sigma.  A non-zero flux on a Dirichlet face is refused by name.
+    // the refusals of a boundary flux; the error indicator takes the same six constants and refuses them in the same words
     void
-    compute_rhs_boundary_flux(const double q[6], std::vector<double> &b) const
+    check_boundary_flux(const double q[6]) const
     {
       for (int f = 0; f < 6; ++f)
         {
@@ -1077,6 +1132,14 @@ namespace mgamd
                                         ") refused: the face is Dirichlet (dirichlet_faces mask " + std::to_string(dirichlet_faces) +
                                         "), a flux load needs a natural face");
         }
+    }
+    // boundary load of a constant flux q[f] through every natural face f of the cube:  b_i = sum_f q_f int_{Gamma_f} phi_i.  Per
+    // boundary cell face the face nodes get q h^2 m (x) m; then C^T through the hanging-node constraints, as the volume load;
+    // constrained rows 0.  Independent of a and sigma.  A non-zero flux on a Dirichlet face is refused by name.
+    void
+    compute_rhs_boundary_flux(const double q[6], std::vector<double> &b) const
+    {
+      check_boundary_flux(q);
       b.assign(n_dofs, 0.0);
       const int             n = p + 1, n3 = n * n * n;
       std::vector<double>   load(n3);

@@ -16,6 +16,7 @@
 #pragma once
 #include "../../include/mgamd.h"
 
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <cmath>
@@ -71,6 +72,26 @@ namespace mgamd
       auto r = std::shared_ptr<Triangulation>(new Triangulation());
       r->h.reset(t, mgamd_tria_destroy);
       r->query();
+      return r;
+    }
+    // Flagged refinement (mgamd_tria_refine; in deal.II: set_refine_flag + execute_coarsening_and_refinement): every leaf with a
+    // non-zero flag (one per leaf, order of mgamd_tria_get_cells) is replaced by its eight children, then the minimal ripple to the
+    // full 2:1 balance runs.  Children inherit their parent's coefficient value; the dirichlet_faces mask and the Robin
+    // coefficients are copied.  parent, if given, receives per new leaf the index of the old leaf that is it or contains it.
+    std::shared_ptr<Triangulation>
+    refine(const std::vector<uint8_t> &flags, std::vector<uint64_t> *parent = nullptr) const
+    {
+      if (flags.size() != n_cells)
+        throw std::runtime_error("refine: " + std::to_string(flags.size()) + " flags for " + std::to_string(n_cells) + " cells");
+      if (parent)
+        parent->assign(8 * n_cells, 0); // (mgamd_tria_refine: at most 8 n_cells new cells, every leaf split once)
+      mgamd_tria *t = nullptr;
+      check(mgamd_tria_refine(h.get(), flags.data(), &t, parent ? parent->data() : nullptr));
+      auto r = std::shared_ptr<Triangulation>(new Triangulation());
+      r->h.reset(t, mgamd_tria_destroy);
+      r->query();
+      if (parent)
+        parent->resize(r->n_cells);
       return r;
     }
     // The diffusion coefficient a > 0 of -div(a grad u) + sigma u: one value per leaf in the order of mgamd_tria_get_cells; an empty
@@ -168,6 +189,21 @@ namespace mgamd
     uint64_t                    n_cells = 0, n_cells_hn = 0;
     uint32_t                    n_levels = 0;
   };
+
+  // The maximum strategy: flag every leaf with eta_K >= theta max eta.  A threshold keeps the exact ties of a symmetric mesh
+  // together, which a fixed-number rule would cut by rounding.  An all-zero eta flags nothing, and so does an eta with a NaN in it.
+  inline std::vector<uint8_t>
+  mark_maximum(const std::vector<double> &eta, double theta)
+  {
+    double top = 0.0;
+    for (double e : eta)
+      top = std::isnan(e) ? e : std::max(top, e); // (NaN stays: std::max(NaN, x) is NaN)
+    std::vector<uint8_t> flags(eta.size(), 0);
+    if (top > 0.0)
+      for (size_t t = 0; t < eta.size(); ++t)
+        flags[t] = eta[t] >= theta * top ? 1 : 0;
+    return flags;
+  }
 
   // MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence (ref:multigrid_throughput.cc:2219-2224)
   inline std::vector<std::shared_ptr<const Triangulation>>
@@ -761,6 +797,19 @@ namespace mgamd
     distribute_values(Vector &solution, const Vector &g) const
     {
       check(mgamd_level_op_distribute_values(h.get(), solution.get(), g.get()));
+    }
+    // The jump error indicator eta_K of u per leaf, in the order of mgamd_tria_get_cells (mgamd_level_op_estimate_error; in
+    // deal.II: KellyErrorEstimator): eta_K^2 = h_K / 24 sum over the faces of the integral of the squared jump of the normal flux
+    // a d_n u.  q: the six boundary fluxes of rhs_boundary_flux for the residual q - beta u - a d_n u on natural and convective
+    // faces, nullptr for no boundary term.  Only entries of u at free and Dirichlet DoFs are read.
+    std::vector<double>
+    estimate_error(const Vector &u, const std::array<double, 6> *q = nullptr) const
+    {
+      if (!dofs)
+        throw std::runtime_error("Operator::estimate_error: reinit first");
+      std::vector<double> eta(dofs->get_triangulation().n_global_active_cells());
+      check(mgamd_level_op_estimate_error(h.get(), u.get(), q ? q->data() : nullptr, eta.data()));
+      return eta;
     }
     mgamd_level_op *
     get() const

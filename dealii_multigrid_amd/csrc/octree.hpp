@@ -261,6 +261,31 @@ namespace mgamd
     Tria
     coarsen_global() const; // one level of the geometric coarsening sequence; the coefficient goes down as the mean over each leaf,
                             // the dirichlet_faces mask and the Robin coefficients unchanged
+    // Flagged refinement (DESIGN.md "Error indicator and refinement"): every leaf t with flags[t] != 0 is replaced by its eight
+    // children, then the minimal ripple to the full 2:1 balance runs (balance_families, as in the generators); the result passes
+    // the checks of from_leaves_checked.  A child inherits its parent's coefficient value; the dirichlet_faces mask and the Robin
+    // coefficients are copied.  parent, if given, receives for every new leaf the index of the old leaf that is it or contains it.
+    // On a balanced mesh no old leaf is split more than once (a flagged cell gains one level, so a neighbour is at most two
+    // levels off and one split restores the balance); that is asserted.  std::invalid_argument for flags == nullptr and for a
+    // flagged leaf at the deepest level the keys allow.
+    Tria
+    refine(const uint8_t *flags, std::vector<uint64_t> *parent = nullptr) const;
+    // The face neighbours of every leaf (error indicator): per leaf and face f = 2 axis + side one code and up to four leaf indices.
+    //   NB_BOUNDARY                 the face lies on the boundary of the cube; no index
+    //   NB_SAME                     one neighbour of the same level: nbr[0]
+    //   NB_COARSER + (c1 | c2 << 1) one neighbour one level coarser: nbr[0]; (c1, c2) is the position of this leaf's face inside the
+    //                               neighbour's, along the lower and the higher in-face axis
+    //   NB_FINER                    four neighbours one level finer: nbr[c1 | c2 << 1] covers the quarter (c1, c2) of this leaf's face
+    enum : uint8_t
+    {
+      NB_BOUNDARY = 0,
+      NB_SAME     = 1,
+      NB_COARSER  = 2,
+      NB_FINER    = 6
+    };
+    void
+    face_neighbours(std::vector<uint8_t> &code, std::vector<uint32_t> &nbr) const; // [n_cells][6], [n_cells][6][4]
+
     // local smoothing: ALL cells of refinement level `level`, active or not (DoFHandler::distribute_mg_dofs levels)
     Tria
     level_mesh(int level) const
@@ -781,5 +806,98 @@ namespace mgamd
     std::vector<Cell> all = out, work = kept;
     balance(ls, work, all);
     return from_cells(collect(ls, all));
+  }
+
+  inline Tria
+  Tria::refine(const uint8_t *flags, std::vector<uint64_t> *parent) const
+  {
+    using namespace detail;
+    if (!flags)
+      throw std::invalid_argument("refine: flags is null (one byte per leaf, in the order of the cells)");
+    LeafSet ls;
+    ls.set.erase_all_and_reserve(cells.size() * 2);
+    for (const Cell &c : cells)
+      ls.add(c);
+    std::vector<Cell> all = cells, parents;
+    for (size_t t = 0; t < cells.size(); ++t)
+      if (flags[t])
+        {
+          const Cell c = cells[t];
+          if (c.level + 1 > LMAX - 1)
+            throw std::invalid_argument("refine: flagged leaf " + std::to_string(t) + " (level " + std::to_string(c.level) + ", " +
+                                        std::to_string(c.i) + ", " + std::to_string(c.j) + ", " + std::to_string(c.k) +
+                                        ") is at the deepest level the octree keys allow (" + std::to_string(LMAX - 1) + ")");
+          ls.remove(c);
+          Cell ch[8];
+          children(c, ch);
+          for (auto &x : ch)
+            {
+              ls.add(x);
+              all.push_back(x);
+            }
+          parents.push_back(c);
+        }
+    balance_families(ls, parents, all);
+    Tria fine            = from_leaves_checked(collect(ls, all));
+    fine.dirichlet_faces = dirichlet_faces;
+    std::copy(robin, robin + 6, fine.robin);
+    if (!coefficient.empty())
+      fine.coefficient.resize(fine.cells.size());
+    if (parent)
+      parent->resize(fine.cells.size());
+    for (size_t t = 0; t < fine.cells.size(); ++t)
+      {
+        const Cell &c  = fine.cells[t];
+        const int   at = find_leaf(c.level, c.i, c.j, c.k);
+        if (at < 0 || (int)cells[at].level + 1 < (int)c.level)
+          throw std::runtime_error("refine: an old leaf was split more than once (was the mesh 2:1 balanced?)");
+        if (parent)
+          (*parent)[t] = (uint64_t)at;
+        if (!coefficient.empty())
+          fine.coefficient[t] = coefficient[at];
+      }
+    return fine;
+  }
+
+  inline void
+  Tria::face_neighbours(std::vector<uint8_t> &code, std::vector<uint32_t> &nbr) const
+  {
+    code.assign(cells.size() * 6, NB_BOUNDARY);
+    nbr.assign(cells.size() * 24, 0u);
+    for (size_t t = 0; t < cells.size(); ++t)
+      {
+        const Cell   &c      = cells[t];
+        const int64_t ijk[3] = {c.i, c.j, c.k};
+        for (int f = 0; f < 6; ++f)
+          {
+            const int d = f >> 1, side = f & 1, u = d == 0 ? 1 : 0, v = d == 2 ? 1 : 2; // the in-face axes, u < v
+            int64_t   n[3] = {ijk[0], ijk[1], ijk[2]};
+            n[d] += side ? 1 : -1;
+            if (n[d] < 0 || n[d] >= ((int64_t)1 << c.level))
+              continue;
+            uint32_t *out = &nbr[(t * 6 + f) * 4];
+            const int nb  = find_leaf(c.level, n[0], n[1], n[2]);
+            if (nb >= 0)
+              {
+                if ((int)cells[nb].level + 1 < (int)c.level)
+                  throw std::runtime_error("face_neighbours: the mesh is not 2:1 balanced");
+                code[t * 6 + f] = cells[nb].level == c.level ? (uint8_t)NB_SAME : (uint8_t)(NB_COARSER + ((ijk[u] & 1) | ((ijk[v] & 1) << 1)));
+                out[0]          = (uint32_t)nb;
+                continue;
+              }
+            code[t * 6 + f] = NB_FINER;
+            for (int s = 0; s < 4; ++s)
+              {
+                int64_t m[3];
+                m[d] = 2 * n[d] + (side ? 0 : 1);
+                m[u] = 2 * ijk[u] + (s & 1);
+                m[v] = 2 * ijk[v] + (s >> 1);
+                const int32_t *fi = index.find(cell_key(c.level + 1, (uint32_t)m[0], (uint32_t)m[1], (uint32_t)m[2]));
+                if (!fi)
+                  throw std::runtime_error("face_neighbours: the mesh is not 2:1 balanced");
+                out[s] = (uint32_t)*fi;
+              }
+          }
+      }
   }
 } // namespace mgamd

@@ -238,6 +238,15 @@ namespace mgamd
     // x: Dirichlet DoFs from g, then hanging DoFs from their parents; free DoFs untouched; stream-ordered
     virtual void
     distribute_values(mgamd_vec &x, const mgamd_vec &g) = 0;
+    // The jump error indicator eta_K of u per leaf, in the order of the mesh's cells, to the host array eta (kernels_estimator.hpp);
+    // q: the six boundary fluxes of rhs_boundary_flux, or null for no boundary term.  Stream-ordered behind whatever the stream
+    // holds for u; returns after the copy to the host.  The tables and the scratch are built by the first call.
+    virtual void
+    estimate_error(const mgamd_vec &u, const double *q, double *eta) = 0;
+    // measurement: bytes of the indicator's device tables and scratch, host time of their build, device time of the two kernels
+    // of the last call (HIP events); all 0 before the first call
+    virtual void
+    estimator_info(uint64_t &bytes, double &build_ms, double &kernel_ms) const = 0;
 
   private:
     // distribute_values without its refusals (sizes, local-smoothing levels): distribute(x, kind) runs on every level

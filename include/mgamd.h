@@ -68,6 +68,15 @@ int mgamd_tria_create_from_leaves(uint64_t n_leaves, const uint8_t *level, const
 /* one level of MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence
  * (ref:multigrid_throughput.cc:2219-2224): coarsen every family once, re-balance. */
 int mgamd_tria_coarsen(const mgamd_tria *fine, mgamd_tria **out);
+/* Flagged refinement, this project's counterpart of Triangulation::execute_coarsening_and_refinement with refine flags only: every
+ * leaf t with flags[t] != 0 (n_cells bytes, order of mgamd_tria_get_cells) is replaced by its eight children, then the minimal ripple
+ * to the full 2:1 balance runs, and the result passes the checks of mgamd_tria_create_from_leaves.  A child inherits its parent's
+ * diffusion coefficient value (if one is set); the dirichlet_faces mask and the Robin coefficients are copied.  parent (may be NULL):
+ * for each cell of *out the index of the cell of t that is it or contains it; the caller provides AT LEAST 8 n_cells(t) entries (no
+ * cell of t is split more than once, so *out has at most that many cells; mgamd_tria_info(*out) gives the number written).  On a balanced mesh no cell of t is split more than
+ * once by one call, so (t, *out) is a pair the two-level transfer describes (coarse = t, fine = *out).
+ * MGAMD_ERR_INVALID, by name: flags == NULL; a flagged cell at the deepest level the octree keys allow. */
+int mgamd_tria_refine(const mgamd_tria *t, const uint8_t *flags, mgamd_tria **out, uint64_t *parent);
 int mgamd_tria_destroy(mgamd_tria *t);
 /* n_global_active_cells(), n_global_levels(), cells with a coarser face/edge neighbour
  * (table columns n_cells / n_cells_hn: ref:multigrid_throughput.cc:2177-2190, 2329-2331). */
@@ -423,6 +432,24 @@ int mgamd_level_op_rhs_dirichlet(mgamd_level_op *op, const mgamd_vec *g, int inc
  * of x are untouched.  mgamd_level_op_distribute runs the same two kernels on the built-in values.  MGAMD_ERR_INVALID for vectors of
  * the wrong size or number type and for the operator of a local-smoothing level. */
 int mgamd_level_op_distribute_values(mgamd_level_op *op, mgamd_vec *x, const mgamd_vec *g);
+/* The jump error indicator, this project's own (in deal.II's place: KellyErrorEstimator).  For the level's Q_p function u_h (the
+ * entries of u at free and Dirichlet DoFs; hanging entries are never read) and every leaf K with edge length h_K
+ *     eta_K^2 = (h_K / 24) sum over the six faces F of K of  int_F r_F^2 dS
+ * with r_F the jump of the normal flux a d_n u_h across F: against a neighbour of the same level; against a neighbour one level
+ * coarser, whose flux is evaluated on K's face; against four finer neighbours as the sum over the four quarter faces (the weight
+ * stays h_K / 24 of the cell that receives it, so a quarter face counts once for the coarse and once for the fine cell, each with
+ * its own h).  On a boundary face f = 2 axis + side: nothing if q == NULL or the face is Dirichlet, else
+ * r = q[f] - beta_f u_h - a d_n u_h with the outward normal, beta_f the Robin coefficient of the tables and q the six constants
+ * of mgamd_level_op_rhs_boundary_flux (a convective face passes q[f] = beta_f u_ext).  a is the per-leaf diffusion coefficient.
+ * h_K is the edge length, not deal.II's diameter: a constant factor that does not change which cells are marked.  The integrals
+ * are exact (mass-matrix quadratic forms); all arithmetic after the load is FP64 for both number types.
+ * eta: host array of n_cells values in the order of mgamd_tria_get_cells.  Two kernels, stream-ordered behind whatever the stream
+ * holds for u; returns after the copy to the host.  No atomics: two calls return bit-identical arrays.  The cell table, the
+ * neighbour table and the flux scratch (4 (p+1)^3 + 48 (p+1)^2 + 128 bytes per cell) are built by the first call and freed
+ * with the operator; an operator that is never asked allocates and launches nothing.
+ * MGAMD_ERR_INVALID, by name: a distributed operator ("not implemented: sharded"); the operator of a local-smoothing level; a
+ * vector of the wrong size or number type; a non-finite q[f]; a non-zero q[f] on a Dirichlet face; eta == NULL. */
+int mgamd_level_op_estimate_error(mgamd_level_op *op, const mgamd_vec *u, const double q[6], double *eta);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is
  * computed internally (DiagonalMatrix preconditioner); eigenvalues are estimated at creation with

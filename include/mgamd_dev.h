@@ -98,6 +98,16 @@ int mgamd_debug_matrix_time_spmv(mgamd_matrix *A, int mode, int lanes, unsigned 
  * in mgamd_last_error(), when the matrix needs more than 2^32 - 1 entries; ptr has n_rows + 1 entries.  No GPU needed. */
 int mgamd_debug_csr_row_pointers(uint32_t n_rows, const uint64_t *row_counts, uint32_t *ptr);
 
+/* ---- the jump error indicator (mgamd_level_op_estimate_error) ----
+ * the face-neighbour table its second kernel walks, host only: code[n_cells][6] and nbr[n_cells][6][4] (either may be null), face
+ * f = 2 axis + side.  code 0: boundary face; 1: one neighbour of the same level, nbr[0]; 2 + (c1 | c2 << 1): one neighbour one level
+ * coarser, nbr[0], (c1, c2) the position of the cell's face inside the neighbour's along the lower and the higher in-face axis;
+ * 6: four neighbours one level finer, nbr[c1 | c2 << 1] on the quarter (c1, c2) */
+int mgamd_debug_tria_face_neighbours(const mgamd_tria *t, uint8_t *code, uint32_t *nbr);
+/* measurement: bytes of the indicator's device tables and scratch, host time of their build, and the device time of the two kernels
+ * of the last call (HIP events); all 0 before the operator's first estimate.  Any pointer may be null. */
+int mgamd_debug_level_op_estimator_info(const mgamd_level_op *op, uint64_t *bytes, double *build_ms, double *kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
