@@ -232,6 +232,21 @@ def mark_maximum(eta, theta: float):
     return (eta >= theta * top).astype(np.uint8)
 
 
+# the norms of Operator.integrate_difference (MGAMD_NORM_*)
+NORM_L2, NORM_H1_SEMINORM, NORM_ENERGY, NORM_LINFTY = 0, 1, 2, 3
+
+
+def compute_global_error(per_cell, norm: int) -> float:
+    """VectorTools::compute_global_error: the global norm from the per-leaf values of Operator.integrate_difference, the l2 norm of
+    the array for NORM_L2, NORM_H1_SEMINORM and NORM_ENERGY and its maximum for NORM_LINFTY"""
+    e = np.asarray(per_cell, np.float64)
+    if norm not in (NORM_L2, NORM_H1_SEMINORM, NORM_ENERGY, NORM_LINFTY):
+        raise ValueError(f"compute_global_error: unknown norm {norm}")
+    if norm == NORM_LINFTY:
+        return float(e.max()) if e.size else 0.0
+    return float(np.sqrt(np.sum(e * e)))
+
+
 def create_geometric_coarsening_sequence(fine: Triangulation, coarse_coefficient=None):
     """MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence: coarsest first.  A diffusion coefficient on `fine`
     goes down mesh by mesh (Triangulation.coarsen: the mean over each coarse leaf); coarse_coefficient(tria) -> values, if given,
@@ -429,6 +444,16 @@ class DoFs:
         """the support point of every DoF, (n_dofs, 3): g = f(*dofs.node_positions().T) is the nodal interpolant of f"""
         xyz = np.zeros((self.n_dofs, 3))
         _chk(_lib.mgamd_dofs_node_positions(self._h, _ptr(xyz)))
+        return xyz
+
+    def quadrature_points(self, n_q: int = 0):
+        """the physical points of QGauss(n_q)^3 on every leaf (mgamd_dofs_quadrature_points), shape (n_cells, n_q, n_q, n_q, 3) indexed
+        [cell, qz, qy, qx]: where Operator.integrate_difference expects caller data.  n_q: degree + 1 ... degree + 3, 0 for degree + 2.
+        Host only."""
+        nq = self.degree + 2 if n_q == 0 else int(n_q)
+        valid = self.degree + 1 <= nq <= self.degree + 3
+        xyz = np.zeros((self.info.n_cells, nq, nq, nq, 3) if valid else 1)
+        _chk(_lib.mgamd_dofs_quadrature_points(self._h, C.c_int(n_q), _ptr(xyz)))  # (refuses n_q by name before it writes)
         return xyz
 
     def _data_array(self, a, who):
@@ -773,6 +798,54 @@ class Operator:
         b, t0, t1 = C.c_uint64(), C.c_double(), C.c_double()
         _chk(_lib.mgamd_debug_level_op_estimator_info(self._h, C.byref(b), C.byref(t0), C.byref(t1)))
         return b.value, t0.value, t1.value
+
+    def integrate_difference(self, u: Vector, exact, norm: int, n_q: int = 0):
+        """the error norm of u_h - w per leaf, in the order of Triangulation.cells() (mgamd_level_op_integrate_difference; in deal.II:
+        VectorTools::integrate_difference): NORM_L2, NORM_H1_SEMINORM, NORM_ENERGY (a |grad e|^2 + sigma e^2 with the sigma the
+        operator was built with; volume terms only) or NORM_LINFTY over QGauss(n_q)^3 per leaf, n_q = 0 for degree + 2.
+        exact, the function w:
+          * an int: the built-in kind, 0 for w = 0 (the norms of u_h), 1 for the Gaussian of SimulationType "Gaussian";
+          * an array or Vector: the values of w at DoFs.quadrature_points(n_q), [cell, qz, qy, qx];
+          * a tuple (values, gradients): gradients [cell, component, qz, qy, qx], read by the two gradient norms; values may be None
+            for the H1 seminorm;
+          * a callable f(x, y, z), or a tuple (f, grad_f) with grad_f(x, y, z) returning the three components: tabulated at the
+            quadrature points on the host and uploaded.
+        Only entries of u at free and Dirichlet DoFs are read.  Returns a host array; compute_global_error gives the global value."""
+        out = np.zeros(self.dofs.info.n_cells, np.float64)
+        if isinstance(exact, (int, np.integer)) and not isinstance(exact, bool):
+            _chk(_lib.mgamd_level_op_integrate_difference(self._h, u._h, C.c_int(int(exact)), C.c_int(n_q), C.c_int(norm), _ptr(out)))
+            return out
+        values, gradients = exact if isinstance(exact, tuple) else (exact, None)
+        points = None
+        if callable(values) or callable(gradients):
+            points = np.moveaxis(self.dofs.quadrature_points(n_q), -1, 0)  # (refuses n_q by name)
+        keep = []
+
+        def device(a, per_point):
+            if a is None or isinstance(a, Vector):
+                return a
+            if callable(a):
+                a = a(*points)
+                if per_point == 3:
+                    a = np.stack([np.broadcast_to(np.asarray(c, np.float64), points[0].shape) for c in a], axis=1)
+                else:
+                    a = np.broadcast_to(np.asarray(a, np.float64), points[0].shape)
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            keep.append(Vector(self.ctx, a.size, self.number_type).from_host(a.ravel()))
+            return keep[-1]
+
+        v, g = device(values, 1), device(gradients, 3)
+        _chk(_lib.mgamd_level_op_integrate_difference_values(self._h, u._h, v._h if v is not None else None, g._h if g is not None else None,
+                                                             C.c_int(n_q), C.c_int(norm), _ptr(out)))
+        return out
+
+    def _error_norm_info(self):
+        """(bytes of the device arrays the error norms use, the shared gather table included; device milliseconds of the kernel of the
+        last call; whether the indicator's neighbour table is built); zeros before the first integrate_difference
+        (mgamd_debug_level_op_error_norm_info)"""
+        b, t, nb = C.c_uint64(), C.c_double(), C.c_int()
+        _chk(_lib.mgamd_debug_level_op_error_norm_info(self._h, C.byref(b), C.byref(t), C.byref(nb)))
+        return b.value, t.value, bool(nb.value)
 
     def get_system_matrix(self) -> "SparseMatrix":
         """Operator::get_trilinos_system_matrix: the assembled matrix of this operator's DoFs on the device (FP64, one rank)"""

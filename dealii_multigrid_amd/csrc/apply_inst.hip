@@ -28,4 +28,7 @@ namespace mgamd
   template void LevelOperator<MGAMD_INST_T>::lift_P<MGAMD_INST_P>(MGAMD_INST_T *, const MGAMD_INST_T *, double, double);
   // the jump error indicator (kernels_estimator.hpp)
   template void LevelOperator<MGAMD_INST_T>::estimate_P<MGAMD_INST_P>(const MGAMD_INST_T *, const double *);
+  // the error norms (kernels_error_norm.hpp)
+  template void LevelOperator<MGAMD_INST_T>::difference_norm_P<MGAMD_INST_P>(const MGAMD_INST_T *, int, const MGAMD_INST_T *, const MGAMD_INST_T *, int,
+                                                                             int);
 } // namespace mgamd

@@ -477,6 +477,45 @@ mgamd_debug_level_op_estimator_info(const mgamd_level_op *op, uint64_t *bytes, d
 }
 
 int
+mgamd_level_op_integrate_difference(mgamd_level_op *op, const mgamd_vec *u, int kind, int n_q, int norm, double *out)
+{
+  MGAMD_TRY
+  REQUIRE(op && u);
+  if (kind != 0 && kind != 1)
+    throw std::invalid_argument("integrate_difference: unknown kind " + std::to_string(kind) + " (0: w = 0, 1: the Gaussian)");
+  op->op->integrate_difference(*u, kind, nullptr, nullptr, n_q, norm, out); // (refuses a null out by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_level_op_integrate_difference_values(mgamd_level_op *op, const mgamd_vec *u, const mgamd_vec *values, const mgamd_vec *gradients, int n_q,
+                                           int norm, double *out)
+{
+  MGAMD_TRY
+  REQUIRE(op && u);
+  op->op->integrate_difference(*u, -1, values, gradients, n_q, norm, out); // (refuses missing data by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_level_op_error_norm_info(const mgamd_level_op *op, uint64_t *bytes, double *kernel_ms, int *neighbours_built)
+{
+  MGAMD_TRY
+  REQUIRE(op);
+  uint64_t b  = 0;
+  double   t  = 0.0;
+  int      nb = 0;
+  op->op->error_norm_info(b, t, nb);
+  if (bytes)
+    *bytes = b;
+  if (kernel_ms)
+    *kernel_ms = t;
+  if (neighbours_built)
+    *neighbours_built = nb;
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_debug_stamps(mgamd_level_op *op, unsigned long long *out, uint64_t max_count, uint64_t *count)
 {
   MGAMD_TRY

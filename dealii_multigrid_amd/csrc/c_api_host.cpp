@@ -709,6 +709,18 @@ mgamd_dofs_node_positions(const mgamd_dofs *d, double *xyz)
 }
 
 int
+mgamd_dofs_quadrature_points(const mgamd_dofs *d, int n_q, double *xyz)
+{
+  MGAMD_TRY
+  if (!d || !xyz)
+    throw std::invalid_argument("null argument");
+  std::vector<double> h;
+  d->tables->quadrature_points(n_q, h); // (refuses n_q, sharded tables and local-smoothing levels by name)
+  std::copy(h.begin(), h.end(), xyz);
+  MGAMD_CATCH
+}
+
+int
 mgamd_dofs_coefficient_range(const mgamd_dofs *d, double *min, double *max)
 {
   MGAMD_TRY

@@ -79,6 +79,44 @@ namespace mgamd
         }
     }
 
+    // QGauss(n) on [0, 1]: points ascending, weights summing to 1 (Newton on P_n in long double).  The rule of FE1D itself
+    // (n = p + 1) and of the error norms (kernels_error_norm.hpp: n = p + 1 ... p + 3, at most MAX_GAUSS_POINTS)
+    static constexpr int MAX_GAUSS_POINTS = 10;
+    static void
+    gauss_rule(int n, std::vector<double> &x01, std::vector<double> &w01)
+    {
+      const long double pi = 3.14159265358979323846264338327950288L;
+      x01.assign(n, 0.0);
+      w01.assign(n, 0.0);
+      for (int i = 0; i < n; ++i)
+        {
+          long double x = -std::cos(pi * (i + 0.75L) / (n + 0.5L));
+          long double dp;
+          for (int it = 0; it < 100; ++it)
+            {
+              long double pn = legendre(n, x, &dp);
+              long double dx = pn / dp;
+              x -= dx;
+              if (std::fabs((double)dx) < 1e-19)
+                break;
+            }
+          legendre(n, x, &dp);
+          x01[i] = (double)(0.5L * (x + 1.0L));
+          w01[i] = (double)(1.0L / ((1 - x * x) * dp * dp)); // = 0.5 * 2/((1-x^2)P'^2)
+        }
+    }
+    // shape values and derivatives of this element at the points of QGauss(nq): S[q*(p+1)+a] = phi_a(x_q), G likewise phi_a'(x_q)
+    void
+    shape_at_gauss(int nq, std::vector<double> &x01, std::vector<double> &w01, std::vector<double> &Sq, std::vector<double> &Gq) const
+    {
+      const int n = p + 1;
+      gauss_rule(nq, x01, w01);
+      Sq.assign((size_t)nq * n, 0.0);
+      Gq.assign((size_t)nq * n, 0.0);
+      for (int q = 0; q < nq; ++q)
+        lagrange(nodes, x01[q], &Sq[q * n], &Gq[q * n]);
+    }
+
     explicit FE1D(int degree)
       : p(degree)
     {
@@ -113,24 +151,7 @@ namespace mgamd
       if (p % 2 == 0)
         nodes[p / 2] = 0.5;
       // Gauss points
-      xq.assign(n, 0.0);
-      wq.assign(n, 0.0);
-      for (int i = 0; i < n; ++i)
-        {
-          long double x = -std::cos(pi * (i + 0.75L) / (n + 0.5L));
-          long double dp;
-          for (int it = 0; it < 100; ++it)
-            {
-              long double pn = legendre(n, x, &dp);
-              long double dx = pn / dp;
-              x -= dx;
-              if (std::fabs((double)dx) < 1e-19)
-                break;
-            }
-          legendre(n, x, &dp);
-          xq[i] = (double)(0.5L * (x + 1.0L));
-          wq[i] = (double)(1.0L / ((1 - x * x) * dp * dp)); // = 0.5 * 2/((1-x^2)P'^2)
-        }
+      gauss_rule(n, xq, wq);
       S.assign(n * n, 0.0);
       G.assign(n * n, 0.0);
       for (int q = 0; q < n; ++q)

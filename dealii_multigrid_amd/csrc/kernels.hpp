@@ -29,14 +29,17 @@
 // K10 face_flux_kernel      the error indicator: nodal normal fluxes a d_n u on the six faces of every leaf
 // K11 flux_jump_kernel      the error indicator: jumps across the faces through the neighbour table, eta_K
 //
+// K12 difference_norm_kernel  the error norms: u_h and grad u_h at the Gauss points of every leaf against w, L2 / H1 / energy / Linfty
+//
 // The kernels live in kernels_common.hpp (1D products, sweeps, constraint passes, argument structs), kernels_apply.hpp (K1-K3),
-// kernels_boundary.hpp (K9), kernels_estimator.hpp (K10, K11), kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header
+// kernels_boundary.hpp (K9), kernels_estimator.hpp (K10, K11), kernels_error_norm.hpp (K12), kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header
 // includes them all.
 #pragma once
 #include "kernels_common.hpp"
 #include "kernels_apply.hpp"
 #include "kernels_boundary.hpp"
 #include "kernels_estimator.hpp"
+#include "kernels_error_norm.hpp"
 #include "kernels_transfer.hpp"
 #include "kernels_vector.hpp"
 #include "kernels_amg.hpp"

@@ -345,9 +345,12 @@ namespace mgamd
       uint32_t       n_rows = 0;
     };
     std::unique_ptr<HangingDev> hanging;
-    // The jump error indicator: device images of LevelTables::EstimatorCells, the face-flux scratch [cell][6][(p+1)^2] and the
-    // result, built by the first estimate_error and freed with the operator.  An operator that is never asked for an estimate
-    // allocates nothing and launches nothing.  Per cell 4 (p+1)^3 + 48 (p+1)^2 + 128 bytes.
+    // The jump error indicator and the error norms: device images of LevelTables::EstimatorCells, built by the first call that needs
+    // them and freed with the operator.  An operator that is never asked allocates nothing and launches nothing.
+    //   gather      idx, mask, scale: ONE copy, shared by estimate_error and integrate_difference, built by whichever comes first
+    //   neighbours  code, nbr, the face-flux scratch [cell][6][(p+1)^2] and eta: the indicator's alone (ensure_estimator(true))
+    //   norms       the leaves' corners (the built-in Gaussian) and the result: the error norms' alone
+    // The indicator's share is, per cell, 4 (p+1)^3 + 48 (p+1)^2 + 128 bytes, the shared gather table included.
     struct EstimatorDev
     {
       DBuf<uint32_t> idx, nbr;
@@ -355,9 +358,15 @@ namespace mgamd
       DBuf<double>   scale, flux, eta;
       DBuf<uint8_t>  code;
       uint32_t       n_cells = 0;
-      uint64_t       bytes   = 0;
+      bool           neighbours = false;
+      uint64_t       gather_bytes = 0, bytes = 0; // bytes: the indicator's share (0 until its first call)
       double         build_ms = 0.0, kernel_ms = 0.0;
       hipEvent_t     e0 = nullptr, e1 = nullptr;
+      // the error norms
+      DBuf<double> origin, norm_out;
+      bool         norms = false;
+      uint64_t     norm_bytes = 0; // corners and result
+      double       norm_kernel_ms = 0.0;
       ~EstimatorDev()
       {
         if (e0)
@@ -367,6 +376,45 @@ namespace mgamd
       }
     };
     std::unique_ptr<EstimatorDev> estimator;
+    // the shared gather table and, with `neighbours`, the indicator's part; `who` names the caller in the refusals
+    void
+    ensure_estimator(bool neighbours, const char *who)
+    {
+      if (estimator && (estimator->neighbours || !neighbours))
+        return;
+      const auto                  t0 = std::chrono::steady_clock::now();
+      LevelTables::EstimatorCells ec;
+      if (!estimator)
+        {
+          tables->build_estimator_cells(ec, neighbours, who);
+          auto dev = std::make_unique<EstimatorDev>();
+          dev->idx.upload(ec.idx);
+          dev->mask.upload(ec.mask);
+          dev->scale.upload(ec.scale);
+          dev->n_cells      = (uint32_t)ec.size();
+          dev->gather_bytes = ec.idx.size() * 4 + ec.mask.size() * 2 + ec.scale.size() * 8;
+          HIP_CHECK(hipEventCreate(&dev->e0));
+          HIP_CHECK(hipEventCreate(&dev->e1));
+          estimator = std::move(dev);
+        }
+      else
+        {
+          tables->refuse_estimate(who);
+          tables->tria->face_neighbours(ec.code, ec.nbr);
+        }
+      if (neighbours)
+        {
+          EstimatorDev &dev = *estimator;
+          const size_t  n2 = (size_t)(p + 1) * (p + 1), nc = dev.n_cells;
+          dev.nbr.upload(ec.nbr);
+          dev.code.upload(ec.code);
+          dev.flux.alloc(nc * 6 * n2);
+          dev.eta.alloc(nc);
+          dev.neighbours = true;
+          dev.bytes      = dev.gather_bytes + ec.nbr.size() * 4 + ec.code.size() + (nc * 6 * n2 + nc) * sizeof(double);
+          dev.build_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+    }
 
     // The kernel launches of one operator application, planned once (build_launch_plan): one step per launch, in launch order.
     enum class LaunchKind
@@ -1232,27 +1280,7 @@ namespace mgamd
       const T *up = u.as<T>(); // (refuses the other number type)
       if (q)
         tables->check_boundary_flux(q);
-      if (!estimator)
-        {
-          const auto                   t0 = std::chrono::steady_clock::now();
-          LevelTables::EstimatorCells  ec;
-          tables->build_estimator_cells(ec);
-          auto         dev = std::make_unique<EstimatorDev>();
-          const size_t n2  = (size_t)(p + 1) * (p + 1);
-          dev->idx.upload(ec.idx);
-          dev->nbr.upload(ec.nbr);
-          dev->mask.upload(ec.mask);
-          dev->scale.upload(ec.scale);
-          dev->code.upload(ec.code);
-          dev->n_cells = (uint32_t)ec.size();
-          dev->flux.alloc(ec.size() * 6 * n2);
-          dev->eta.alloc(ec.size());
-          dev->bytes = ec.bytes() + (ec.size() * 6 * n2 + ec.size()) * sizeof(double);
-          HIP_CHECK(hipEventCreate(&dev->e0));
-          HIP_CHECK(hipEventCreate(&dev->e1));
-          dev->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-          estimator     = std::move(dev);
-        }
+      ensure_estimator(true, "estimate_error");
       HIP_CHECK(hipEventRecord(estimator->e0, ctx->stream));
       if (!dispatch_degree(p, [&](auto P) { estimate_P<P()>(up, q); }))
         throw std::runtime_error("degree not instantiated");
@@ -1269,6 +1297,84 @@ namespace mgamd
       bytes     = estimator ? estimator->bytes : 0;
       build_ms  = estimator ? estimator->build_ms : 0.0;
       kernel_ms = estimator ? estimator->kernel_ms : 0.0;
+    }
+
+    // defined in level_operator_apply.hpp, instantiated in apply_inst.hip: the launch of difference_norm_kernel
+    template <int P>
+    void
+    difference_norm_P(const T *u, int kind, const T *values, const T *gradients, int n_q, int norm);
+
+    void
+    integrate_difference(const mgamd_vec &u, int kind, const mgamd_vec *values, const mgamd_vec *gradients, int n_q, int norm, double *out) override
+    {
+      const char *who = "integrate_difference";
+      if (comm || halo_plan)
+        throw std::invalid_argument("integrate_difference: not implemented: sharded (the operator is distributed; one rank only)");
+      tables->refuse_estimate(who);
+      if (!out)
+        throw std::invalid_argument("integrate_difference: out is null (a host array of n_cells values)");
+      if (norm != NORM_L2 && norm != NORM_H1_SEMINORM && norm != NORM_ENERGY && norm != NORM_LINFTY)
+        throw std::invalid_argument("integrate_difference: unknown norm " + std::to_string(norm) +
+                                    " (MGAMD_NORM_L2, MGAMD_NORM_H1_SEMINORM, MGAMD_NORM_ENERGY or MGAMD_NORM_LINFTY)");
+      if (kind != -1 && kind != 0 && kind != 1)
+        throw std::invalid_argument("integrate_difference: unknown kind " + std::to_string(kind) + " (0: w = 0, 1: the Gaussian)");
+      const int nq = tables->resolve_n_q(n_q, who);
+      if (u.n != n_dofs())
+        throw std::invalid_argument("integrate_difference: vector size mismatch (" + std::to_string(u.n) + " for " + std::to_string(n_dofs()) + " DoFs)");
+      const T     *up = u.as<T>(); // (refuses the other number type)
+      const T     *vp = nullptr, *gp = nullptr;
+      const size_t n_points = tables->tria->cells.size() * (size_t)nq * nq * nq;
+      const bool   with_gradient = norm == NORM_H1_SEMINORM || norm == NORM_ENERGY;
+      if (kind == -1)
+        {
+          if (norm != NORM_H1_SEMINORM)
+            {
+              if (!values)
+                throw std::invalid_argument("integrate_difference: values is null (n_cells n_q^3 values of w at the quadrature points)");
+              if (values->n != n_points)
+                throw std::invalid_argument("integrate_difference: values size mismatch (" + std::to_string(values->n) + " for " +
+                                            std::to_string(n_points) + " quadrature points)");
+              vp = values->as<T>();
+            }
+          if (with_gradient)
+            {
+              if (!gradients)
+                throw std::invalid_argument("integrate_difference: a gradient norm without gradients (3 n_cells n_q^3 values of grad w at the "
+                                            "quadrature points)");
+              if (gradients->n != 3 * n_points)
+                throw std::invalid_argument("integrate_difference: gradients size mismatch (" + std::to_string(gradients->n) + " for 3 x " +
+                                            std::to_string(n_points) + " quadrature points)");
+              gp = gradients->as<T>();
+            }
+        }
+      ensure_estimator(false, who);
+      EstimatorDev &e = *estimator;
+      if (!e.norms)
+        {
+          std::vector<double> o;
+          tables->cell_origins(o);
+          e.origin.upload(o);
+          e.norm_out.alloc(e.n_cells);
+          e.norm_bytes = (o.size() + e.n_cells) * sizeof(double);
+          e.norms      = true;
+        }
+      HIP_CHECK(hipEventRecord(e.e0, ctx->stream));
+      if (!dispatch_degree(p, [&](auto P) { difference_norm_P<P()>(up, kind, vp, gp, nq, norm); }))
+        throw std::runtime_error("degree not instantiated");
+      HIP_CHECK(hipEventRecord(e.e1, ctx->stream));
+      HIP_CHECK(hipMemcpyAsync(out, e.norm_out.p, (size_t)e.n_cells * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      ctx->sync();
+      float ms = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&ms, e.e0, e.e1));
+      e.norm_kernel_ms = ms;
+    }
+    void
+    error_norm_info(uint64_t &bytes, double &kernel_ms, int &neighbours_built) const override
+    {
+      const bool on    = estimator && estimator->norms;
+      bytes            = on ? estimator->gather_bytes + estimator->norm_bytes : 0;
+      kernel_ms        = on ? estimator->norm_kernel_ms : 0.0;
+      neighbours_built = estimator && estimator->neighbours ? 1 : 0;
     }
 
     size_t

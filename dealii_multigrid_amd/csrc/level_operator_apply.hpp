@@ -173,4 +173,52 @@ namespace mgamd
     HIP_CHECK(hipGetLastError());
   }
 
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::difference_norm_P(const T *u, int kind, const T *values, const T *gradients, int n_q, int norm)
+  {
+    constexpr int N = P + 1, N2 = N * N;
+    EstimatorDev &e = *estimator;
+    if (!e.n_cells)
+      return;
+    DifferenceNormArgs<T, P> a;
+    static_assert(DifferenceNormArgs<T, P>::NQM <= FE1D::MAX_GAUSS_POINTS, "the rule generator is held to 10 points");
+    if (n_q < N || n_q > DifferenceNormArgs<T, P>::NQM)
+      throw std::invalid_argument("integrate_difference: n_q outside p + 1 ... p + 3"); // (resolve_n_q refused it already: the LDS bound)
+    a.idx       = e.idx.p;
+    a.mask      = e.mask.p;
+    a.scale     = e.scale.p;
+    a.origin    = e.origin.p;
+    a.n_cells   = e.n_cells;
+    a.n_dofs    = n_dofs();
+    a.u         = u;
+    a.values    = values;
+    a.gradients = gradients;
+    a.out       = e.norm_out.p;
+    a.kind      = kind;
+    a.norm      = norm;
+    a.n_q       = n_q;
+    a.sigma     = sigma; // the operator's own: what it was built with
+    std::vector<double> xq, wq, S, G;
+    tables->fe.shape_at_gauss(n_q, xq, wq, S, G);
+    std::memset(a.S, 0, sizeof(a.S));
+    std::memset(a.G, 0, sizeof(a.G));
+    std::memset(a.xq, 0, sizeof(a.xq));
+    std::memset(a.wq, 0, sizeof(a.wq));
+    std::copy(S.begin(), S.end(), a.S);
+    std::copy(G.begin(), G.end(), a.G);
+    std::copy(xq.begin(), xq.end(), a.xq);
+    std::copy(wq.begin(), wq.end(), a.wq);
+    for (int i = 0; i < N2; ++i)
+      {
+        a.I0[i] = tables->fe.I[0][i];
+        a.I1[i] = tables->fe.I[1][i];
+      }
+    // two groups of leaves per workgroup where there are that many: the 1D matrices are staged in LDS once per workgroup
+    const uint32_t groups = (e.n_cells + dirichlet_cells_per_workgroup<P>() - 1) / dirichlet_cells_per_workgroup<P>();
+    hipLaunchKernelGGL((difference_norm_kernel<T, P>), std::min<uint32_t>(4096u, (groups + 1) / 2), 256, 0, ctx->stream, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
 } // namespace mgamd

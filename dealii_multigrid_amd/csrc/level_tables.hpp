@@ -484,7 +484,8 @@ namespace mgamd
       }
     } dirichlet_cells;
     // Error indicator (DESIGN.md "Error indicator and refinement"): the tables of the two jump kernels, over ALL leaves in Morton
-    // order.  Not a member: the first estimate of an operator builds them (LevelOperator), nothing else pays for them.
+    // order.  Not a member: the first estimate of an operator builds them (LevelOperator), nothing else pays for them.  The gather
+    // part (idx, mask, scale) is also the table of the error norms (DESIGN.md "Error norms"), which leave code and nbr empty.
     //   idx    [n][n3]    as DirichletCells::idx: hanging entities resolved to the parent's DoFs, Dirichlet DoFs with their real
     //                     index, so that only free and Dirichlet entries of the vector are read
     //   mask   [n]        the cell's constraint mask
@@ -513,19 +514,22 @@ namespace mgamd
       return owned != nullptr;
     }
     void
-    refuse_estimate() const
+    refuse_estimate(const char *who = "estimate_error") const
     {
       if (is_sharded())
-        throw std::invalid_argument("estimate_error: not implemented: sharded (the tables hold one rank's cells of a distributed level; the "
-                                    "jumps across the cut need the neighbour rank's fluxes)");
+        throw std::invalid_argument(std::string(who) + ": not implemented: sharded (the tables hold one rank's cells of a distributed level" +
+                                    (std::strcmp(who, "estimate_error") == 0 ? "; the jumps across the cut need the neighbour rank's fluxes)" :
+                                                                               "; the per-leaf order is that of one rank's whole mesh)"));
       if (ls_level)
-        throw std::invalid_argument("estimate_error: refused on the level of a local-smoothing hierarchy (its cells cover part of the domain "
-                                    "and its refinement-edge DoFs are constrained); use the active-mesh operator");
+        throw std::invalid_argument(std::string(who) + ": refused on the level of a local-smoothing hierarchy (its cells cover part of the domain "
+                                                       "and its refinement-edge DoFs are constrained); use the active-mesh operator");
     }
+    // the gather part (idx, mask, scale) is what the error norms need too (kernels_error_norm.hpp); the neighbour part (code, nbr)
+    // is the indicator's alone and is added by whichever estimate comes first (LevelOperator keeps ONE idx for both)
     void
-    build_estimator_cells(EstimatorCells &ec) const
+    build_estimator_cells(EstimatorCells &ec, bool with_neighbours = true, const char *who = "estimate_error") const
     {
-      refuse_estimate();
+      refuse_estimate(who);
       const int    n = p + 1, n3 = n * n * n;
       const size_t nc = tria->cells.size();
       ec.idx.resize(nc * n3);
@@ -538,7 +542,60 @@ namespace mgamd
           ec.scale[2 * ci]     = coefficient_of(ci) / h;
           ec.scale[2 * ci + 1] = h;
         }
-      tria->face_neighbours(ec.code, ec.nbr);
+      if (with_neighbours)
+        tria->face_neighbours(ec.code, ec.nbr);
+    }
+    // Error norms (DESIGN.md "Error norms"): n_q of integrate_difference, 0 standing for p + 2; refused outside p + 1 ... p + 3
+    int
+    resolve_n_q(int n_q, const char *who) const
+    {
+      if (n_q == 0)
+        return p + 2;
+      if (n_q < p + 1 || n_q > p + 3)
+        throw std::invalid_argument(std::string(who) + ": n_q = " + std::to_string(n_q) + " refused: 0 (for p + 2) or one of p + 1, p + 2, p + 3 = " +
+                                    std::to_string(p + 1) + ", " + std::to_string(p + 2) + ", " + std::to_string(p + 3));
+      return n_q;
+    }
+    // the lower corner of every leaf, [n_cells][3]
+    void
+    cell_origins(std::vector<double> &o) const
+    {
+      const size_t nc = tria->cells.size();
+      o.resize(nc * 3);
+      for (size_t ci = 0; ci < nc; ++ci)
+        {
+          const Cell  &c = tria->cells[ci];
+          const double h = 2.0 / (double)(1u << c.level);
+          o[3 * ci]      = -1.0 + h * c.i;
+          o[3 * ci + 1]  = -1.0 + h * c.j;
+          o[3 * ci + 2]  = -1.0 + h * c.k;
+        }
+    }
+    // the physical points of the tensor rule QGauss(n_q)^3 on every leaf, [cell][qz][qy][qx][3]: corner + h x_q per coordinate (one
+    // multiplication and one addition in double, the expression of compute_rhs_function), leaves in the order of the mesh's cells
+    void
+    quadrature_points(int n_q, std::vector<double> &xyz) const
+    {
+      refuse_estimate("quadrature_points");
+      const int           nq = resolve_n_q(n_q, "quadrature_points");
+      std::vector<double> x01, w01, o;
+      FE1D::gauss_rule(nq, x01, w01);
+      cell_origins(o);
+      const size_t nc = tria->cells.size(), nq3 = (size_t)nq * nq * nq;
+      xyz.resize(nc * nq3 * 3);
+      for (size_t ci = 0; ci < nc; ++ci)
+        {
+          const double h = 2.0 / (double)(1u << tria->cells[ci].level);
+          double      *x = &xyz[ci * nq3 * 3];
+          for (int qz = 0; qz < nq; ++qz)
+            for (int qy = 0; qy < nq; ++qy)
+              for (int qx = 0; qx < nq; ++qx, x += 3)
+                {
+                  x[0] = o[3 * ci] + h * x01[qx];
+                  x[1] = o[3 * ci + 1] + h * x01[qy];
+                  x[2] = o[3 * ci + 2] + h * x01[qz];
+                }
+        }
     }
     bool
     is_dirichlet_index(uint32_t gi) const

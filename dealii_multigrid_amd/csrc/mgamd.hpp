@@ -205,6 +205,19 @@ namespace mgamd
     return flags;
   }
 
+  // VectorTools::compute_global_error: the global norm from the per-leaf values of Operator::integrate_difference, the l2 norm of
+  // the array for MGAMD_NORM_L2, _H1_SEMINORM and _ENERGY and its maximum for MGAMD_NORM_LINFTY
+  inline double
+  compute_global_error(const std::vector<double> &per_cell, int norm)
+  {
+    if (norm != MGAMD_NORM_L2 && norm != MGAMD_NORM_H1_SEMINORM && norm != MGAMD_NORM_ENERGY && norm != MGAMD_NORM_LINFTY)
+      throw std::runtime_error("compute_global_error: unknown norm " + std::to_string(norm));
+    double r = 0.0;
+    for (double e : per_cell)
+      r = norm == MGAMD_NORM_LINFTY ? std::max(r, e) : r + e * e;
+    return norm == MGAMD_NORM_LINFTY ? r : std::sqrt(r);
+  }
+
   // MGTransferGlobalCoarseningTools::create_geometric_coarsening_sequence (ref:multigrid_throughput.cc:2219-2224)
   inline std::vector<std::shared_ptr<const Triangulation>>
   create_geometric_coarsening_sequence(const std::shared_ptr<const Triangulation> &fine)
@@ -416,6 +429,18 @@ namespace mgamd
     {
       std::vector<double> xyz(3 * (size_t)info.n_dofs);
       check(mgamd_dofs_node_positions(h.get(), xyz.data()));
+      return xyz;
+    }
+    // The physical points of QGauss(n_q)^3 on every leaf (mgamd_dofs_quadrature_points; in deal.II: FEValues::get_quadrature_points):
+    // xyz[3 (((cell n_q + qz) n_q + qy) n_q + qx) ..], the points at which Operator::integrate_difference expects caller data.
+    // n_q: degree + 1 ... degree + 3; 0 stands for degree + 2.
+    std::vector<double>
+    quadrature_points(int n_q = 0) const
+    {
+      const int           nq    = n_q == 0 ? (int)info.degree + 2 : n_q;
+      const bool          valid = nq >= (int)info.degree + 1 && nq <= (int)info.degree + 3;
+      std::vector<double> xyz(valid ? 3 * (size_t)info.n_cells * nq * nq * nq : 1);
+      check(mgamd_dofs_quadrature_points(h.get(), n_q, xyz.data())); // (refuses n_q by name before it writes)
       return xyz;
     }
     mgamd_dofs_info_t info;
@@ -810,6 +835,39 @@ namespace mgamd
       std::vector<double> eta(dofs->get_triangulation().n_global_active_cells());
       check(mgamd_level_op_estimate_error(h.get(), u.get(), q ? q->data() : nullptr, eta.data()));
       return eta;
+    }
+    // The error norms of u_h - w per leaf, in the order of mgamd_tria_get_cells (mgamd_level_op_integrate_difference; in deal.II:
+    // VectorTools::integrate_difference).  norm: MGAMD_NORM_L2, _H1_SEMINORM, _ENERGY (a |grad e|^2 + sigma e^2, volume terms only) or
+    // _LINFTY; n_q Gauss points per direction, 0 for degree + 2.  kind: the built-in w (0: zero, 1: the Gaussian).  Only entries of u
+    // at free and Dirichlet DoFs are read.  compute_global_error gives the global value.
+    std::vector<double>
+    integrate_difference(const Vector &u, int kind, int norm, int n_q = 0) const
+    {
+      if (!dofs)
+        throw std::runtime_error("Operator::integrate_difference: reinit first");
+      std::vector<double> out(dofs->get_triangulation().n_global_active_cells());
+      check(mgamd_level_op_integrate_difference(h.get(), u.get(), kind, n_q, norm, out.data()));
+      return out;
+    }
+    // the same with caller data at DoFHandler::quadrature_points(n_q): values [cell][qz][qy][qx]
+    std::vector<double>
+    integrate_difference(const Vector &u, const Vector &values, int norm, int n_q = 0) const
+    {
+      if (!dofs)
+        throw std::runtime_error("Operator::integrate_difference: reinit first");
+      std::vector<double> out(dofs->get_triangulation().n_global_active_cells());
+      check(mgamd_level_op_integrate_difference_values(h.get(), u.get(), values.get(), nullptr, n_q, norm, out.data()));
+      return out;
+    }
+    // ... and gradients [cell][component][qz][qy][qx] for the two gradient norms (values may be an empty Vector for the H1 seminorm)
+    std::vector<double>
+    integrate_difference(const Vector &u, const Vector &values, const Vector &gradients, int norm, int n_q = 0) const
+    {
+      if (!dofs)
+        throw std::runtime_error("Operator::integrate_difference: reinit first");
+      std::vector<double> out(dofs->get_triangulation().n_global_active_cells());
+      check(mgamd_level_op_integrate_difference_values(h.get(), u.get(), values.get(), gradients.get(), n_q, norm, out.data()));
+      return out;
     }
     mgamd_level_op *
     get() const

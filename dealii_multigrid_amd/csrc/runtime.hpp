@@ -247,6 +247,16 @@ namespace mgamd
     // of the last call (HIP events); all 0 before the first call
     virtual void
     estimator_info(uint64_t &bytes, double &build_ms, double &kernel_ms) const = 0;
+    // The error norms per leaf (kernels_error_norm.hpp), in the order of the mesh's cells, to the host array out.  kind 0, 1: the
+    // built-in w (values and gradients null); kind -1: caller data at the quadrature points.  n_q: 0 for p + 2.  norm: MGAMD_NORM_*.
+    // Stream-ordered behind whatever the stream holds for u; returns after the copy to the host.  The gather table is the
+    // indicator's, built by whichever of the two comes first.
+    virtual void
+    integrate_difference(const mgamd_vec &u, int kind, const mgamd_vec *values, const mgamd_vec *gradients, int n_q, int norm, double *out) = 0;
+    // measurement: bytes of the device arrays the error norms use (the shared gather table, the corners, the result), device time
+    // of the kernel of the last call (HIP events), and whether the indicator's neighbour table is built; 0 before the first call
+    virtual void
+    error_norm_info(uint64_t &bytes, double &kernel_ms, int &neighbours_built) const = 0;
 
   private:
     // distribute_values without its refusals (sizes, local-smoothing levels): distribute(x, kind) runs on every level

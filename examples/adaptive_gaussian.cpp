@@ -3,7 +3,8 @@
 // hypercube NRefGlobal 2, every cycle builds the HMG-global hierarchy of the current mesh, solves with CG (reltol 1e-10), fills the
 // constrained entries, computes the jump error indicator eta_K on the device (Operator::estimate_error), flags the cells with
 // eta_K >= 0.5 max eta (mark_maximum) and refines them (Triangulation::refine, which restores the 2:1 balance).  Prints per cycle the
-// cells, the DoFs, sum eta_K^2 and the largest nodal error against the exact solution.  The example of INTEGRATION.md section 2d.
+// cells, the DoFs, sum eta_K^2, the largest nodal error against the exact solution, the L2 and H1 errors (Operator::integrate_difference)
+// and the effectivity index sqrt(sum eta_K^2) / energy error.  The example of INTEGRATION.md section 2d.
 //   adaptive_gaussian [degree = 2] [cycles = 4]
 #include "../dealii_multigrid_amd/csrc/mgamd.hpp"
 
@@ -54,8 +55,15 @@ main(int argc, char **argv)
               const double exact = std::exp(-r2 / (width * width)) / std::pow(std::sqrt(2.0 * pi) * width, 3.0);
               error              = std::max(error, std::fabs(uh[d] - exact));
             }
-          std::printf("cycle %u cells %llu dofs %llu cg_iterations %u sum_eta2 %.6e max_nodal_error %.6e\n", cycle,
-                      (unsigned long long)mesh->n_global_active_cells(), (unsigned long long)dofs.n_dofs(), control.last_step(), sum, error);
+          // the true error on the device (Operator::integrate_difference against the built-in Gaussian, QGauss(degree + 2) per leaf) and
+          // the effectivity index sqrt(sum eta_K^2) / |||e|||: a = 1 and sigma = 0 here, so the energy norm is the H1 seminorm
+          const double l2     = compute_global_error(A.integrate_difference(u, 1, MGAMD_NORM_L2, degree + 2), MGAMD_NORM_L2);
+          const double h1     = compute_global_error(A.integrate_difference(u, 1, MGAMD_NORM_H1_SEMINORM, degree + 2), MGAMD_NORM_H1_SEMINORM);
+          const double energy = compute_global_error(A.integrate_difference(u, 1, MGAMD_NORM_ENERGY, degree + 2), MGAMD_NORM_ENERGY);
+          std::printf("cycle %u cells %llu dofs %llu cg_iterations %u sum_eta2 %.6e max_nodal_error %.6e l2_error %.6e h1_error %.6e "
+                      "effectivity %.6e\n",
+                      cycle, (unsigned long long)mesh->n_global_active_cells(), (unsigned long long)dofs.n_dofs(), control.last_step(), sum, error,
+                      l2, h1, std::sqrt(sum) / energy);
           if (cycle + 1 < cycles)
             mesh = mesh->refine(mark_maximum(eta, 0.5));
         }

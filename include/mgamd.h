@@ -213,6 +213,13 @@ int mgamd_dofs_dirichlet_face_values(const mgamd_dofs *d, const double v[6], dou
 int mgamd_dofs_dirichlet_cells(const mgamd_dofs *d, uint64_t *n_cells, uint32_t *idx, uint16_t *mask, double *scale);
 /* support point of every DoF: xyz[3 i ..] */
 int mgamd_dofs_node_positions(const mgamd_dofs *d, double *xyz);
+/* The physical points of the tensor Gauss rule QGauss(n_q)^3 on every leaf (in deal.II: FEValues::get_quadrature_points over the
+ * active cells), the points at which mgamd_level_op_integrate_difference_values expects its data: xyz[3 ((cell n_q + qz) n_q + qy) n_q
+ * + qx) ..], leaves in the order of mgamd_tria_get_cells, qx fastest; 3 n_cells n_q^3 doubles.  Each coordinate is the leaf's corner plus
+ * h times the point of the rule on [0, 1], one multiplication and one addition in double.  n_q: p + 1, p + 2 or p + 3; 0 stands for
+ * p + 2.  Host only, no GPU needed.  MGAMD_ERR_INVALID, by name: any other n_q; sharded tables ("not implemented: sharded"); the
+ * tables of a local-smoothing level. */
+int mgamd_dofs_quadrature_points(const mgamd_dofs *d, int n_q, double *xyz);
 /* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
  * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
  * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
@@ -450,6 +457,43 @@ int mgamd_level_op_distribute_values(mgamd_level_op *op, mgamd_vec *x, const mga
  * MGAMD_ERR_INVALID, by name: a distributed operator ("not implemented: sharded"); the operator of a local-smoothing level; a
  * vector of the wrong size or number type; a non-finite q[f]; a non-zero q[f] on a Dirichlet face; eta == NULL. */
 int mgamd_level_op_estimate_error(mgamd_level_op *op, const mgamd_vec *u, const double q[6], double *eta);
+
+/* The error norms per leaf, the partner of the indicator (in deal.II: VectorTools::integrate_difference into a per-cell vector; the
+ * global value is the l2 norm of that vector for the first three norms and its maximum for the last, VectorTools::compute_global_error,
+ * which mgamd.hpp and the Python module provide as compute_global_error). */
+#define MGAMD_NORM_L2 0
+#define MGAMD_NORM_H1_SEMINORM 1
+#define MGAMD_NORM_ENERGY 2
+#define MGAMD_NORM_LINFTY 3
+/* For the level's Q_p function u_h (the entries of u at free and Dirichlet DoFs; hanging entries are never read), an "exact" function
+ * w and the tensor rule QGauss(n_q)^3 with weights w_q (summing to 1) on every leaf K with edge length h_K:
+ *     MGAMD_NORM_L2           sqrt( sum_q w_q h_K^3 (u_h - w)^2 )
+ *     MGAMD_NORM_H1_SEMINORM  sqrt( sum_q w_q h_K^3 |grad u_h - grad w|^2 )
+ *     MGAMD_NORM_ENERGY       sqrt( sum_q w_q h_K^3 ( a_K |grad u_h - grad w|^2 + sigma (u_h - w)^2 ) )
+ *     MGAMD_NORM_LINFTY       max_q |u_h - w|
+ * a_K is the leaf's diffusion coefficient and sigma the mass coefficient the operator was BUILT with.  The energy norm has volume
+ * terms only: no Robin surface term beta int u^2 is added.  The values are norms, not squares, like eta.
+ * kind: the built-in w, evaluated on the device in double: 0 is w = 0 (the norms of u_h itself), 1 the Gaussian of SimulationType
+ * "Gaussian" (the function mgamd_dofs_rhs(kind = 1) takes its data from), value and gradient in closed form.
+ * n_q: p + 1, p + 2 or p + 3 points per direction; 0 stands for p + 2.
+ * out: host array of n_cells values in the order of mgamd_tria_get_cells.  One kernel, stream-ordered behind whatever the stream holds
+ * for u; returns after the copy to the host.  All arithmetic after the loads is FP64 for both number types; no atomics and a fixed
+ * order of every leaf's sum: two calls return bit-identical arrays.  The gather table (4 (p+1)^3 + 18 bytes per cell) is the
+ * indicator's, one copy, built by whichever of the two calls comes first; the norms add 32 bytes per cell.  An operator that is never
+ * asked allocates and launches nothing.
+ * MGAMD_ERR_INVALID, by name: a distributed operator or sharded tables ("integrate_difference: not implemented: sharded"); the
+ * operator of a local-smoothing level (the active-mesh operator of such a hierarchy works); u of the wrong size or number type; n_q
+ * outside {0, p + 1, p + 2, p + 3}; an unknown norm or kind; out == NULL. */
+int mgamd_level_op_integrate_difference(mgamd_level_op *op, const mgamd_vec *u, int kind, int n_q, int norm, double *out);
+/* The same with caller data for w at the points of mgamd_dofs_quadrature_points(d, n_q, .), device vectors in the operator's number
+ * type (converted to double at the load): values, n_cells n_q^3 entries laid out [cell][qz][qy][qx], read by every norm but
+ * MGAMD_NORM_H1_SEMINORM (may be NULL there); gradients, 3 n_cells n_q^3 entries laid out [cell][component][qz][qy][qx], read by
+ * MGAMD_NORM_H1_SEMINORM and MGAMD_NORM_ENERGY only (may be NULL for the other two).  Note the layouts: the points come interleaved
+ * (x, y, z per point), the gradients come by component.
+ * MGAMD_ERR_INVALID, by name: the refusals above; values or gradients of the wrong size or number type; values == NULL where they are
+ * read; a gradient norm without gradients. */
+int mgamd_level_op_integrate_difference_values(mgamd_level_op *op, const mgamd_vec *u, const mgamd_vec *values, const mgamd_vec *gradients,
+                                               int n_q, int norm, double *out);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is
  * computed internally (DiagonalMatrix preconditioner); eigenvalues are estimated at creation with

@@ -108,6 +108,12 @@ int mgamd_debug_tria_face_neighbours(const mgamd_tria *t, uint8_t *code, uint32_
  * of the last call (HIP events); all 0 before the operator's first estimate.  Any pointer may be null. */
 int mgamd_debug_level_op_estimator_info(const mgamd_level_op *op, uint64_t *bytes, double *build_ms, double *kernel_ms);
 
+/* ---- the error norms (mgamd_level_op_integrate_difference) ----
+ * measurement: bytes of the device arrays the norms use (the gather table shared with the indicator, the leaves' corners, the result),
+ * the device time of the kernel of the last call (HIP events), and whether the indicator's neighbour table has been built (1) or not
+ * (0: a norm-only operator never builds it).  bytes and kernel_ms are 0 before the operator's first norm.  Any pointer may be null. */
+int mgamd_debug_level_op_error_norm_info(const mgamd_level_op *op, uint64_t *bytes, double *kernel_ms, int *neighbours_built);
+
 #ifdef __cplusplus
 }
 #endif
