@@ -456,6 +456,38 @@ class DoFs:
         _chk(_lib.mgamd_dofs_quadrature_points(self._h, C.c_int(n_q), _ptr(xyz)))  # (refuses n_q by name before it writes)
         return xyz
 
+    def _points_array(self, a, per_point, n_q, who):
+        """caller data at the quadrature points as a contiguous double array of the layout's size, None passed through"""
+        if a is None:
+            return None
+        nq = self.degree + 2 if n_q == 0 else int(n_q)
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if self.degree + 1 <= nq <= self.degree + 3 and a.size != per_point * self.info.n_cells * nq ** 3:  # (another n_q is refused by name)
+            raise ValueError(f"{who}: {a.size} values for {per_point} x {self.info.n_cells * nq ** 3} quadrature points")
+        return a
+
+    def integrate(self, values=None, gradients=None, n_q: int = 0):
+        """the load of data at quadrature_points(n_q), host vector (mgamd_dofs_integrate; in deal.II: FEEvaluation::integrate,
+        VectorTools::create_right_hand_side): b_i = sum_K sum_q w_q h_K^3 (values_q phi_i(x_q) + gradients_q . grad phi_i(x_q)) through
+        the transposed hanging-node interpolation, constrained rows 0.  values [cell, qz, qy, qx], gradients [cell, component, qz, qy,
+        qx]; either may be None, not both.  No coefficient and no sigma are applied."""
+        v, g = self._points_array(values, 1, n_q, "integrate"), self._points_array(gradients, 3, n_q, "integrate")
+        b = np.zeros(self.n_dofs)
+        _chk(_lib.mgamd_dofs_integrate(self._h, None if v is None else _ptr(v), None if g is None else _ptr(g), C.c_int(n_q), _ptr(b)))
+        return b
+
+    def evaluate(self, u, n_q: int = 0, values: bool = True, gradients: bool = False):
+        """u_h [cell, qz, qy, qx] and/or grad u_h [cell, component, qz, qy, qx] of the host vector u at quadrature_points(n_q)
+        (mgamd_dofs_evaluate; in deal.II: FEEvaluation::evaluate): the values, the gradients, or the tuple of both.  Hanging entries of
+        u are never read."""
+        u = self._data_array(u, "evaluate")
+        nq = self.degree + 2 if n_q == 0 else int(n_q)
+        shape = (self.info.n_cells, nq, nq, nq) if self.degree + 1 <= nq <= self.degree + 3 else (1, 1, 1, 1)
+        v = np.zeros(shape) if values else None
+        g = np.zeros((shape[0], 3) + shape[1:]) if gradients else None
+        _chk(_lib.mgamd_dofs_evaluate(self._h, _ptr(u), C.c_int(n_q), None if v is None else _ptr(v), None if g is None else _ptr(g)))
+        return (v, g) if values and gradients else (v if values else g)
+
     def _data_array(self, a, who):
         a = np.ascontiguousarray(a, dtype=np.float64)
         if a.shape != (self.n_dofs,):
@@ -816,10 +848,19 @@ class Operator:
             _chk(_lib.mgamd_level_op_integrate_difference(self._h, u._h, C.c_int(int(exact)), C.c_int(n_q), C.c_int(norm), _ptr(out)))
             return out
         values, gradients = exact if isinstance(exact, tuple) else (exact, None)
+        v, g = self._quadrature_data(values, gradients, n_q)
+        _chk(_lib.mgamd_level_op_integrate_difference_values(self._h, u._h, v._h if v is not None else None, g._h if g is not None else None,
+                                                             C.c_int(n_q), C.c_int(norm), _ptr(out)))
+        return out
+
+    def _quadrature_data(self, values, gradients, n_q):
+        """caller data at DoFs.quadrature_points(n_q) as device Vectors of the operator's number type (the rule of integrate_difference
+        and integrate): each of values [cell, qz, qy, qx] and gradients [cell, component, qz, qy, qx] may be None, a Vector (passed
+        through), an array (uploaded), or a callable of (x, y, z) tabulated at the points on the host (gradients: returning the three
+        components) and uploaded"""
         points = None
         if callable(values) or callable(gradients):
             points = np.moveaxis(self.dofs.quadrature_points(n_q), -1, 0)  # (refuses n_q by name)
-        keep = []
 
         def device(a, per_point):
             if a is None or isinstance(a, Vector):
@@ -831,13 +872,39 @@ class Operator:
                 else:
                     a = np.broadcast_to(np.asarray(a, np.float64), points[0].shape)
             a = np.ascontiguousarray(a, dtype=np.float64)
-            keep.append(Vector(self.ctx, a.size, self.number_type).from_host(a.ravel()))
-            return keep[-1]
+            return Vector(self.ctx, a.size, self.number_type).from_host(a.ravel())
 
-        v, g = device(values, 1), device(gradients, 3)
-        _chk(_lib.mgamd_level_op_integrate_difference_values(self._h, u._h, v._h if v is not None else None, g._h if g is not None else None,
-                                                             C.c_int(n_q), C.c_int(norm), _ptr(out)))
-        return out
+        return device(values, 1), device(gradients, 3)
+
+    def evaluate(self, u: Vector, n_q: int = 0, values: bool = True, gradients: bool = False):
+        """u_h and/or grad u_h at DoFs.quadrature_points(n_q) on the device (mgamd_level_op_evaluate; in deal.II:
+        FEEvaluation::evaluate over a cell loop): device Vectors of the operator's number type, values laid out [cell, qz, qy, qx] and
+        gradients [cell, component, qz, qy, qx].  Returns the values, the gradients, or the tuple (values, gradients) for both.  Only
+        entries of u at free and Dirichlet DoFs are read; two calls give the same bits.  n_q = 0 for degree + 2."""
+        nq = self.dofs.degree + 2 if n_q == 0 else int(n_q)
+        n_points = self.dofs.info.n_cells * nq ** 3 if self.dofs.degree + 1 <= nq <= self.dofs.degree + 3 else 1  # (n_q is refused by name)
+        v = Vector(self.ctx, n_points, self.number_type) if values else None
+        g = Vector(self.ctx, 3 * n_points, self.number_type) if gradients else None
+        _chk(_lib.mgamd_level_op_evaluate(self._h, u._h if u is not None else None, C.c_int(n_q), v._h if v is not None else None,
+                                          g._h if g is not None else None))
+        return (v, g) if values and gradients else (v if values else g)
+
+    def integrate(self, b: Vector, values=None, gradients=None, n_q: int = 0):
+        """b_i = sum_K sum_q w_q h_K^3 (values_q phi_i(x_q) + gradients_q . grad phi_i(x_q)) through C^T on the device
+        (mgamd_level_op_integrate; in deal.II: FEEvaluation::integrate, VectorTools::create_right_hand_side): the load of a source
+        (values = f), the divergence-form load (gradients = F) or both.  Each of values and gradients is a Vector, an array or a
+        callable tabulated at DoFs.quadrature_points(n_q), by the rule of integrate_difference's `exact`; at least one is given.  b is
+        overwritten, constrained rows are 0; no coefficient and no sigma are applied.  Not bit-reproducible across calls."""
+        v, g = self._quadrature_data(values, gradients, n_q)
+        _chk(_lib.mgamd_level_op_integrate(self._h, v._h if v is not None else None, g._h if g is not None else None, C.c_int(n_q),
+                                           b._h if b is not None else None))
+
+    def _cell_values_info(self):
+        """(bytes of the device arrays evaluate and integrate use: the shared gather table; device milliseconds of the last evaluate
+        and of the last integrate); zeros before the first call (mgamd_debug_level_op_cell_values_info)"""
+        b, t0, t1 = C.c_uint64(), C.c_double(), C.c_double()
+        _chk(_lib.mgamd_debug_level_op_cell_values_info(self._h, C.byref(b), C.byref(t0), C.byref(t1)))
+        return b.value, t0.value, t1.value
 
     def _error_norm_info(self):
         """(bytes of the device arrays the error norms use, the shared gather table included; device milliseconds of the kernel of the

@@ -31,4 +31,7 @@ namespace mgamd
   // the error norms (kernels_error_norm.hpp)
   template void LevelOperator<MGAMD_INST_T>::difference_norm_P<MGAMD_INST_P>(const MGAMD_INST_T *, int, const MGAMD_INST_T *, const MGAMD_INST_T *, int,
                                                                              int);
+  // the cell evaluate and integrate (kernels_cell_values.hpp)
+  template void LevelOperator<MGAMD_INST_T>::cell_evaluate_P<MGAMD_INST_P>(const MGAMD_INST_T *, int, MGAMD_INST_T *, MGAMD_INST_T *);
+  template void LevelOperator<MGAMD_INST_T>::cell_integrate_P<MGAMD_INST_P>(const MGAMD_INST_T *, const MGAMD_INST_T *, int, MGAMD_INST_T *);
 } // namespace mgamd

@@ -516,6 +516,41 @@ mgamd_debug_level_op_error_norm_info(const mgamd_level_op *op, uint64_t *bytes, 
 }
 
 int
+mgamd_level_op_evaluate(mgamd_level_op *op, const mgamd_vec *u, int n_q, mgamd_vec *values, mgamd_vec *gradients)
+{
+  MGAMD_TRY
+  REQUIRE(op);
+  op->op->evaluate(u, n_q, values, gradients); // (refuses a null u and missing outputs by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_level_op_integrate(mgamd_level_op *op, const mgamd_vec *values, const mgamd_vec *gradients, int n_q, mgamd_vec *b)
+{
+  MGAMD_TRY
+  REQUIRE(op);
+  op->op->integrate(values, gradients, n_q, b); // (refuses a null b and missing data by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_level_op_cell_values_info(const mgamd_level_op *op, uint64_t *bytes, double *evaluate_ms, double *integrate_ms)
+{
+  MGAMD_TRY
+  REQUIRE(op);
+  uint64_t b  = 0;
+  double   t0 = 0.0, t1 = 0.0;
+  op->op->cell_values_info(b, t0, t1);
+  if (bytes)
+    *bytes = b;
+  if (evaluate_ms)
+    *evaluate_ms = t0;
+  if (integrate_ms)
+    *integrate_ms = t1;
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_debug_stamps(mgamd_level_op *op, unsigned long long *out, uint64_t max_count, uint64_t *count)
 {
   MGAMD_TRY

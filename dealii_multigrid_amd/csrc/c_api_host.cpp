@@ -721,6 +721,30 @@ mgamd_dofs_quadrature_points(const mgamd_dofs *d, int n_q, double *xyz)
 }
 
 int
+mgamd_dofs_integrate(const mgamd_dofs *d, const double *values, const double *gradients, int n_q, double *out)
+{
+  MGAMD_TRY
+  if (!d)
+    throw std::invalid_argument("null argument");
+  if (!out)
+    throw std::invalid_argument("integrate: out is null (n_dofs values)");
+  std::vector<double> b;
+  d->tables->integrate_values(values, gradients, n_q, b); // (refuses n_q, missing data, sharded tables and local-smoothing levels by name)
+  std::copy(b.begin(), b.end(), out);
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_evaluate(const mgamd_dofs *d, const double *u, int n_q, double *values, double *gradients)
+{
+  MGAMD_TRY
+  if (!d)
+    throw std::invalid_argument("null argument");
+  d->tables->evaluate_values(u, n_q, values, gradients); // (refuses a null u, n_q, missing outputs, sharded tables and local-smoothing levels)
+  MGAMD_CATCH
+}
+
+int
 mgamd_dofs_coefficient_range(const mgamd_dofs *d, double *min, double *max)
 {
   MGAMD_TRY

@@ -1377,6 +1377,140 @@ namespace mgamd
       neighbours_built = estimator && estimator->neighbours ? 1 : 0;
     }
 
+    // Cell evaluate and integrate (kernels_cell_values.hpp).  They hold nothing of their own but the events of their timings: the
+    // gather table is the estimator's (ensure_estimator(false)), neither the neighbour table nor the norms' part is built.
+    struct CellValuesDev
+    {
+      hipEvent_t ev[4]     = {nullptr, nullptr, nullptr, nullptr}; // evaluate: 0, 1; integrate: 2, 3
+      bool       timed[2]  = {false, false};
+      ~CellValuesDev()
+      {
+        for (hipEvent_t e : ev)
+          if (e)
+            (void)hipEventDestroy(e);
+      }
+    };
+    std::unique_ptr<CellValuesDev> cell_values;
+    // the refusals the two calls share, then the shared table; returns the resolved n_q
+    int
+    ensure_cell_values(int n_q, const char *who)
+    {
+      if (comm || halo_plan)
+        throw std::invalid_argument(std::string(who) + ": not implemented: sharded (the operator is distributed; one rank only)");
+      tables->refuse_estimate(who);
+      return tables->resolve_n_q(n_q, who);
+    }
+    void
+    build_cell_values(const char *who)
+    {
+      ensure_estimator(false, who);
+      if (!cell_values)
+        {
+          auto dev = std::make_unique<CellValuesDev>();
+          for (hipEvent_t &e : dev->ev)
+            HIP_CHECK(hipEventCreate(&e));
+          cell_values = std::move(dev);
+        }
+    }
+    // defined in level_operator_apply.hpp, instantiated in apply_inst.hip: the launches of cell_evaluate_kernel and cell_integrate_kernel
+    template <int P>
+    void
+    cell_evaluate_P(const T *u, int n_q, T *values, T *gradients);
+    template <int P>
+    void
+    cell_integrate_P(const T *values, const T *gradients, int n_q, T *b);
+
+    void
+    evaluate(const mgamd_vec *u, int n_q, mgamd_vec *values, mgamd_vec *gradients) override
+    {
+      const char *who = "evaluate";
+      const int   nq  = ensure_cell_values(n_q, who);
+      if (!u)
+        throw std::invalid_argument("evaluate: u is null (a device vector of n_dofs values)");
+      if (!values && !gradients)
+        throw std::invalid_argument("evaluate: neither values nor gradients (at least one output)");
+      if (u->n != n_dofs())
+        throw std::invalid_argument("evaluate: vector size mismatch (" + std::to_string(u->n) + " for " + std::to_string(n_dofs()) + " DoFs)");
+      const T     *up = u->as<T>(); // (refuses the other number type)
+      T           *vp = nullptr, *gp = nullptr;
+      const size_t n_points = tables->tria->cells.size() * (size_t)nq * nq * nq;
+      if (values)
+        {
+          if (values->n != n_points)
+            throw std::invalid_argument("evaluate: values size mismatch (" + std::to_string(values->n) + " for " + std::to_string(n_points) +
+                                        " quadrature points)");
+          vp = values->as<T>();
+        }
+      if (gradients)
+        {
+          if (gradients->n != 3 * n_points)
+            throw std::invalid_argument("evaluate: gradients size mismatch (" + std::to_string(gradients->n) + " for 3 x " +
+                                        std::to_string(n_points) + " quadrature points)");
+          gp = gradients->as<T>();
+        }
+      if ((vp && (const void *)vp == (const void *)up) || (gp && (const void *)gp == (const void *)up) || (vp && vp == gp))
+        throw std::invalid_argument("evaluate: u, values and gradients must differ");
+      build_cell_values(who);
+      HIP_CHECK(hipEventRecord(cell_values->ev[0], ctx->stream));
+      if (!dispatch_degree(p, [&](auto P) { cell_evaluate_P<P()>(up, nq, vp, gp); }))
+        throw std::runtime_error("degree not instantiated");
+      HIP_CHECK(hipEventRecord(cell_values->ev[1], ctx->stream));
+      cell_values->timed[0] = true;
+    }
+    void
+    integrate(const mgamd_vec *values, const mgamd_vec *gradients, int n_q, mgamd_vec *b) override
+    {
+      const char *who = "integrate";
+      const int   nq  = ensure_cell_values(n_q, who);
+      if (!b)
+        throw std::invalid_argument("integrate: b is null (a device vector of n_dofs values)");
+      if (!values && !gradients)
+        throw std::invalid_argument("integrate: neither values nor gradients (at least one input)");
+      if ((values && values->data == b->data) || (gradients && gradients->data == b->data))
+        throw std::invalid_argument(std::string("integrate: b aliases ") + (values && values->data == b->data ? "values" : "gradients") +
+                                    " (b is overwritten before the data is read)");
+      if (b->n != n_dofs())
+        throw std::invalid_argument("integrate: vector size mismatch (" + std::to_string(b->n) + " for " + std::to_string(n_dofs()) + " DoFs)");
+      T           *bp = b->as<T>(); // (refuses the other number type)
+      const T     *vp = nullptr, *gp = nullptr;
+      const size_t n_points = tables->tria->cells.size() * (size_t)nq * nq * nq;
+      if (values)
+        {
+          if (values->n != n_points)
+            throw std::invalid_argument("integrate: values size mismatch (" + std::to_string(values->n) + " for " + std::to_string(n_points) +
+                                        " quadrature points)");
+          vp = values->as<T>();
+        }
+      if (gradients)
+        {
+          if (gradients->n != 3 * n_points)
+            throw std::invalid_argument("integrate: gradients size mismatch (" + std::to_string(gradients->n) + " for 3 x " +
+                                        std::to_string(n_points) + " quadrature points)");
+          gp = gradients->as<T>();
+        }
+      build_cell_values(who);
+      HIP_CHECK(hipEventRecord(cell_values->ev[2], ctx->stream));
+      HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)n_dofs() * sizeof(T), ctx->stream));
+      if (!dispatch_degree(p, [&](auto P) { cell_integrate_P<P()>(vp, gp, nq, bp); }))
+        throw std::runtime_error("degree not instantiated");
+      HIP_CHECK(hipEventRecord(cell_values->ev[3], ctx->stream));
+      cell_values->timed[1] = true;
+    }
+    void
+    cell_values_info(uint64_t &bytes, double &evaluate_ms, double &integrate_ms) const override
+    {
+      bytes       = cell_values && estimator ? estimator->gather_bytes : 0;
+      evaluate_ms = integrate_ms = 0.0;
+      for (int k = 0; k < 2; ++k)
+        if (cell_values && cell_values->timed[k])
+          {
+            float ms = 0.f;
+            HIP_CHECK(hipEventSynchronize(cell_values->ev[2 * k + 1]));
+            HIP_CHECK(hipEventElapsedTime(&ms, cell_values->ev[2 * k], cell_values->ev[2 * k + 1]));
+            (k == 0 ? evaluate_ms : integrate_ms) = ms;
+          }
+    }
+
     size_t
     read_debug_stamps(unsigned long long *out, size_t max_count) override
     {

@@ -221,4 +221,78 @@ namespace mgamd
     HIP_CHECK(hipGetLastError());
   }
 
+  // the 1D matrices of cell_evaluate_kernel and cell_integrate_kernel for the rule QGauss(n_q): the members both argument structs share
+  template <typename Args>
+  static void
+  fill_cell_values_matrices(Args &a, const FE1D &fe, int n_q, std::vector<double> &wq)
+  {
+    const int n = fe.p + 1;
+    static_assert(Args::NQM <= FE1D::MAX_GAUSS_POINTS, "the rule generator is held to 10 points");
+    if (n_q < n || n_q > Args::NQM)
+      throw std::invalid_argument("cell values: n_q outside p + 1 ... p + 3"); // (resolve_n_q refused it already: the LDS bound)
+    std::vector<double> xq, S, G;
+    fe.shape_at_gauss(n_q, xq, wq, S, G);
+    std::memset(a.S, 0, sizeof(a.S));
+    std::memset(a.G, 0, sizeof(a.G));
+    std::copy(S.begin(), S.end(), a.S);
+    std::copy(G.begin(), G.end(), a.G);
+    for (int i = 0; i < n * n; ++i)
+      {
+        a.I0[i] = fe.I[0][i];
+        a.I1[i] = fe.I[1][i];
+      }
+    a.n_q = n_q;
+  }
+
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::cell_evaluate_P(const T *u, int n_q, T *values, T *gradients)
+  {
+    EstimatorDev &e = *estimator;
+    if (!e.n_cells)
+      return;
+    CellEvaluateArgs<T, P> a;
+    std::vector<double>    wq;
+    fill_cell_values_matrices(a, tables->fe, n_q, wq);
+    a.idx       = e.idx.p;
+    a.mask      = e.mask.p;
+    a.scale     = e.scale.p;
+    a.n_cells   = e.n_cells;
+    a.n_dofs    = n_dofs();
+    a.u         = u;
+    a.values    = values;
+    a.gradients = gradients;
+    // two groups of leaves per workgroup where there are that many: the 1D matrices are staged in LDS once per workgroup
+    const uint32_t groups = (e.n_cells + dirichlet_cells_per_workgroup<P>() - 1) / dirichlet_cells_per_workgroup<P>();
+    hipLaunchKernelGGL((cell_evaluate_kernel<T, P>), std::min<uint32_t>(4096u, (groups + 1) / 2), 256, 0, ctx->stream, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::cell_integrate_P(const T *values, const T *gradients, int n_q, T *b)
+  {
+    EstimatorDev &e = *estimator;
+    if (!e.n_cells)
+      return;
+    CellIntegrateArgs<T, P> a;
+    std::vector<double>     wq;
+    fill_cell_values_matrices(a, tables->fe, n_q, wq);
+    std::memset(a.wq, 0, sizeof(a.wq));
+    std::copy(wq.begin(), wq.end(), a.wq);
+    a.idx           = e.idx.p;
+    a.mask          = e.mask.p;
+    a.scale         = e.scale.p;
+    a.n_cells       = e.n_cells;
+    a.scatter_limit = tables->first_constrained(); // the free rows
+    a.values        = values;
+    a.gradients     = gradients;
+    a.dst           = b;
+    const uint32_t groups = (e.n_cells + integrate_cells_per_workgroup<P>() - 1) / integrate_cells_per_workgroup<P>();
+    hipLaunchKernelGGL((cell_integrate_kernel<T, P>), std::min<uint32_t>(4096u, (groups + 1) / 2), 256, 0, ctx->stream, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
 } // namespace mgamd

@@ -1176,6 +1176,105 @@ namespace mgamd
       dirichlet_lift_add(g.data(), true, -1.0, b);
     }
 
+    // ---- cell evaluate and integrate (DESIGN.md "Cell evaluate and integrate"; on the device: kernels_cell_values.hpp) -------------
+    // sweep_1d for the rectangular matrices of a rule with n_q != p + 1: out = A (or A^T) along direction d of a tensor with the
+    // extents dims[3] (x fastest); A is rows x cols, row-major.  Not transposed: dims[d] == cols, the extent becomes rows;
+    // transposed: dims[d] == rows, the extent becomes cols.  dims is updated.
+    static void
+    sweep_1d_rect(const double *A, int rows, int cols, bool transposed, int d, int dims[3], const double *in, std::vector<double> &out)
+    {
+      const int n_in = dims[d], n_out = transposed ? cols : rows;
+      const int st = d == 0 ? 1 : (d == 1 ? dims[0] : dims[0] * dims[1]), outer = dims[0] * dims[1] * dims[2] / (st * n_in);
+      out.assign((size_t)st * n_out * outer, 0.0);
+      for (int o = 0; o < outer; ++o)
+        for (int a = 0; a < n_out; ++a)
+          for (int i = 0; i < st; ++i)
+            {
+              double s = 0;
+              for (int b = 0; b < n_in; ++b)
+                s += (transposed ? A[b * cols + a] : A[a * cols + b]) * in[(o * n_in + b) * st + i];
+              out[(o * n_out + a) * st + i] = s;
+            }
+      dims[d] = n_out;
+    }
+    // values [cell][qz][qy][qx] and/or gradients [cell][component][qz][qy][qx] (either may be null, not both) of the level's Q_p
+    // function of u at the points of quadrature_points(n_q): free and Dirichlet entries of u are read, hanging entries never
+    void
+    evaluate_values(const double *u, int n_q, double *values, double *gradients) const
+    {
+      refuse_estimate("evaluate");
+      const int nq = resolve_n_q(n_q, "evaluate");
+      if (!u)
+        throw std::invalid_argument("evaluate: u is null (n_dofs values)");
+      if (!values && !gradients)
+        throw std::invalid_argument("evaluate: neither values nor gradients (at least one output)");
+      const int             n = p + 1, n3 = n * n * n, nq3 = nq * nq * nq;
+      std::vector<double>   xq, wq, S, G, loc(n3), t1, t2, t3;
+      std::vector<uint32_t> idx(n3);
+      fe.shape_at_gauss(nq, xq, wq, S, G);
+      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
+        {
+          const double h = 2.0 / (double)(1u << tria->cells[ci].level);
+          gather_cell(ci, idx.data(), true);
+          for (int t = 0; t < n3; ++t)
+            loc[t] = idx[t] != INVALID_DOF ? u[idx[t]] : 0.0;
+          interpolate_hanging(fe, tria->masks[ci], loc.data(), false);
+          // component -1: the value (S, S, S); component c: G along c
+          for (int c = values ? -1 : 0; c < (gradients ? 3 : 0); ++c)
+            {
+              int dims[3] = {n, n, n};
+              sweep_1d_rect((c == 0 ? G : S).data(), nq, n, false, 0, dims, loc.data(), t1);
+              sweep_1d_rect((c == 1 ? G : S).data(), nq, n, false, 1, dims, t1.data(), t2);
+              sweep_1d_rect((c == 2 ? G : S).data(), nq, n, false, 2, dims, t2.data(), t3);
+              double *out = c < 0 ? values + ci * nq3 : gradients + (ci * 3 + c) * nq3;
+              for (int q = 0; q < nq3; ++q)
+                out[q] = c < 0 ? t3[q] : t3[q] / h;
+            }
+        }
+    }
+    // b_i = sum_K sum_q w_q h_K^3 (v_q phi_i(x_q) + V_q . grad phi_i(x_q)) through C^T; b is overwritten, constrained rows 0; no
+    // coefficient and no sigma (values, gradients in the layouts of evaluate_values; either may be null, not both)
+    void
+    integrate_values(const double *values, const double *gradients, int n_q, std::vector<double> &b) const
+    {
+      refuse_estimate("integrate");
+      const int nq = resolve_n_q(n_q, "integrate");
+      if (!values && !gradients)
+        throw std::invalid_argument("integrate: neither values nor gradients (at least one input)");
+      b.assign(n_dofs, 0.0);
+      const int             n = p + 1, n3 = n * n * n, nq3 = nq * nq * nq;
+      std::vector<double>   xq, wq, S, G, fq(nq3), load(n3), t1, t2, t3;
+      std::vector<uint32_t> idx(n3);
+      fe.shape_at_gauss(nq, xq, wq, S, G);
+      for (size_t ci = 0; ci < tria->cells.size(); ++ci)
+        {
+          const double h = 2.0 / (double)(1u << tria->cells[ci].level);
+          std::fill(load.begin(), load.end(), 0.0);
+          for (int c = values ? -1 : 0; c < (gradients ? 3 : 0); ++c)
+            {
+              const double *in = c < 0 ? values + ci * nq3 : gradients + (ci * 3 + c) * nq3;
+              const double  jw = c < 0 ? h * h * h : h * h; // JxW, with the 1 / h of the gradient
+              for (int qz = 0; qz < nq; ++qz)
+                for (int qy = 0; qy < nq; ++qy)
+                  for (int qx = 0; qx < nq; ++qx)
+                    fq[(qz * nq + qy) * nq + qx] = in[(qz * nq + qy) * nq + qx] * jw * wq[qx] * wq[qy] * wq[qz];
+              int dims[3] = {nq, nq, nq};
+              sweep_1d_rect((c == 0 ? G : S).data(), nq, n, true, 0, dims, fq.data(), t1);
+              sweep_1d_rect((c == 1 ? G : S).data(), nq, n, true, 1, dims, t1.data(), t2);
+              sweep_1d_rect((c == 2 ? G : S).data(), nq, n, true, 2, dims, t2.data(), t3);
+              for (int t = 0; t < n3; ++t)
+                load[t] += t3[t];
+            }
+          interpolate_hanging(fe, tria->masks[ci], load.data(), true);
+          gather_cell(ci, idx.data(), false);
+          for (int t = 0; t < n3; ++t)
+            if (idx[t] != INVALID_DOF)
+              b[idx[t]] += load[t];
+        }
+      for (uint32_t i = first_constrained(); i < n_dofs; ++i)
+        b[i] = 0.0;
+    }
+
     // the refusals of a boundary flux; the error indicator takes the same six constants and refuses them in the same words
     void
     check_boundary_flux(const double q[6]) const

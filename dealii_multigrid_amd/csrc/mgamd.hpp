@@ -869,6 +869,25 @@ namespace mgamd
       check(mgamd_level_op_integrate_difference_values(h.get(), u.get(), values.get(), gradients.get(), n_q, norm, out.data()));
       return out;
     }
+    // u_h and grad u_h at DoFHandler::quadrature_points(n_q) on the device (mgamd_level_op_evaluate; in deal.II:
+    // FEEvaluation::evaluate over a cell loop): values [cell][qz][qy][qx], n_cells n_q^3 entries, and gradients
+    // [cell][component][qz][qy][qx], three times as many, in the operator's number type.  An empty Vector is an output not asked for.
+    // Only entries of u at free and Dirichlet DoFs are read.  Stream-ordered, nothing is copied to the host.
+    void
+    evaluate(const Vector &u, Vector &values, Vector &gradients, int n_q = 0) const
+    {
+      check(mgamd_level_op_evaluate(h.get(), u.get(), n_q, values.get(), gradients.get()));
+    }
+    // load_i = sum_K sum_q w_q h_K^3 (values_q phi_i + gradients_q . grad phi_i) through C^T (mgamd_level_op_integrate; in deal.II:
+    // FEEvaluation::integrate + distribute_local_to_global, VectorTools::create_right_hand_side): the load of a source f (values =
+    // f at the points), the divergence-form load (gradients = F) or both.  An empty Vector is an input not given.  load is
+    // overwritten, constrained rows are 0; no coefficient and no sigma are applied.  Additive to rhs_dirichlet() and
+    // rhs_boundary_flux().  Stream-ordered, nothing is copied to the host; not bit-reproducible across calls (atomic adds).
+    void
+    integrate(Vector &load, const Vector &values, const Vector &gradients, int n_q = 0) const
+    {
+      check(mgamd_level_op_integrate(h.get(), values.get(), gradients.get(), n_q, load.get()));
+    }
     mgamd_level_op *
     get() const
     {

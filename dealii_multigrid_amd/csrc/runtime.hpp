@@ -257,6 +257,20 @@ namespace mgamd
     // of the kernel of the last call (HIP events), and whether the indicator's neighbour table is built; 0 before the first call
     virtual void
     error_norm_info(uint64_t &bytes, double &kernel_ms, int &neighbours_built) const = 0;
+    // Cell evaluate and integrate (kernels_cell_values.hpp), device vectors in the operator's number type at the points of
+    // LevelTables::quadrature_points(n_q), n_q: 0 for p + 2.  evaluate: values [cell][qz][qy][qx] and/or gradients
+    // [cell][component][qz][qy][qx] of the level's Q_p function of u; either output may be null.  integrate: b is OVERWRITTEN with
+    // sum_K sum_q w_q h_K^3 (v_q phi_i + V_q . grad phi_i) through C^T, constrained rows 0; either input may be null, not both.
+    // Stream-ordered, nothing is copied to the host.  The gather table is the indicator's and the norms', built by whichever call
+    // comes first.
+    virtual void
+    evaluate(const mgamd_vec *u, int n_q, mgamd_vec *values, mgamd_vec *gradients) = 0;
+    virtual void
+    integrate(const mgamd_vec *values, const mgamd_vec *gradients, int n_q, mgamd_vec *b) = 0;
+    // measurement: bytes of the device arrays the two calls use (the shared gather table; they hold nothing else) and the device
+    // times of the last evaluate and the last integrate (HIP events; waits for them); 0 before the first call
+    virtual void
+    cell_values_info(uint64_t &bytes, double &evaluate_ms, double &integrate_ms) const = 0;
 
   private:
     // distribute_values without its refusals (sizes, local-smoothing levels): distribute(x, kind) runs on every level

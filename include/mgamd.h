@@ -220,6 +220,21 @@ int mgamd_dofs_node_positions(const mgamd_dofs *d, double *xyz);
  * p + 2.  Host only, no GPU needed.  MGAMD_ERR_INVALID, by name: any other n_q; sharded tables ("not implemented: sharded"); the
  * tables of a local-smoothing level. */
 int mgamd_dofs_quadrature_points(const mgamd_dofs *d, int n_q, double *xyz);
+/* Cell evaluate and integrate on the host, in double (in deal.II: FEEvaluation::evaluate / FEEvaluation::integrate over a cell loop;
+ * the load of a function is VectorTools::create_right_hand_side).  The rule is QGauss(n_q)^3 on every leaf K with edge h_K, weights
+ * w_q summing to 1, at the points of mgamd_dofs_quadrature_points(d, n_q, .); values are laid out [cell][qz][qy][qx], gradients
+ * [cell][component][qz][qy][qx], leaves in the order of mgamd_tria_get_cells.
+ * mgamd_dofs_integrate: out_i = sum_K sum_q w_q h_K^3 ( values_q phi_i(x_q) + gradients_q . grad phi_i(x_q) ), mapped through the
+ * transposed hanging-node interpolation; out (n_dofs values) is overwritten and every constrained row (Dirichlet and hanging) is 0.
+ * Either of values and gradients may be NULL, not both.  No coefficient and no sigma are applied: a caller who wants the load of
+ * a_K F or sigma f multiplies the data.  values = f at the points is the load of the source f; gradients = F is the divergence-form
+ * load int F . grad phi_i.
+ * mgamd_dofs_evaluate: values and/or gradients (either may be NULL, not both) of the level's Q_p function of u, the physical
+ * gradient included; entries of u at free and Dirichlet DoFs are read, hanging entries never.
+ * No GPU needed.  MGAMD_ERR_INVALID, by name: n_q outside {0, p + 1, p + 2, p + 3}; sharded tables ("integrate: not implemented:
+ * sharded"); the tables of a local-smoothing level; neither values nor gradients; out == NULL, u == NULL. */
+int mgamd_dofs_integrate(const mgamd_dofs *d, const double *values, const double *gradients, int n_q, double *out);
+int mgamd_dofs_evaluate(const mgamd_dofs *d, const double *u, int n_q, double *values, double *gradients);
 /* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
  * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
  * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
@@ -494,6 +509,29 @@ int mgamd_level_op_integrate_difference(mgamd_level_op *op, const mgamd_vec *u, 
  * read; a gradient norm without gradients. */
 int mgamd_level_op_integrate_difference_values(mgamd_level_op *op, const mgamd_vec *u, const mgamd_vec *values, const mgamd_vec *gradients,
                                                int n_q, int norm, double *out);
+/* mgamd_dofs_evaluate on the device (in deal.II: FEEvaluation::evaluate with EvaluationFlags::values | gradients over a cell loop):
+ * values (n_cells n_q^3 entries, [cell][qz][qy][qx]) and/or gradients (3 n_cells n_q^3 entries, [cell][component][qz][qy][qx]) of
+ * the level's Q_p function of u at the points of mgamd_dofs_quadrature_points(d, n_q, .), device vectors in the operator's number
+ * type; either output may be NULL, not both.  Entries of u at free and Dirichlet DoFs are read, hanging entries never.  All arithmetic
+ * after the gather is FP64 for both number types and the store converts; no atomics and a fixed order of every sum: two calls give
+ * the same bits.  One kernel, stream-ordered; nothing is copied to the host.  The gather table (4 (p+1)^3 + 18 bytes per cell) is the
+ * one of the indicator and the error norms, built by whichever call comes first; neither the neighbour table nor the norms' arrays
+ * are built.  An operator that is never asked allocates and launches nothing.
+ * MGAMD_ERR_INVALID, by name: a distributed operator or sharded tables ("evaluate: not implemented: sharded"); the operator of a
+ * local-smoothing level; n_q outside {0, p + 1, p + 2, p + 3}; a vector of the wrong size or number type; neither values nor
+ * gradients; u == NULL; an output that is u or the other output. */
+int mgamd_level_op_evaluate(mgamd_level_op *op, const mgamd_vec *u, int n_q, mgamd_vec *values, mgamd_vec *gradients);
+/* mgamd_dofs_integrate on the device (in deal.II: FEEvaluation::integrate + distribute_local_to_global over a cell loop; with
+ * values = f at the points it is VectorTools::create_right_hand_side):
+ *     b_i = sum_K sum_q w_q h_K^3 ( values_q phi_i(x_q) + gradients_q . grad phi_i(x_q) )   through C^T,
+ * device vectors in the operator's number type in the layouts above; either input may be NULL, not both.  b is OVERWRITTEN: a
+ * stream-ordered memset comes before the kernel, and every constrained row (Dirichlet and hanging) is exactly 0 whatever b held.
+ * No coefficient and no sigma are applied.  The arithmetic is FP64 up to the scatter; the scatter is an atomic add in the vector's
+ * number type, so a row that several leaves share takes its addends in no fixed order: the result is NOT bit-reproducible across
+ * calls (it is where every row has one addend, as on a one-leaf mesh).  Stream-ordered, nothing is copied to the host; the data
+ * never leaves the device.  Tables as for mgamd_level_op_evaluate.
+ * MGAMD_ERR_INVALID, by name: the refusals above with "integrate:"; neither values nor gradients; b == NULL; b aliasing an input. */
+int mgamd_level_op_integrate(mgamd_level_op *op, const mgamd_vec *values, const mgamd_vec *gradients, int n_q, mgamd_vec *b);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is
  * computed internally (DiagonalMatrix preconditioner); eigenvalues are estimated at creation with

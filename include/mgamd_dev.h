@@ -114,6 +114,12 @@ int mgamd_debug_level_op_estimator_info(const mgamd_level_op *op, uint64_t *byte
  * (0: a norm-only operator never builds it).  bytes and kernel_ms are 0 before the operator's first norm.  Any pointer may be null. */
 int mgamd_debug_level_op_error_norm_info(const mgamd_level_op *op, uint64_t *bytes, double *kernel_ms, int *neighbours_built);
 
+/* ---- cell evaluate and integrate (mgamd_level_op_evaluate, mgamd_level_op_integrate) ----
+ * measurement: bytes of the device arrays the two calls use (the gather table shared with the indicator and the norms; they hold
+ * nothing else), and the device times of the last evaluate and of the last integrate (its memset included) by HIP events; the call
+ * waits for those events.  All 0 before the operator's first evaluate or integrate.  Any pointer may be null. */
+int mgamd_debug_level_op_cell_values_info(const mgamd_level_op *op, uint64_t *bytes, double *evaluate_ms, double *integrate_ms);
+
 #ifdef __cplusplus
 }
 #endif
