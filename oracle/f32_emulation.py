@@ -9,6 +9,8 @@ functions here redo mgoracle.Chebyshev.vmult / step and mgoracle.Multigrid.vcycl
     as the product's runtime does.
 With dtype=float64 they are mgoracle's own arithmetic; with float32 their distance from the float64 result is the rounding
 error a float32 implementation of the SAME algorithm makes, which is the yardstick for the product's float32 tolerances.
+ls_vcycle and pls_vcycle do the same for ls_oracle's local-smoothing cycle (`HMG-local`) and for the p-multigrid over it
+(`HPMG-local`); the objects are passed in, ls_oracle is not imported.
 numpy/scipy only; the product is never imported."""
 import copy
 
@@ -88,6 +90,89 @@ def vcycle(mg, r, dtype):
         sol[l] = sol[l] + P[l] @ sol[l - 1]
         sol[l] = chebyshev_step(mg.sm[l], sol[l], defect[l], dtype)
     return sol[-1]
+
+
+def _ls_operands(ls, dtype):
+    """per level A_down and A_edge_in, and P, P^T of the ls_oracle.LocalSmoothing ls in `dtype`: its own objects in float64,
+    rounded once per level / per ls otherwise"""
+    nl = len(ls.levels)
+    if dtype is np.float64:
+        return ([L.A_down for L in ls.levels], [L.A_edge_in for L in ls.levels], ls.P, [None] + [ls.P[l].T for l in range(1, nl)])
+    down, edge_in = zip(*[_rounded(L, dtype, lambda L=L: (L.A_down.astype(dtype), L.A_edge_in.astype(dtype))) for L in ls.levels])
+    P, R = _rounded(ls, dtype, lambda: ([None] + [ls.P[l].astype(dtype) for l in range(1, nl)],
+                                        [None] + [ls.P[l].T.tocsr().astype(dtype) for l in range(1, nl)]))
+    return down, edge_in, P, R
+
+
+def ls_vcycle(ls, r, dtype):
+    """ls_oracle.LocalSmoothing.vcycle with the level vectors, the copies to and from the levels, the level matrices, both
+    edge matrices and the transfers in `dtype`; the level-0 solve in double"""
+    dtype = np.dtype(dtype).type
+    nl = len(ls.levels)
+    A_down, A_edge_in, P, R = _ls_operands(ls, dtype)
+    r = np.asarray(r, dtype=dtype)
+    defect = [np.zeros(L.n, dtype=dtype) for L in ls.levels]
+    for l, (g, li) in enumerate(ls.copy):
+        defect[l][li] = r[g]
+    sol, x = [None] * nl, [None] * nl
+    for l in range(nl - 1, 0, -1):
+        x[l] = chebyshev_vmult(ls.sm[l], defect[l], dtype)
+        t = defect[l] - A_down[l] @ x[l]  # the residual carries the refinement-edge rows
+        defect[l - 1] += R[l] @ t
+    sol[0] = ls.A0.solve(defect[0].astype(np.float64)).astype(dtype)
+    for l in range(1, nl):
+        xl = x[l] + P[l] @ sol[l - 1]
+        if ls.levels[l].edge.any():
+            defect[l] -= A_edge_in[l] @ xl
+        sol[l] = chebyshev_step(ls.sm[l], xl, defect[l], dtype)
+    z = np.zeros(ls.G.n, dtype=dtype)
+    for l, (g, li) in enumerate(ls.copy):
+        z[g] = sol[l][li]
+    return z
+
+
+def ls_with_max_evs(ls, max_evs, smoothing_range=20.0):
+    """a copy of the ls_oracle.LocalSmoothing ls (levels, transfers, copy indices and factorisation shared) whose smoothers
+    take the given estimates, one per level"""
+    ls = copy.copy(ls)
+    ls.sm = [with_max_ev(c, ev, smoothing_range) for c, ev in zip(ls.sm, max_evs)]
+    return ls
+
+
+def ls_with_degree(ls, degree):
+    """a copy of ls whose smoothers have another degree"""
+    ls = copy.copy(ls)
+    ls.sm = [copy.copy(c) for c in ls.sm]
+    for c in ls.sm:
+        c.k = degree
+    return ls
+
+
+def _pls_over(pls, mg, ls):
+    """a copy of the ls_oracle.PolynomialOverLocalSmoothing pls on the p-multigrid mg whose coarse solve is ls's V-cycle"""
+    pls = copy.copy(pls)
+    pls.ls, pls.mg = ls, copy.copy(mg)
+    pls.mg.coarse = ls.vcycle
+    return pls
+
+
+def pls_with_max_evs(pls, max_evs_p, max_evs_ls, smoothing_range=20.0):
+    """a copy of pls whose p-level smoothers and whose local-smoothing smoothers take the given estimates"""
+    return _pls_over(pls, with_max_evs(pls.mg, max_evs_p, smoothing_range), ls_with_max_evs(pls.ls, max_evs_ls, smoothing_range))
+
+
+def pls_with_degree(pls, degree):
+    return _pls_over(pls, with_degree(pls.mg, degree), ls_with_degree(pls.ls, degree))
+
+
+def pls_vcycle(pls, r, dtype):
+    """PolynomialOverLocalSmoothing.vcycle in `dtype`: vcycle() of its p-multigrid with ls_vcycle of its ls as the coarse solve
+    (vcycle() hands the coarse defect over through float64, which is exact for float32 data)"""
+    dtype = np.dtype(dtype).type
+    pls.mg.__dict__.setdefault("_rounded", {})  # (kept on pls.mg: the copy below shares it)
+    mg = copy.copy(pls.mg)
+    mg.coarse = lambda d: ls_vcycle(pls.ls, d, dtype).astype(np.float64)
+    return vcycle(mg, r, dtype)
 
 
 def eigenvalue_estimate(A, inv_diag, dtype, start=None, eig_cg_n_iterations=20):

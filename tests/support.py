@@ -109,6 +109,24 @@ def oracle_hierarchy(dofs, case, problem=Problem(), restrict=None):
     return oracle_hierarchy_on(dofs, *po.level_plan_on(mesh(*case[:2]), *case[2:]), problem, restrict)
 
 
+_local_smoothings = {}
+
+
+def local_smoothing_oracle(h, geo, L, p):
+    """ls_oracle.LocalSmoothing(geo, L, p) in the numbering of the product's `HMG-local` hierarchy h, assembled once per session.
+    The numbering at max_brick=0 depends on neither the number type nor the smoother degree: asserted through the keys of every
+    hierarchy that asks."""
+    import ls_oracle
+
+    keys = [h.active_dofs.keys()] + [d.keys() for d in h.dofs]
+    if (geo, L, p) not in _local_smoothings:
+        ref = ls_oracle.LocalSmoothing(geo, L, p, numbering_keys_global=keys[0], numbering_keys_levels=keys[1:])
+        _local_smoothings[(geo, L, p)] = (keys, ref)
+    kept, ref = _local_smoothings[(geo, L, p)]
+    assert len(kept) == len(keys) and all(np.array_equal(a, b) for a, b in zip(kept, keys))
+    return ref
+
+
 # ------------------------------------------------------------------ the product's side of a Problem
 def set_problem(mgamd, t, problem):
     """mask, Robin coefficients and coefficient of the problem on the product's mesh t"""

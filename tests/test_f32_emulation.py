@@ -117,3 +117,131 @@ def test_float32_cycle_keeps_the_cg_iteration_count(oracle, emu, multigrids, geo
     x32, it32, _ = oracle.pcg(Lf.A, Lf.rhs_constant, lambda r: emu.vcycle(mg, r, np.float32).astype(np.float64), 1e-4)
     assert it32 == it64
     assert rel_err(x32, x64) < 1e-3
+
+
+# ------------------------------------------------------------------ local smoothing (HMG-local, HPMG-local)
+LS_CASES = [("quadrant", 3, 1), ("quadrant", 3, 3), ("quadrant", 3, 4), ("quadrant", 4, 2), ("circle", 5, 2), ("quadrant", 3, 5)]
+PLS_CASES = [("quadrant", 3, 4)]
+LS_DEGREES = [1, 2, 3]
+UNIT_ROUNDOFF, MARGIN, CAP = 2.0 ** -24, 16, 5e-5  # tests/test_gpu_float_levels.py
+
+
+@pytest.fixture(scope="module")
+def local_smoothings():
+    import ls_oracle
+
+    cache = {}
+
+    def get(geo, L, p, composed=False):
+        if (geo, L, p, composed) not in cache:
+            cache[(geo, L, p, composed)] = (ls_oracle.PolynomialOverLocalSmoothing if composed else ls_oracle.LocalSmoothing)(geo, L, p)
+        return cache[(geo, L, p, composed)]
+
+    return get
+
+
+def ls_input(ref):
+    r = np.random.default_rng(42).standard_normal(ref.G.n)
+    r[ref.G.constrained] = 0.0
+    return r
+
+
+def check_e_ref(e_ref):
+    """a condition on the case, not on the product: float32 rounding, and so small that 16 e_ref stays under half the cap"""
+    assert UNIT_ROUNDOFF < e_ref <= CAP / 2
+
+
+@pytest.mark.parametrize("geo,L,p", LS_CASES)
+@pytest.mark.parametrize("k", LS_DEGREES)
+def test_local_smoothing_cycle(oracle, emu, local_smoothings, geo, L, p, k):
+    ls = emu.ls_with_degree(local_smoothings(geo, L, p), k)
+    assert ls is not local_smoothings(geo, L, p) and all(c.k == k for c in ls.sm) and all(c.k == 3 for c in local_smoothings(geo, L, p).sm)
+    r = ls_input(ls)
+    z64 = ls.vcycle(r)
+    assert np.array_equal(emu.ls_vcycle(ls, r, np.float64), z64)
+    same = emu.ls_with_max_evs(ls, [c.max_ev for c in ls.sm])
+    assert same is not ls and np.array_equal(same.vcycle(r), z64)
+    other = emu.ls_with_max_evs(ls, [2.0 * c.max_ev for c in ls.sm])
+    assert [c.theta for c in other.sm] == pytest.approx([2.0 * c.theta for c in ls.sm], rel=1e-15) and all(c.k == k for c in other.sm)
+    z32 = emu.ls_vcycle(ls, r, np.float32)
+    assert z32.dtype == np.float32
+    e_ref = rel_err(z32.astype(np.float64), z64)
+    print(f"local smoothing {geo} {L} p={p} k={k}: e_ref = {e_ref:.2e}")
+    check_e_ref(e_ref)
+    # every operand of the smoother is float32 (the level matrix, D^-1, the defect after the edge subtraction, the iterates)
+    seen = []
+    orig = emu._iterate
+
+    def spy(c, A, dinv, x, xold, b, dtype):
+        out = orig(c, A, dinv, x, xold, b, dtype)
+        seen.extend([A.dtype, dinv.dtype, x.dtype, xold.dtype, b.dtype, out.dtype])
+        return out
+
+    emu._iterate = spy
+    try:
+        emu.ls_vcycle(ls, r, np.float32)
+    finally:
+        emu._iterate = orig
+    assert seen and all(d == np.float32 for d in seen)
+    # the preconditioned CG does not notice the difference
+    x64, it64, _ = oracle.pcg(ls.G.A, ls.G.rhs_constant, ls.vcycle, 1e-4)
+    x32, it32, _ = oracle.pcg(ls.G.A, ls.G.rhs_constant, lambda v: emu.ls_vcycle(ls, v, np.float32).astype(np.float64), 1e-4)
+    assert it32 == it64
+    assert rel_err(x32, x64) < 1e-3
+
+
+def wrong_variant(ls, which):
+    """ls with every level's A_down := A (a residual without the refinement-edge rows) or A_edge_in := 0 (no edge-in correction)"""
+    import copy
+
+    ls = copy.copy(ls)
+    ls.levels = [copy.copy(Lv) for Lv in ls.levels]
+    for Lv in ls.levels:
+        Lv.__dict__.pop("_rounded", None)
+        if which == "A_down := A":
+            Lv.A_down = Lv.A
+        else:
+            Lv.A_edge_in = Lv.A_edge_in * 0.0
+    return ls
+
+
+@pytest.mark.parametrize("geo,L,p", LS_CASES)
+@pytest.mark.parametrize("k", LS_DEGREES)
+@pytest.mark.parametrize("which", ["A_down := A", "A_edge_in := 0"])
+def test_a_wrong_local_smoothing_cycle_is_far_outside_the_bound(emu, local_smoothings, geo, L, p, k, which):
+    """what a bound of 16 e_ref tells apart: a cycle without the edge rows in the residual, or without the edge-in correction"""
+    ls = emu.ls_with_degree(local_smoothings(geo, L, p), k)
+    r = ls_input(ls)
+    z64 = ls.vcycle(r)
+    e_ref = rel_err(emu.ls_vcycle(ls, r, np.float32).astype(np.float64), z64)
+    wrong = wrong_variant(ls, which)
+    for dtype in (np.float64, np.float32):
+        dist = rel_err(emu.ls_vcycle(wrong, r, dtype).astype(np.float64), z64)
+        print(f"local smoothing {geo} {L} p={p} k={k} {which} in {np.dtype(dtype).name}: {dist:.2e} = {dist / e_ref:.1e} e_ref")
+        assert dist >= 1000 * MARGIN * e_ref
+    assert np.array_equal(ls.vcycle(r), z64)  # the original is untouched
+
+
+@pytest.mark.parametrize("geo,L,p", PLS_CASES)
+@pytest.mark.parametrize("k", LS_DEGREES)
+def test_polynomial_over_local_smoothing_cycle(oracle, emu, local_smoothings, geo, L, p, k):
+    ref = local_smoothings(geo, L, p, composed=True)
+    pls = emu.pls_with_degree(ref, k)
+    assert all(c.k == k for c in pls.mg.sm + pls.ls.sm) and all(c.k == 3 for c in ref.mg.sm + ref.ls.sm)
+    r = ls_input(pls)
+    z64 = pls.vcycle(r)
+    assert np.array_equal(z64, oracle.Multigrid.vcycle(pls.mg, r))
+    assert np.array_equal(emu.pls_vcycle(pls, r, np.float64), z64)
+    same = emu.pls_with_max_evs(pls, [c.max_ev for c in pls.mg.sm], [c.max_ev for c in pls.ls.sm])
+    assert same is not pls and same.ls is not pls.ls and np.array_equal(same.vcycle(r), z64)
+    other = emu.pls_with_max_evs(pls, [c.max_ev for c in pls.mg.sm], [2.0 * c.max_ev for c in pls.ls.sm])
+    assert not np.array_equal(other.vcycle(r), z64)  # the coarse solve of the copy is the copy's local-smoothing cycle
+    z32 = emu.pls_vcycle(pls, r, np.float32)
+    assert z32.dtype == np.float32
+    e_ref = rel_err(z32.astype(np.float64), z64)
+    print(f"HPMG-local {geo} {L} p={p} k={k}: e_ref = {e_ref:.2e}")
+    check_e_ref(e_ref)
+    x64, it64, _ = oracle.pcg(pls.G.A, pls.G.rhs_constant, pls.vcycle, 1e-4)
+    x32, it32, _ = oracle.pcg(pls.G.A, pls.G.rhs_constant, lambda v: emu.pls_vcycle(pls, v, np.float32).astype(np.float64), 1e-4)
+    assert it32 == it64
+    assert rel_err(x32, x64) < 1e-3

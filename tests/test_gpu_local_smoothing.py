@@ -6,7 +6,9 @@ through the geometric DoF keys."""
 import numpy as np
 import pytest
 
+import support as su
 from conftest import rel_err
+from support import emu  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -15,20 +17,21 @@ CASES = [("quadrant", 3, 1), ("quadrant", 4, 1), ("quadrant", 4, 2), ("quadrant"
          # circle: point refinement at the origin, entirely in the interior.  The refinement levels above 3 are patches that never touch
          # the boundary: their whole surface is refinement edge, the Dirichlet block of [I | T | E | D] is empty, and the patch repeats
          # with identical size level after level (125 DoFs of which 98 edge at p = 1)
-         ("circle", 5, 1), ("circle", 5, 2), ("circle", 6, 1), ("circle", 6, 2)]
+         ("circle", 5, 1), ("circle", 5, 2), ("circle", 6, 1), ("circle", 6, 2),
+         # several bricks per level: the finest level is 33^3 DoFs = eight 17-point bricks whose shared faces carry refinement-edge DoFs
+         # (2977 of them, in the tail segment of [I | T | E | D]); the level below mixes bricks with smaller slots
+         ("quadrant", 4, 4), ("quadrant", 5, 2)]
+EIGHT_BRICKS = {("quadrant", 4, 4): 1657, ("quadrant", 5, 2): 1141}  # edge DoFs of the level below the finest
 
 
 @pytest.fixture(scope="module")
 def ls_hierarchies(mgamd, ctx):
-    import ls_oracle
-
     cache = {}
 
     def get(geo, L, p):
         if (geo, L, p) not in cache:
             h = mgamd.Hierarchy(ctx, geo, L, p, "HMG-local", coarse_solver="amg", max_brick=0)
-            ref = ls_oracle.LocalSmoothing(geo, L, p, numbering_keys_global=h.active_dofs.keys(), numbering_keys_levels=[d.keys() for d in h.dofs])
-            cache[(geo, L, p)] = (h, ref)
+            cache[(geo, L, p)] = (h, su.local_smoothing_oracle(h, geo, L, p))  # (shared with test_gpu_local_smoothing_float.py)
         return cache[(geo, L, p)]
 
     return get
@@ -39,6 +42,10 @@ def test_level_operators_edge_matrices_and_transfers(mgamd, ctx, ls_hierarchies,
     h, ref = ls_hierarchies(geo, L, p)
     rng = np.random.default_rng(41)
     assert len(h.operators) == len(ref.levels)
+    if (geo, L, p) in EIGHT_BRICKS:
+        assert sum(n for B, n in h.dofs[-1].groups()) == 8 and all(B * p + 1 == 17 for B, n in h.dofs[-1].groups() if n)
+        assert (h.dofs[-1].n_dofs, h.dofs[-1].info.n_edge, h.dofs[-1].info.n_tail > 0) == (33 ** 3, 2977, True)
+        assert h.dofs[-2].info.n_edge == EIGHT_BRICKS[(geo, L, p)] and len({B for B, n in h.dofs[-2].groups() if n}) > 1
     for l, (op, Lv) in enumerate(zip(h.operators, ref.levels)):
         info = h.dofs[l].info
         first_edge = info.n_interior + info.n_tail
@@ -104,16 +111,20 @@ def test_local_smoothing_vcycle_and_solve(mgamd, oracle, ctx, ls_hierarchies, ge
         assert ms[5].sum() < 0.2 * ms.sum()  # empty stage: only the event pairs
 
 
-def test_float_levels_local_smoothing(mgamd, ctx):
-    """MGNumberType float (the reference's default) under the FP64 outer CG"""
-    import ls_oracle
-
-    ref = ls_oracle.LocalSmoothing("quadrant", 4, 2)
+def test_float_levels_local_smoothing(mgamd, oracle, emu, ctx):
+    """MGNumberType float (the reference's default) under the FP64 outer CG: the iteration count of the float32 emulation of the
+    cycle (oracle/f32_emulation.py), which is the FP64 oracle's; tests/test_gpu_local_smoothing_float.py holds the kernels"""
     h = mgamd.Hierarchy(ctx, "quadrant", 4, 2, "HMG-local", coarse_solver="amg", number_type=mgamd.F32, max_brick=0)
+    ref = su.local_smoothing_oracle(h, "quadrant", 4, 2)
     b, x = h.fine_operator.initialize_dof_vector(), h.fine_operator.initialize_dof_vector()
     h.fine_operator.rhs(b)
     it, res = mgamd.solve_cg(h.fine_operator, h.mg, x, b, 1e-4)
-    assert abs(it - ref.solve(1e-4)[1]) <= 1
+    xref, it64, _ = ref.solve(1e-4)
+    x32, it32, _ = oracle.pcg(ref.G.A, ref.G.rhs_constant, lambda r: emu.ls_vcycle(ref, r, np.float32).astype(np.float64), 1e-4)
+    err = rel_err(x.to_host(), xref)
+    print(f"FP32 local smoothing CG: iterations gpu {it}, float32 emulation {it32}, FP64 oracle {it64}, rel.err {err:.2e}")
+    assert it == it32 and it32 == it64
+    assert err < 1e-3
 
 
 @pytest.mark.parametrize("geo,L,p", [("quadrant", 3, 4), ("annulus", 5, 2), ("quadrant", 4, 2), ("circle", 5, 2)])

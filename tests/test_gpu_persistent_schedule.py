@@ -11,6 +11,9 @@ MGAMD_PERSISTENT_GRID caps the grid, so that the small meshes below draw several
   quadrant 7, p = 1     27 plain and 37 constrained 16^3 bricks in one launch of the pair kernel, whose two halves draw from two
                         sets of counters (the uniform p = 1 mesh has no constrained bricks, so it never reaches that kernel)
 
+  quadrant 5, p = 4,    a local-smoothing level: 64 bricks with refinement-edge DoFs on three inner faces, in the three edge modes
+  refinement level 5    (identity edge rows, edge DoFs as ordinary rows, edge columns alone): 7 and 5 tickets per counter at the caps 8, 24
+
 and without a cap every one of them has fewer bricks than resident workgroups: the branch that draws no ticket.
 
 Passes: the operator (mode 0), the zero-start Chebyshev sweep (modes 4, 5, 2) and one Chebyshev step (mode 2) on the finest level;
@@ -202,3 +205,64 @@ def test_float_levels(mgamd, oracle, emu, ctx, hierarchies, references):
         print(f"FP32 V-cycle {trial}: rel.err {err:.2e}, e_ref {e_ref:.2e}, ratio {err / e_ref:.2f}")
         assert err <= MARGIN_F32 * e_ref
         assert err < CAP_F32
+
+
+@pytest.fixture(scope="module")
+def edge_level():
+    """ls_oracle.LSLevel of refinement level 5 of quadrant 5 at p = 4, assembled once for both caps"""
+    import ls_oracle
+
+    kept = {}
+
+    def get(d):
+        if not kept:
+            kept["keys"] = d.keys()
+            kept["level"] = ls_oracle.LSLevel(ls_oracle.level_meshes(su.mesh("quadrant", 5))[5], 4, kept["keys"])
+        assert np.array_equal(kept["keys"], d.keys())  # the numbering does not depend on the cap
+        return kept["level"]
+
+    return get
+
+
+@pytest.mark.parametrize("cap", [8, 24], ids=cap_id)
+def test_tickets_in_the_edge_modes(mgamd, oracle, ctx, edge_level, cap):
+    """A local-smoothing level operator on 64 bricks: refinement level 5 of quadrant 5 at p = 4, 16^3 cells whose three inner faces
+    are refinement edge, the smallest mesh on which a refinement edge meets more bricks than the smallest cap.  Identity edge rows
+    (vmult, the Chebyshev passes), the edge DoFs as ordinary rows (vmult_interface_down) and the edge columns alone
+    (vmult_interface_up) all draw tickets; each twice, then vmult again."""
+    before = os.environ.get("MGAMD_PERSISTENT_GRID")
+    os.environ["MGAMD_PERSISTENT_GRID"] = str(cap)
+    try:
+        d = mgamd.DoFs(mgamd.Triangulation("quadrant", 5).level_mesh(5), 4, 0, local_smoothing_level=True)
+        op = mgamd.Operator(ctx, d, mgamd.F64)
+    finally:
+        if before is None:
+            os.environ.pop("MGAMD_PERSISTENT_GRID", None)
+        else:
+            os.environ["MGAMD_PERSISTENT_GRID"] = before
+    assert sum(n for B, n in d.groups() if B * 4 + 1 == 17) == 64 and sum(n for B, n in d.groups()) == 64
+    assert (d.n_dofs, d.info.n_edge, d.info.n_dirichlet) == (274625, 12097, 12481)
+    lv = edge_level(d)
+    assert lv.n == d.n_dofs and lv.edge.sum() == d.info.n_edge
+    ch = mgamd.PreconditionChebyshev(op, 3, 20.0, 20)
+    cref = oracle.Chebyshev(lv.A, lv.inv_diag, 3, 20.0, 20)
+    assert ch.eigenvalue_estimates()[1] == pytest.approx(cref.max_ev, rel=1e-10)
+    rng = np.random.default_rng(3)
+    tag = f"quadrant-5-4 level 5 {cap_id(cap)}"
+    for trial in range(2):
+        x, b = rng.standard_normal(lv.n), rng.standard_normal(lv.n)
+        ea = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
+        ed = rel_err(su.apply_nan(mgamd, ctx, op.vmult_interface_down, x), lv.A_down @ x)
+        t = lv.A_edge_in @ x
+        eu = np.abs(su.apply_nan(mgamd, ctx, op.vmult_interface_up, x) - t).max() / max(np.abs(t).max(), 1.0)
+        ev = rel_err(su.apply_nan(mgamd, ctx, ch.vmult, b), cref.vmult(b))
+        vx, vb = op.initialize_dof_vector().from_host(x), op.initialize_dof_vector().from_host(b)
+        ch.step(vx, vb)
+        es = rel_err(vx.to_host(), cref.step(x, b))
+        print(f"{tag} pass {trial}: vmult {ea:.2e}, interface down {ed:.2e}, interface up (max norm) {eu:.2e}, Chebyshev vmult {ev:.2e}, "
+              f"step {es:.2e}")
+        assert ea < su.TOL_OP and ed < su.TOL_OP and eu <= su.TOL_OP
+        assert ev < su.TOL_CHEB and es < su.TOL_CHEB
+    ea = rel_err(su.apply_nan(mgamd, ctx, op.vmult, x), lv.A @ x)
+    print(f"{tag}: vmult after them {ea:.2e}")
+    assert ea < su.TOL_OP
