@@ -9,7 +9,7 @@ LIB        := $(LIBDIR)/libmgamd.so
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/mgamd.h include/mgamd_dev.h
 
 BIN        := dealii_multigrid_amd/bin/multigrid_throughput
-EXAMPLE    := bin/heat_equation bin/layered_wall bin/convective_wall bin/heated_wall bin/adaptive_gaussian bin/manufactured_solution
+EXAMPLE    := bin/heat_equation bin/layered_wall bin/convective_wall bin/heated_wall bin/adaptive_gaussian bin/manufactured_solution bin/point_source
 
 all: $(LIB) $(BIN) $(EXAMPLE) oracle
 
@@ -43,7 +43,8 @@ $(BIN): dealii_multigrid_amd/harness/multigrid_throughput.cpp $(CSRC)/mgamd.hpp 
 
 # the examples of INTEGRATION.md: time stepping (examples/heat_equation.cpp), boundary conditions (examples/layered_wall.cpp,
 # examples/convective_wall.cpp), non-zero Dirichlet data (examples/heated_wall.cpp), the adaptive loop (examples/adaptive_gaussian.cpp),
-# a load from caller data at the quadrature points (examples/manufactured_solution.cpp)
+# a load from caller data at the quadrature points (examples/manufactured_solution.cpp), a point source and probes at caller points
+# (examples/point_source.cpp)
 $(EXAMPLE): bin/%: examples/%.cpp $(CSRC)/mgamd.hpp include/mgamd.h $(LIB)
 	@mkdir -p bin
 	g++ -O2 -std=c++17 -Wall -Iinclude $< -o $@ -L$(LIBDIR) -lmgamd -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)'

@@ -488,6 +488,60 @@ class DoFs:
         _chk(_lib.mgamd_dofs_evaluate(self._h, _ptr(u), C.c_int(n_q), None if v is None else _ptr(v), None if g is None else _ptr(g)))
         return (v, g) if values and gradients else (v if values else g)
 
+    @staticmethod
+    def _points(points, who):
+        """caller points as a contiguous double array [n, 3]"""
+        xyz = np.ascontiguousarray(points, dtype=np.float64)
+        if xyz.size == 0:
+            return xyz.reshape(0, 3)
+        if xyz.ndim == 1 and xyz.size == 3:
+            xyz = xyz.reshape(1, 3)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"{who}: points of shape {xyz.shape}, expected [n, 3]")
+        return xyz
+
+    def locate_points(self, points):
+        """(cells [n] int32, -1: not found; reference_points [n, 3]) of points [n, 3] in [-1, 1]^3 (mgamd_dofs_locate_points; in deal.II:
+        GridTools::find_active_cell_around_point).  A point on an interior face, edge or vertex belongs to the leaf on its upper side, a
+        point on a face = +1 to the last leaf; no tolerance outside the cube."""
+        xyz = self._points(points, "locate_points")
+        cell, ref = np.full(len(xyz), -1, np.int32), np.zeros((len(xyz), 3))
+        _chk(_lib.mgamd_dofs_locate_points(self._h, C.c_uint64(len(xyz)), _ptr(xyz), _ptr(cell), _ptr(ref)))
+        return cell, ref
+
+    def point_evaluate(self, points, u, values: bool = True, gradients: bool = False):
+        """u_h [n] and/or grad u_h [3, n] of the host vector u at points [n, 3] (mgamd_dofs_point_evaluate; in deal.II:
+        VectorTools::point_value / point_gradient): the values, the gradients, or the tuple of both.  Gradients are the one-sided
+        gradients of the point's leaf; points that are not found get exactly 0 (locate_points tells); hanging entries of u are never read."""
+        xyz = self._points(points, "point_evaluate")
+        u = self._data_array(u, "point_evaluate")
+        v = np.zeros(len(xyz)) if values else None
+        g = np.zeros((3, len(xyz))) if gradients else None
+        _chk(_lib.mgamd_dofs_point_evaluate(self._h, C.c_uint64(len(xyz)), _ptr(xyz), _ptr(u), None if v is None else _ptr(v),
+                                            None if g is None else _ptr(g)))
+        return (v, g) if values and gradients else (v if values else g)
+
+    def point_integrate(self, points, values=None, gradients=None):
+        """b_i = sum_k (values_k phi_i(x_k) + gradients_k . grad phi_i(x_k)) through the transposed hanging-node interpolation, host
+        vector (mgamd_dofs_point_integrate; in deal.II: VectorTools::create_point_source_vector): point loads without quadrature weight
+        or h^3, values [n] (Dirac), gradients [3, n] (dipole); either may be None, not both.  Constrained rows are 0, points that are
+        not found add nothing."""
+        xyz = self._points(points, "point_integrate")
+
+        def data(a, per_point):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != per_point * len(xyz):
+                raise ValueError(f"point_integrate: {a.size} values for {per_point} x {len(xyz)} points")
+            return a
+
+        v, g = data(values, 1), data(gradients, 3)
+        b = np.zeros(self.n_dofs)
+        _chk(_lib.mgamd_dofs_point_integrate(self._h, C.c_uint64(len(xyz)), _ptr(xyz), None if v is None else _ptr(v),
+                                             None if g is None else _ptr(g), _ptr(b)))
+        return b
+
     def _data_array(self, a, who):
         a = np.ascontiguousarray(a, dtype=np.float64)
         if a.shape != (self.n_dofs,):
@@ -731,6 +785,66 @@ class Vector:
             self._h = None
 
 
+class PointSet:
+    """Located points of one Operator (Utilities::MPI::RemotePointEvaluation): built once, used for many vectors.  Location follows
+    DoFs.locate_points bit for bit.  A point that is not found gets exactly 0 from evaluate and adds nothing in integrate, silently:
+    check `found`."""
+
+    def __init__(self, op: "Operator", points):
+        self.op = op  # (the set belongs to the operator: keep it alive)
+        self._h = C.c_void_p()
+        xyz = DoFs._points(points, "point_set")
+        _chk(_lib.mgamd_level_op_point_set_create(op._h, C.c_uint64(len(xyz)), _ptr(xyz), C.byref(self._h)))
+        self.n = len(xyz)
+        self.cells, self.reference_points = np.full(self.n, -1, np.int32), np.zeros((self.n, 3))
+        _chk(_lib.mgamd_point_set_get(self._h, None, None, _ptr(self.cells), _ptr(self.reference_points)))
+        self.found = self.cells >= 0
+
+    def all_points_found(self) -> bool:
+        return bool(self.found.all())
+
+    def evaluate(self, u: "Vector", values: bool = True, gradients: bool = False):
+        """u_h [n] and/or grad u_h [3, n] (flat, component by component) at the points, in the caller's point order, as device Vectors of
+        the operator's number type (mgamd_point_set_evaluate; in deal.II: VectorTools::point_values, point_gradients): the values, the
+        gradients, or the tuple of both.  Gradients are the one-sided gradients of the point's leaf.  Two calls give the same bits."""
+        op = self.op
+        v = Vector(op.ctx, self.n, op.number_type) if values else None
+        g = Vector(op.ctx, 3 * self.n, op.number_type) if gradients else None
+        _chk(_lib.mgamd_point_set_evaluate(self._h, op._h, u._h if u is not None else None, v._h if v is not None else None,
+                                           g._h if g is not None else None))
+        return (v, g) if values and gradients else (v if values else g)
+
+    def integrate(self, b: "Vector", values=None, gradients=None):
+        """b_i = sum_k (values_k phi_i(x_k) + gradients_k . grad phi_i(x_k)) through C^T on the device (mgamd_point_set_integrate; in
+        deal.II: VectorTools::create_point_source_vector).  values [n] and gradients [3, n] are Vectors or arrays (uploaded); at least
+        one is given.  b is overwritten, constrained rows are 0.  Not bit-reproducible across calls where occupied leaves share rows."""
+        op = self.op
+
+        def device(a, per_point):
+            if a is None or isinstance(a, Vector):
+                return a
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.size != per_point * self.n:
+                raise ValueError(f"point_integrate: {a.size} values for {per_point} x {self.n} points")
+            return Vector(op.ctx, a.size, op.number_type).from_host(a.ravel())
+
+        v, g = device(values, 1), device(gradients, 3)
+        _chk(_lib.mgamd_point_set_integrate(self._h, op._h, v._h if v is not None else None, g._h if g is not None else None,
+                                            b._h if b is not None else None))
+
+    def _info(self):
+        """(device bytes of the set, host milliseconds of its build, device milliseconds of the locate kernel, of the last evaluate and
+        of the last integrate; each time 0 before the first such call) (mgamd_debug_point_set_info)"""
+        b, t = C.c_uint64(), [C.c_double() for _ in range(4)]
+        _chk(_lib.mgamd_debug_point_set_info(None, self._h, None, None, C.byref(b), *[C.byref(x) for x in t]))
+        return (b.value,) + tuple(x.value for x in t)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mgamd_point_set_destroy(self._h)
+            self._h = None
+
+
 class Operator:
     """Operator<3,1,Number> (ref:include/operator.h:11-557)."""
 
@@ -905,6 +1019,18 @@ class Operator:
         b, t0, t1 = C.c_uint64(), C.c_double(), C.c_double()
         _chk(_lib.mgamd_debug_level_op_cell_values_info(self._h, C.byref(b), C.byref(t0), C.byref(t1)))
         return b.value, t0.value, t1.value
+
+    def point_set(self, points) -> "PointSet":
+        """points [n, 3] of [-1, 1]^3 located on the operator's leaves on the device, once, for many vectors
+        (mgamd_level_op_point_set_create; in deal.II: Utilities::MPI::RemotePointEvaluation::reinit)"""
+        return PointSet(self, points)
+
+    def _point_tables_bytes(self):
+        """(bytes of the device arrays only the operator's point sets use, 0 before the first point set; bytes of the shared gather
+        table, 0 until some call has built it) (mgamd_debug_point_set_info)"""
+        b, g = C.c_uint64(), C.c_uint64()
+        _chk(_lib.mgamd_debug_point_set_info(self._h, None, C.byref(b), C.byref(g), None, None, None, None, None))
+        return b.value, g.value
 
     def _error_norm_info(self):
         """(bytes of the device arrays the error norms use, the shared gather table included; device milliseconds of the kernel of the

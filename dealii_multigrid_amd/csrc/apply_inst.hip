@@ -34,4 +34,9 @@ namespace mgamd
   // the cell evaluate and integrate (kernels_cell_values.hpp)
   template void LevelOperator<MGAMD_INST_T>::cell_evaluate_P<MGAMD_INST_P>(const MGAMD_INST_T *, int, MGAMD_INST_T *, MGAMD_INST_T *);
   template void LevelOperator<MGAMD_INST_T>::cell_integrate_P<MGAMD_INST_P>(const MGAMD_INST_T *, const MGAMD_INST_T *, int, MGAMD_INST_T *);
+  // point evaluation and point sources (kernels_point_values.hpp)
+  template void LevelOperator<MGAMD_INST_T>::point_evaluate_P<MGAMD_INST_P>(const LevelOperator<MGAMD_INST_T>::PointSetDev &, const MGAMD_INST_T *,
+                                                                            MGAMD_INST_T *, MGAMD_INST_T *);
+  template void LevelOperator<MGAMD_INST_T>::point_integrate_P<MGAMD_INST_P>(const LevelOperator<MGAMD_INST_T>::PointSetDev &, const MGAMD_INST_T *,
+                                                                             const MGAMD_INST_T *, MGAMD_INST_T *);
 } // namespace mgamd

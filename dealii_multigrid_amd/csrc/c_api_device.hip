@@ -551,6 +551,109 @@ mgamd_debug_level_op_cell_values_info(const mgamd_level_op *op, uint64_t *bytes,
 }
 
 int
+mgamd_level_op_number_type(const mgamd_level_op *op, int *number_type)
+{
+  MGAMD_TRY
+  REQUIRE(op && number_type);
+  *number_type = op->op->type;
+  MGAMD_CATCH
+}
+
+int
+mgamd_level_op_point_set_create(mgamd_level_op *op, uint64_t n, const double *xyz, mgamd_point_set **out)
+{
+  MGAMD_TRY
+  if (!op || !out)
+    throw std::invalid_argument("point_set: a null pointer (the operator and the result)");
+  auto ps = op->op->point_set_create(n, xyz); // (refuses a null xyz, a distributed operator and a local-smoothing level by name)
+  *out    = new mgamd_point_set{std::move(ps)};
+  MGAMD_CATCH
+}
+
+int
+mgamd_point_set_destroy(mgamd_point_set *ps)
+{
+  MGAMD_TRY
+  if (ps)
+    {
+      if (ps->ps->op)
+        ps->ps->op->point_set_destroy(ps->ps.get());
+      delete ps;
+    }
+  MGAMD_CATCH
+}
+
+int
+mgamd_point_set_get(const mgamd_point_set *ps, uint64_t *n, uint64_t *n_found, int32_t *cell, double *ref)
+{
+  MGAMD_TRY
+  if (!ps)
+    throw std::invalid_argument("point_set: a null pointer (the point set)");
+  if (n)
+    *n = ps->ps->n;
+  if (n_found)
+    *n_found = ps->ps->n_found;
+  if (cell || ref)
+    ps->ps->get(cell, ref);
+  MGAMD_CATCH
+}
+
+// the set against the operator the caller names
+static void
+require_own_operator(const mgamd_point_set *ps, const mgamd_level_op *op, const char *who)
+{
+  if (!ps || !op)
+    throw std::invalid_argument(std::string(who) + ": a null pointer (the point set and its operator)");
+  if (ps->ps->op != op->op.get())
+    throw std::invalid_argument(std::string(who) + ": the point set belongs to another operator (a set is located on the leaves of the operator "
+                                                   "that created it)");
+}
+
+int
+mgamd_point_set_evaluate(mgamd_point_set *ps, mgamd_level_op *op, const mgamd_vec *u, mgamd_vec *values, mgamd_vec *gradients)
+{
+  MGAMD_TRY
+  require_own_operator(ps, op, "point_evaluate");
+  ps->ps->evaluate(u, values, gradients); // (refuses a null u and missing outputs by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_point_set_integrate(mgamd_point_set *ps, mgamd_level_op *op, const mgamd_vec *values, const mgamd_vec *gradients, mgamd_vec *b)
+{
+  MGAMD_TRY
+  require_own_operator(ps, op, "point_integrate");
+  ps->ps->integrate(values, gradients, b); // (refuses a null b and missing data by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_debug_point_set_info(const mgamd_level_op *op, const mgamd_point_set *ps, uint64_t *operator_bytes, uint64_t *gather_bytes, uint64_t *set_bytes,
+                           double *build_ms, double *locate_ms, double *evaluate_ms, double *integrate_ms)
+{
+  MGAMD_TRY
+  REQUIRE(op || ps);
+  uint64_t b  = 0;
+  double   t[4] = {0.0, 0.0, 0.0, 0.0};
+  if (ps)
+    ps->ps->info(b, t[0], t[1], t[2], t[3]);
+  uint64_t locator = 0, gather = 0;
+  if (op)
+    op->op->point_tables_bytes(locator, gather);
+  if (operator_bytes)
+    *operator_bytes = locator;
+  if (gather_bytes)
+    *gather_bytes = gather;
+  if (set_bytes)
+    *set_bytes = b;
+  double *out[4] = {build_ms, locate_ms, evaluate_ms, integrate_ms};
+  for (int k = 0; k < 4; ++k)
+    if (out[k])
+      *out[k] = t[k];
+  MGAMD_CATCH
+}
+
+int
 mgamd_level_op_debug_stamps(mgamd_level_op *op, unsigned long long *out, uint64_t max_count, uint64_t *count)
 {
   MGAMD_TRY

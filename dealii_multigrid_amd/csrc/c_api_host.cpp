@@ -745,6 +745,40 @@ mgamd_dofs_evaluate(const mgamd_dofs *d, const double *u, int n_q, double *value
 }
 
 int
+mgamd_dofs_locate_points(const mgamd_dofs *d, uint64_t n, const double *xyz, int32_t *cell, double *ref)
+{
+  MGAMD_TRY
+  if (!d)
+    throw std::invalid_argument("null argument");
+  d->tables->locate_points(n, xyz, cell, ref); // (refuses null pointers, sharded tables and local-smoothing levels by name)
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_point_evaluate(const mgamd_dofs *d, uint64_t n, const double *xyz, const double *u, double *values, double *gradients)
+{
+  MGAMD_TRY
+  if (!d)
+    throw std::invalid_argument("null argument");
+  d->tables->point_evaluate(n, xyz, u, values, gradients); // (refuses a null u or xyz, missing outputs, sharded tables, local-smoothing levels)
+  MGAMD_CATCH
+}
+
+int
+mgamd_dofs_point_integrate(const mgamd_dofs *d, uint64_t n, const double *xyz, const double *values, const double *gradients, double *out)
+{
+  MGAMD_TRY
+  if (!d)
+    throw std::invalid_argument("null argument");
+  if (!out)
+    throw std::invalid_argument("point_integrate: out is null (n_dofs values)");
+  std::vector<double> b;
+  d->tables->point_integrate(n, xyz, values, gradients, b); // (refuses a null xyz, missing data, sharded tables and local-smoothing levels by name)
+  std::copy(b.begin(), b.end(), out);
+  MGAMD_CATCH
+}
+
+int
 mgamd_dofs_coefficient_range(const mgamd_dofs *d, double *min, double *max)
 {
   MGAMD_TRY

@@ -34,8 +34,12 @@
 // K13 cell_evaluate_kernel    u_h and grad u_h at the Gauss points of every leaf, stored
 // K14 cell_integrate_kernel   the transpose: data at the Gauss points tested against phi_i and grad phi_i, through C^T into a vector
 //
+// K15 point_locate_kernel     caller points -> leaf and reference coordinate (Morton key, binary search over the sorted leaf keys)
+// K16 point_evaluate_kernel   u_h and grad u_h at the located points of the occupied leaves, stored in the caller's order
+// K17 point_integrate_kernel  the transpose: point loads (Dirac, dipole) tested against phi_i and grad phi_i, through C^T into a vector
+//
 // The kernels live in kernels_common.hpp (1D products, sweeps, constraint passes, argument structs), kernels_apply.hpp (K1-K3),
-// kernels_boundary.hpp (K9), kernels_estimator.hpp (K10, K11), kernels_error_norm.hpp (K12), kernels_cell_values.hpp (K13, K14), kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header
+// kernels_boundary.hpp (K9), kernels_estimator.hpp (K10, K11), kernels_error_norm.hpp (K12), kernels_cell_values.hpp (K13, K14), kernels_point_values.hpp (K15-K17), kernels_transfer.hpp (K4), kernels_vector.hpp (K5, K6) and kernels_amg.hpp (K7); this header
 // includes them all.
 #pragma once
 #include "kernels_common.hpp"
@@ -44,6 +48,7 @@
 #include "kernels_estimator.hpp"
 #include "kernels_error_norm.hpp"
 #include "kernels_cell_values.hpp"
+#include "kernels_point_values.hpp"
 #include "kernels_transfer.hpp"
 #include "kernels_vector.hpp"
 #include "kernels_amg.hpp"

@@ -1511,6 +1511,327 @@ namespace mgamd
           }
     }
 
+    // Point evaluation and point sources (kernels_point_values.hpp).  Of the operator: the sorted Morton keys of the leaves and their
+    // corners and edges in integer coordinates (8 + 16 bytes per leaf), uploaded by the first point set.  Of a point set: the leaf and
+    // the reference coordinate per point (the locate kernel's outputs) and the CSR list of occupied leaves with the sorted points.
+    // The binning by leaf runs on the HOST when the set is built (the stated debt for moving points: DESIGN.md).
+    struct PointLocatorDev
+    {
+      DBuf<uint64_t> keys;
+      DBuf<uint32_t> corner; // [n_cells][4]: i, j, k, edge, in integer coordinates
+      uint32_t       n_cells = 0;
+      uint64_t       bytes   = 0;
+    };
+    std::unique_ptr<PointLocatorDev> point_locator;
+    struct PointSetDev : PointSetBase
+    {
+      LevelOperator *self = nullptr;
+      DBuf<int32_t>  cell;
+      DBuf<double>   ref;
+      DBuf<uint32_t> leaf, ptr, perm, occ;
+      uint32_t       n_occupied = 0;
+      uint64_t       bytes      = 0;
+      double         build_ms   = 0.0;
+      hipEvent_t     ev[6]      = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // locate: 0, 1; evaluate: 2, 3; integrate: 4, 5
+      bool           timed[3]   = {false, false, false};
+      ~PointSetDev() override
+      {
+        for (hipEvent_t e : ev)
+          if (e)
+            (void)hipEventDestroy(e);
+      }
+      void
+      orphan()
+      {
+        this->op = nullptr;
+        self     = nullptr;
+        for (DBuf<uint32_t> *b : {&leaf, &ptr, &perm, &occ})
+          b->alloc(0);
+        cell.alloc(0);
+        ref.alloc(0);
+        bytes = 0;
+      }
+      void
+      alive(const char *who) const
+      {
+        if (!self)
+          throw std::invalid_argument(std::string(who) + ": the point set's operator was destroyed");
+      }
+      void
+      get(int32_t *cell_out, double *ref_out) const override
+      {
+        alive("point_set");
+        if (!this->n)
+          return;
+        HIP_CHECK(hipStreamSynchronize(self->ctx->stream));
+        if (cell_out)
+          HIP_CHECK(hipMemcpy(cell_out, cell.p, this->n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (ref_out)
+          HIP_CHECK(hipMemcpy(ref_out, ref.p, 3 * this->n * sizeof(double), hipMemcpyDeviceToHost));
+      }
+      void
+      evaluate(const mgamd_vec *u, mgamd_vec *values, mgamd_vec *gradients) override
+      {
+        alive("point_evaluate");
+        self->point_evaluate(*this, u, values, gradients);
+      }
+      void
+      integrate(const mgamd_vec *values, const mgamd_vec *gradients, mgamd_vec *b) override
+      {
+        alive("point_integrate");
+        self->point_integrate(*this, values, gradients, b);
+      }
+      void
+      info(uint64_t &bytes_out, double &build, double &locate_ms, double &evaluate_ms, double &integrate_ms) const override
+      {
+        bytes_out = bytes;
+        build     = build_ms;
+        double *out[3] = {&locate_ms, &evaluate_ms, &integrate_ms};
+        for (int k = 0; k < 3; ++k)
+          {
+            *out[k] = 0.0;
+            if (timed[k])
+              {
+                float ms = 0.f;
+                HIP_CHECK(hipEventSynchronize(ev[2 * k + 1]));
+                HIP_CHECK(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
+                *out[k] = ms;
+              }
+          }
+      }
+    };
+    // the operator's sets; a set whose handle outlives the operator is emptied here and refuses every later call
+    struct PointSets
+    {
+      std::vector<std::shared_ptr<PointSetDev>> v;
+      ~PointSets()
+      {
+        for (auto &ps : v)
+          ps->orphan();
+      }
+    } point_sets;
+    void
+    refuse_points(const char *who) const
+    {
+      if (comm || halo_plan)
+        throw std::invalid_argument(std::string(who) + ": not implemented: sharded (the operator is distributed; one rank only)");
+      tables->refuse_estimate(who);
+    }
+    std::shared_ptr<PointSetBase>
+    point_set_create(uint64_t n, const double *xyz) override
+    {
+      const char *who = "point_set";
+      static_assert(LMAX <= 21, "spread3 takes 21 bits per coordinate");
+      refuse_points(who);
+      if (n && !xyz)
+        throw std::invalid_argument("point_set: xyz is null (3 n doubles)");
+      if (n > 0x7fffffffu)
+        throw std::invalid_argument("point_set: " + std::to_string(n) + " points refused (at most 2^31 - 1 per set)");
+      if (n && !point_locator) // (an empty set uploads and launches nothing)
+        {
+          auto                  dev = std::make_unique<PointLocatorDev>();
+          std::vector<uint64_t> keys;
+          tables->leaf_keys(keys);
+          std::vector<uint32_t> corner(4 * keys.size());
+          for (size_t ci = 0; ci < keys.size(); ++ci)
+            {
+              const Cell    &c = tables->tria->cells[ci];
+              const uint32_t e = 1u << (LMAX - c.level);
+              corner[4 * ci]     = c.i * e;
+              corner[4 * ci + 1] = c.j * e;
+              corner[4 * ci + 2] = c.k * e;
+              corner[4 * ci + 3] = e;
+            }
+          dev->keys.upload(keys);
+          dev->corner.upload(corner);
+          dev->n_cells  = (uint32_t)keys.size();
+          dev->bytes    = keys.size() * 8 + corner.size() * 4;
+          point_locator = std::move(dev);
+        }
+      auto ps  = std::make_shared<PointSetDev>();
+      ps->op   = this;
+      ps->self = this;
+      ps->n    = n;
+      for (hipEvent_t &e : ps->ev)
+        HIP_CHECK(hipEventCreate(&e));
+      if (n)
+        {
+          // locate on the device; the coordinates are not kept
+          DBuf<double> d_xyz;
+          d_xyz.alloc(3 * n);
+          HIP_CHECK(hipMemcpyAsync(d_xyz.p, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+          ps->cell.alloc(n);
+          ps->ref.alloc(3 * n);
+          PointLocateArgs a;
+          a.xyz     = d_xyz.p;
+          a.n       = n;
+          a.keys    = point_locator->keys.p;
+          a.corner  = point_locator->corner.p;
+          a.n_cells = point_locator->n_cells;
+          a.cell    = ps->cell.p;
+          a.ref     = ps->ref.p;
+          HIP_CHECK(hipEventRecord(ps->ev[0], ctx->stream));
+          hipLaunchKernelGGL((point_locate_kernel<LMAX>), (unsigned)std::min<uint64_t>(4096u, (n + 255) / 256), 256, 0, ctx->stream, a);
+          HIP_CHECK(hipGetLastError());
+          HIP_CHECK(hipEventRecord(ps->ev[1], ctx->stream));
+          ps->timed[0] = true;
+          std::vector<int32_t> cell(n);
+          HIP_CHECK(hipMemcpyAsync(cell.data(), ps->cell.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+          HIP_CHECK(hipStreamSynchronize(ctx->stream));
+          // bin by leaf on the host: a counting sort, stable, so the points of a leaf keep the caller's order
+          const auto            t0 = std::chrono::steady_clock::now();
+          const uint32_t        nc = point_locator->n_cells;
+          std::vector<uint32_t> count(nc + 1, 0), leaf, ptr, perm, occ;
+          for (uint64_t k = 0; k < n; ++k)
+            if (cell[k] >= 0)
+              {
+                if ((uint32_t)cell[k] >= nc)
+                  throw std::runtime_error("point_set: the locate kernel returned a leaf outside the mesh");
+                ++count[cell[k] + 1];
+              }
+          std::vector<uint32_t> slot(nc, 0); // leaf -> its occupied index
+          ptr.push_back(0);
+          for (uint32_t ci = 0; ci < nc; ++ci)
+            {
+              if (count[ci + 1])
+                {
+                  slot[ci] = (uint32_t)leaf.size();
+                  leaf.push_back(ci);
+                  ptr.push_back(ptr.back() + count[ci + 1]);
+                }
+              count[ci + 1] += count[ci]; // -> the first sorted position of leaf ci + 1
+            }
+          ps->n_found = ptr.back();
+          perm.resize(ps->n_found);
+          occ.resize(ps->n_found);
+          for (uint64_t k = 0; k < n; ++k)
+            if (cell[k] >= 0)
+              {
+                const uint32_t j = count[cell[k]]++;
+                perm[j]          = (uint32_t)k;
+                occ[j]           = slot[cell[k]];
+              }
+          ps->n_occupied = (uint32_t)leaf.size();
+          ps->leaf.upload(leaf);
+          ps->ptr.upload(ptr);
+          ps->perm.upload(perm);
+          ps->occ.upload(occ);
+          ps->bytes    = n * (sizeof(int32_t) + 3 * sizeof(double)) + (leaf.size() + ptr.size() + perm.size() + occ.size()) * sizeof(uint32_t);
+          ps->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+      point_sets.v.push_back(ps);
+      return ps;
+    }
+    void
+    point_set_destroy(PointSetBase *ps) override
+    {
+      for (size_t i = 0; i < point_sets.v.size(); ++i)
+        if (point_sets.v[i].get() == ps)
+          {
+            HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (a kernel of the set may be in flight)
+            point_sets.v[i]->orphan();
+            point_sets.v.erase(point_sets.v.begin() + i);
+            return;
+          }
+    }
+    void
+    point_tables_bytes(uint64_t &locator, uint64_t &gather) const override
+    {
+      locator = point_locator ? point_locator->bytes : 0;
+      gather  = estimator ? estimator->gather_bytes : 0;
+    }
+    // defined in level_operator_apply.hpp, instantiated in apply_inst.hip: the launches of point_evaluate_kernel and point_integrate_kernel
+    template <int P>
+    void
+    point_evaluate_P(const PointSetDev &ps, const T *u, T *values, T *gradients);
+    template <int P>
+    void
+    point_integrate_P(const PointSetDev &ps, const T *values, const T *gradients, T *b);
+    void
+    point_evaluate(PointSetDev &ps, const mgamd_vec *u, mgamd_vec *values, mgamd_vec *gradients)
+    {
+      const char *who = "point_evaluate";
+      refuse_points(who);
+      if (!u)
+        throw std::invalid_argument("point_evaluate: u is null (a device vector of n_dofs values)");
+      if (!values && !gradients)
+        throw std::invalid_argument("point_evaluate: neither values nor gradients (at least one output)");
+      if (u->n != n_dofs())
+        throw std::invalid_argument("point_evaluate: vector size mismatch (" + std::to_string(u->n) + " for " + std::to_string(n_dofs()) + " DoFs)");
+      const T *up = u->as<T>(); // (refuses the other number type)
+      T       *vp = nullptr, *gp = nullptr;
+      if (values)
+        {
+          if (values->n != ps.n)
+            throw std::invalid_argument("point_evaluate: values size mismatch (" + std::to_string(values->n) + " for " + std::to_string(ps.n) + " points)");
+          vp = values->as<T>();
+        }
+      if (gradients)
+        {
+          if (gradients->n != 3 * ps.n)
+            throw std::invalid_argument("point_evaluate: gradients size mismatch (" + std::to_string(gradients->n) + " for 3 x " + std::to_string(ps.n) +
+                                        " points)");
+          gp = gradients->as<T>();
+        }
+      if (ps.n && ((vp && (const void *)vp == (const void *)up) || (gp && (const void *)gp == (const void *)up) || (vp && vp == gp)))
+        throw std::invalid_argument("point_evaluate: u, values and gradients must differ");
+      if (!ps.n)
+        return; // (nothing is built and nothing is launched)
+      ensure_estimator(false, who);
+      HIP_CHECK(hipEventRecord(ps.ev[2], ctx->stream));
+      if (ps.n_found < ps.n) // points that were not found: exactly 0 in every output
+        {
+          if (vp)
+            HIP_CHECK(hipMemsetAsync(vp, 0, ps.n * sizeof(T), ctx->stream));
+          if (gp)
+            HIP_CHECK(hipMemsetAsync(gp, 0, 3 * ps.n * sizeof(T), ctx->stream));
+        }
+      if (ps.n_found)
+        if (!dispatch_degree(p, [&](auto P) { point_evaluate_P<P()>(ps, up, vp, gp); }))
+          throw std::runtime_error("degree not instantiated");
+      HIP_CHECK(hipEventRecord(ps.ev[3], ctx->stream));
+      ps.timed[1] = true;
+    }
+    void
+    point_integrate(PointSetDev &ps, const mgamd_vec *values, const mgamd_vec *gradients, mgamd_vec *b)
+    {
+      const char *who = "point_integrate";
+      refuse_points(who);
+      if (!b)
+        throw std::invalid_argument("point_integrate: b is null (a device vector of n_dofs values)");
+      if (!values && !gradients)
+        throw std::invalid_argument("point_integrate: neither values nor gradients (at least one input)");
+      if (ps.n && ((values && values->data == b->data) || (gradients && gradients->data == b->data)))
+        throw std::invalid_argument(std::string("point_integrate: b aliases ") + (values && values->data == b->data ? "values" : "gradients") +
+                                    " (b is overwritten before the data is read)");
+      if (b->n != n_dofs())
+        throw std::invalid_argument("point_integrate: vector size mismatch (" + std::to_string(b->n) + " for " + std::to_string(n_dofs()) + " DoFs)");
+      T       *bp = b->as<T>(); // (refuses the other number type)
+      const T *vp = nullptr, *gp = nullptr;
+      if (values)
+        {
+          if (values->n != ps.n)
+            throw std::invalid_argument("point_integrate: values size mismatch (" + std::to_string(values->n) + " for " + std::to_string(ps.n) + " points)");
+          vp = values->as<T>();
+        }
+      if (gradients)
+        {
+          if (gradients->n != 3 * ps.n)
+            throw std::invalid_argument("point_integrate: gradients size mismatch (" + std::to_string(gradients->n) + " for 3 x " + std::to_string(ps.n) +
+                                        " points)");
+          gp = gradients->as<T>();
+        }
+      if (ps.n_found)
+        ensure_estimator(false, who);
+      HIP_CHECK(hipEventRecord(ps.ev[4], ctx->stream));
+      HIP_CHECK(hipMemsetAsync(bp, 0, (size_t)n_dofs() * sizeof(T), ctx->stream));
+      if (ps.n_found)
+        if (!dispatch_degree(p, [&](auto P) { point_integrate_P<P()>(ps, vp, gp, bp); }))
+          throw std::runtime_error("degree not instantiated");
+      HIP_CHECK(hipEventRecord(ps.ev[5], ctx->stream));
+      ps.timed[2] = true;
+    }
+
     size_t
     read_debug_stamps(unsigned long long *out, size_t max_count) override
     {

@@ -295,4 +295,68 @@ namespace mgamd
     HIP_CHECK(hipGetLastError());
   }
 
+  // what point_evaluate_kernel and point_integrate_kernel share: the gather table, the set's CSR list and the 1D element
+  template <int P, typename Estimator, typename Set>
+  static void
+  fill_point_walk(PointWalkArgs<P> &w, const Estimator &e, const Set &ps, const FE1D &fe)
+  {
+    const int n = P + 1;
+    w.idx        = e.idx.p;
+    w.mask       = e.mask.p;
+    w.scale      = e.scale.p;
+    w.leaf       = ps.leaf.p;
+    w.ptr        = ps.ptr.p;
+    w.perm       = ps.perm.p;
+    w.occ        = ps.occ.p;
+    w.ref        = ps.ref.p;
+    w.n_occupied = ps.n_occupied;
+    w.n_points   = (uint32_t)ps.n;
+    for (int i = 0; i < n * n; ++i)
+      {
+        w.I0[i] = fe.I[0][i];
+        w.I1[i] = fe.I[1][i];
+      }
+    for (int a = 0; a < n; ++a)
+      {
+        long double den = 1.0L;
+        for (int b = 0; b < n; ++b)
+          if (b != a)
+            den *= (long double)fe.nodes[a] - fe.nodes[b];
+        w.nodes[a]   = fe.nodes[a];
+        w.inv_den[a] = (double)(1.0L / den);
+      }
+  }
+
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::point_evaluate_P(const PointSetDev &ps, const T *u, T *values, T *gradients)
+  {
+    PointEvaluateArgs<T, P> a;
+    fill_point_walk<P>(a.w, *estimator, ps, tables->fe);
+    a.n_dofs    = n_dofs();
+    a.u         = u;
+    a.values    = values;
+    a.gradients = gradients;
+    const uint32_t groups = (ps.n_occupied + dirichlet_cells_per_workgroup<P>() - 1) / dirichlet_cells_per_workgroup<P>();
+    hipLaunchKernelGGL((point_evaluate_kernel<T, P>), std::min<uint32_t>(4096u, groups), 256, 0, ctx->stream, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  template <typename T>
+  template <int P>
+  void
+  LevelOperator<T>::point_integrate_P(const PointSetDev &ps, const T *values, const T *gradients, T *b)
+  {
+    PointIntegrateArgs<T, P> a;
+    fill_point_walk<P>(a.w, *estimator, ps, tables->fe);
+    a.scatter_limit = tables->first_constrained(); // the free rows
+    a.values        = values;
+    a.gradients     = gradients;
+    a.dst           = b;
+    const uint32_t groups = (ps.n_occupied + dirichlet_cells_per_workgroup<P>() - 1) / dirichlet_cells_per_workgroup<P>();
+    hipLaunchKernelGGL((point_integrate_kernel<T, P>), std::min<uint32_t>(4096u, groups), 256, 0, ctx->stream, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
 } // namespace mgamd

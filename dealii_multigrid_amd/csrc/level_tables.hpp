@@ -1275,6 +1275,143 @@ namespace mgamd
         b[i] = 0.0;
     }
 
+    // ---- point evaluation and point sources (DESIGN.md "Point evaluation and point sources"; on the device: kernels_point_values.hpp)
+    // The sorted Morton keys of the leaves (the mesh's cells ARE in this order: Tria::finalize); leaf t covers [key_t, key_{t+1}).
+    void
+    leaf_keys(std::vector<uint64_t> &keys) const
+    {
+      keys.resize(tria->cells.size());
+      for (size_t ci = 0; ci < keys.size(); ++ci)
+        keys[ci] = morton(tria->cells[ci]);
+    }
+    // the leaf and the reference coordinate of one point by the rule of octree.hpp point_key: false when the point is not found
+    bool
+    locate_point(const std::vector<uint64_t> &keys, const double x[3], int32_t &cell, double ref[3]) const
+    {
+      double   s[3];
+      uint64_t key;
+      cell   = -1;
+      ref[0] = ref[1] = ref[2] = 0.0;
+      if (!point_key(x, s, key))
+        return false;
+      cell          = (int32_t)(std::upper_bound(keys.begin(), keys.end(), key) - keys.begin()) - 1;
+      const Cell  &c = tria->cells[cell];
+      const double e = (double)(1u << (LMAX - c.level)); // the leaf's edge in integer coordinates
+      ref[0]         = (s[0] - (double)c.i * e) / e;     // exact: s - corner is a multiple of ulp(s) below s, e a power of two
+      ref[1]         = (s[1] - (double)c.j * e) / e;
+      ref[2]         = (s[2] - (double)c.k * e) / e;
+      return true;
+    }
+    // cell[k] (-1: not found) and ref[3k...] in [0, 1] (0 where not found) of the n points xyz[3k...]
+    void
+    locate_points(size_t n, const double *xyz, int32_t *cell, double *ref) const
+    {
+      refuse_estimate("locate_points");
+      if (n && (!xyz || !cell || !ref))
+        throw std::invalid_argument("locate_points: a null pointer (xyz and ref: 3 n doubles, cell: n integers)");
+      std::vector<uint64_t> keys;
+      leaf_keys(keys);
+      for (size_t k = 0; k < n; ++k)
+        locate_point(keys, xyz + 3 * k, cell[k], ref + 3 * k);
+    }
+    // values[k] = u_h(x_k) and/or gradients[c n + k] = d_c u_h(x_k) (either may be null, not both), the one-sided gradient of the
+    // point's leaf; exactly 0 where the point is not found.  Free and Dirichlet entries of u are read, hanging entries never.
+    void
+    point_evaluate(size_t n, const double *xyz, const double *u, double *values, double *gradients) const
+    {
+      refuse_estimate("point_evaluate");
+      if (!u)
+        throw std::invalid_argument("point_evaluate: u is null (n_dofs values)");
+      if (n && !xyz)
+        throw std::invalid_argument("point_evaluate: xyz is null (3 n doubles)");
+      if (!values && !gradients)
+        throw std::invalid_argument("point_evaluate: neither values nor gradients (at least one output)");
+      const int             n1 = p + 1, n3 = n1 * n1 * n1;
+      std::vector<uint64_t> keys;
+      std::vector<double>   loc(n3), L(3 * n1), D(3 * n1);
+      std::vector<uint32_t> idx(n3);
+      leaf_keys(keys);
+      int32_t held = -1; // the leaf whose conforming nodal values loc holds
+      for (size_t k = 0; k < n; ++k)
+        {
+          int32_t ci;
+          double  ref[3], v = 0.0, g[3] = {0.0, 0.0, 0.0};
+          if (locate_point(keys, xyz + 3 * k, ci, ref))
+            {
+              if (ci != held)
+                {
+                  gather_cell(ci, idx.data(), true);
+                  for (int t = 0; t < n3; ++t)
+                    loc[t] = idx[t] != INVALID_DOF ? u[idx[t]] : 0.0;
+                  interpolate_hanging(fe, tria->masks[ci], loc.data(), false);
+                  held = ci;
+                }
+              const double h = 2.0 / (double)(1u << tria->cells[ci].level);
+              for (int d = 0; d < 3; ++d)
+                FE1D::lagrange(fe.nodes, ref[d], &L[d * n1], &D[d * n1]);
+              for (int c = 0; c < n1; ++c)
+                for (int b = 0; b < n1; ++b)
+                  for (int a = 0; a < n1; ++a)
+                    {
+                      const double w = loc[(c * n1 + b) * n1 + a];
+                      v += L[2 * n1 + c] * L[n1 + b] * L[a] * w;
+                      g[0] += L[2 * n1 + c] * L[n1 + b] * D[a] * w;
+                      g[1] += L[2 * n1 + c] * D[n1 + b] * L[a] * w;
+                      g[2] += D[2 * n1 + c] * L[n1 + b] * L[a] * w;
+                    }
+              for (int d = 0; d < 3; ++d)
+                g[d] /= h;
+            }
+          if (values)
+            values[k] = v;
+          if (gradients)
+            for (int d = 0; d < 3; ++d)
+              gradients[d * n + k] = g[d];
+        }
+    }
+    // b_i = sum_k ( w_k phi_i(x_k) + W_k . grad phi_i(x_k) ) through C^T: point functionals, no quadrature weight and no h^3.  b is
+    // overwritten, constrained rows 0, points that are not found add nothing; no coefficient and no sigma.  values [n], gradients
+    // [3][n]; either may be null, not both.
+    void
+    point_integrate(size_t n, const double *xyz, const double *values, const double *gradients, std::vector<double> &b) const
+    {
+      refuse_estimate("point_integrate");
+      if (n && !xyz)
+        throw std::invalid_argument("point_integrate: xyz is null (3 n doubles)");
+      if (!values && !gradients)
+        throw std::invalid_argument("point_integrate: neither values nor gradients (at least one input)");
+      b.assign(n_dofs, 0.0);
+      const int             n1 = p + 1, n3 = n1 * n1 * n1;
+      std::vector<uint64_t> keys;
+      std::vector<double>   load(n3), L(3 * n1), D(3 * n1);
+      std::vector<uint32_t> idx(n3);
+      leaf_keys(keys);
+      for (size_t k = 0; k < n; ++k)
+        {
+          int32_t ci;
+          double  ref[3];
+          if (!locate_point(keys, xyz + 3 * k, ci, ref))
+            continue;
+          const double h = 2.0 / (double)(1u << tria->cells[ci].level);
+          const double w = values ? values[k] : 0.0;
+          const double W[3] = {gradients ? gradients[k] / h : 0.0, gradients ? gradients[n + k] / h : 0.0, gradients ? gradients[2 * n + k] / h : 0.0};
+          for (int d = 0; d < 3; ++d)
+            FE1D::lagrange(fe.nodes, ref[d], &L[d * n1], &D[d * n1]);
+          for (int c = 0; c < n1; ++c)
+            for (int bb = 0; bb < n1; ++bb)
+              for (int a = 0; a < n1; ++a)
+                load[(c * n1 + bb) * n1 + a] = w * L[2 * n1 + c] * L[n1 + bb] * L[a] + W[0] * L[2 * n1 + c] * L[n1 + bb] * D[a] +
+                                               W[1] * L[2 * n1 + c] * D[n1 + bb] * L[a] + W[2] * D[2 * n1 + c] * L[n1 + bb] * L[a];
+          interpolate_hanging(fe, tria->masks[ci], load.data(), true);
+          gather_cell(ci, idx.data(), false);
+          for (int t = 0; t < n3; ++t)
+            if (idx[t] != INVALID_DOF)
+              b[idx[t]] += load[t];
+        }
+      for (uint32_t i = first_constrained(); i < n_dofs; ++i)
+        b[i] = 0.0;
+    }
+
     // the refusals of a boundary flux; the error indicator takes the same six constants and refuses them in the same words
     void
     check_boundary_flux(const double q[6]) const

@@ -900,6 +900,96 @@ namespace mgamd
     std::shared_ptr<const DoFHandler> dofs;
   };
 
+  // Utilities::MPI::RemotePointEvaluation with VectorTools::point_values / point_gradients and, for the transpose,
+  // VectorTools::create_point_source_vector: caller points of [-1, 1]^3 located once on the leaves of one Operator (on the device,
+  // mgamd_level_op_point_set_create), then used for many vectors.  A point on an interior face, edge or vertex belongs to the leaf on
+  // its upper side (values do not depend on this, gradients are the one-sided gradients of that leaf); a point outside the cube is
+  // NOT found, gets exactly 0 from point_values / point_gradients and adds nothing in point_source, silently: check
+  // all_points_found().  The object keeps its Operator alive.
+  class PointEvaluation
+  {
+  public:
+    // the outputs are created in the operator's number type
+    PointEvaluation(const Context &ctx, const Operator &op)
+      : context(ctx)
+      , op(op)
+    {
+      check(mgamd_level_op_number_type(op.get(), &number_type));
+    }
+    // points: xyz[3k...], always double
+    void
+    reinit(const std::vector<double> &points)
+    {
+      mgamd_point_set *p = nullptr;
+      check(mgamd_level_op_point_set_create(op.get(), points.size() / 3, points.data(), &p));
+      h.reset(p, mgamd_point_set_destroy);
+      uint64_t n = 0;
+      check(mgamd_point_set_get(p, &n, nullptr, nullptr, nullptr));
+      cells.assign(n, -1);
+      check(mgamd_point_set_get(p, nullptr, nullptr, cells.data(), nullptr));
+    }
+    uint64_t
+    n_points() const
+    {
+      return cells.size();
+    }
+    bool
+    all_points_found() const
+    {
+      for (int32_t c : cells)
+        if (c < 0)
+          return false;
+      return true;
+    }
+    bool
+    point_found(uint64_t k) const
+    {
+      return cells.at(k) >= 0;
+    }
+    // the leaf of point k in the order of the mesh's cells, -1 where the point was not found
+    int32_t
+    cell(uint64_t k) const
+    {
+      return cells.at(k);
+    }
+    // u_h(x_k), n entries in the caller's point order, on the device in the operator's number type (mgamd_point_set_evaluate)
+    Vector
+    point_values(const Vector &u) const
+    {
+      Vector values(context, n_points(), number_type);
+      check(mgamd_point_set_evaluate(h.get(), op.get(), u.get(), values.get(), nullptr));
+      return values;
+    }
+    // grad u_h(x_k), 3 n entries [component][point]
+    Vector
+    point_gradients(const Vector &u) const
+    {
+      Vector gradients(context, 3 * n_points(), number_type);
+      check(mgamd_point_set_evaluate(h.get(), op.get(), u.get(), nullptr, gradients.get()));
+      return gradients;
+    }
+    // b_i = sum_k w_k phi_i(x_k) through C^T: the load of the Dirac sources w_k delta(x - x_k) (mgamd_point_set_integrate;
+    // VectorTools::create_point_source_vector).  b is overwritten, constrained rows are 0.  With `dipoles` (3 n entries
+    // [component][point]) the terms W_k . grad phi_i(x_k) are added; an empty Vector is an input not given.
+    void
+    point_source(const Vector &w, Vector &b, const Vector &dipoles = Vector()) const
+    {
+      check(mgamd_point_set_integrate(h.get(), op.get(), w.get(), dipoles.get(), b.get()));
+    }
+    mgamd_point_set *
+    get() const
+    {
+      return h.get();
+    }
+
+  private:
+    Context                          context;
+    Operator                         op;
+    int                              number_type = MGAMD_F64;
+    std::shared_ptr<mgamd_point_set> h;
+    std::vector<int32_t>             cells;
+  };
+
   class PreconditionChebyshev
   {
   public:

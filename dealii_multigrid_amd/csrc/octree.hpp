@@ -54,6 +54,28 @@ namespace mgamd
     return spread3((uint64_t)c.i << s) | (spread3((uint64_t)c.j << s) << 1) | (spread3((uint64_t)c.k << s) << 2);
   }
 
+  // Locating a point of [-1, 1]^3 (DESIGN.md "Point evaluation and point sources"; on the device: point_locate_kernel).  Per
+  // coordinate s = (x + 1) 2^(LMAX-1), one addition in double and an exact scale; the point is found iff every s lies in
+  // [0, 2^LMAX] (NaN is not), its integer coordinate is min(2^LMAX - 1, floor(s)), and its leaf is the one whose Morton interval
+  // holds the key of the three integer coordinates: a point on an interior face, edge or vertex belongs to the leaf on its upper
+  // side, a point on a face = +1 to the last leaf along that axis.
+  constexpr double POINT_SCALE = (double)(1u << (LMAX - 1));
+  inline bool
+  point_key(const double x[3], double s[3], uint64_t &key)
+  {
+    uint64_t c[3];
+    for (int d = 0; d < 3; ++d)
+      {
+        s[d] = (x[d] + 1.0) * POINT_SCALE;
+        if (!(s[d] >= 0.0 && s[d] <= 2.0 * POINT_SCALE))
+          return false;
+        const uint64_t f = (uint64_t)s[d]; // floor: s >= 0
+        c[d]             = f < ((uint64_t)1 << LMAX) - 1 ? f : ((uint64_t)1 << LMAX) - 1;
+      }
+    key = spread3(c[0]) | (spread3(c[1]) << 1) | (spread3(c[2]) << 2);
+    return true;
+  }
+
   // open-addressing hash map uint64 -> int32 (keys never removed except via rebuild)
   class FlatMap
   {

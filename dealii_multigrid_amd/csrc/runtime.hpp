@@ -164,6 +164,28 @@ namespace mgamd
   double
   vec_dot(const mgamd_vec &x, const mgamd_vec &y);
 
+  struct LevelOperatorBase;
+  // A located point set of one operator (LevelOperatorBase::point_set_create); device vectors in the operator's number type.
+  // evaluate: values [n] and/or gradients [3][n] in the caller's point order, exactly 0 where a point was not found; either output
+  // may be null.  integrate: b is OVERWRITTEN with sum_k (w_k phi_i(x_k) + W_k . grad phi_i(x_k)) through C^T, constrained rows 0;
+  // either input may be null, not both.  Stream-ordered, nothing is copied to the host.
+  struct PointSetBase
+  {
+    LevelOperatorBase *op = nullptr;
+    uint64_t           n = 0, n_found = 0;
+    virtual ~PointSetBase() = default;
+    virtual void
+    get(int32_t *cell, double *ref) const = 0; // leaf (-1: not found) and reference coordinate [n][3] per point; either may be null
+    virtual void
+    evaluate(const mgamd_vec *u, mgamd_vec *values, mgamd_vec *gradients) = 0;
+    virtual void
+    integrate(const mgamd_vec *values, const mgamd_vec *gradients, mgamd_vec *b) = 0;
+    // measurement: device bytes of the set, host time of its build (the binning by leaf), device times of its locate kernel and of
+    // the last evaluate and the last integrate (HIP events; waits for them), 0 before the first
+    virtual void
+    info(uint64_t &bytes, double &build_ms, double &locate_ms, double &evaluate_ms, double &integrate_ms) const = 0;
+  };
+
   struct LevelOperatorBase
   {
     Ctx                         *ctx  = nullptr;
@@ -271,6 +293,19 @@ namespace mgamd
     // times of the last evaluate and the last integrate (HIP events; waits for them); 0 before the first call
     virtual void
     cell_values_info(uint64_t &bytes, double &evaluate_ms, double &integrate_ms) const = 0;
+    // Point evaluation and point sources (kernels_point_values.hpp).  A point set is n caller points (xyz[3k...], always double)
+    // located on the device and binned by leaf once, then used for many vectors.  It belongs to this operator: its device arrays
+    // are freed with the operator at the latest (a handle that outlives the operator refuses every call), point_set_destroy frees
+    // them earlier.  The sorted Morton keys of the leaves are uploaded by the first point set,
+    // the gather table (the indicator's, the norms' and the cell values') by the first evaluate or integrate.
+    virtual std::shared_ptr<PointSetBase>
+    point_set_create(uint64_t n, const double *xyz) = 0;
+    virtual void
+    point_set_destroy(PointSetBase *ps) = 0;
+    // measurement: bytes of the operator's device arrays that only the point sets use (the keys and corners of the leaves), 0
+    // before the first point set; and of the shared gather table, 0 until some call has built it
+    virtual void
+    point_tables_bytes(uint64_t &locator, uint64_t &gather) const = 0;
 
   private:
     // distribute_values without its refusals (sizes, local-smoothing levels): distribute(x, kind) runs on every level
@@ -488,6 +523,10 @@ namespace mgamd
 struct mgamd_level_op
 {
   std::unique_ptr<mgamd::LevelOperatorBase> op;
+};
+struct mgamd_point_set
+{
+  std::shared_ptr<mgamd::PointSetBase> ps;
 };
 struct mgamd_cheb
 {

@@ -44,6 +44,7 @@ typedef struct mgamd_matrix    mgamd_matrix;    /* TrilinosWrappers::SparseMatri
 typedef struct mgamd_amg       mgamd_amg;       /* TrilinosWrappers::PreconditionAMG on that matrix                                    */
 typedef struct mgamd_partition mgamd_partition; /* domain decomposition of the level hierarchy (one rank per GPU) */
 typedef struct mgamd_comm      mgamd_comm;      /* communicator: RCCL over xGMI, or the in-process simulator      */
+typedef struct mgamd_point_set mgamd_point_set; /* Utilities::MPI::RemotePointEvaluation: located points of one operator           */
 typedef struct mgamd_sim_group mgamd_sim_group; /* the ranks of one in-process simulation                         */
 
 const char *mgamd_last_error(void);
@@ -235,6 +236,28 @@ int mgamd_dofs_quadrature_points(const mgamd_dofs *d, int n_q, double *xyz);
  * sharded"); the tables of a local-smoothing level; neither values nor gradients; out == NULL, u == NULL. */
 int mgamd_dofs_integrate(const mgamd_dofs *d, const double *values, const double *gradients, int n_q, double *out);
 int mgamd_dofs_evaluate(const mgamd_dofs *d, const double *u, int n_q, double *values, double *gradients);
+/* Point evaluation and point sources on the host, in double (in deal.II: GridTools::find_active_cell_around_point;
+ * VectorTools::point_value / point_gradient, FEPointEvaluation; VectorTools::create_point_source_vector).  The domain is [-1, 1]^3;
+ * points are n triples xyz[3k...], always double.
+ * Location.  Per coordinate s = (x + 1) 2^14 (one addition in double, then an exact scale) and c = min(2^15 - 1, floor(s)); a point
+ * is FOUND iff all three s lie in [0, 2^15] (NaN is not found).  Its leaf is the one whose Morton interval holds the key of
+ * (c_x, c_y, c_z): a point on an interior face, edge or vertex belongs to the leaf on its UPPER side, a point on a face = +1 to the
+ * last leaf.  The reference coordinate is (s - corner) / edge per coordinate, exact after the one addition, in [0, 1) and 1 only on
+ * the +1 faces.  There is no search radius and no tolerance outside the cube beyond the rounding of x + 1: a point outside by 2^-40 is not found.
+ * mgamd_dofs_locate_points: cell[k] in the order of mgamd_tria_get_cells (-1: not found) and ref[3k...] (0 where not found).
+ * mgamd_dofs_point_evaluate: values[k] = u_h(x_k) and/or gradients[c n + k] = d_c u_h(x_k), the physical gradient, laid out by
+ * component [3][n]; either may be NULL, not both.  u_h is continuous, so values do not depend on the tie rule; gradients are the
+ * ONE-SIDED gradients of the point's leaf.  Entries of u at free and Dirichlet DoFs are read, hanging entries never.  A point
+ * that is not found gets exactly 0 in every output, silently: check cell[k] >= 0.
+ * mgamd_dofs_point_integrate: out_i = sum_k ( values_k phi_i(x_k) + gradients_k . grad phi_i(x_k) ), mapped through the transposed
+ * hanging-node interpolation: point functionals, a Dirac load and (through gradients) a dipole, with NO quadrature weight and NO
+ * h^3.  out (n_dofs values) is overwritten, every constrained row (Dirichlet and hanging) is 0, points that are not found add
+ * nothing; no coefficient and no sigma are applied.  Either of values and gradients may be NULL, not both.
+ * No GPU needed.  MGAMD_ERR_INVALID, by name ("locate_points: ...", "point_evaluate: ...", "point_integrate: ..."): sharded tables
+ * ("not implemented: sharded"); the tables of a local-smoothing level; a null pointer; neither values nor gradients. */
+int mgamd_dofs_locate_points(const mgamd_dofs *d, uint64_t n, const double *xyz, int32_t *cell, double *ref);
+int mgamd_dofs_point_evaluate(const mgamd_dofs *d, uint64_t n, const double *xyz, const double *u, double *values, double *gradients);
+int mgamd_dofs_point_integrate(const mgamd_dofs *d, uint64_t n, const double *xyz, const double *values, const double *gradients, double *out);
 /* The mass term: the operator becomes A = K + sigma M, the weak form of -Laplace u + sigma u (sigma = 1 / dt for a backward-Euler
  * step of the heat equation); this project's extension, the reference solves sigma = 0 only.  sigma is a property of the level
  * tables, next to the cell sizes and the constraints; the default is 0.  Everything DERIVED from the tables reads it when it is
@@ -532,6 +555,43 @@ int mgamd_level_op_evaluate(mgamd_level_op *op, const mgamd_vec *u, int n_q, mga
  * never leaves the device.  Tables as for mgamd_level_op_evaluate.
  * MGAMD_ERR_INVALID, by name: the refusals above with "integrate:"; neither values nor gradients; b == NULL; b aliasing an input. */
 int mgamd_level_op_integrate(mgamd_level_op *op, const mgamd_vec *values, const mgamd_vec *gradients, int n_q, mgamd_vec *b);
+/* Point sets: the host functions above on the device (in deal.II: Utilities::MPI::RemotePointEvaluation::reinit, then
+ * VectorTools::point_values / point_gradients for many vectors, and VectorTools::create_point_source_vector for the transpose).
+ * mgamd_level_op_point_set_create locates n points (xyz[3k...], host memory, always double) on the leaves of the operator with one
+ * kernel, by the rule of mgamd_dofs_locate_points bit for bit, and bins them by leaf into a list of occupied leaves; the set is
+ * then used for many vectors (a probe inside a time loop).  The binning runs on the host when the set is built and the call
+ * returns after it.  n = 0 is allowed: it uploads nothing and launches no kernel (integrate on an empty set, or on a set
+ * without a found point, still overwrites b with its stream-ordered memset and records its two timing events).  The sorted Morton keys of the leaves with their corners (24 bytes per
+ * leaf) are uploaded by the operator's first point set, the gather table (shared with the indicator, the norms and
+ * mgamd_level_op_evaluate) by the first evaluate or integrate; an operator that is never asked holds nothing.  A set holds 28 bytes
+ * per point plus 8 per found point and 8 per occupied leaf.  It belongs to its operator: its device arrays are freed by
+ * mgamd_point_set_destroy or with the operator, whichever comes first, and a handle that outlives its operator refuses every call
+ * but destroy.
+ * mgamd_point_set_get: n, the number of found points, and per point the leaf (-1: not found) and the reference coordinate; any
+ * pointer may be NULL.
+ * mgamd_point_set_evaluate (VectorTools::point_values, point_gradients): values (n entries) and/or gradients (3 n entries,
+ * [component][point]) of u at the points, device vectors in the operator's number type, in the CALLER'S point order; either
+ * output may be NULL, not both.  Values do not depend on the tie rule of the location, gradients are the one-sided gradients of the
+ * point's leaf.  Points that are not found get exactly 0, silently (mgamd_point_set_get tells).  Entries of u at free and
+ * Dirichlet DoFs are read, hanging entries never.  All arithmetic after the gather is FP64 for both number types and the store
+ * converts; no atomics and a fixed order of every sum: two calls give the same bits.  Stream-ordered, nothing is copied to the host.
+ * mgamd_point_set_integrate (VectorTools::create_point_source_vector): b_i = sum_k ( values_k phi_i(x_k) + gradients_k . grad
+ * phi_i(x_k) ) through C^T, no quadrature weight and no h^3; b is OVERWRITTEN (a stream-ordered memset comes before the kernel),
+ * every constrained row is exactly 0, points that are not found add nothing, no coefficient and no sigma are applied.  The points
+ * of a leaf are summed in a fixed order in FP64; the scatter is an atomic add in the vector's number type, so a row shared by
+ * several occupied leaves takes its addends in no fixed order: NOT bit-reproducible across calls (it is where every row has one
+ * addend, as on a one-leaf mesh).
+ * op is the operator that created the set.  MGAMD_ERR_INVALID, by name ("point_set: ...", "point_evaluate: ...",
+ * "point_integrate: ..."): a distributed operator or sharded tables ("not implemented: sharded"); the operator of a local-smoothing
+ * level; a null pointer; a vector of the wrong size or number type; neither values nor gradients; b aliasing an input; an output
+ * that is u or the other output; a point set used with an operator other than its own. */
+/* the number type of the operator's vectors, MGAMD_F64 or MGAMD_F32: what the outputs of a point set must have */
+int mgamd_level_op_number_type(const mgamd_level_op *op, int *number_type);
+int mgamd_level_op_point_set_create(mgamd_level_op *op, uint64_t n, const double *xyz, mgamd_point_set **out);
+int mgamd_point_set_destroy(mgamd_point_set *ps);
+int mgamd_point_set_get(const mgamd_point_set *ps, uint64_t *n, uint64_t *n_found, int32_t *cell, double *ref);
+int mgamd_point_set_evaluate(mgamd_point_set *ps, mgamd_level_op *op, const mgamd_vec *u, mgamd_vec *values, mgamd_vec *gradients);
+int mgamd_point_set_integrate(mgamd_point_set *ps, mgamd_level_op *op, const mgamd_vec *values, const mgamd_vec *gradients, mgamd_vec *b);
 
 /* PreconditionChebyshev (ref:multigrid_throughput.cc:849-852, 867-883): the inverse diagonal is
  * computed internally (DiagonalMatrix preconditioner); eigenvalues are estimated at creation with

@@ -120,6 +120,17 @@ int mgamd_debug_level_op_error_norm_info(const mgamd_level_op *op, uint64_t *byt
  * waits for those events.  All 0 before the operator's first evaluate or integrate.  Any pointer may be null. */
 int mgamd_debug_level_op_cell_values_info(const mgamd_level_op *op, uint64_t *bytes, double *evaluate_ms, double *integrate_ms);
 
+/* ---- point sets (mgamd_level_op_point_set_create, mgamd_point_set_evaluate, mgamd_point_set_integrate) ----
+ * measurement.  Of the operator op (may be null): operator_bytes, the device arrays only its point sets use (sorted leaf keys and
+ * corners), 0 before its first non-empty point set; gather_bytes, the gather table shared with the indicator, the norms and the
+ * cell values, 0 until some call has built it (a point set does at its first evaluate or integrate).  Of the set ps (may be
+ * null): its device bytes, the host time of its build (the binning by leaf), and the device times by HIP events of its locate
+ * kernel and of its last evaluate and last integrate (memsets included), each 0 before the first such call; the call waits
+ * for those events.  Not both of op and ps null; any output pointer may be null. */
+int mgamd_debug_point_set_info(const mgamd_level_op *op, const mgamd_point_set *ps, uint64_t *operator_bytes,
+                               uint64_t *gather_bytes, uint64_t *set_bytes, double *build_ms, double *locate_ms,
+                               double *evaluate_ms, double *integrate_ms);
+
 #ifdef __cplusplus
 }
 #endif
